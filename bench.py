@@ -498,11 +498,32 @@ def timed_oneshots(ctx, w, steps, warmup):
     assert cnt.value == steps, (cnt.value, steps)
     spans = [sums[0], sums[1], sums[2]]
     res = shots[(warmup + steps - 1) % len(shots)].result()
+    w.last_step = shots[(warmup + steps - 1) % len(shots)].result()  # the last step's own tally (--dump-outputs)
     res.fail_count = fails
     hp = (ctypes.c_double * 4)()
     lib.zk_last_host_phases(hp)
     w.host_phases_us = {"open": hp[0], "launch": hp[1], "collect": hp[2], "close": hp[3]}  # of the last timed step
     return dt, res, [x / steps for x in spans]
+
+
+DUMP_FIELDS = ("fail_count", "first_fail_row", "first_fail_code", "rows_evaluated", "launches")  # a tally's computed fields (not its timings)
+
+
+def dump_outputs(out_dir, last):
+    """--dump-outputs: what the caller of the timed path received from its LAST timed step, one float64 .npy per array
+    (`<circuit>_<field>` per circuit of the super block).  A tally field a result does not carry is omitted; a first_fail_row of
+    None (no failing row) is written as -1.  Timings are not outputs and are not written."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    items = last.items() if isinstance(last, dict) else [(None, last)]
+    for circuit, r in items:
+        for f in DUMP_FIELDS:
+            if not hasattr(r, f):
+                continue
+            v = getattr(r, f)
+            name = f if circuit is None else f"{circuit}_{f}"
+            np.save(os.path.join(out_dir, name + ".npy"), np.array([-1 if v is None else int(v)], dtype=np.float64))
 
 
 def resolve_super(w, res):
@@ -797,6 +818,8 @@ def main():
     ap.add_argument("--no-fresh-leg", action="store_true", help="skip the open / pass split with explicit cache flushes")
     ap.add_argument("--full-line", action="store_true", help="print the full nested record on stdout instead of the compact line (it is always written to bench_full.json)")
     ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs[0], [1], [3], [4] after the headline (default: run them at N = 1, evm workload)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (rank 0) as DIR/<name>.npy, float64")
     args = ap.parse_args()
     global STATE_COMPACT
     STATE_COMPACT = bool(args.state_compact)
@@ -833,6 +856,7 @@ def main():
     batch_side = None
     if oneshot_mode:
         dt, res, spans = timed_oneshots(ctx, w, args.steps, args.warmup)
+        last_step = w.last_step
         if not args.no_batch_leg:
             batch_side = legs.timed_batch(ctx, w, args.steps, args.warmup)
         if sess is not None:
@@ -841,8 +865,12 @@ def main():
     else:
         dt, res = timed_passes(ctx, sess, args.steps, args.warmup)
         pre_ramp = timed_passes.last_ramp
+        last_step = res
         if args.workload == "super":
             res, per_circuit = resolve_super(w, res)
+            last_step = dict(last_step[0], block=res)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step)
 
     # Cold-cache leg (outside the timed region): the timed passes re-read the same witness, so page-table lines and part of
     # the rows are still in L2 / Infinity Cache from the previous pass.  Here every pass is preceded by a read-only sweep over

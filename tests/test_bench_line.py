@@ -99,3 +99,26 @@ def test_compact_line_pass_workloads(bench):
 def test_effective_cores(bench):
     n, how = bench.legs.effective_cores()
     assert 1 <= n <= (os.cpu_count() or 1) and how
+
+
+def test_dump_outputs_writes_the_last_steps_tally(bench, tmp_path):
+    """--dump-outputs: one float64 .npy per computed tally field (a None first_fail_row as -1), per circuit for the super block;
+    timings are not outputs"""
+    import numpy as np
+
+    class R:
+        fail_count, first_fail_row, first_fail_code, rows_evaluated, launches, kernel_ms = 3, 17, (1 << 24) | 8, 1 << 18, 2, 0.25
+
+    class Clean:
+        fail_count, first_fail_row, first_fail_code, kernel_ms = 0, None, 0, 0.1
+
+    bench.dump_outputs(str(tmp_path / "one"), R)
+    got = {p.stem: np.load(p) for p in (tmp_path / "one").glob("*.npy")}
+    assert set(got) == set(bench.DUMP_FIELDS)
+    assert all(a.dtype == np.float64 and a.shape == (1,) for a in got.values())
+    assert {k: int(a[0]) for k, a in got.items()} == {"fail_count": 3, "first_fail_row": 17, "first_fail_code": (1 << 24) | 8,
+                                                      "rows_evaluated": 1 << 18, "launches": 2}
+    bench.dump_outputs(str(tmp_path / "super"), {"evm": R, "block": Clean})
+    got = {p.stem: float(np.load(p)[0]) for p in (tmp_path / "super").glob("*.npy")}
+    assert got["block_first_fail_row"] == -1 and got["block_fail_count"] == 0 and "block_rows_evaluated" not in got
+    assert got["evm_fail_count"] == 3 and not any("kernel_ms" in k for k in got)

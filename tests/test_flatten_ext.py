@@ -98,11 +98,11 @@ def test_dedup_rows_order_is_the_integer_order():
     assert [tuple(flat[i : i + 3]) for i in range(0, len(flat), 3)] == want
 
 
-REF = "/root/reference/src"
 SHIM = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "refshim")
+REF = os.path.join(os.path.dirname(SHIM), "_ref", "src")  # staged by build() (oracle/stage_ref.py)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference lives in the build container only")
+@pytest.mark.skipif(not os.path.isdir(REF), reason="no reference staged under oracle/_ref/")
 def test_reference_objects():
     """the reference's own FQ / Word / RLC / IntEnum cells (child process: PYTHONPATH = oracle/refshim + the reference): real
     RWTableRow / BytecodeTableRow / BlockTableRow / TxTableRow / StepState objects through both paths"""

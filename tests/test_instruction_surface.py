@@ -96,10 +96,10 @@ def test_word_arithmetic_against_bigints():
         I.mul_word_by_u64(Word(M256), FQ(2))
 
 
-REF = "/root/reference/src"
+REF = os.path.join(ROOT, "oracle", "_ref", "src")  # staged by build() (oracle/stage_ref.py)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference lives in the build container only")
+@pytest.mark.skipif(not os.path.isdir(REF), reason="no reference staged under oracle/_ref/")
 def test_differential_against_the_reference_class():
     """same inputs through the reference's Instruction (child process: PYTHONPATH = oracle/refshim + the reference) and through the
     mirror; results and exception classes must agree"""

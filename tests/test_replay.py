@@ -1,7 +1,7 @@
 """Failure replay (zkevm_specs_amd/replay.py) in the build container.  Since round 4 replay is an opt-in
 diagnostic (ZK_REPLAY=always: the reference's own message): every golden pair — word cells >= 2^128 included — has a verdict of
 its own, and the mirror's `verify_steps` must raise the class the unmodified reference raises without executing the reference.  The device is stood in for by the oracle (as in tests/test_dropin_cpu.py); the replay
-itself runs the reference (needs /root/reference + oracle/refshim: skipped elsewhere, e.g. on the GPU box)."""
+itself runs the reference (needs the copy build() stages under oracle/_ref/ + oracle/refshim: skipped where no reference was staged)."""
 import os
 import sys
 
@@ -9,8 +9,8 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference/src"
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference is not on this machine")
+REF = os.path.join(ROOT, "oracle", "_ref", "src")  # staged by build() (oracle/stage_ref.py)
+pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="no reference staged under oracle/_ref/")
 
 
 @pytest.fixture()

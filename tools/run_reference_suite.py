@@ -122,7 +122,10 @@ def main():
         _lib.init()
     plugin = Rebind()
     targets = [os.path.join(tests_dir, t) for t in args.select] if args.select else [tests_dir]
-    pa = ["-q", "-p", "no:cacheprovider", "--rootdir", tests_dir, "-c", "/dev/null", "--tb=short", "-o", "python_files=test_*.py"] + targets
+    # --confcutdir: with `-c /dev/null` pytest would otherwise start collecting at the filesystem root and list every directory above
+    # the tests, which fails where one of them is not readable by this user
+    pa = ["-q", "-p", "no:cacheprovider", "--rootdir", tests_dir, "-c", "/dev/null", "--confcutdir", tests_dir, "--tb=short",
+          "-o", "python_files=test_*.py"] + targets
     if args.keyword:
         pa += ["-k", args.keyword]
     if args.exitfirst:
