@@ -91,6 +91,9 @@ const char* zk_last_error(void);
 /* BN254-Fr vector ops on the device: op 0 add, 1 sub, 2 mul, 3 montmul, 4 neg, 5 inv (of a; inv(0) = 0 as py_ecc's
  * prime_field_inv), 6 div (a * inv(b)); 16 / 17: the secp256k1 BASE-field product a * b / square a^2 mod 2^256 - 2^32 - 977
  * (operands are residues below that prime; unit-test hooks of the ECDSA kernel's multiplier).
+ * 18: the BN254 BASE-field product a * b mod p (p = 2188...8583, residues in and out; unit-test hook of csrc/bn254_fq.hpp);
+ * 19: the Fq12 product a * b, n a multiple of 12, every 12 consecutive elements one Fq12 in tower order (c0.c0.c0, c0.c0.c1,
+ * c0.c1.c0, ..., c1.c2.c1: Fq12 = Fq6 + Fq6 w, Fq6 = Fq2 + Fq2 v + Fq2 v^2, Fq2 = Fq + Fq u; residues in and out).
  * (reference: FQ.__add__/__sub__/__mul__/__neg__/__truediv__ via py_ecc and FQ.inv, util/arithmetic.py:41-60) */
 int zk_fr_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t n, uint32_t opts);
 
@@ -525,6 +528,28 @@ int zk_dist_close(zk_comm* c);
 /* Re-bind a session to another stream of its device (NULL = the engine's own); waits for its enqueued passes first. */
 int zk_session_set_stream(zk_session* s, void* hip_stream);
 int zk_close(zk_session* s);
+
+/* ---- ECC circuit: replaces circuit2rows + the row loop of ecc_circuit.verify_circuit (src/zkevm_specs/ecc_circuit.py:386-433;
+ *      EccCircuitRow.assign* :35-232, verify :234-333, util/ec.py ECCVerifyChip / ECCPairingVerifyChip :120-201).
+ *      Rows in circuit2rows order: the n_add adds, the n_mul muls, then the n_pairing pairings.
+ *      points: uint64[n_add + n_mul][6][4], 256-bit words (4 x u64 little-endian, NOT reduced):
+ *              add: p.x, p.y, q.x, q.y, out.x, out.y;   mul: p.x, p.y, s, 0, out.x, out.y.
+ *      pair_pts: uint64[pair_off[n_pairing]][6][4], one entry per (g1_pts[i], g2_pts[i]) in EIP-197 order:
+ *              p.x, p.y, x.c1, x.c0, y.c1, y.c0 (imaginary part first); pairing op k owns entries [pair_off[k], pair_off[k + 1]).
+ *      pair_off: uint32[n_pairing + 1], pair_off[0] = 0, non-decreasing.   pair_out: uint64[n_pairing][4], the op's `out` word.
+ *      randomness: one cell (keccak_randomness).  max_add / max_mul / max_pairing: the circuit's max_*_ops (clamped to 0 / 1 by the
+ *      caller: the reference's counters are locals of verify(), so only a max below 1 can fail).
+ *      rows (zk_ecc_assign's output, zk_ecc_verify's input): uint64[n][13][4], the EccTableRow cells as flatten_ecc_table lays them
+ *      out — op_type, px lo / hi, py lo / hi, qx lo / hi, qy lo / hi, input_rlc, out_x, out_y, is_valid.  zk_ecc_verify checks
+ *      the rows against the chips built from the ops, as verify_circuit does (status: (kind << 24) | site, csrc/ecc_circuit.hpp). */
+typedef struct zk_ecc_ops {
+    const uint64_t* points;     uint64_t n_add;              uint64_t n_mul;
+    const uint64_t* pair_pts;   const uint32_t* pair_off;    const uint64_t* pair_out;   uint64_t n_pairing;
+    const uint64_t* randomness;
+    uint32_t max_add, max_mul, max_pairing;
+} zk_ecc_ops;
+int zk_ecc_assign(const zk_ecc_ops* ops, uint32_t opts, uint64_t* rows_out);
+int zk_ecc_verify(const zk_ecc_ops* ops, const uint64_t* rows, uint32_t opts, uint32_t* status_out, zk_result* result);
 
 #ifdef __cplusplus
 }

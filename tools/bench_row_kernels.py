@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Throughput of the row-stencil kernels (Bytecode / Exp / Tx-Sig circuits) on synthetic witnesses:
+"""Throughput of the row-stencil kernels (Bytecode / Exp / Tx-Sig circuits, the ECC circuit) on synthetic witnesses:
 rows/s and algorithmic GB/s (SURVEY.md §8d bytes per unit), device-resident inputs, HIP-event kernel
-time.  bench.py carries the headline EVM / State workloads; this is the side table in DESIGN.md §3."""
+time.  bench.py carries the headline EVM / State workloads; this is the side table in DESIGN.md §3.
+`bench_row_kernels.py ecc` runs only the ECC leg."""
 import json
 import os
 import random
@@ -34,6 +35,51 @@ def run(name, sess, units, bytes_per_unit):
                  "frac_of_8TBps": round(units * bytes_per_unit / r.kernel_ms / 1e6 / 8000, 4)}
     print(name, out[name], flush=True)
 
+
+def ecc_leg():
+    """ECC circuit verification (zk_ecc_verify, one-shot from host buffers; kernel_ms = HIP-event span of the pass): add rows/s at
+    2^14 adds, mul rows/s at 2^12 muls, pairings/s at 2^10 two-pair pairing ops, on HIP and on the CPU backend (wall time)."""
+    import time
+
+    from tests import bn254_ref as b
+    from zkevm_specs_amd import oneshot
+    from zkevm_specs_amd.flatten import flatten_ecc_ops
+
+    g = random.Random(4)
+    F, F2 = b.Fq, b.Fq2
+    pts = [b.multiply(b.G1, g.randrange(1, b.R), F) for _ in range(64)]
+    adds = [(pts[i % 64], pts[(7 * i + 3) % 64], b.add(pts[i % 64], pts[(7 * i + 3) % 64], F)) for i in range(64)]
+    scal = [g.randrange(1, b.R) for _ in range(64)]
+    muls = [(pts[i], scal[i], b.multiply(pts[i], scal[i], F)) for i in range(64)]
+    a = g.randrange(1, b.R)
+    qa = b.multiply(b.G2, a, F2)
+    q1, qa_w = (b.G2[0][1], b.G2[0][0], b.G2[1][1], b.G2[1][0]), (qa[0][1], qa[0][0], qa[1][1], qa[1][0])
+    pairing = ([b.multiply(b.G1, a, F), b.neg(b.G1, F)], [q1, qa_w], 1)
+    rk = 0x5EED % b.R
+    for name, n, ops in (("ecc_add", 1 << 14, ([adds[i % 64] for i in range(1 << 14)], [], [])),
+                         ("ecc_mul", 1 << 12, ([], [muls[i % 64] for i in range(1 << 12)], [])),
+                         ("ecc_pairing_2pairs", 1 << 10, ([], [], [pairing] * (1 << 10)))):
+        w = flatten_ecc_ops(*ops)
+        rows = oneshot.ecc_assign(w, rk)
+        ms = []
+        for _ in range(4):
+            res, st = oneshot.ecc_verify(w, rows, rk)
+            assert res.fail_count == 0, (name, res.first_fail_code)
+            ms.append(res.kernel_ms)
+        kms = min(ms[1:])
+        t0 = time.perf_counter()
+        res_c, _ = oneshot.ecc_verify(w, rows, rk, device="cpu")
+        cpu_s = time.perf_counter() - t0
+        assert res_c.fail_count == 0
+        out[name] = {"rows": n, "hip_kernel_ms": round(kms, 3), "hip_rows_per_s": round(n / kms * 1e3),
+                     "cpu_wall_ms": round(cpu_s * 1e3, 1), "cpu_rows_per_s": round(n / cpu_s), "cpu_threads": os.cpu_count()}
+        print(name, out[name], flush=True)
+
+
+if sys.argv[1:] == ["ecc"]:
+    ecc_leg()
+    print(json.dumps(out))
+    sys.exit(0)
 
 rng = random.Random(1)
 r = rng.randrange(P)
@@ -125,4 +171,5 @@ packed = np.frombuffer(b"".join(x.to_bytes(32, "little") + y.to_bytes(32, "littl
 for reps in (1, 2, 4, 8):
     d = torch.from_numpy(np.tile(packed, (reps, 1, 1))).cuda()
     run(f"ecdsa_verify_{n_sig * reps}", engine.open_ecdsa(d), n_sig * reps, 160 + 4)
+ecc_leg()
 print(json.dumps(out))

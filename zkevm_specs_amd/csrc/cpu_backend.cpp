@@ -32,6 +32,7 @@
 #include "state_assign.hpp"
 #include "bytecode_assign.hpp"
 #include "state_rekey.hpp"
+#include "ecc_circuit.hpp"
 
 static thread_local std::string g_err;
 #define ARG_TRY(cond, msg) do { if (!(cond)) { g_err = msg; return -1; } } while (0)
@@ -314,6 +315,8 @@ extern "C" int zk_fr_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* 
         case 4: r = fr_neg(x); break;
         case 5: r = fr_inv(x); break;
         case 6: r = fr_div(x, y); break;
+        case 18: r = ecc_fq_mul_hook(x, y); break;
+        case 19: if (i % 12 == 0 && i + 12 <= (long long)n) ecc_fq12_mul_hook(a + 4 * i, b + 4 * i, out + 4 * i); continue;
         default: r = fr_zero();
         }
         for (int k = 0; k < 4; k++) out[4 * i + k] = (u64)r.v[2 * k] | ((u64)r.v[2 * k + 1] << 32);
@@ -1131,4 +1134,32 @@ extern "C" int zk_copy_assign(const zk_copy_events* t, uint64_t* rows_out, uint3
     if (!rc) rc = zk_copy_assign_read(s, rows_out, row_flags_out, table_out, rw_out, rw_flags_out);
     zk_close(s);
     return rc;
+}
+
+// ---- ECC circuit ------------------------------------------------------------------------------------------------------
+extern "C" int zk_ecc_assign(const zk_ecc_ops* ops, uint32_t opts, uint64_t* rows_out) {
+    NO_DEVICE_PTRS(opts, "zk_ecc_assign");
+    EccArgs a;
+    const char* err = ecc_args_from_ops(ops, a);
+    ARG_TRY(!err, err ? (std::string("zk_ecc_assign: ") + err).c_str() : "");
+    ARG_TRY(rows_out, "zk_ecc_assign: rows_out is null");
+    const u64 np = a.n_add + a.n_mul, n = np + a.n_pairing;
+#pragma omp parallel for schedule(dynamic, 16)
+    for (long long i = 0; i < (long long)n; i++) {
+        u64* row = rows_out + (u64)i * ECC_NCELLS * 4;
+        if ((u64)i < np) ecc_assign_point_row(a, (u64)i, row);
+        else ecc_assign_pairing_row(a, (u64)i - np, row);
+    }
+    return 0;
+}
+extern "C" int zk_ecc_verify(const zk_ecc_ops* ops, const uint64_t* rows, uint32_t opts, uint32_t* status_out, zk_result* result) {
+    NO_DEVICE_PTRS(opts, "zk_ecc_verify");
+    ARG_TRY(result && rows, "zk_ecc_verify: rows / result is null");
+    EccArgs a;
+    const char* err = ecc_args_from_ops(ops, a);
+    ARG_TRY(!err, err ? (std::string("zk_ecc_verify: ") + err).c_str() : "");
+    a.rows = rows;
+    zk_session* s = new_session(a.n_add + a.n_mul + a.n_pairing, true);
+    s->row = [a](u64 i) { return ecc_verify_row(a, i); };
+    return one_shot(s, status_out, result);
 }

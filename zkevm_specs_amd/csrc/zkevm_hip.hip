@@ -539,6 +539,7 @@ __global__ void fr_op_kernel(int op, const u64* a, const u64* b, u64* out, u64 n
     case 6: r = fr_div(x, y); break;
     case 16: r = sp_mul_p(x, y); break;   // secp256k1 base field (unit-test hooks of csrc/secp256k1.hpp): a * b mod P, residues in and out
     case 17: r = sp_sqr_p(x); break;
+    case 18: r = ecc_fq_mul_hook(x, y); break;  // BN254 base field (unit-test hook of csrc/bn254_fq.hpp)
     default: r = fr_zero();
     }
     for (int k = 0; k < 4; k++) out[4 * i + k] = (u64)r.v[2 * k] | ((u64)r.v[2 * k + 1] << 32);
@@ -2752,7 +2753,12 @@ extern "C" int zk_fr_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* 
         db = (const u64*)tb;
         dout = (u64*)to;
     }
-    hipLaunchKernelGGL(fr_op_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, t_stream, op, da, db, dout, n);
+    if (op == 19) {  // Fq12 products: 12 elements each (k_ecc.hip)
+        ARG_TRY(n % 12 == 0, "zk_fr_op 19: n must be a multiple of 12");
+        zk_launch_fq12_mul(t_stream, da, db, dout, n / 12);
+    } else {
+        hipLaunchKernelGGL(fr_op_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, t_stream, op, da, db, dout, n);
+    }
     HIP_TRY(hipGetLastError());
     if (!dev) {
         HIP_TRY(hipMemcpyAsync(out, to, n * 32, hipMemcpyDeviceToHost, t_stream));
@@ -3198,4 +3204,89 @@ extern "C" int zk_block_verify(const zk_block* b, uint32_t opts, zk_result* resu
     for (int c = 0; c < 4; c++)
         if (sh.rc[c]) { g_err = sh.err[c]; return sh.rc[c]; }
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------
+// ECC circuit (include/zkevm_hip.h "ECC circuit"): one-shot, host buffers staged through one device allocation
+// ---------------------------------------------------------------------------------------
+namespace {
+struct EccStage {
+    void* base = nullptr;
+    ~EccStage() { if (base) (void)hipFree(base); }
+};
+}  // namespace
+static int ecc_run(const zk_ecc_ops* ops, const uint64_t* rows, bool assign, uint64_t* rows_out, uint32_t* status_out,
+                   zk_result* result, const char* name) {
+    ARG_TRY(t_device >= 0, "zk_ecc: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    EccArgs a;
+    const char* err = ecc_args_from_ops(ops, a);
+    if (err) {
+        g_err = std::string(name) + ": " + err;
+        return -1;
+    }
+    const u64 np = a.n_add + a.n_mul, n = np + a.n_pairing;
+    const u64 n_pp = a.n_pairing ? ops->pair_off[a.n_pairing] : 0;
+    // one allocation: points | pair_pts | pair_out | pair_off | rows | status | tally (each part 256-byte aligned)
+    auto al = [](u64 b) { return (b + 255) & ~255ull; };
+    const u64 b_pts = np * 192, b_pp = n_pp * 192, b_out = a.n_pairing * 32, b_off = (a.n_pairing + 1) * 4, b_rows = n * ECC_NCELLS * 32,
+              b_st = n * 4;
+    const u64 o_pp = al(b_pts), o_out = o_pp + al(b_pp), o_off = o_out + al(b_out), o_rows = o_off + al(b_off), o_st = o_rows + al(b_rows),
+              o_tally = o_st + al(b_st), total = o_tally + 256;
+    EccStage stg;
+    HIP_TRY(hipMalloc(&stg.base, total));
+    char* d = (char*)stg.base;
+    hipStream_t st = t_stream;
+    if (b_pts) HIP_TRY(hipMemcpyAsync(d, a.pts, b_pts, hipMemcpyHostToDevice, st));
+    if (b_pp) HIP_TRY(hipMemcpyAsync(d + o_pp, a.pair_pts, b_pp, hipMemcpyHostToDevice, st));
+    if (b_out) HIP_TRY(hipMemcpyAsync(d + o_out, a.pair_out, b_out, hipMemcpyHostToDevice, st));
+    if (a.n_pairing) HIP_TRY(hipMemcpyAsync(d + o_off, a.pair_off, b_off, hipMemcpyHostToDevice, st));
+    if (!assign) HIP_TRY(hipMemcpyAsync(d + o_rows, rows, b_rows, hipMemcpyHostToDevice, st));
+    ZkTally t0 = {0ull, ~0ull};
+    HIP_TRY(hipMemcpyAsync(d + o_tally, &t0, sizeof t0, hipMemcpyHostToDevice, st));
+    a.pts = (const u64*)d;
+    a.pair_pts = (const u64*)(d + o_pp);
+    a.pair_out = (const u64*)(d + o_out);
+    a.pair_off = (const u32*)(d + o_off);
+    a.rows = (const u64*)(d + o_rows);
+    a.rows_out = (u64*)(d + o_rows);
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0));
+    HIP_TRY(hipEventCreate(&e1));
+    (void)hipEventRecord(e0, st);
+    zk_launch_ecc(st, a, assign, assign ? nullptr : (u32*)(d + o_st), (ZkTally*)(d + o_tally));
+    const hipError_t le = hipGetLastError();
+    (void)hipEventRecord(e1, st);
+    ZkTally t1 = t0;
+    if (assign) HIP_TRY(hipMemcpyAsync(rows_out, d + o_rows, b_rows, hipMemcpyDeviceToHost, st));
+    else {
+        if (status_out) HIP_TRY(hipMemcpyAsync(status_out, d + o_st, b_st, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&t1, d + o_tally, sizeof t1, hipMemcpyDeviceToHost, st));
+    }
+    const hipError_t se = hipStreamSynchronize(st);
+    float ms = 0.f;
+    if (se == hipSuccess && le == hipSuccess) (void)hipEventElapsedTime(&ms, e0, e1);
+    (void)hipEventDestroy(e0);
+    (void)hipEventDestroy(e1);
+    HIP_TRY(le);
+    HIP_TRY(se);
+    if (result) {
+        result->fail_count = t1.fail_count;
+        result->first_fail_row = t1.first_fail == ~0ull ? UINT64_MAX : (t1.first_fail >> 32);
+        result->first_fail_code = t1.first_fail == ~0ull ? 0u : (u32)t1.first_fail;
+        result->launches = 1;
+        result->rows_evaluated = n;
+        result->kernel_ms = ms;
+    }
+    return 0;
+}
+extern "C" int zk_ecc_assign(const zk_ecc_ops* ops, uint32_t opts, uint64_t* rows_out) {
+    ARG_TRY(!(opts & ZK_OPT_DEVICE_PTRS), "zk_ecc_assign: ZK_OPT_DEVICE_PTRS is not supported (the ops are read on the host)");
+    ARG_TRY(rows_out, "zk_ecc_assign: rows_out is null");
+    return ecc_run(ops, nullptr, true, rows_out, nullptr, nullptr, "zk_ecc_assign");
+}
+extern "C" int zk_ecc_verify(const zk_ecc_ops* ops, const uint64_t* rows, uint32_t opts, uint32_t* status_out, zk_result* result) {
+    ARG_TRY(!(opts & ZK_OPT_DEVICE_PTRS), "zk_ecc_verify: ZK_OPT_DEVICE_PTRS is not supported (the ops are read on the host)");
+    ARG_TRY(rows && result, "zk_ecc_verify: rows / result is null");
+    return ecc_run(ops, rows, false, nullptr, status_out, result, "zk_ecc_verify");
 }

@@ -676,3 +676,33 @@ def flatten_pi_gas_table(table):
     """set of TxCallDataGasCostAccRow (pi_circuit.py:64-68) -> uint64[m, 3, 4]"""
     rows = sorted(set((_n(g.tx_id), _n(g.is_final), _n(g.gas_cost_acc)) for g in table))
     return rows_to_rowmajor([list(r) for r in rows], 3)
+
+
+def _word_limbs(v):
+    """a 256-bit word -> 4 x u64 little-endian (Word(v) of the reference: asserts v < 2^256)"""
+    v = int(v.n if hasattr(v, "n") else v)
+    assert 0 <= v < 1 << 256, f"Word expects a 256-bit value, got {v}"
+    return [(v >> (64 * k)) & 0xFFFFFFFFFFFFFFFF for k in range(4)]
+
+
+def flatten_ecc_ops(add_ops, mul_ops, pairing_ops, max_add_ops=1, max_mul_ops=1, max_pairing_ops=1):
+    """The ECC circuit's ops (ecc_circuit.py:336-383: EcAdd(p, q, out), EcMul(p, s, out), EcPairing(g1_pts, g2_pts, out), or
+    tuples in that field order) -> the zk_ecc_ops arrays (include/zkevm_hip.h): points uint64[n_add + n_mul, 6, 4], pair_pts
+    uint64[m, 6, 4] (EIP-197 order, as g2_pts holds it), pair_off uint32[n_pairing + 1], pair_out uint64[n_pairing, 4], and the
+    max_*_ops clamped to 0 / 1 (verify's counters are locals that reach 1 at most)."""
+    pts = [[_word_limbs(x) for x in (op[0][0], op[0][1], op[1][0], op[1][1], op[2][0], op[2][1])] for op in add_ops]
+    pts += [[_word_limbs(x) for x in (op[0][0], op[0][1], op[1], 0, op[2][0], op[2][1])] for op in mul_ops]
+    pair_pts, off, outs = [], [0], []
+    for g1s, g2s, out in pairing_ops:
+        for g1, g2 in zip(g1s, g2s):  # zip: as the reference's circuit2rows pairs them
+            pair_pts.append([_word_limbs(x) for x in (g1[0], g1[1], g2[0], g2[1], g2[2], g2[3])])
+        off.append(len(pair_pts))
+        outs.append(_word_limbs(out))
+    return {
+        "points": np.array(pts, dtype=np.uint64).reshape(len(pts), 6, 4),
+        "n_add": len(add_ops), "n_mul": len(mul_ops),
+        "pair_pts": np.array(pair_pts, dtype=np.uint64).reshape(len(pair_pts), 6, 4),
+        "pair_off": np.array(off, dtype=np.uint32),
+        "pair_out": np.array(outs, dtype=np.uint64).reshape(len(outs), 4),
+        "max_ok": np.array([int(m >= 1) for m in (max_add_ops, max_mul_ops, max_pairing_ops)], dtype=np.uint32),
+    }

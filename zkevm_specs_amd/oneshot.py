@@ -262,3 +262,47 @@ def pi_copy_verify(cells, data, lens, device=None):
     check(lib.zk_pi_copy_verify(_p(cells), _p(data), _p(lens), n, 0, _p(status), ctypes.byref(r)), "zk_pi_copy_verify")
     return Result(r), status
 
+
+
+def _ecc_ops(w, randomness):
+    """the zk_ecc_ops block over the arrays of flatten.flatten_ecc_ops (kept alive by the caller)"""
+    from ._lib import ZkEccOps
+
+    pts, pair_pts, pair_off, pair_out = w["points"], w["pair_pts"], w["pair_off"], w["pair_out"]
+    _expect(pts, "ecc points", 8, (None, 6, 4))
+    _expect(pair_pts, "ecc pair_pts", 8, (None, 6, 4))
+    _expect(pair_out, "ecc pair_out", 8, (None, 4))
+    _expect(pair_off, "ecc pair_off", 4, (pair_out.shape[0] + 1,))
+    n_add, n_mul = int(w["n_add"]), int(w["n_mul"])
+    if n_add + n_mul != pts.shape[0]:
+        raise ValueError("ecc points: n_add + n_mul != rows of points")
+    max_ok = w["max_ok"]
+    return ZkEccOps(_p(pts, pts.shape[0]), n_add, n_mul, _p(pair_pts, pair_pts.shape[0]), _p(pair_off), _p(pair_out, pair_out.shape[0]),
+                    int(pair_out.shape[0]), _p(randomness), int(max_ok[0]), int(max_ok[1]), int(max_ok[2]))
+
+
+def ecc_assign(w, randomness, device=None):
+    """zk_ecc_assign over flatten_ecc_ops output -> EccTableRow wire rows uint64[n, 13, 4] (circuit2rows order)"""
+    lib = _lib.init(device)
+    w = {k: (_c(v) if isinstance(v, np.ndarray) else v) for k, v in w.items()}
+    rc = _c(_randomness_cells(randomness, None))
+    ops = _ecc_ops(w, rc)
+    n = int(w["points"].shape[0] + w["pair_out"].shape[0])
+    rows = np.zeros((n, 13, 4), dtype=np.uint64)
+    if n:
+        check(lib.zk_ecc_assign(ctypes.byref(ops), 0, _p(rows)), "zk_ecc_assign", lib)
+    return rows
+
+
+def ecc_verify(w, rows, randomness, device=None):
+    """zk_ecc_verify: the rows against the ops' chips -> (Result, status uint32[n])"""
+    lib = _lib.init(device)
+    w = {k: (_c(v) if isinstance(v, np.ndarray) else v) for k, v in w.items()}
+    rows = _c(rows)
+    rc = _c(_randomness_cells(randomness, None))
+    ops = _ecc_ops(w, rc)
+    _expect(rows, "ecc rows", 8, (int(w["points"].shape[0] + w["pair_out"].shape[0]), 13, 4))
+    n = int(rows.shape[0])
+    status, r = np.zeros(n, dtype=np.uint32), ZkResult()
+    check(lib.zk_ecc_verify(ctypes.byref(ops), _p(rows), 0, _p(status), ctypes.byref(r)), "zk_ecc_verify", lib)
+    return Result(r), status
