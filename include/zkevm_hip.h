@@ -94,6 +94,13 @@ const char* zk_last_error(void);
  * 18: the BN254 BASE-field product a * b mod p (p = 2188...8583, residues in and out; unit-test hook of csrc/bn254_fq.hpp);
  * 19: the Fq12 product a * b, n a multiple of 12, every 12 consecutive elements one Fq12 in tower order (c0.c0.c0, c0.c0.c1,
  * c0.c1.c0, ..., c1.c2.c1: Fq12 = Fq6 + Fq6 w, Fq6 = Fq2 + Fq2 v + Fq2 v^2, Fq2 = Fq + Fq u; residues in and out).
+ * 20..25: per 12 elements of a, as 19 (b is not read but must not be null): 20 a^2, 21 a^-1 (0 -> 0), 22 a^p (Frobenius),
+ * 23 the final exponentiation of the pairing, f^((p^12 - 1) / r * m) with the fixed m = 2x(6x^2 + 3x + 1) of its hard part;
+ * 24 the pairing of one pair, final_exp(miller_loop(P, Q)): a holds the six words of a zk_ecc_ops pairing point (EIP-197 order
+ * p.x, p.y, x.c1, x.c0, y.c1, y.c0, reduced mod p), then zeros; a pair with a point at infinity gives 1.  Neither point is checked;
+ * 25 the G2 scalar chain of the ECC circuit (py_ecc's multiply over Fq2, exact also off the twist): a = Q (x.c1, x.c0, y.c1, y.c0,
+ * reduced mod p, all zero = None), then the scalar as a 256-bit integer, then zeros; out = affine x.c0, x.c1, y.c0, y.c1, then
+ * 1 if the result is None (its coordinates 0) else 0, then zeros.
  * (reference: FQ.__add__/__sub__/__mul__/__neg__/__truediv__ via py_ecc and FQ.inv, util/arithmetic.py:41-60) */
 int zk_fr_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t n, uint32_t opts);
 

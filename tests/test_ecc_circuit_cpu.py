@@ -4,7 +4,7 @@ import numpy as np
 import pytest
 
 from tests import bn254_ref as b
-from tests.ecc_cases import golden_cases, random_point_ops, rng, rows_to_ints
+from tests.ecc_cases import fq12_tower_mul, golden_cases, random_point_ops, rng, rows_to_ints
 from zkevm_specs_amd import oneshot
 from zkevm_specs_amd.flatten import flatten_ecc_ops
 
@@ -116,23 +116,3 @@ def test_fr_op_fq_and_fq12_cpu():
     got = [sum(int(x[k]) << (64 * k) for k in range(4)) for x in out]
     assert got == fq12_tower_mul(a[:12], c[:12]) + fq12_tower_mul(a[12:], c[12:])
 
-
-def fq12_tower_mul(x, y):
-    """Fq12 = Fq6[w]/(w^2 - v), Fq6 = Fq2[v]/(v^3 - (9 + u)) by schoolbook over Fq2 on the w-power basis: tower order
-    (c0.c0, c0.c1, c0.c2, c1.c0, c1.c1, c1.c2) holds the coefficients of w^0, w^2, w^4, w^1, w^3, w^5, and w^6 = 9 + u"""
-    F2 = b.Fq2
-    pos = [0, 2, 4, 1, 3, 5]
-    cx, cy = [None] * 6, [None] * 6
-    for k in range(6):
-        cx[pos[k]] = (x[2 * k], x[2 * k + 1])
-        cy[pos[k]] = (y[2 * k], y[2 * k + 1])
-    t = [(0, 0)] * 11
-    for i in range(6):
-        for j in range(6):
-            t[i + j] = F2.add(t[i + j], F2.mul(cx[i], cy[j]))
-    for k in range(10, 5, -1):
-        t[k - 6] = F2.add(t[k - 6], F2.mul(t[k], (9, 1)))
-    out = []
-    for k in range(6):
-        out += list(t[pos[k]])
-    return out

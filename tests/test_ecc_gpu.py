@@ -4,8 +4,7 @@ import numpy as np
 import pytest
 
 from tests import bn254_ref as b
-from tests.ecc_cases import golden_cases, ops_from_table_rows, random_point_ops, rng, rows_to_ints
-from tests.test_ecc_circuit_cpu import fq12_tower_mul
+from tests.ecc_cases import fq12_tower_mul, golden_cases, ops_from_table_rows, random_point_ops, rng, rows_to_ints
 from zkevm_specs_amd import oneshot
 from zkevm_specs_amd.flatten import flatten_ecc_ops
 
@@ -24,7 +23,7 @@ def test_golden_cases_hip():
         if fails:
             assert (res.first_fail_row, res.first_fail_code) == (fails[0], status[fails[0]]), m["name"]
         n += 1
-    assert n >= 60
+    assert n >= 75
 
 
 def test_bench_size_tampered_hip_vs_cpu():

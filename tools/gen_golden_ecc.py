@@ -24,6 +24,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from tests import bn254_ref as b  # noqa: E402
+from tests.ecc_cases import fq2_sqrt, g2_words, order3_point, rng, zero_y_chain_point  # noqa: E402
+from tests.ecc_kat import chain_scalars  # noqa: E402
 from zkevm_specs_amd.flatten import flatten_ecc_ops  # noqa: E402
 
 RANDOMNESS = 0x2F1E0D0C0B0A09080706050403020100F0E0D0C0B0A090807060504030201  # < r
@@ -143,27 +145,120 @@ def non_subgroup_g2():
     raise AssertionError("no non-subgroup twist point found")
 
 
-def fq2_sqrt(a):
-    # p = 3 mod 4: Algorithm 9 of Adj and Rodriguez-Henriquez, "Square root computation over even extension fields"
-    F = b.Fq2
+def _right_and_wrong(pt, scalars, g):
+    """mul ops of pt: each scalar with the model's result and with a wrong one (is_valid tampered to 1: off-curve rows pass iff the
+    chain lands on out)"""
+    ops = []
+    for s in scalars:
+        r = b.multiply(b._g1(pt[0] % P, pt[1] % P), s % P, b.Fq)
+        r = (0, 0) if r is None else r
+        ops.append((pt, s, r))
+        ops.append((pt, s, ((r[0] + 1) % P, r[1]) if g.random() < 0.5 else (r[0], (r[1] + 7) % P)))
+    return ops
 
-    def pw(x, e):
-        acc = (1, 0)
-        while e:
-            if e & 1:
-                acc = F.mul(acc, x)
-            x = F.mul(x, x)
-            e >>= 1
-        return acc
 
-    a1 = pw(a, (P - 3) // 4)
-    alpha = F.mul(a1, F.mul(a1, a))
-    x0 = F.mul(a1, a)
-    if alpha == (P - 1, 0):
-        x = F.mul((0, 1), x0)
-    else:
-        x = F.mul(pw(F.add((1, 0), alpha), (P - 1) // 2), x0)
-    return x if F.mul(x, x) == a else None
+def chain_cases():
+    """off-curve chains that leave the group law: G1 (x, 0) and (0, y) as mul and add rows; (x, 0), (0, y) and depth-1 twist-field
+    points as P or Q of pairing ops (PAIR_SUBGROUP or PAIR_ON_CURVE by the model).  (A G1 chain can meet y = 0 only at its first
+    point: see zero_y_chain_point.)"""
+    F, F2 = b.Fq, b.Fq2
+    g = rng(44)
+    out = []
+    for name, pt in (("x0", (g.randrange(1, P), 0)), ("x0b", (g.randrange(1, P), 0)), ("order3", order3_point(F, g)),
+                     ("order3b", order3_point(F, g))):
+        muls = _right_and_wrong(pt, chain_scalars(0, g), g)
+        out.append(case(f"chain_g1_{name}_mul", [], muls, [], tamper=[(i, 12, 1) for i in range(len(muls))]))
+        out.append(case(f"chain_g1_{name}_mul_assigned", [], muls[:16], []))
+    y = order3_point(F, g)
+    y2 = b.double(y, F)
+    adds = [(y, y, y2), (y, b.neg(y, F), (0, 0)), (y, y2, (0, 0)), (y2, y, (1, 1)), (y, (0, 0), y), (y, y, (0, 0))]
+    out.append(case("chain_g1_order3_add", adds, [], [], tamper=[(i, 12, 1) for i in range(len(adds))]))
+    q1 = g2_words(b.G2)
+    qs = [g2_words(((g.randrange(P), g.randrange(P)), (0, 0))), g2_words(order3_point(F2, g)), g2_words(zero_y_chain_point(F2, 1, g)),
+          g2_words(zero_y_chain_point(F2, 1, g))]
+    ps = [(g.randrange(1, P), 0), order3_point(F, g), (2, 3)]
+    # order r off the curve / twist: [r] of the chain is None, so these pass the subgroup check and fail the on-curve check
+    ops = [([b.G1], [g2_words(((1, 0), (2, 0)))], 0), ([iso_image(b.G1, F, g)], [q1], 1), ([b.G1], [g2_words(iso_image(b.G2, F2, g))], 0),
+           ([b.G1, iso_image(b.multiply(b.G1, 5, F), F, g)], [q1, q1], 1)]
+    ops += [([b.G1], [q], g.choice([0, 1])) for q in qs] + [([p], [q1], 0) for p in ps]
+    ops += [([b.G1, p], [q1, q], 1) for p, q in zip(ps, qs)] + [([b.G1, ps[0]], [q1, (0, 0, 0, 0)], 1), ([(0, 0)], [qs[2]], 1)]
+    out.append(case("chain_pairing_offcurve", [], [], ops))
+    return out
+
+
+def iso_image(pt, F, g):
+    """(c^2 x, c^3 y) for a random c: on y^2 = x^3 + c^6 b, off the curve of pt, of pt's order"""
+    c = (g.randrange(2, P), g.randrange(P)) if F is b.Fq2 else g.randrange(2, P)
+    c2 = F.mul(c, c)
+    return (F.mul(c2, pt[0]), F.mul(F.mul(c2, c), pt[1]))
+
+
+def pairing_volume_cases():
+    """160 pairing ops with 0..4 pairs, the count changing between neighbouring lanes: true products (sum a_i b_i = 0 mod r), the same
+    off by one, infinity in either slot, off-curve points"""
+    F, F2 = b.Fq, b.Fq2
+    g = rng(45)
+    pool_a = [g.randrange(1, b.R) for _ in range(6)]
+    pool_b = [g.randrange(1, b.R) for _ in range(6)]
+    ga = {a: b.multiply(b.G1, a, F) for a in pool_a}
+    gb = {c: b.multiply(b.G2, c, F2) for c in pool_b}
+    odd = [g2_words(((g.randrange(P), g.randrange(P)), (0, 0))), g2_words(zero_y_chain_point(F2, 1, g)), g2_words(iso_image(b.G2, F2, g))]
+    ops = []
+    for k in range(160):
+        n = (0, 3, 1, 4, 2)[k % 5]
+        kind = k % 4
+        if n == 0:
+            ops.append(([], [], k & 1))
+            continue
+        a = [g.choice(pool_a) for _ in range(n)]
+        c = [g.choice(pool_b) for _ in range(n - 1)]
+        s = sum(x * y for x, y in zip(a, c)) % b.R
+        last = (-s * pow(a[-1], -1, b.R)) % b.R if kind != 1 else (-s * pow(a[-1], -1, b.R) + 1) % b.R
+        g1s = [ga[x] for x in a]
+        g2s = [g2_words(gb[y]) for y in c] + [g2_words(b.multiply(b.G2, last, F2))]
+        if kind == 2:  # infinity in either slot of one pair
+            i = g.randrange(n)
+            if g.random() < 0.5:
+                g1s[i] = (0, 0)
+            else:
+                g2s[i] = (0, 0, 0, 0)
+        if kind == 3 and k % 8 == 3:
+            g2s[g.randrange(n)] = g.choice(odd)
+        if kind == 3 and k % 8 == 7:
+            g1s[g.randrange(n)] = g.choice([(g.randrange(1, P), 0), order3_point(F, g), iso_image(b.G1, F, g)])
+        ops.append((g1s, g2s, g.choice([0, 1]) if kind == 2 else int(kind != 1)))
+    return [case("pairing_volume", [], [], ops)]
+
+
+def mixed_wave_cases():
+    """229 add / mul rows (not a multiple of 64), the muls shuffled so that every wave mixes Jacobian-only lanes, replay lanes ((x, 0): the
+    y = 0 step at j = 0), order-3 chains, infinity and failing lanes; some outputs are words >= 5p"""
+    F = b.Fq
+    g = rng(46)
+    adds, muls = [], []
+    for _ in range(24):
+        p = b.multiply(b.G1, g.randrange(1, 1 << 20), F)
+        adds.append((p, b.G1, b.add(p, b.G1, F) if g.random() < 0.8 else (1, 2)))
+    for _ in range(205):
+        t = g.random()
+        if t < 0.3:
+            p, s = b.multiply(b.G1, g.randrange(1, 1 << 16), F), g.randrange(1 << 256)
+        elif t < 0.55:
+            p, s = (g.randrange(1, P), 0), g.choice([g.randrange(64), g.randrange(1 << 256), b.R, P - 1])
+        elif t < 0.7:
+            p, s = order3_point(F, g), g.choice([g.randrange(64), g.randrange(1 << 256)])
+        elif t < 0.85:
+            p, s = g.choice([((0, 0), g.randrange(1 << 256)), (b.G1, 0), (b.G1, b.R)])
+        else:
+            p, s = (g.randrange(P), g.randrange(P)), g.randrange(1 << 256)
+        r = b.multiply(b._g1(p[0] % P, p[1] % P), s % P, F)
+        r = (0, 0) if r is None else r
+        if g.random() < 0.2 and max(r) < (1 << 256) - 5 * P:  # the same residues as words in [5p, 2^256): fq_reduce's fifth step
+            r = (r[0] + 5 * P, r[1] + 5 * P)
+        muls.append((p, s, r if g.random() < 0.75 else ((r[0] + 1) % P, r[1])))
+    g.shuffle(muls)
+    tamper = [(i, 12, 1) for i in range(24, 229) if g.random() < 0.5]
+    return [case("mixed_wave_229", adds, muls, [], tamper=tamper)]
 
 
 def main():
@@ -171,7 +266,7 @@ def main():
     ap.add_argument("--ref-root", default=os.path.join(ROOT, "oracle", "_ref"), help="the reference checkout (build() stages one here)")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden", "ecc_cases.npz"))
     args = ap.parse_args()
-    cases = reference_cases(args.ref_root) + trap_cases()
+    cases = reference_cases(args.ref_root) + trap_cases() + chain_cases() + pairing_volume_cases() + mixed_wave_cases()
     arrays, metas = {}, []
     for i, (meta, w) in enumerate(cases):
         metas.append(meta)

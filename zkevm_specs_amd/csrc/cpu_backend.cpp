@@ -303,6 +303,7 @@ static int one_shot(zk_session* s, uint32_t* status_out, zk_result* result) {
 extern "C" int zk_fr_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t n, uint32_t opts) {
     NO_DEVICE_PTRS(opts, "zk_fr_op");
     ARG_TRY(a && b && out, "zk_fr_op: null pointer");
+    ARG_TRY(op < 19 || op > 25 || n % 12 == 0, "zk_fr_op 19..25: n must be a multiple of 12");
 #pragma omp parallel for
     for (long long i = 0; i < (long long)n; i++) {
         const Fr x = fr_load(a + 4 * i), y = fr_load(b + 4 * i);
@@ -316,7 +317,9 @@ extern "C" int zk_fr_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* 
         case 5: r = fr_inv(x); break;
         case 6: r = fr_div(x, y); break;
         case 18: r = ecc_fq_mul_hook(x, y); break;
-        case 19: if (i % 12 == 0 && i + 12 <= (long long)n) ecc_fq12_mul_hook(a + 4 * i, b + 4 * i, out + 4 * i); continue;
+        case 19: case 20: case 21: case 22: case 23: case 24: case 25:
+            if (i % 12 == 0 && i + 12 <= (long long)n) ecc_fq12_op_hook(op, a + 4 * i, b + 4 * i, out + 4 * i);
+            continue;
         default: r = fr_zero();
         }
         for (int k = 0; k < 4; k++) out[4 * i + k] = (u64)r.v[2 * k] | ((u64)r.v[2 * k + 1] << 32);

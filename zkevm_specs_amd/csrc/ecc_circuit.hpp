@@ -301,7 +301,8 @@ ZK_HD u32 ecc_verify_row(const EccArgs& a, u64 i) {
     return i < a.n_add + a.n_mul ? ecc_verify_point_row(a, i) : ecc_verify_pairing_row(a, i);
 }
 
-// zk_fr_op known-answer hooks (ops 18 / 19): Fq product and Fq12 product of residues (words are reduced first)
+// zk_fr_op known-answer hooks (ops 18 .. 25): Fq product, Fq12 operations of residues (words are reduced first), the pairing of one
+// pair and the G2 scalar chain
 ZK_HD Fr ecc_fq_mul_hook(const Fr& x, const Fr& y) {
     using namespace bn;
     Fq a, b;
@@ -323,13 +324,67 @@ ZK_HD bn::Fq12 ecc_fq12_load(const u64* p) {
     r.c1 = fq6_make(fq2_make(c[6], c[7]), fq2_make(c[8], c[9]), fq2_make(c[10], c[11]));
     return r;
 }
-ZK_HD void ecc_fq12_mul_hook(const u64* a, const u64* b, u64* out) {
+ZK_HD void ecc_fq12_store(const bn::Fq12& r, u64* out) {
     using namespace bn;
-    const Fq12 r = fq12_mul(ecc_fq12_load(a), ecc_fq12_load(b));
     const Fq2* c = &r.c0.c0;  // the six Fq2 coefficients are contiguous in tower order
     for (int e = 0; e < 6; e++) {
         fq_store_raw(fq_from_mont(c[e].c0), out + 8 * e);
         fq_store_raw(fq_from_mont(c[e].c1), out + 8 * e + 4);
+    }
+}
+ZK_HD void ecc_fq12_mul_hook(const u64* a, const u64* b, u64* out) { ecc_fq12_store(bn::fq12_mul(ecc_fq12_load(a), ecc_fq12_load(b)), out); }
+// zk_fr_op 25: the G2 scalar chain of the circuit (mul_by_r_is_inf / mul_equals over Fq2) on Q = words 0..3 (EIP-197 order x.c1,
+// x.c0, y.c1, y.c0; reduced mod p, all zero = None) and the 256-bit scalar word 4 (as it is).  Out: affine x.c0, x.c1, y.c0, y.c1
+// and an infinity flag (coordinates 0 for None), words 5..11 zero.
+ZK_HD void ecc_g2_chain_hook(const u64* a, u64* out) {
+    using namespace bn;
+    Aff<Fq2> q;
+    q.x = fq2_make(fq_word_mont(a + 4), fq_word_mont(a));
+    q.y = fq2_make(fq_word_mont(a + 12), fq_word_mont(a + 8));
+    q.inf = f_is_zero(q.x) && f_is_zero(q.y);
+    const Fq n = fq_raw_word(a + 16);
+    int j;
+    const Jac<Fq2> r = jac_mul_checked(q, n, &j);
+    Aff<Fq2> o;
+    if (j >= 0) {
+        o = aff_mul_slow(q, n, j);
+    } else {
+        o.inf = jac_is_inf(r);
+        const Fq2 zi = f_inv(r.Z), zi2 = f_sqr(zi);  // (0 for None)
+        o.x = f_mul(r.X, zi2);
+        o.y = f_mul(r.Y, f_mul(zi2, zi));
+    }
+    if (o.inf) {
+        f_zero(o.x);
+        f_zero(o.y);
+    }
+    for (int e = 0; e < 12; e++) fq_store_raw(fq_zero(), out + 4 * e);
+    fq_store_raw(fq_from_mont(o.x.c0), out);
+    fq_store_raw(fq_from_mont(o.x.c1), out + 4);
+    fq_store_raw(fq_from_mont(o.y.c0), out + 8);
+    fq_store_raw(fq_from_mont(o.y.c1), out + 12);
+    out[16] = o.inf ? 1 : 0;
+}
+// zk_fr_op 19..25 on one lane's 12 words (see include/zkevm_hip.h): the functions the circuit's kernels run
+ZK_HD void ecc_fq12_op_hook(int op, const u64* a, const u64* b, u64* out) {
+    using namespace bn;
+    switch (op) {
+    case 19: ecc_fq12_mul_hook(a, b, out); return;
+    case 20: ecc_fq12_store(fq12_sqr(ecc_fq12_load(a)), out); return;
+    case 21: ecc_fq12_store(fq12_inv(ecc_fq12_load(a)), out); return;
+    case 22: ecc_fq12_store(fq12_frob(ecc_fq12_load(a)), out); return;
+    case 23: ecc_fq12_store(final_exp(ecc_fq12_load(a)), out); return;
+    case 24: {  // one pair, words in the wire's EIP-197 order (p.x, p.y, x.c1, x.c0, y.c1, y.c0), as the verifier reads them
+        Fq c[6];
+        ecc_pair_words(a, c);
+        for (int e = 0; e < 6; e++) c[e] = fq_reduce(c[e]);
+        Aff<Fq> p;
+        Aff<Fq2> q;
+        ecc_pair_points(c, p, q);
+        ecc_fq12_store(final_exp(p.inf || q.inf ? fq12_one() : miller_loop(p.x, p.y, q.x, q.y)), out);
+        return;
+    }
+    case 25: ecc_g2_chain_hook(a, out); return;
     }
 }
 

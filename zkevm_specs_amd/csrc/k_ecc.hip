@@ -26,10 +26,10 @@ __global__ __launch_bounds__(64) void ecc_pairing_rows_kernel(EccArgs a, u32 ass
     }
     if (!assign) tally_commit(tally, i, code);
 }
-// zk_fr_op 19: one Fq12 product per lane (12 elements each)
-__global__ __launch_bounds__(64) void ecc_fq12_mul_kernel(const u64* x, const u64* y, u64* out, u64 n12) {
+// zk_fr_op 19..25: one Fq12 operation (or one pairing, one G2 chain) per lane, 12 elements each
+__global__ __launch_bounds__(64) void ecc_fq12_op_kernel(int op, const u64* x, const u64* y, u64* out, u64 n12) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n12) ecc_fq12_mul_hook(x + 48 * i, y + 48 * i, out + 48 * i);
+    if (i < n12) ecc_fq12_op_hook(op, x + 48 * i, y + 48 * i, out + 48 * i);
 }
 
 void zk_launch_ecc(hipStream_t st, const EccArgs& a, bool assign, u32* status, ZkTally* tally) {
@@ -38,6 +38,6 @@ void zk_launch_ecc(hipStream_t st, const EccArgs& a, bool assign, u32* status, Z
     if (a.n_pairing)
         hipLaunchKernelGGL(ecc_pairing_rows_kernel, dim3((u32)((a.n_pairing + 63) / 64)), dim3(64), 0, st, a, (u32)assign, status, tally);
 }
-void zk_launch_fq12_mul(hipStream_t st, const u64* x, const u64* y, u64* out, u64 n12) {
-    hipLaunchKernelGGL(ecc_fq12_mul_kernel, dim3((u32)((n12 + 63) / 64)), dim3(64), 0, st, x, y, out, n12);
+void zk_launch_fq12_op(hipStream_t st, int op, const u64* x, const u64* y, u64* out, u64 n12) {
+    hipLaunchKernelGGL(ecc_fq12_op_kernel, dim3((u32)((n12 + 63) / 64)), dim3(64), 0, st, op, x, y, out, n12);
 }

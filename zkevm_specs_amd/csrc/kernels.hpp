@@ -77,4 +77,4 @@ void zk_launch_ecdsa(hipStream_t st, const EcdsaArgs& a, u32* status, ZkTally* t
 void zk_launch_ecdsa_comb_build(hipStream_t st, u32* table);  // the device's 8-bit fixed-base table of G (522 KB), built once
 // ECC circuit (k_ecc.hip): assign = circuit2rows into a.rows_out, else verify a.rows (status / tally)
 void zk_launch_ecc(hipStream_t st, const EccArgs& a, bool assign, u32* status, ZkTally* tally);
-void zk_launch_fq12_mul(hipStream_t st, const u64* x, const u64* y, u64* out, u64 n12);  // zk_fr_op 19
+void zk_launch_fq12_op(hipStream_t st, int op, const u64* x, const u64* y, u64* out, u64 n12);  // zk_fr_op 19..25

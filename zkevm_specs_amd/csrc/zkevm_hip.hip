@@ -2753,9 +2753,9 @@ extern "C" int zk_fr_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* 
         db = (const u64*)tb;
         dout = (u64*)to;
     }
-    if (op == 19) {  // Fq12 products: 12 elements each (k_ecc.hip)
-        ARG_TRY(n % 12 == 0, "zk_fr_op 19: n must be a multiple of 12");
-        zk_launch_fq12_mul(t_stream, da, db, dout, n / 12);
+    if (op >= 19 && op <= 25) {  // Fq12 operations, pairing, G2 chain: 12 elements each (k_ecc.hip)
+        ARG_TRY(n % 12 == 0, "zk_fr_op 19..25: n must be a multiple of 12");
+        zk_launch_fq12_op(t_stream, op, da, db, dout, n / 12);
     } else {
         hipLaunchKernelGGL(fr_op_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, t_stream, op, da, db, dout, n);
     }
