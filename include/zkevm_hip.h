@@ -118,7 +118,9 @@ int zk_state_set_range(zk_session* s, uint64_t row_lo, uint64_t row_hi);
 /* The same for every row-circuit session (State, Bytecode, Copy, Exp, Tx / Sig units, PI): a rank of a row-sharded
  * run opens its session over rows [lo, hi + halo) of the global witness (halo = the rows after the range that the
  * range's last rows read: State 1 before + 1 after, Bytecode / Exp / PI 1 after, Copy 2 after, Tx / Sig none;
- * SURVEY.md §8e) and evaluates [0, hi - lo) (State: [1, 1 + hi - lo)).  zk_result.rows_evaluated reports the range.
+ * SURVEY.md §8e) and evaluates [0, hi - lo) (State: [1, 1 + hi - lo)).  Withdrawal: 1 before + 1 after without wrap-around — a
+ * rank opens over rows [max(lo - 1, 0), min(hi + 1, len(rows))) with row_base = max(lo - 1, 0) and evaluates the held rows of
+ * [lo, hi) (a held row whose neighbour is missing reports ZK_UNSUPPORTED).  zk_result.rows_evaluated reports the range.
  * EVM sessions shard by the step rows they are opened over (pairs [lo, hi) need steps [lo, hi]). */
 int zk_set_range(zk_session* s, uint64_t row_lo, uint64_t row_hi);
 /* One-shot convenience: open + launch + collect (+ copy per-row status to host) + close. */
@@ -557,6 +559,33 @@ typedef struct zk_ecc_ops {
 } zk_ecc_ops;
 int zk_ecc_assign(const zk_ecc_ops* ops, uint32_t opts, uint64_t* rows_out);
 int zk_ecc_verify(const zk_ecc_ops* ops, const uint64_t* rows, uint32_t opts, uint32_t* status_out, zk_result* result);
+
+/* ---- Withdrawal circuit: replaces the row loop of withdrawal_circuit.verify_circuit (src/zkevm_specs/withdrawal_circuit.py:128-201)
+ *      and the reference test's withdrawals2witness (tests/test_withdrawal_circuit.py).
+ *      rows: uint64[n_rows][8][4] — id, validator_id, address, amount, hash lo, hash hi, root lo, root hi (canonical cells).
+ *      mpt: uint64[n_mpt][12][4], the State circuit's MPT-table layout (zk_state_open).   keccak: uint64[n_keccak][5][4] —
+ *      is_enabled, input_rlc, input_len, output lo, hi (the (0, 0, 0, 0, 0) row is in it only when the caller put it there).
+ *      block: uint64[n_block][4][4] — field_tag, block_number_or_zero, value lo, hi.   randomness: one cell (keccak_randomness).
+ *      max_withdrawals: MAX_WITHDRAWALS (rows at or beyond it are not read; fewer rows than it raise IndexError, as the reference).
+ *      total_rows: len(rows) of the whole witness; row_base: the global index of rows[0] (0 unless the session holds a shard).
+ *      The session evaluates global rows [row_base, row_base + n) with n = max(1, min(max_withdrawals, total_rows)) - row_base,
+ *      capped at n_rows (status[j] is global row row_base + j); the WithdrawalRoot block lookup rides on the row max_withdrawals - 1.
+ *      Status: (kind << 24) | site, csrc/withdrawal_circuit.hpp (1 id chain, 2 keccak, 3 MPT, 4 block lookup).
+ *      zk_withdrawal_assign: withdrawals uint64[n][5][4] — id, validator_id, address, amount (canonical cells), root (a 256-bit word)
+ *      -> rows_out uint64[max(n, max_withdrawals)][8][4], the digest keccak(rlp([id, validator_id, address, amount])) computed on the
+ *      device, rows from n on padding rows (0, 0, 0, 0, Word(0), the last root); keccak_out (optional) uint64[n][5][4], the rows
+ *      KeccakTable.add makes: (1, RLC of the RLP, its length, digest lo, hi). */
+typedef struct zk_withdrawal_witness {
+    const uint64_t* rows;     uint64_t n_rows;    uint64_t row_base;   uint64_t total_rows;   uint64_t max_withdrawals;
+    const uint64_t* mpt;      uint64_t n_mpt;
+    const uint64_t* keccak;   uint64_t n_keccak;
+    const uint64_t* block;    uint64_t n_block;
+    const uint64_t* randomness;
+} zk_withdrawal_witness;
+int zk_withdrawal_open(const zk_withdrawal_witness* w, uint32_t opts, zk_session** out);
+int zk_withdrawal_verify(const zk_withdrawal_witness* w, uint32_t opts, uint32_t* status_out, zk_result* result);
+int zk_withdrawal_assign(const uint64_t* withdrawals, uint64_t n, uint64_t max_withdrawals, const uint64_t* randomness, uint32_t opts,
+                         uint64_t* rows_out, uint64_t* keccak_out);
 
 #ifdef __cplusplus
 }

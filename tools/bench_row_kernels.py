@@ -2,7 +2,7 @@
 """Throughput of the row-stencil kernels (Bytecode / Exp / Tx-Sig circuits, the ECC circuit) on synthetic witnesses:
 rows/s and algorithmic GB/s (SURVEY.md §8d bytes per unit), device-resident inputs, HIP-event kernel
 time.  bench.py carries the headline EVM / State workloads; this is the side table in DESIGN.md §3.
-`bench_row_kernels.py ecc` runs only the ECC leg."""
+`bench_row_kernels.py ecc` runs only the ECC leg, `bench_row_kernels.py withdrawal` only the Withdrawal leg."""
 import json
 import os
 import random
@@ -76,6 +76,33 @@ def ecc_leg():
         print(name, out[name], flush=True)
 
 
+def withdrawal_leg():
+    """Withdrawal circuit at 2^16 rows: verification in a resident session (zk_withdrawal_open; kernel_ms = HIP-event span of a pass,
+    bytes per row = its own row + the MPT row + the keccak row it reads, 8 + 12 + 5 cells), and the assignment (zk_withdrawal_assign,
+    one-shot from host buffers: wall time including the staging copies, best of 5 after a warm-up)."""
+    import time
+
+    from tests.withdrawal_cases import big_witness
+    from zkevm_specs_amd import oneshot
+
+    n, rk = 1 << 16, 0x5EED % P
+    w, inp = big_witness(n, seed=1, r=rk, device="cpu")
+    run("withdrawal_verify", engine.open_withdrawal(w, rk), n, (8 + 12 + 5) * 32)
+    walls = []
+    for _ in range(6):
+        t0 = time.perf_counter()
+        rows, krows = oneshot.withdrawal_assign(inp, n, rk)
+        walls.append(time.perf_counter() - t0)
+    assert np.array_equal(rows, w["rows"]) and np.array_equal(krows, w["keccak"][1:])
+    ms = min(walls[1:]) * 1e3
+    out["withdrawal_assign"] = {"units": n, "oneshot_wall_ms": round(ms, 3), "units_per_s": round(n / ms * 1e3)}
+    print("withdrawal_assign", out["withdrawal_assign"], flush=True)
+
+
+if sys.argv[1:] == ["withdrawal"]:
+    withdrawal_leg()
+    print(json.dumps(out))
+    sys.exit(0)
 if sys.argv[1:] == ["ecc"]:
     ecc_leg()
     print(json.dumps(out))

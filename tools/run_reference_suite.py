@@ -9,8 +9,8 @@ A pytest plugin rebinds, inside every reference test module that imported them, 
     check_bytecode_row              zkevm_specs/bytecode_circuit.py:37      -> zkevm_specs_amd.bytecode_circuit.check_bytecode_row
     verify_copy_table               zkevm_specs/copy_circuit.py:92          -> zkevm_specs_amd.copy_circuit.verify_copy_table
     verify_exp_circuit              zkevm_specs/exp_circuit.py:88           -> zkevm_specs_amd.exp_circuit.verify_exp_circuit
-    verify_circuit (tx / sig / pi / ecc)  tx_circuit.py:253, sig_circuit.py:113, pi_circuit.py:338, ecc_circuit.py:424
-                                    -> the four mirrors
+    verify_circuit (tx / sig / pi / ecc / withdrawal)  tx_circuit.py:253, sig_circuit.py:113, pi_circuit.py:338, ecc_circuit.py:424,
+                                    withdrawal_circuit.py:128 -> the five mirrors
 
 — to the host mirrors, which flatten the reference's own witness objects to the wire and evaluate them behind the C ABI
 (`--backend cpu`: libzkevm_cpu.so, runs in the GPU-less build container; `--backend hip`: libzkevm_hip.so on an MI355X).
@@ -39,11 +39,12 @@ REBIND = {  # name in the test module -> (module the test imported it from, mirr
     "verify_copy_table": ("zkevm_specs.copy_circuit", "zkevm_specs_amd.copy_circuit", "verify_copy_table"),
     "verify_exp_circuit": ("zkevm_specs.exp_circuit", "zkevm_specs_amd.exp_circuit", "verify_exp_circuit"),
 }
-VERIFY_CIRCUIT = {  # `verify_circuit` exists four times: told apart by the module that defined the imported function
+VERIFY_CIRCUIT = {  # `verify_circuit` exists five times: told apart by the module that defined the imported function
     "zkevm_specs.tx_circuit": ("zkevm_specs_amd.tx_circuit", "verify_circuit"),
     "zkevm_specs.sig_circuit": ("zkevm_specs_amd.sig_circuit", "verify_circuit"),
     "zkevm_specs.pi_circuit": ("zkevm_specs_amd.pi_circuit", "verify_circuit"),
     "zkevm_specs.ecc_circuit": ("zkevm_specs_amd.ecc_circuit", "verify_circuit"),
+    "zkevm_specs.withdrawal_circuit": ("zkevm_specs_amd.withdrawal_circuit", "verify_circuit"),
 }
 
 
@@ -151,8 +152,8 @@ def main():
         "rebound": {m: d for m, d in sorted(plugin.rebound_modules.items()) if d},
         "by_file": dict(sorted(by_file.items())),
         "not_passed_detail": not_passed,
-        "notes": "Modules without a rebound driver test circuits outside SURVEY.md section 8 (Withdrawal): they run on the reference's own "
-                 "Python path, unchanged.  In the build container the reference's third-party dependencies are the stand-ins of oracle/refshim; "
+        "notes": "Every reference test module that drives a circuit is rebound to its mirror.  In the build container the reference's "
+                 "third-party dependencies are the stand-ins of oracle/refshim; "
                  "its py_ecc stand-in has no FQ2 / pairing arithmetic, so test_ecc_circuit.py passes only through the ECC mirror "
                  "(zkevm_specs_amd.ecc_circuit.verify_circuit, which needs no py_ecc): on the unmodified reference under the shim its seven "
                  "test_ecc_pairing cases fail.",

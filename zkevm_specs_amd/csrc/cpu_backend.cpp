@@ -33,6 +33,7 @@
 #include "bytecode_assign.hpp"
 #include "state_rekey.hpp"
 #include "ecc_circuit.hpp"
+#include "withdrawal_circuit.hpp"
 
 static thread_local std::string g_err;
 #define ARG_TRY(cond, msg) do { if (!(cond)) { g_err = msg; return -1; } } while (0)
@@ -1165,4 +1166,59 @@ extern "C" int zk_ecc_verify(const zk_ecc_ops* ops, const uint64_t* rows, uint32
     zk_session* s = new_session(a.n_add + a.n_mul + a.n_pairing, true);
     s->row = [a](u64 i) { return ecc_verify_row(a, i); };
     return one_shot(s, status_out, result);
+}
+
+// ---- Withdrawal circuit -----------------------------------------------------------------------------------------------
+extern "C" int zk_withdrawal_open(const zk_withdrawal_witness* w, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_withdrawal_open");
+    ARG_TRY(w && out && w->randomness && (w->rows || w->n_rows == 0), "zk_withdrawal_open: bad arguments");
+    ARG_TRY(w->n_rows < (1ull << 32) && w->n_mpt < (1ull << 31) && w->n_keccak < (1ull << 31) && w->n_block < (1ull << 31),
+            "zk_withdrawal_open: table too large");
+    ARG_TRY(w->row_base + w->n_rows <= w->total_rows || (w->n_rows == 0 && w->row_base == 0), "zk_withdrawal_open: rows beyond total_rows");
+    WithdrawalArgs a = {};
+    a.n_rows = w->n_rows;
+    a.row_base = w->row_base;
+    a.total_rows = w->total_rows;
+    a.max_w = w->max_withdrawals;
+    const u64 n = wd_eval_rows(a);
+    ARG_TRY(n > 0, "zk_withdrawal_open: row_base lies beyond the evaluated rows");
+    zk_session* s = new_session(n, true);
+    s->a64[0].assign(w->rows, w->rows + w->n_rows * WD_NCELLS * 4);
+    s->a64[1].assign(w->block, w->block + w->n_block * WD_BLOCK_NCELLS * 4);
+    cpu_table(s->tab[0], w->keccak, nullptr, w->n_keccak, KECCAK_NCELLS, keccak_key_hash);
+    cpu_table(s->tab[1], w->mpt, nullptr, w->n_mpt, MPT_NCELLS, wd_mpt_key_hash);
+    a.rows = s->a64[0].data();
+    a.block = s->a64[1].data();
+    a.n_block = w->n_block;
+    a.keccak = s->tab[0].t;
+    a.mpt = s->tab[1].t;
+    a.r = cell_of(w->randomness);
+    s->row = [s, a](u64 j) { (void)s; return wd_verify_row(a, j); };
+    *out = s;
+    return 0;
+}
+extern "C" int zk_withdrawal_verify(const zk_withdrawal_witness* w, uint32_t opts, uint32_t* status_out, zk_result* result) {
+    ARG_TRY(result, "zk_withdrawal_verify: result is null");
+    zk_session* s = nullptr;
+    const int rc = zk_withdrawal_open(w, opts, &s);
+    return rc ? rc : one_shot(s, status_out, result);
+}
+extern "C" int zk_withdrawal_assign(const uint64_t* withdrawals, uint64_t n, uint64_t max_withdrawals, const uint64_t* randomness,
+                                    uint32_t opts, uint64_t* rows_out, uint64_t* keccak_out) {
+    NO_DEVICE_PTRS(opts, "zk_withdrawal_assign");
+    ARG_TRY(randomness && rows_out && (withdrawals || n == 0), "zk_withdrawal_assign: bad arguments");
+    ARG_TRY(n < (1ull << 32) && max_withdrawals < (1ull << 32), "zk_withdrawal_assign: too many rows");
+    WithdrawalArgs a = {};
+    a.in = withdrawals;
+    a.n_in = n;
+    a.n_out = n > max_withdrawals ? n : max_withdrawals;
+    a.rows_out = rows_out;
+    a.keccak_out = keccak_out;
+    a.r = cell_of(randomness);
+#pragma omp parallel for schedule(dynamic, 256)
+    for (long long i = 0; i < (long long)a.n_out; i++) {
+        uint8_t m[136];
+        wd_assign_row(a, (u64)i, m);
+    }
+    return 0;
 }

@@ -17,6 +17,7 @@
 #include "pi_circuit.hpp"
 #include "state_rekey.hpp"
 #include "ecc_circuit.hpp"
+#include "withdrawal_circuit.hpp"
 
 // The single-kernel row sessions keep two tallies and alternate between them: a pass accumulates into one and its first
 // lane clears the other for the pass after it, so that no reset kernel sits in front of every evaluation kernel (a kernel
@@ -78,3 +79,6 @@ void zk_launch_ecdsa_comb_build(hipStream_t st, u32* table);  // the device's 8-
 // ECC circuit (k_ecc.hip): assign = circuit2rows into a.rows_out, else verify a.rows (status / tally)
 void zk_launch_ecc(hipStream_t st, const EccArgs& a, bool assign, u32* status, ZkTally* tally);
 void zk_launch_fq12_op(hipStream_t st, int op, const u64* x, const u64* y, u64* out, u64 n12);  // zk_fr_op 19..25
+// Withdrawal circuit (k_withdrawal.hip): verify held rows [lo, hi) (status / twin tally); assign rows [0, a.n_out) (+ keccak rows)
+void zk_launch_withdrawal_rows(hipStream_t st, const WithdrawalArgs& a, u64 lo, u64 hi, u32* status, ZkTally* tally);
+void zk_launch_withdrawal_assign(hipStream_t st, const WithdrawalArgs& a);

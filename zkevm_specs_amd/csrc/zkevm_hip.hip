@@ -568,7 +568,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -598,6 +598,7 @@ struct zk_session {
     CpaArgs cpa;
     PiArgs pi;
     PiCopyArgs picopy;
+    WithdrawalArgs withdrawal;
     RekeyArgs rekey;
     RwkPlan rekey_plan_host;      // the compact-key plan as uploaded (host copy owned by the session: the upload needs no synchronisation of its own)
     bool assign_from_rw = false;  // SESSION_ASSIGN over an RW table: every pass starts with the re-keying and the sort (rekey)
@@ -2273,7 +2274,7 @@ static inline u64 range_lo(const zk_session* s) { return s->eval_hi ? s->eval_lo
 static inline u64 range_hi(const zk_session* s) { return s->eval_hi ? s->eval_hi : s->n; }
 extern "C" int zk_set_range(zk_session* s, uint64_t row_lo, uint64_t row_hi) {
     ARG_TRY(s && (s->kind == SESSION_STATE || s->kind == SESSION_BYTECODE || s->kind == SESSION_COPY || s->kind == SESSION_EXP ||
-                  s->kind == SESSION_SIGN || s->kind == SESSION_PI),
+                  s->kind == SESSION_SIGN || s->kind == SESSION_PI || s->kind == SESSION_WITHDRAWAL),
             "zk_set_range: not a row-circuit session (EVM sessions shard by the steps they are opened over)");
     ARG_TRY(row_lo < row_hi && row_hi <= s->n, "zk_set_range: bad range");
     HIP_TRY(hipSetDevice(s->device));
@@ -2401,7 +2402,8 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
         e1 = s->ev[2 * s->launches + 1];
     }
     const bool twin_tally = s->kind == SESSION_STATE || s->kind == SESSION_BYTECODE || s->kind == SESSION_COPY ||
-                            s->kind == SESSION_SIGN || s->kind == SESSION_EXP || s->kind == SESSION_PI || s->kind == SESSION_PICOPY;
+                            s->kind == SESSION_SIGN || s->kind == SESSION_EXP || s->kind == SESSION_PI || s->kind == SESSION_PICOPY ||
+                            s->kind == SESSION_WITHDRAWAL;
     ZkTally* const tally = twin_tally ? s->d_tally + (s->tally_pass++ & 1u) : s->d_tally;
     s->tally_last = tally;
     if (!twin_tally && !(s->kind == SESSION_EVM && s->evm.perm))
@@ -2454,6 +2456,7 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     case SESSION_ECDSA: zk_launch_ecdsa(s->stream, s->ecdsa, status, s->d_tally); break;
     case SESSION_BCA: zk_launch_bytecode_assign(s->stream, s->bca, status, s->d_tally); break;
     case SESSION_PI: zk_launch_pi_rows(s->stream, s->pi, range_lo(s), range_hi(s), status, tally); break;
+    case SESSION_WITHDRAWAL: zk_launch_withdrawal_rows(s->stream, s->withdrawal, range_lo(s), range_hi(s), status, tally); break;
     case SESSION_PICOPY: zk_launch_pi_copy(s->stream, s->picopy, status, tally); break;
     case SESSION_CPA: zk_launch_copy_assign(s->stream, s->cpa, status, s->d_tally); break;
     case SESSION_REKEY: zk_launch_state_rekey(s->stream, s->rekey, status, s->d_tally); break;
@@ -3289,4 +3292,114 @@ extern "C" int zk_ecc_verify(const zk_ecc_ops* ops, const uint64_t* rows, uint32
     ARG_TRY(!(opts & ZK_OPT_DEVICE_PTRS), "zk_ecc_verify: ZK_OPT_DEVICE_PTRS is not supported (the ops are read on the host)");
     ARG_TRY(rows && result, "zk_ecc_verify: rows / result is null");
     return ecc_run(ops, rows, false, nullptr, status_out, result, "zk_ecc_verify");
+}
+
+// ---------------------------------------------------------------------------------------
+// Withdrawal circuit (include/zkevm_hip.h "Withdrawal circuit"): a row-circuit session (zk_set_range: 1 row before + 1 after), and a
+// one-shot assignment staged through one device allocation
+// ---------------------------------------------------------------------------------------
+// the MPT index of this circuit keeps plain row numbers in its slots (table_probe_inline reads them so), keyed on the State hash
+__global__ void wd_mpt_index_kernel(ZkTable t, u32* slots) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= t.n) return;
+    u32 s = (u32)wd_mpt_key_hash(t, r) & t.mask;
+    while (atomicCAS(&slots[s], ZK_EMPTY_SLOT, r) != ZK_EMPTY_SLOT) s = (s + 1) & t.mask;
+}
+extern "C" int zk_withdrawal_open(const zk_withdrawal_witness* w, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_withdrawal_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(w && out && w->randomness && (w->rows || w->n_rows == 0), "zk_withdrawal_open: bad arguments");
+    ARG_TRY(w->n_rows < (1ull << 32) && w->n_mpt < (1ull << 31) && w->n_keccak < (1ull << 31) && w->n_block < (1ull << 31),
+            "zk_withdrawal_open: table too large");
+    ARG_TRY(w->row_base + w->n_rows <= w->total_rows || (w->n_rows == 0 && w->row_base == 0), "zk_withdrawal_open: rows beyond total_rows");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    WithdrawalArgs a = {};
+    a.n_rows = w->n_rows;
+    a.row_base = w->row_base;
+    a.total_rows = w->total_rows;
+    a.max_w = w->max_withdrawals;
+    const u64 n = wd_eval_rows(a);
+    ARG_TRY(n > 0, "zk_withdrawal_open: row_base lies beyond the evaluated rows");
+    zk_session* s = new zk_session();
+    s->kind = SESSION_WITHDRAWAL;
+    s->n = n;
+    int rc = 0;
+    const void* p = nullptr;
+    u64 rh[4];
+    if ((rc = stage(s, w->rows, (size_t)w->n_rows * WD_NCELLS * 32, dev, &p))) goto fail;
+    a.rows = (const u64*)p;
+    if ((rc = table_stage(s, a.keccak, w->keccak, nullptr, w->n_keccak, KECCAK_NCELLS, dev))) goto fail;
+    if ((rc = build_index<keccak_key_hash>(s, a.keccak))) goto fail;
+    if ((rc = table_stage(s, a.mpt, w->mpt, nullptr, w->n_mpt, MPT_NCELLS, dev))) goto fail;
+    {
+        u32 cap = 16;
+        while (cap < 2 * a.mpt.n + 2) cap <<= 1;
+        u32* slots = nullptr;
+        if ((rc = dev_alloc(s, (void**)&slots, (size_t)cap * sizeof(u32)))) goto fail;
+        a.mpt.mask = cap - 1;
+        a.mpt.slots = slots;
+        hipLaunchKernelGGL(slots_fill_kernel, dim3((cap + 255) / 256), dim3(256), 0, s->stream, slots, cap);
+        if (a.mpt.n) hipLaunchKernelGGL(wd_mpt_index_kernel, dim3((a.mpt.n + 255) / 256), dim3(256), 0, s->stream, a.mpt, slots);
+        if (hipGetLastError() != hipSuccess) { rc = -2; g_err = "zk_withdrawal_open: MPT index launch failed"; goto fail; }
+    }
+    if ((rc = stage(s, w->block, (size_t)w->n_block * WD_BLOCK_NCELLS * 32, dev, &p))) goto fail;
+    a.block = (const u64*)p;
+    a.n_block = w->n_block;
+    if (dev) {
+        if (fetch_small(s->stream, rh, w->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
+    } else {
+        memcpy(rh, w->randomness, 32);
+    }
+    for (int k = 0; k < 4; k++) { a.r.v[2 * k] = (u32)rh[k]; a.r.v[2 * k + 1] = (u32)(rh[k] >> 32); }
+    s->withdrawal = a;
+    if ((rc = session_common_init(s))) goto fail;
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_withdrawal_verify(const zk_withdrawal_witness* w, uint32_t opts, uint32_t* status_out, zk_result* result) {
+    ARG_TRY(result, "zk_withdrawal_verify: result is null");
+    zk_session* s = nullptr;
+    int rc = zk_withdrawal_open(w, opts, &s);
+    if (rc) return rc;
+    return one_shot(s, opts & ZK_OPT_DEVICE_PTRS, status_out, result);
+}
+extern "C" int zk_withdrawal_assign(const uint64_t* withdrawals, uint64_t n, uint64_t max_withdrawals, const uint64_t* randomness,
+                                    uint32_t opts, uint64_t* rows_out, uint64_t* keccak_out) {
+    ARG_TRY(t_device >= 0, "zk_withdrawal_assign: call zk_init first");
+    ARG_TRY(!(opts & ZK_OPT_DEVICE_PTRS), "zk_withdrawal_assign: ZK_OPT_DEVICE_PTRS is not supported");
+    ARG_TRY(randomness && rows_out && (withdrawals || n == 0), "zk_withdrawal_assign: bad arguments");
+    ARG_TRY(n < (1ull << 32) && max_withdrawals < (1ull << 32), "zk_withdrawal_assign: too many rows");
+    HIP_TRY(hipSetDevice(t_device));
+    WithdrawalArgs a = {};
+    a.n_in = n;
+    a.n_out = n > max_withdrawals ? n : max_withdrawals;
+    for (int k = 0; k < 4; k++) { a.r.v[2 * k] = (u32)randomness[k]; a.r.v[2 * k + 1] = (u32)(randomness[k] >> 32); }
+    if (a.n_out == 0) return 0;
+    // one allocation: withdrawals | rows | keccak rows (each part 256-byte aligned)
+    auto al = [](u64 b) { return (b + 255) & ~255ull; };
+    const u64 b_in = n * WD_IN_NCELLS * 32, b_rows = a.n_out * WD_NCELLS * 32, b_k = keccak_out ? n * KECCAK_NCELLS * 32 : 0;
+    const u64 o_rows = al(b_in), o_k = o_rows + al(b_rows), total = o_k + al(b_k) + 256;
+    void* base = nullptr;
+    HIP_TRY(hipMalloc(&base, total));
+    char* d = (char*)base;
+    hipStream_t st = t_stream;
+    hipError_t e = hipSuccess;
+    if (b_in) e = hipMemcpyAsync(d, withdrawals, b_in, hipMemcpyHostToDevice, st);
+    a.in = (const u64*)d;
+    a.rows_out = (u64*)(d + o_rows);
+    a.keccak_out = keccak_out ? (u64*)(d + o_k) : nullptr;
+    if (e == hipSuccess) {
+        zk_launch_withdrawal_assign(st, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(rows_out, d + o_rows, b_rows, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess && b_k) e = hipMemcpyAsync(keccak_out, d + o_k, b_k, hipMemcpyDeviceToHost, st);
+    const hipError_t se = hipStreamSynchronize(st);
+    (void)hipFree(base);
+    HIP_TRY(e);
+    HIP_TRY(se);
+    return 0;
 }

@@ -22,7 +22,8 @@ def shard_state(cols, flags, rank, world):
     return shard_rows(cols, flags, rank, world, "state")
 
 
-HALO = {"state": (1, 1), "bytecode": (0, 1), "exp": (0, 1), "pi": (0, 1), "copy": (0, 2), "tx": (0, 0), "sig": (0, 0)}
+HALO = {"state": (1, 1), "bytecode": (0, 1), "exp": (0, 1), "pi": (0, 1), "copy": (0, 2), "tx": (0, 0), "sig": (0, 0),
+        "withdrawal": (1, 1)}
 """rows before / after a rank's range that its boundary rows read (SURVEY.md §8e; the neighbours wrap modulo n:
 state_circuit.py:492 prev / next, bytecode_circuit.py:37 next, exp_circuit.py:88-97 next, copy_circuit.py:92-130
 rows i + 1 and i + 2, tx_circuit.py:253-291 none)"""
@@ -37,11 +38,22 @@ def _take(a, idx, axis):
     return np.ascontiguousarray(np.take(a, idx, axis=axis))
 
 
-def shard_rows(cols, flags, rank, world, circuit):
+def shard_rows(cols, flags, rank, world, circuit, max_withdrawals=None, total_rows=None):
     """Row shard of a column-major circuit witness cols[c, n, 4] (+ optional flags[n]): the rank's rows [lo, hi) with the
     circuit's halo (HALO) on either side, modulo n.  Returns (cols_local, flags_local, eval_lo, eval_hi, lo): the
     session over the local rows evaluates [eval_lo, eval_hi) (Session.set_range) and its row i is global row
-    lo + i - eval_lo."""
+    lo + i - eval_lo.
+    "withdrawal": cols is the row-major rows[n, 8, 4] of flatten_withdrawal_witness (max_withdrawals / total_rows: its
+    MAX_WITHDRAWALS and len(rows)); the evaluated rows max(1, min(MAX, len(rows))) are split, and the halo does NOT wrap (row 0's
+    previous root is Word(0), the last row reads no next id): rows [max(lo - 1, 0), min(hi + 1, n)).  The local session is opened
+    with row_base = lo - eval_lo."""
+    if circuit == "withdrawal":
+        n = int(cols.shape[0])
+        total = n if total_rows is None else int(total_rows)
+        m = n if max_withdrawals is None else int(max_withdrawals)
+        lo, hi = shard_bounds(max(1, min(m, total)), rank, world)
+        start, end = max(lo - 1, 0), (n if m == 0 else min(hi + 1, n))
+        return _take(cols, np.arange(start, end), 0), None, lo - start, lo - start + (hi - lo), lo
     n = int(cols.shape[1])
     before, after = HALO[circuit]
     lo, hi = shard_bounds(n, rank, world)

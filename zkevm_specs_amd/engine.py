@@ -733,3 +733,17 @@ def fr_op(op, a, b):
     out = np.empty_like(a)
     check(lib.zk_fr_op(int(op), _lib.ptr(a), _lib.ptr(b), _lib.ptr(out), a.shape[0], 0), "zk_fr_op")
     return out
+
+
+def open_withdrawal(w, randomness, device=None):
+    """Withdrawal circuit session over a wire dict (flatten.flatten_withdrawal_witness, or a shard of it: distributed.shard_rows(...,
+    "withdrawal") with row_base set) -> Session; zk_set_range applies (1 row before + 1 after, include/zkevm_hip.h)"""
+    from .oneshot import _withdrawal_witness, withdrawal_arrays
+    from .withdrawal_circuit import eval_rows
+
+    lib = _lib.init(device)
+    arrs = withdrawal_arrays(w, randomness)
+    ww = _withdrawal_witness(w, *arrs)
+    h = ctypes.c_void_p()
+    check(lib.zk_withdrawal_open(ctypes.byref(ww), 0, ctypes.byref(h)), "zk_withdrawal_open", lib)
+    return Session(h, eval_rows(w), (arrs, ww), lib=lib)

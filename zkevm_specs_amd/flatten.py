@@ -706,3 +706,60 @@ def flatten_ecc_ops(add_ops, mul_ops, pairing_ops, max_add_ops=1, max_mul_ops=1,
         "pair_out": np.array(outs, dtype=np.uint64).reshape(len(outs), 4),
         "max_ok": np.array([int(m >= 1) for m in (max_add_ops, max_mul_ops, max_pairing_ops)], dtype=np.uint32),
     }
+
+
+WITHDRAWAL_NCELLS = 8
+
+
+def _withdrawal_cell(x):
+    """an FQ field of a withdrawal Row, or the plain int the reference tests write into one (0 <= x < p: int(x) is what rlp.encode
+    sees there, and only a canonical value reaches the wire unchanged)"""
+    if hasattr(x, "n") or hasattr(x, "expr"):
+        return _n(x)
+    v = int(x)
+    if not 0 <= v < FR_MODULUS:
+        from .errors import UnsupportedOnDevice
+
+        raise UnsupportedOnDevice(f"withdrawal row: plain int {v} outside [0, p)")
+    return v
+
+
+def _withdrawal_root(x):
+    """(lo, hi) of a Row's root: a Word, or the plain int padding_withdrawal stores there (its type fails on the host)"""
+    if hasattr(x, "lo"):
+        return [_n(x.lo), _n(x.hi)]
+    v = int(x) % (1 << 256)
+    return [v & ((1 << 128) - 1), v >> 128]
+
+
+def flatten_withdrawal_rows(rows):
+    """withdrawal_circuit.Row (withdrawal_circuit.py:21-46: withdrawal_id, validator_id, address, amount, hash, root) -> uint64[n, 8, 4]:
+    id, validator_id, address, amount, hash lo, hi, root lo, hi"""
+    out = [[_withdrawal_cell(r.withdrawal_id), _withdrawal_cell(r.validator_id), _withdrawal_cell(r.address), _withdrawal_cell(r.amount),
+            _n(r.hash.lo), _n(r.hash.hi), *_withdrawal_root(r.root)] if hasattr(r, "withdrawal_id") else [0] * WITHDRAWAL_NCELLS
+           for r in rows]  # (a row without the fields — padding_withdrawal's one-element list — fails on the host: withdrawal_circuit.type_quirks)
+    return rows_to_rowmajor(out, WITHDRAWAL_NCELLS).reshape(len(out), WITHDRAWAL_NCELLS, 4)
+
+
+def _table_rows(t):
+    """MPTTable / BlockTable / KeccakTable of withdrawal_circuit.py (their `.table` set), or the set itself"""
+    return getattr(t, "table", t)
+
+
+def flatten_withdrawal_witness(witness, max_withdrawals):
+    """withdrawal_circuit.Witness (rows, mpt_table, keccak_table, block_table) -> the zk_withdrawal_witness arrays (include/zkevm_hip.h):
+    rows uint64[n, 8, 4] (rows[:MAX]; every row when MAX is 0, whose block lookup reads rows[-1]), mpt uint64[m, 12, 4], keccak
+    uint64[k, 5, 4] (the table's own rows: its (0, 0, 0, Word(0)) row only if the caller's KeccakTable() added it), block
+    uint64[b, 4, 4], max_withdrawals, total_rows = len(rows), row_base 0.  Duplicate rows collapse as the reference's sets do."""
+    rows = list(witness.rows)
+    m = int(max_withdrawals)
+    held = rows if m == 0 else rows[:m]
+    return {
+        "rows": flatten_withdrawal_rows(held),
+        "mpt": flatten_mpt_table(_table_rows(witness.mpt_table)).reshape(-1, MPT_NCELLS, 4),
+        "keccak": flatten_keccak_tuples(_table_rows(witness.keccak_table)).reshape(-1, KECCAK_NCELLS, 4),
+        "block": flatten_block_table(_table_rows(witness.block_table))[0].reshape(-1, BLOCK_NCELLS, 4),
+        "max_withdrawals": m,
+        "total_rows": len(rows),
+        "row_base": 0,
+    }

@@ -306,3 +306,54 @@ def ecc_verify(w, rows, randomness, device=None):
     status, r = np.zeros(n, dtype=np.uint32), ZkResult()
     check(lib.zk_ecc_verify(ctypes.byref(ops), _p(rows), 0, _p(status), ctypes.byref(r)), "zk_ecc_verify", lib)
     return Result(r), status
+
+
+def _withdrawal_witness(w, rows, mpt, keccak, block, rc):
+    """the zk_withdrawal_witness block over the arrays of flatten.flatten_withdrawal_witness (kept alive by the caller)"""
+    from ._lib import ZkWithdrawalWitness
+
+    _expect(rows, "withdrawal rows", 8, (None, 8, 4))
+    _expect(mpt, "mpt", 8, (None, 12, 4))
+    _expect(keccak, "keccak", 8, (None, 5, 4))
+    _expect(block, "block", 8, (None, 4, 4))
+    n, m, k, b = (int(x.shape[0]) for x in (rows, mpt, keccak, block))
+
+    def p(x, cnt):
+        v = _p(x, cnt)
+        return v.value if v is not None else None
+
+    return ZkWithdrawalWitness(p(rows, n), n, int(w.get("row_base", 0)), int(w.get("total_rows", n)), int(w["max_withdrawals"]),
+                               p(mpt, m), m, p(keccak, k), k, p(block, b), b, p(rc, 1))
+
+
+def withdrawal_arrays(w, randomness):
+    """(rows, mpt, keccak, block, randomness cell) of a withdrawal wire dict, C-contiguous uint64"""
+    return (_c(w["rows"], np.uint64), _c(w["mpt"], np.uint64), _c(w["keccak"], np.uint64), _c(w["block"], np.uint64),
+            _c(_randomness_cells(int(randomness), None)))
+
+
+def withdrawal_verify(w, randomness, device=None):
+    """zk_withdrawal_verify over flatten_withdrawal_witness output -> (Result, status uint32[n]); status[j] is global row row_base + j"""
+    lib = _lib.init(device)
+    arrs = withdrawal_arrays(w, randomness)
+    ww = _withdrawal_witness(w, *arrs)
+    from .withdrawal_circuit import eval_rows
+
+    status, r = np.zeros(eval_rows(w), dtype=np.uint32), ZkResult()
+    check(lib.zk_withdrawal_verify(ctypes.byref(ww), 0, _p(status), ctypes.byref(r)), "zk_withdrawal_verify", lib)
+    return Result(r), status
+
+
+def withdrawal_assign(withdrawals, max_withdrawals, randomness, keccak_rows=True, device=None):
+    """zk_withdrawal_assign: withdrawals uint64[n, 5, 4] (id, validator_id, address, amount, root) -> (rows uint64[max(n, MAX), 8, 4],
+    keccak rows uint64[n, 5, 4] or None)"""
+    lib = _lib.init(device)
+    wd = _c(withdrawals, np.uint64)
+    _expect(wd, "withdrawals", 8, (None, 5, 4))
+    n, m = int(wd.shape[0]), int(max_withdrawals)
+    rc = _c(_randomness_cells(int(randomness), None))
+    rows = np.zeros((max(n, m), 8, 4), dtype=np.uint64)
+    kr = np.zeros((n, 5, 4), dtype=np.uint64) if keccak_rows else None
+    check(lib.zk_withdrawal_assign(_p(wd, n), n, m, _p(rc), 0, _p(rows, rows.shape[0]), _p(kr, n) if kr is not None else None),
+          "zk_withdrawal_assign", lib)
+    return rows, kr
