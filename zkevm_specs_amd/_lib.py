@@ -277,9 +277,10 @@ def init(device=None):
     return lib
 
 
-def ptr(x):
-    """void* of a numpy array (host) or a torch tensor (device / host)."""
-    if x is None:
+def ptr(x, n=1):
+    """void* of a numpy array (host) or a torch tensor (device / host); None (a null pointer) for no array, or when its count
+    `n` is 0."""
+    if x is None or not n:
         return None
     if hasattr(x, "data_ptr"):
         return ctypes.c_void_p(x.data_ptr())

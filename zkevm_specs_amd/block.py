@@ -46,34 +46,21 @@ def stage_block(parts, to_device):
 
 
 def native_block(b):
-    """the zk_block struct of a staged block (stage_block): built once, every pointer is a device pointer of a tensor `b` keeps alive"""
-    def p(x, n=1):
-        return ctypes.c_void_p(x.data_ptr()).value if (x is not None and n) else None
-
-    def rows(x):
-        return 0 if x is None else int(x.shape[0])
-
+    """the zk_block struct of a staged block (stage_block): built once, every pointer is a device pointer of a tensor `b` keeps alive.
+    The device derives the EVM circuit's copy and keccak tables; a block has no aux, withdrawal, sig or ecc table."""
+    ptr = _lib.ptr
     e = b["evm"]
-    evm = _lib.ZkEvmTables(
-        p(e["steps"]), rows(e["steps"]), p(e.get("rw"), rows(e.get("rw"))), p(e.get("rw_flags"), rows(e.get("rw"))), rows(e.get("rw")),
-        p(e.get("bytecode"), rows(e.get("bytecode"))), rows(e.get("bytecode")),
-        p(e.get("tx"), rows(e.get("tx"))), p(e.get("tx_flags"), rows(e.get("tx"))), rows(e.get("tx")),
-        p(e.get("block"), rows(e.get("block"))), p(e.get("block_flags"), rows(e.get("block"))), rows(e.get("block")),
-        0, 0, None, 0, None, 0, p(e.get("exp"), rows(e.get("exp"))), rows(e.get("exp")),
-        None, None, None, 0, None, 0, None, 0, 0, 0)
+    evm = engine._evm_struct({k: e.get(k) for k in ("steps", "rw", "rw_flags", "bytecode", "tx", "tx_flags", "block", "block_flags", "exp")})
     data, offsets, n_codes, n_msgs = b["keccak"]
     ub_rows, ub_off, ub_len, k = b["bytecode"]
     ev, fl, da, of, r_copy = b["copy_events"]
-    ce = _lib.ZkCopyEvents(p(ev), p(fl), rows(ev), p(da, rows(da)), p(of), p(r_copy))
     tx_w, r_tx = b["tx"]
-    n_tx = rows(tx_w.get("bytes"))
-    tx = _lib.ZkSignUnits(p(tx_w.get("bytes"), n_tx), p(tx_w.get("cells"), n_tx), p(tx_w.get("meta"), n_tx), n_tx, p(r_tx),
-                          p(tx_w.get("keccak"), rows(tx_w.get("keccak"))), rows(tx_w.get("keccak")),
-                          p(tx_w.get("tx_rows"), rows(tx_w.get("tx_rows"))), p(tx_w.get("tx_flags"), rows(tx_w.get("tx_rows"))), rows(tx_w.get("tx_rows")), 0)
+    tx = engine._sign_struct({name: tx_w.get(name) for name in engine._SIGN_WIRE}, r_tx, False)
     ex = b["exp_rows"]
     n_exp = 0 if ex is None else int(ex.shape[1])
-    return _lib.ZkBlock(evm, p(data, int(data.shape[0])), int(data.shape[0]), p(offsets), int(n_codes), int(n_msgs), p(b["r"]),
-                        p(ub_off), p(ub_len), int(ub_len.shape[0]), int(k), 0, ce, p(ex, n_exp), n_exp, tx)
+    return _lib.ZkBlock(evm, ptr(data, int(data.shape[0])), int(data.shape[0]), ptr(offsets), int(n_codes), int(n_msgs), ptr(b["r"]),
+                        ptr(ub_off), ptr(ub_len), int(ub_len.shape[0]), int(k), 0, engine._copy_events_struct(ev, fl, da, of, r_copy),
+                        ptr(ex, n_exp), n_exp, tx)
 
 
 def verify_block_native(b, device=0, state_compact=False, state_rows=False):

@@ -125,7 +125,7 @@ class RcclTally:
         import ctypes
 
         from . import _lib
-        from .engine import check
+        from ._lib import check
 
         self._lib = _lib.init(device)
         self._check = check

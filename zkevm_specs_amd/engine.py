@@ -4,7 +4,8 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import OPT_DEVICE_PTRS, ZkResult, check
+from ._lib import OPT_DEVICE_PTRS, ZkResult, check, ptr
+from .errors import exception_for_code
 
 
 class Result:
@@ -48,7 +49,7 @@ class Session:
             _expect(status_dev, "status_dev", 4, (self.n,))
             if not _is_contiguous(status_dev):
                 raise ValueError("status_dev must be contiguous")
-        check(self._lib.zk_launch(self._h, _lib.ptr(status_dev)), "zk_launch", self._lib)
+        check(self._lib.zk_launch(self._h, ptr(status_dev)), "zk_launch", self._lib)
 
     def collect(self):
         r = ZkResult()
@@ -77,7 +78,7 @@ class Session:
 
     def read_status(self):
         out = np.empty(self.n, dtype=np.uint32)
-        check(self._lib.zk_read_status(self._h, _lib.ptr(out)), "zk_read_status", self._lib)
+        check(self._lib.zk_read_status(self._h, ptr(out)), "zk_read_status", self._lib)
         return out
 
     def close(self):
@@ -96,6 +97,13 @@ class Session:
             self.close()
         except Exception:  # noqa: BLE001
             pass
+
+
+def _open(lib, fn, n, keep, *args, cls=Session):
+    """one `fn(*args, &handle)` call of a zk_*_open entry -> a `cls` session over n rows that keeps the arrays `keep` alive"""
+    h = ctypes.c_void_p()
+    check(fn(*args, ctypes.byref(h)), fn.__name__, lib)
+    return cls(h, n, keep, lib=lib)
 
 
 def _is_contiguous(a):
@@ -153,61 +161,67 @@ def _randomness_cells(randomness, like):
     return cells
 
 
+def _host(x, dtype=None):
+    """a C-contiguous host array of `x` (None stays None): the one-shot entries and the host-only argument blocks"""
+    return None if x is None else np.ascontiguousarray(x, dtype=dtype)
+
+
+def _rows(x):
+    return 0 if x is None else int(x.shape[0])
+
+
+def _state_args(rows, flags, mpt, compact=False):
+    """zk_state_open / zk_state_verify -> ((rows, flags, n, mpt, m), opts, kept arrays)"""
+    _expect(rows, "state rows", 8, (15 if compact else 57, None, 4))
+    _expect(flags, "state flags", 4, (rows.shape[1],))
+    _expect(mpt, "mpt", 8, (None, 12, 4))
+    keep, opts = _prep([rows, flags, mpt])
+    rows, flags, mpt = keep
+    if compact:
+        opts |= _lib.OPT_STATE_COMPACT
+    m = _rows(mpt)
+    return (ptr(rows), ptr(flags), int(rows.shape[1]), ptr(mpt, m), m), opts, keep
+
+
 def open_state(rows, flags, mpt, device=None, compact=False):
     """rows uint64[57, n, 4], flags uint32[n], mpt uint64[m, 12, 4] -> Session.  compact: rows uint64[15, n, 4], a device-assigned
     witness without the limb / byte columns (ZK_OPT_STATE_COMPACT, include/zkevm_hip.h)"""
     lib = _lib.init(device)
-    _expect(rows, "state rows", 8, (15 if compact else 57, None, 4))
-    _expect(flags, "state flags", 4, (rows.shape[1],))
-    _expect(mpt, "mpt", 8, (None, 12, 4))
-    (rows, flags, mpt), opts = _prep([rows, flags, mpt])
-    if compact:
-        opts |= _lib.OPT_STATE_COMPACT
-    n = rows.shape[1]
-    m = mpt.shape[0] if mpt is not None else 0
-    h = ctypes.c_void_p()
-    check(lib.zk_state_open(_lib.ptr(rows), _lib.ptr(flags), n, _lib.ptr(mpt) if m else None, m, opts,
-                            ctypes.byref(h)), "zk_state_open")
-    return Session(h, n, (rows, flags, mpt), lib=lib)
+    args, opts, keep = _state_args(rows, flags, mpt, compact)
+    return _open(lib, lib.zk_state_open, args[2], keep, *args, opts)
+
+
+# cells per row of each zk_evm_tables table (aux: 2 or 12), and the per-row words that go with a table
+_EVM_CELLS = {"steps": 13, "rw": 14, "bytecode": 6, "tx": 5, "block": 4, "copy": 14, "keccak": 5, "exp": 11, "withdrawals": 4,
+              "sig": 9, "ecc": 13, "aux": None}
+_EVM_FLAGS = {"rw_flags": "rw", "tx_flags": "tx", "block_flags": "block", "aux_kind": "steps"}
+_EVM_WIRE = list(_EVM_CELLS) + list(_EVM_FLAGS)
 
 
 def _evm_tables(wire, begin_with_first_step, end_with_last_step):
-    """wire dict -> (ZkEvmTables, opts, kept arrays); host arrays are made contiguous, device tensors are used in place"""
-    names = ["steps", "rw", "rw_flags", "bytecode", "tx", "tx_flags", "block", "block_flags", "copy", "keccak", "exp", "aux",
-             "aux_kind", "withdrawals", "sig", "ecc"]
-    cells = {"steps": 13, "rw": 14, "bytecode": 6, "tx": 5, "block": 4, "copy": 14, "keccak": 5, "exp": 11, "withdrawals": 4,
-             "sig": 9, "ecc": 13, "aux": None}
-    for k, nc in cells.items():
+    """wire dict -> (ZkEvmTables, opts, kept arrays, n_pairs); host arrays are made contiguous, device tensors are used in place"""
+    for k, nc in _EVM_CELLS.items():
         _expect(wire.get(k), k, 8, (None, nc, 4))
-    for k, of in (("rw_flags", "rw"), ("tx_flags", "tx"), ("block_flags", "block"), ("aux_kind", "steps")):
+    for k, of in _EVM_FLAGS.items():
         if wire.get(k) is not None and wire.get(of) is not None:
             _expect(wire[k], k, 4, (wire[of].shape[0],))
-    arrs, opts = _prep([wire.get(k) for k in names])
-    a = dict(zip(names, arrs))
+    arrs, opts = _prep([wire.get(k) for k in _EVM_WIRE])
+    a = dict(zip(_EVM_WIRE, arrs))
+    return _evm_struct(a, begin_with_first_step, end_with_last_step), opts, arrs, int(a["steps"].shape[0]) - 1
 
-    def rows(x):
-        return 0 if x is None else int(x.shape[0])
 
-    def p(x):
-        v = _lib.ptr(x)
-        return v.value if v is not None else None
-
-    t = _lib.ZkEvmTables(
-        p(a["steps"]), int(a["steps"].shape[0]),
-        p(a["rw"]) if rows(a["rw"]) else None, p(a["rw_flags"]) if rows(a["rw"]) else None, rows(a["rw"]),
-        p(a["bytecode"]) if rows(a["bytecode"]) else None, rows(a["bytecode"]),
-        p(a["tx"]) if rows(a["tx"]) else None, p(a["tx_flags"]) if rows(a["tx"]) else None, rows(a["tx"]),
-        p(a["block"]) if rows(a["block"]) else None, p(a["block_flags"]) if rows(a["block"]) else None, rows(a["block"]),
+def _evm_struct(a, begin_with_first_step=False, end_with_last_step=False):
+    """the ZkEvmTables block over prepared wire arrays `a`: a table that is missing from the dict or empty is a null pointer"""
+    n = {k: _rows(a.get(k)) for k in _EVM_CELLS}
+    return _lib.ZkEvmTables(
+        ptr(a["steps"]), n["steps"], ptr(a.get("rw"), n["rw"]), ptr(a.get("rw_flags"), n["rw"]), n["rw"],
+        ptr(a.get("bytecode"), n["bytecode"]), n["bytecode"], ptr(a.get("tx"), n["tx"]), ptr(a.get("tx_flags"), n["tx"]), n["tx"],
+        ptr(a.get("block"), n["block"]), ptr(a.get("block_flags"), n["block"]), n["block"],
         int(bool(begin_with_first_step)), int(bool(end_with_last_step)),
-        p(a["copy"]) if rows(a["copy"]) else None, rows(a["copy"]),
-        p(a["keccak"]) if rows(a["keccak"]) else None, rows(a["keccak"]),
-        p(a["exp"]) if rows(a["exp"]) else None, rows(a["exp"]),
-        p(a["aux"]) if rows(a["aux"]) else None, p(a["aux_kind"]) if rows(a["aux"]) else None,
-        p(a["withdrawals"]) if rows(a["withdrawals"]) else None, rows(a["withdrawals"]),
-        p(a["sig"]) if rows(a["sig"]) else None, rows(a["sig"]),
-        p(a["ecc"]) if rows(a["ecc"]) else None, rows(a["ecc"]),
-        int(a["aux"].shape[1]) if rows(a["aux"]) else 0, 0)
-    return t, opts, arrs, int(a["steps"].shape[0]) - 1
+        ptr(a.get("copy"), n["copy"]), n["copy"], ptr(a.get("keccak"), n["keccak"]), n["keccak"], ptr(a.get("exp"), n["exp"]), n["exp"],
+        ptr(a.get("aux"), n["aux"]), ptr(a.get("aux_kind"), n["aux"]),
+        ptr(a.get("withdrawals"), n["withdrawals"]), n["withdrawals"], ptr(a.get("sig"), n["sig"]), n["sig"],
+        ptr(a.get("ecc"), n["ecc"]), n["ecc"], int(a["aux"].shape[1]) if n["aux"] else 0, 0)
 
 
 def open_evm(wire, begin_with_first_step=False, end_with_last_step=False, device=None, state_sort=True,
@@ -226,21 +240,15 @@ def open_evm(wire, begin_with_first_step=False, end_with_last_step=False, device
         opts |= _lib.OPT_SINGLE_PASS
     if side_stream:  # warm / cold launches beside the hot one: pays when other sessions' passes share the device (include/zkevm_hip.h)
         opts |= _lib.OPT_SIDE_STREAM
-    h = ctypes.c_void_p()
-    check(lib.zk_evm_open(ctypes.byref(t), opts, ctypes.byref(h)), "zk_evm_open")
-    return Session(h, n_pairs, arrs, lib=lib)
+    return _open(lib, lib.zk_evm_open, n_pairs, arrs, ctypes.byref(t), opts)
 
 
 def evm_verify(wire, begin_with_first_step=False, end_with_last_step=False, status_dev=None, device=None):
     """The one-shot C entry zk_evm_verify (open + one pass + collect + close) over a wire dict of host arrays or of torch
     CUDA tensors (then status_dev, an optional CUDA uint32[n - 1] tensor, receives the per-pair status) -> Result."""
-    lib = _lib.init(device)
-    t, opts, arrs, n_pairs = _evm_tables(wire, begin_with_first_step, end_with_last_step)
-    if status_dev is not None:
-        _expect(status_dev, "status_dev", 4, (n_pairs,))
-    r = ZkResult()
-    check(lib.zk_evm_verify(ctypes.byref(t), opts, _lib.ptr(status_dev), ctypes.byref(r)), "zk_evm_verify")
-    return Result(r)
+    call = EvmOneShot(wire, begin_with_first_step, end_with_last_step, status_dev, device)
+    call()
+    return call.result()
 
 
 class EvmOneShot:
@@ -253,7 +261,7 @@ class EvmOneShot:
         if status_dev is not None:
             _expect(status_dev, "status_dev", 4, (self.n_pairs,))
         self._status = status_dev
-        self._status_ptr = _lib.ptr(status_dev)
+        self._status_ptr = ptr(status_dev)
         self._r = ZkResult()
         self._tref, self._rref = ctypes.byref(self._t), ctypes.byref(self._r)
 
@@ -306,88 +314,91 @@ def last_timing(lib=None):
     return a.value, b.value, c.value
 
 
-def open_bytecode(rows, keccak, randomness, device=None):
-    """rows uint64[12, n, 4], keccak uint64[m, 5, 4], randomness uint64[4] (or an int) -> Session"""
-    lib = _lib.init(device)
+def _bytecode_args(rows, keccak, randomness):
+    """zk_bytecode_open / zk_bytecode_verify -> ((rows, n, keccak, m, randomness), opts, kept arrays)"""
     randomness = _randomness_cells(randomness, rows)
     _expect(rows, "bytecode rows", 8, (12, None, 4))
     _expect(keccak, "keccak", 8, (None, 5, 4))
     _expect(randomness, "randomness", 8, (4,))
-    (rows, keccak, randomness), opts = _prep([rows, keccak, randomness])
-    n = rows.shape[1]
-    m = keccak.shape[0] if keccak is not None else 0
-    h = ctypes.c_void_p()
-    check(lib.zk_bytecode_open(_lib.ptr(rows), n, _lib.ptr(keccak) if m else None, m, _lib.ptr(randomness), opts,
-                               ctypes.byref(h)), "zk_bytecode_open")
-    return Session(h, n, (rows, keccak, randomness), lib=lib)
+    keep, opts = _prep([rows, keccak, randomness])
+    rows, keccak, randomness = keep
+    m = _rows(keccak)
+    return (ptr(rows), int(rows.shape[1]), ptr(keccak, m), m, ptr(randomness)), opts, keep
+
+
+def open_bytecode(rows, keccak, randomness, device=None):
+    """rows uint64[12, n, 4], keccak uint64[m, 5, 4], randomness uint64[4] (or an int) -> Session"""
+    lib = _lib.init(device)
+    args, opts, keep = _bytecode_args(rows, keccak, randomness)
+    return _open(lib, lib.zk_bytecode_open, args[1], keep, *args, opts)
+
+
+def _exp_args(rows):
+    """zk_exp_open / zk_exp_verify -> ((rows, n), opts, kept arrays)"""
+    _expect(rows, "exp rows", 8, (21, None, 4))
+    keep, opts = _prep([rows])
+    return (ptr(keep[0]), int(keep[0].shape[1])), opts, keep
 
 
 def open_exp(rows, device=None):
     """rows uint64[21, n, 4] -> Session"""
     lib = _lib.init(device)
-    _expect(rows, "exp rows", 8, (21, None, 4))
-    (rows,), opts = _prep([rows])
-    h = ctypes.c_void_p()
-    check(lib.zk_exp_open(_lib.ptr(rows), rows.shape[1], opts, ctypes.byref(h)), "zk_exp_open")
-    return Session(h, rows.shape[1], (rows,), lib=lib)
+    args, opts, keep = _exp_args(rows)
+    return _open(lib, lib.zk_exp_open, args[1], keep, *args, opts)
 
 
-def open_copy(rows, row_flags, randomness, rw, rw_flags, bytecode, tx, tx_flags, device=None, generic_index=False):
-    """Copy circuit session: rows uint64[20, n, 4] + flags, randomness (int or uint64[4]), EVM-format tables."""
-    lib = _lib.init(device)
+def _copy_tables(rows, row_flags, randomness, rw, rw_flags, bytecode, tx, tx_flags):
+    """zk_copy_open / zk_copy_verify -> (ZkCopyTables, opts, kept arrays)"""
     randomness = _randomness_cells(randomness, rows)
     _expect(rows, "copy rows", 8, (20, None, 4))
     _expect(row_flags, "copy row_flags", 4, (rows.shape[1],))
     _expect(rw, "rw", 8, (None, 14, 4))
     _expect(bytecode, "bytecode", 8, (None, 6, 4))
     _expect(tx, "tx", 8, (None, 5, 4))
-    arrs, opts = _prep([rows, row_flags, randomness, rw, rw_flags, bytecode, tx, tx_flags])
-    rows, row_flags, randomness, rw, rw_flags, bytecode, tx, tx_flags = arrs
+    keep, opts = _prep([rows, row_flags, randomness, rw, rw_flags, bytecode, tx, tx_flags])
+    rows, row_flags, randomness, rw, rw_flags, bytecode, tx, tx_flags = keep
+    n_rw, n_bc, n_tx = _rows(rw), _rows(bytecode), _rows(tx)
+    t = _lib.ZkCopyTables(ptr(rows), ptr(row_flags), int(rows.shape[1]), ptr(randomness), ptr(rw, n_rw), ptr(rw_flags, n_rw), n_rw,
+                          ptr(bytecode, n_bc), n_bc, ptr(tx, n_tx), ptr(tx_flags, n_tx), n_tx)
+    return t, opts, keep
 
-    def nrows(x):
-        return 0 if x is None else int(x.shape[0])
 
-    def p(x, n=1):
-        v = _lib.ptr(x) if n else None
-        return v.value if v is not None else None
-
-    t = _lib.ZkCopyTables(p(rows), p(row_flags), int(rows.shape[1]), p(randomness),
-                          p(rw, nrows(rw)), p(rw_flags, nrows(rw)), nrows(rw), p(bytecode, nrows(bytecode)), nrows(bytecode),
-                          p(tx, nrows(tx)), p(tx_flags, nrows(tx)), nrows(tx))
+def open_copy(rows, row_flags, randomness, rw, rw_flags, bytecode, tx, tx_flags, device=None, generic_index=False):
+    """Copy circuit session: rows uint64[20, n, 4] + flags, randomness (int or uint64[4]), EVM-format tables."""
+    lib = _lib.init(device)
+    t, opts, keep = _copy_tables(rows, row_flags, randomness, rw, rw_flags, bytecode, tx, tx_flags)
     if generic_index:
         opts |= _lib.OPT_GENERIC_INDEX
-    h = ctypes.c_void_p()
-    check(lib.zk_copy_open(ctypes.byref(t), opts, ctypes.byref(h)), "zk_copy_open")
-    return Session(h, int(rows.shape[1]), arrs, lib=lib)
+    return _open(lib, lib.zk_copy_open, int(t.n_rows), keep, ctypes.byref(t), opts)
 
 
-def open_sign(wire, randomness, is_sig, device=None):
-    """Tx / Sig circuit session over `wire` = dict(bytes, cells, meta, keccak, tx_rows, tx_flags)."""
-    lib = _lib.init(device)
+_SIGN_WIRE = ("bytes", "cells", "meta", "keccak", "tx_rows", "tx_flags")
+
+
+def _sign_units(wire, randomness, is_sig):
+    """zk_sign_open / zk_sign_verify over `wire` = dict(bytes, cells, meta, keccak, tx_rows, tx_flags) -> (ZkSignUnits, opts, kept arrays)"""
     randomness = _randomness_cells(randomness, wire.get("bytes"))
-    names = ["bytes", "cells", "meta", "keccak", "tx_rows", "tx_flags"]
     _expect(wire.get("bytes"), "sign bytes", 1, (None, 9, 32))
     _expect(wire.get("cells"), "sign cells", 8, (8, wire["bytes"].shape[0], 4))
     _expect(wire.get("meta"), "sign meta", 4, (wire["bytes"].shape[0], 4))
     _expect(wire.get("keccak"), "keccak", 8, (None, 5, 4))
     _expect(wire.get("tx_rows"), "tx_rows", 8, (None, 5, 4))
-    arrs, opts = _prep([wire.get(k) for k in names] + [randomness])
-    a = dict(zip(names + ["r"], arrs))
+    keep, opts = _prep([wire.get(k) for k in _SIGN_WIRE] + [randomness])
+    return _sign_struct(dict(zip(_SIGN_WIRE, keep)), keep[-1], is_sig), opts, keep
 
-    def nrows(x):
-        return 0 if x is None else int(x.shape[0])
 
-    def p(x, n=1):
-        v = _lib.ptr(x) if n else None
-        return v.value if v is not None else None
+def _sign_struct(a, randomness, is_sig):
+    """the ZkSignUnits block over prepared arrays `a` (by _SIGN_WIRE name): an empty keccak or tx table is a null pointer"""
+    n_k, n_tx = _rows(a["keccak"]), _rows(a["tx_rows"])
+    return _lib.ZkSignUnits(ptr(a["bytes"]), ptr(a["cells"]), ptr(a["meta"]), _rows(a["bytes"]), ptr(randomness), ptr(a["keccak"], n_k), n_k,
+                            ptr(a["tx_rows"], n_tx), ptr(a["tx_flags"], n_tx), n_tx, int(bool(is_sig)))
 
-    n = int(a["bytes"].shape[0])
-    t = _lib.ZkSignUnits(p(a["bytes"]), p(a["cells"]), p(a["meta"]), n, p(a["r"]), p(a["keccak"], nrows(a["keccak"])),
-                         nrows(a["keccak"]), p(a["tx_rows"], nrows(a["tx_rows"])), p(a["tx_flags"], nrows(a["tx_rows"])),
-                         nrows(a["tx_rows"]), int(bool(is_sig)))
-    h = ctypes.c_void_p()
-    check(lib.zk_sign_open(ctypes.byref(t), opts, ctypes.byref(h)), "zk_sign_open")
-    return Session(h, n, arrs, lib=lib)
+
+def open_sign(wire, randomness, is_sig, device=None):
+    """Tx / Sig circuit session over `wire` = dict(bytes, cells, meta, keccak, tx_rows, tx_flags)."""
+    lib = _lib.init(device)
+    t, opts, keep = _sign_units(wire, randomness, is_sig)
+    return _open(lib, lib.zk_sign_open, int(t.n_units), keep, ctypes.byref(t), opts)
 
 
 KECCAK_MODE_CIRCUIT = 0  # KeccakCircuit.add rows (EVM / bytecode circuits)
@@ -399,7 +410,7 @@ class KeccakSession(Session):
 
     def rows(self):
         out = np.empty((self.n, 5, 4), dtype=np.uint64)
-        check(self._lib.zk_keccak_read_rows(self._h, _lib.ptr(out)), "zk_keccak_read_rows", self._lib)
+        check(self._lib.zk_keccak_read_rows(self._h, ptr(out)), "zk_keccak_read_rows", self._lib)
         return out
 
 
@@ -412,33 +423,32 @@ def pack_messages(messages):
     return data, offsets
 
 
+def _keccak_args(data, offsets, randomness, mode, rows_out=None):
+    """zk_keccak_open / zk_keccak_table -> ((data, n_bytes, offsets, n, randomness, mode, rows_out), opts, kept arrays); rows_out:
+    uint64[n, 5, 4] receiving the rows (optional for a session)"""
+    randomness = _randomness_cells(randomness, data)
+    _expect(data, "keccak data", 1, (None,))
+    _expect(offsets, "keccak offsets", 8, (None,))
+    _expect(rows_out, "keccak rows_dev", 8, (int(offsets.shape[0]) - 1, 5, 4))
+    keep, opts = _prep([data, offsets, randomness, rows_out], outputs=(3,))
+    data, offsets, randomness, rows_out = keep
+    n_bytes = _rows(data)
+    return (ptr(data, n_bytes), n_bytes, ptr(offsets), int(offsets.shape[0]) - 1, ptr(randomness), int(mode), ptr(rows_out)), opts, keep
+
+
 def open_keccak(data, offsets, randomness, mode=KECCAK_MODE_CIRCUIT, rows_dev=None, device=None):
     """data uint8[total], offsets uint64[n + 1], randomness (int or uint64[4]) -> KeccakSession.
     numpy arrays are staged to HBM; torch CUDA tensors are used in place (rows_dev: optional
     CUDA uint64[n, 5, 4] tensor receiving the rows)."""
     lib = _lib.init(device)
-    if isinstance(randomness, int):
-        randomness = np.frombuffer(int(randomness).to_bytes(32, "little"), dtype="<u8").copy()
-        if _is_device(data):
-            import torch
-            randomness = torch.from_numpy(randomness.view(np.int64)).to(data.device)
-    _expect(data, "keccak data", 1, (None,))
-    _expect(offsets, "keccak offsets", 8, (None,))
-    _expect(rows_dev, "keccak rows_dev", 8, (int(offsets.shape[0]) - 1, 5, 4))
-    (data, offsets, randomness, rows_dev), opts = _prep([data, offsets, randomness, rows_dev], outputs=(3,))
-    n = int(offsets.shape[0]) - 1
-    n_bytes = int(data.shape[0]) if data is not None else 0
-    h = ctypes.c_void_p()
-    check(lib.zk_keccak_open(_lib.ptr(data) if n_bytes else None, n_bytes, _lib.ptr(offsets), n, _lib.ptr(randomness),
-                             int(mode), _lib.ptr(rows_dev), opts, ctypes.byref(h)), "zk_keccak_open")
-    return KeccakSession(h, n, (data, offsets, randomness, rows_dev), lib=lib)
+    args, opts, keep = _keccak_args(data, offsets, randomness, mode, rows_dev)
+    return _open(lib, lib.zk_keccak_open, args[3], keep, *args, opts, cls=KeccakSession)
 
 
 def keccak_table(messages, randomness, mode=KECCAK_MODE_CIRCUIT, device=None):
     """Keccak table rows uint64[n, 5, 4] of a list of byte strings, computed on the GPU
     (replaces KeccakCircuit.add / KeccakTable.add loops; see include/zkevm_hip.h).  Raises the
     reference's ValueError for a mode-1 input longer than 64 bytes."""
-    from .errors import exception_for_code
     if len(messages) == 0:
         return np.zeros((0, 5, 4), dtype=np.uint64)
     data, offsets = pack_messages(messages)
@@ -466,9 +476,24 @@ class AssignSession(Session):
         flags = np.empty(self.n, dtype=np.uint32)
         mpt = np.empty((m, 12, 4), dtype=np.uint64)
         got = ctypes.c_uint64()
-        check(self._lib.zk_state_assign_read(self._h, _lib.ptr(rows), _lib.ptr(flags), _lib.ptr(mpt) if m else None, m,
-                                               ctypes.byref(got)), "zk_state_assign_read")
+        check(self._lib.zk_state_assign_read(self._h, ptr(rows), ptr(flags), ptr(mpt, m), m, ctypes.byref(got)), "zk_state_assign_read")
         return rows, flags, mpt
+
+
+def _state_assign_args(ops, op_flags, outs=(None, None, None), compact=False):
+    """zk_state_assign_open / zk_state_assign -> ((ops, op_flags, n), opts, kept arrays); outs: a session's (rows_dev,
+    row_flags_dev, mpt_dev), prepared with the inputs (kept arrays 2..4)"""
+    _expect(ops, "state ops", 8, (12, None, 4))
+    n = int(ops.shape[1])
+    _expect(op_flags, "op_flags", 4, (n,))
+    rows_dev, row_flags_dev, mpt_dev = outs
+    _expect(rows_dev, "rows_dev", 8, (15 if compact else 57, n, 4))
+    _expect(row_flags_dev, "row_flags_dev", 4, (n,))
+    _expect(mpt_dev, "mpt_dev", 8, (n, 12, 4))
+    keep, opts = _prep([ops, op_flags, *outs], outputs=(2, 3, 4))
+    if compact:
+        opts |= _lib.OPT_STATE_COMPACT
+    return (ptr(keep[0]), ptr(keep[1]), n), opts, keep
 
 
 def open_state_assign(ops, op_flags, rows_dev=None, row_flags_dev=None, mpt_dev=None, device=None, compact=False):
@@ -477,22 +502,24 @@ def open_state_assign(ops, op_flags, rows_dev=None, row_flags_dev=None, mpt_dev=
     row_flags_dev uint32[n] / mpt_dev uint64[n, 12, 4] (optional CUDA tensors) then receive the outputs, ready
     to be handed to open_state()."""
     lib = _lib.init(device)
-    _expect(ops, "state ops", 8, (12, None, 4))
-    n = int(ops.shape[1])
-    _expect(op_flags, "op_flags", 4, (n,))
-    _expect(rows_dev, "rows_dev", 8, (15 if compact else 57, n, 4))
-    _expect(row_flags_dev, "row_flags_dev", 4, (n,))
-    _expect(mpt_dev, "mpt_dev", 8, (n, 12, 4))
-    (ops, op_flags, rows_dev, row_flags_dev, mpt_dev), opts = _prep([ops, op_flags, rows_dev, row_flags_dev, mpt_dev],
-                                                                    outputs=(2, 3, 4))
-    if compact:
-        opts |= _lib.OPT_STATE_COMPACT
-    h = ctypes.c_void_p()
-    check(lib.zk_state_assign_open(_lib.ptr(ops), _lib.ptr(op_flags), n, _lib.ptr(rows_dev), _lib.ptr(row_flags_dev),
-                                   _lib.ptr(mpt_dev), opts, ctypes.byref(h)), "zk_state_assign_open")
-    s = AssignSession(h, n, (ops, op_flags, rows_dev, row_flags_dev, mpt_dev), lib=lib)
+    args, opts, keep = _state_assign_args(ops, op_flags, (rows_dev, row_flags_dev, mpt_dev), compact)
+    s = _open(lib, lib.zk_state_assign_open, args[2], keep, *args, ptr(keep[2]), ptr(keep[3]), ptr(keep[4]), opts, cls=AssignSession)
     s.compact = bool(compact)
     return s
+
+
+def _rw_args(rw, rw_flags, outs=()):
+    """zk_state_ops_from_rw* / zk_state_assign_from_rw_open / zk_state_verify_from_rw* -> ((rw, rw_flags, n), opts, kept arrays);
+    outs: a session's flat output buffers as (buffer, name, itemsize, entries per RW row + 1), prepared with the inputs"""
+    _expect(rw, "rw table", 8, (None, 14, 4))
+    n = int(rw.shape[0])
+    _expect(rw_flags, "rw_flags", 4, (n,))
+    for buf, name, size, per_row in outs:
+        _expect(buf, name, size, (None,))
+        if buf is not None and int(buf.shape[0]) < per_row * (n + 1):
+            raise ValueError(f"{name} holds fewer than {per_row * (n + 1)} entries")
+    keep, opts = _prep([rw, rw_flags] + [o[0] for o in outs], outputs=range(2, 2 + len(outs)))
+    return (ptr(keep[0]), ptr(keep[1]), n), opts, keep
 
 
 def open_state_assign_from_rw(rw, rw_flags, rows_dev=None, row_flags_dev=None, mpt_dev=None, device=None, compact=False):
@@ -502,20 +529,14 @@ def open_state_assign_from_rw(rw, rw_flags, rows_dev=None, row_flags_dev=None, m
     57 * (n + 1) * 4 / n + 1 / (n + 1) * 12 * 4 receiving the outputs packed for n_ops: rows_dev[: 57 * n_ops * 4].view(57, n_ops, 4)
     etc. are what open_state takes."""
     lib = _lib.init(device)
-    _expect(rw, "rw table", 8, (None, 14, 4))
-    n = int(rw.shape[0])
-    _expect(rw_flags, "rw_flags", 4, (n,))
-    for buf, name, size, cap in ((rows_dev, "rows_dev", 8, (15 if compact else 57) * 4 * (n + 1)), (row_flags_dev, "row_flags_dev", 4, n + 1), (mpt_dev, "mpt_dev", 8, 48 * (n + 1))):
-        _expect(buf, name, size, (None,))
-        if buf is not None and int(buf.shape[0]) < cap:
-            raise ValueError(f"{name} holds fewer than {cap} entries")
-    (rw, rw_flags, rows_dev, row_flags_dev, mpt_dev), opts = _prep([rw, rw_flags, rows_dev, row_flags_dev, mpt_dev], outputs=(2, 3, 4))
+    outs = ((rows_dev, "rows_dev", 8, (15 if compact else 57) * 4), (row_flags_dev, "row_flags_dev", 4, 1), (mpt_dev, "mpt_dev", 8, 48))
+    args, opts, keep = _rw_args(rw, rw_flags, outs)
     if compact:
         opts |= _lib.OPT_STATE_COMPACT
     h, n_ops = ctypes.c_void_p(), ctypes.c_uint64()
-    check(lib.zk_state_assign_from_rw_open(_lib.ptr(rw), _lib.ptr(rw_flags), n, _lib.ptr(rows_dev), _lib.ptr(row_flags_dev), _lib.ptr(mpt_dev),
-                                           opts, ctypes.byref(n_ops), ctypes.byref(h)), "zk_state_assign_from_rw_open")
-    s = AssignSession(h, int(n_ops.value), (rw, rw_flags, rows_dev, row_flags_dev, mpt_dev), lib=lib)
+    check(lib.zk_state_assign_from_rw_open(*args, ptr(keep[2]), ptr(keep[3]), ptr(keep[4]), opts, ctypes.byref(n_ops), ctypes.byref(h)),
+          "zk_state_assign_from_rw_open")
+    s = AssignSession(h, int(n_ops.value), keep, lib=lib)
     s.compact = bool(compact)
     return s
 
@@ -525,13 +546,10 @@ def open_state_verify_from_rw(rw, rw_flags, device=None):
     (session.n), which are evaluated where they are computed and never stored (zk_state_verify_from_rw_open): collect() is the State
     circuit's Result; an RW row the re-keying rejects or an op the assignment raises on makes collect() raise EngineError."""
     lib = _lib.init(device)
-    _expect(rw, "rw table", 8, (None, 14, 4))
-    n = int(rw.shape[0])
-    _expect(rw_flags, "rw_flags", 4, (n,))
-    (rw, rw_flags), opts = _prep([rw, rw_flags])
+    args, opts, keep = _rw_args(rw, rw_flags)
     h, n_ops = ctypes.c_void_p(), ctypes.c_uint64()
-    check(lib.zk_state_verify_from_rw_open(_lib.ptr(rw), _lib.ptr(rw_flags), n, opts, ctypes.byref(n_ops), ctypes.byref(h)), "zk_state_verify_from_rw_open", lib)
-    return Session(h, int(n_ops.value), (rw, rw_flags), lib=lib)
+    check(lib.zk_state_verify_from_rw_open(*args, opts, ctypes.byref(n_ops), ctypes.byref(h)), "zk_state_verify_from_rw_open", lib)
+    return Session(h, int(n_ops.value), keep, lib=lib)
 
 
 class RekeySession(Session):
@@ -543,7 +561,7 @@ class RekeySession(Session):
     def read(self):
         ops = np.empty((12, self.n_ops, 4), dtype=np.uint64)
         flags = np.empty(self.n_ops, dtype=np.uint32)
-        check(self._lib.zk_state_ops_from_rw_read(self._h, _lib.ptr(ops), _lib.ptr(flags), None), "zk_state_ops_from_rw_read", self._lib)
+        check(self._lib.zk_state_ops_from_rw_read(self._h, ptr(ops), ptr(flags), None), "zk_state_ops_from_rw_read", self._lib)
         return ops, flags
 
 
@@ -553,20 +571,10 @@ def open_state_ops_from_rw(rw, rw_flags, ops_dev=None, op_flags_dev=None, device
     (n + 1 uint32) then receive the op list packed for session.n_ops ops: ops_dev[: 12 * n_ops * 4].view(12, n_ops, 4) is what
     open_state_assign takes."""
     lib = _lib.init(device)
-    _expect(rw, "rw table", 8, (None, 14, 4))
-    n = int(rw.shape[0])
-    _expect(rw_flags, "rw_flags", 4, (n,))
-    _expect(ops_dev, "ops_dev", 8, (None,))
-    _expect(op_flags_dev, "op_flags_dev", 4, (None,))
-    if ops_dev is not None and int(ops_dev.shape[0]) < 48 * (n + 1):
-        raise ValueError("ops_dev holds fewer than 12 * (n + 1) cells")
-    if op_flags_dev is not None and int(op_flags_dev.shape[0]) < n + 1:
-        raise ValueError("op_flags_dev holds fewer than n + 1 entries")
-    (rw, rw_flags, ops_dev, op_flags_dev), opts = _prep([rw, rw_flags, ops_dev, op_flags_dev], outputs=(2, 3))
+    args, opts, keep = _rw_args(rw, rw_flags, ((ops_dev, "ops_dev", 8, 48), (op_flags_dev, "op_flags_dev", 4, 1)))
     h, n_ops = ctypes.c_void_p(), ctypes.c_uint64()
-    check(lib.zk_state_ops_from_rw_open(_lib.ptr(rw), _lib.ptr(rw_flags), n, _lib.ptr(ops_dev), _lib.ptr(op_flags_dev), opts,
-                                        ctypes.byref(n_ops), ctypes.byref(h)), "zk_state_ops_from_rw_open")
-    s = RekeySession(h, n, (rw, rw_flags, ops_dev, op_flags_dev), lib=lib)
+    check(lib.zk_state_ops_from_rw_open(*args, ptr(keep[2]), ptr(keep[3]), opts, ctypes.byref(n_ops), ctypes.byref(h)), "zk_state_ops_from_rw_open")
+    s = RekeySession(h, args[2], keep, lib=lib)
     s.n_ops = int(n_ops.value)
     return s
 
@@ -576,8 +584,22 @@ class BytecodeAssignSession(Session):
 
     def rows(self):
         out = np.empty((12, self.n, 4), dtype=np.uint64)
-        check(self._lib.zk_bytecode_assign_read(self._h, _lib.ptr(out)), "zk_bytecode_assign_read", self._lib)
+        check(self._lib.zk_bytecode_assign_read(self._h, ptr(out)), "zk_bytecode_assign_read", self._lib)
         return out
+
+
+def _bytecode_assign_args(in_rows, offsets, lengths, k, randomness, rows_out=None):
+    """zk_bytecode_assign_open / zk_bytecode_assign -> ((in_rows, n_rows, offsets, lengths, n_codes, k, randomness, rows_out), opts,
+    kept arrays); rows_out: uint64[12, 2^k, 4] receiving the circuit rows (optional for a session)"""
+    randomness = _randomness_cells(randomness, in_rows)
+    _expect(in_rows, "unrolled bytecode rows", 8, (None, 6, 4))
+    _expect(offsets, "offsets", 8, (int(lengths.shape[0]) + 1,))
+    _expect(lengths, "lengths", 8, (None,))
+    _expect(rows_out, "rows_dev", 8, (12, 1 << int(k), 4))
+    keep, opts = _prep([in_rows, offsets, lengths, randomness, rows_out], outputs=(4,))
+    in_rows, offsets, lengths, randomness, rows_out = keep
+    n_rows, n_codes = _rows(in_rows), _rows(lengths)
+    return (ptr(in_rows, n_rows), n_rows, ptr(offsets), ptr(lengths, n_codes), n_codes, int(k), ptr(randomness), ptr(rows_out)), opts, keep
 
 
 def open_bytecode_assign(in_rows, offsets, lengths, k, randomness, rows_dev=None, device=None):
@@ -585,43 +607,42 @@ def open_bytecode_assign(in_rows, offsets, lengths, k, randomness, rows_dev=None
     randomness (int or uint64[4]) -> BytecodeAssignSession over the 2^k circuit rows; rows_dev: optional CUDA tensor
     uint64[12, 2^k, 4] receiving them in place (ready for open_bytecode)."""
     lib = _lib.init(device)
-    randomness = _randomness_cells(randomness, in_rows)
-    _expect(in_rows, "unrolled bytecode rows", 8, (None, 6, 4))
-    _expect(offsets, "offsets", 8, (int(lengths.shape[0]) + 1,))
-    _expect(lengths, "lengths", 8, (None,))
-    _expect(rows_dev, "rows_dev", 8, (12, 1 << int(k), 4))
-    (in_rows, offsets, lengths, randomness, rows_dev), opts = _prep([in_rows, offsets, lengths, randomness, rows_dev],
-                                                                    outputs=(4,))
-    n_rows, n_codes = int(in_rows.shape[0]), int(lengths.shape[0])
-    h = ctypes.c_void_p()
-    check(lib.zk_bytecode_assign_open(_lib.ptr(in_rows) if n_rows else None, n_rows, _lib.ptr(offsets), _lib.ptr(lengths) if n_codes else None,
-                                      n_codes, int(k), _lib.ptr(randomness), _lib.ptr(rows_dev), opts, ctypes.byref(h)),
-          "zk_bytecode_assign_open")
-    return BytecodeAssignSession(h, 1 << int(k), (in_rows, offsets, lengths, randomness, rows_dev), lib=lib)
+    args, opts, keep = _bytecode_assign_args(in_rows, offsets, lengths, k, randomness, rows_dev)
+    return _open(lib, lib.zk_bytecode_assign_open, 1 << int(k), keep, *args, opts, cls=BytecodeAssignSession)
+
+
+def _pi_args(rows, keccak, gas, circuit_len, keccak_rand, byte_pow_base):
+    """zk_pi_open / zk_pi_verify -> ((rows, n, keccak, m, gas, k, circuit_len, keccak_rand, byte_pow_base), opts, kept arrays)"""
+    kr, bp = _randomness_cells(int(keccak_rand), rows), _randomness_cells(int(byte_pow_base), rows)
+    _expect(rows, "pi rows", 8, (24, None, 4))
+    _expect(keccak, "keccak", 8, (None, 5, 4))
+    _expect(gas, "gas-cost table", 8, (None, 3, 4))
+    keep, opts = _prep([rows, keccak, gas, kr, bp])
+    rows, keccak, gas, kr, bp = keep
+    m, k = _rows(keccak), _rows(gas)
+    return (ptr(rows), int(rows.shape[1]), ptr(keccak, m), m, ptr(gas, k), k, int(circuit_len), ptr(kr), ptr(bp)), opts, keep
 
 
 def open_pi(rows, keccak, gas, circuit_len, keccak_rand=255, byte_pow_base=255, device=None):
     """Public-inputs circuit session: rows uint64[24, n, 4], keccak uint64[m, 5, 4], gas uint64[k, 3, 4] (include/zkevm_hip.h)"""
     lib = _lib.init(device)
-    kr, bp = _randomness_cells(int(keccak_rand), rows), _randomness_cells(int(byte_pow_base), rows)
-    _expect(rows, "pi rows", 8, (24, None, 4))
-    _expect(keccak, "keccak", 8, (None, 5, 4))
-    _expect(gas, "gas-cost table", 8, (None, 3, 4))
-    (rows, keccak, gas, kr, bp), opts = _prep([rows, keccak, gas, kr, bp])
-    n, m, k = int(rows.shape[1]), int(keccak.shape[0]) if keccak is not None else 0, int(gas.shape[0]) if gas is not None else 0
-    h = ctypes.c_void_p()
-    check(lib.zk_pi_open(_lib.ptr(rows), n, _lib.ptr(keccak) if m else None, m, _lib.ptr(gas) if k else None, k, int(circuit_len), _lib.ptr(kr),
-                         _lib.ptr(bp), opts, ctypes.byref(h)), "zk_pi_open")
-    return Session(h, n, (rows, keccak, gas, kr, bp), lib=lib)
+    args, opts, keep = _pi_args(rows, keccak, gas, circuit_len, keccak_rand, byte_pow_base)
+    return _open(lib, lib.zk_pi_open, args[1], keep, *args, opts)
+
+
+def _pi_copy_args(cells, data, lens):
+    """zk_pi_copy_verify -> ((cells, data, lens, n), opts, kept arrays)"""
+    _expect(cells, "pi copy cells", 8, (None, 4))
+    _expect(data, "pi copy bytes", 1, (cells.shape[0], 32))
+    _expect(lens, "pi copy lens", 4, (cells.shape[0],))
+    keep, opts = _prep([cells, data, lens])
+    cells, data, lens = keep
+    return (ptr(cells), ptr(data), ptr(lens), int(cells.shape[0])), opts, keep
 
 
 def _copy_events_struct(events, flags, data, offsets, randomness):
-    def p(x):
-        v = _lib.ptr(x)
-        return v.value if v is not None else None
-
-    return _lib.ZkCopyEvents(p(events), p(flags), int(events.shape[0]), p(data) if data is not None and int(data.shape[0]) else None,
-                             p(offsets), p(randomness))
+    """the ZkCopyEvents block over prepared arrays: empty source data is a null pointer"""
+    return _lib.ZkCopyEvents(ptr(events), ptr(flags), int(events.shape[0]), ptr(data, _rows(data)), ptr(offsets), ptr(randomness))
 
 
 def copy_assign_sizes(events, flags, data, offsets, device=None):
@@ -635,6 +656,25 @@ def copy_assign_sizes(events, flags, data, offsets, device=None):
     return int(a.value), int(b.value), int(c.value)
 
 
+def _copy_assign_args(events, flags, data, offsets, randomness, device, outs=(None,) * 5):
+    """zk_copy_assign_open / zk_copy_assign -> (ZkCopyEvents, opts, kept arrays, (n_rows, n_table, n_rw)); outs: a session's
+    (rows_dev, row_flags_dev, table_dev, rw_dev, rw_flags_dev), checked against the sizes and prepared with the inputs (kept arrays 5..9)"""
+    randomness = _randomness_cells(randomness, events)
+    _expect(events, "copy events", 8, (None, 12, 4))
+    _expect(flags, "copy event flags", 4, (events.shape[0],))
+    _expect(data, "copy source data", 2, (None,))
+    _expect(offsets, "copy data offsets", 8, (int(events.shape[0]) + 1,))
+    sizes = n_rows, n_table, n_rw = copy_assign_sizes(events, flags, data, offsets, device)
+    rows_dev, row_flags_dev, table_dev, rw_dev, rw_flags_dev = outs
+    _expect(rows_dev, "rows_dev", 8, (20, n_rows, 4))
+    _expect(row_flags_dev, "row_flags_dev", 4, (n_rows,))
+    _expect(table_dev, "table_dev", 8, (n_table, 14, 4))
+    _expect(rw_dev, "rw_dev", 8, (n_rw, 14, 4))
+    _expect(rw_flags_dev, "rw_flags_dev", 4, (n_rw,))
+    keep, opts = _prep([events, flags, data, offsets, randomness, *outs], outputs=(5, 6, 7, 8, 9))
+    return _copy_events_struct(*keep[:5]), opts, keep, sizes
+
+
 class CopyAssignSession(Session):
     """Copy-circuit witness assignment session: launch()/collect() like the circuits; read() for the outputs."""
 
@@ -643,8 +683,8 @@ class CopyAssignSession(Session):
         rows, rf = np.empty((20, self.n, 4), dtype=np.uint64), np.empty(self.n, dtype=np.uint32)
         table = np.empty((self.n_table, 14, 4), dtype=np.uint64)
         rw, rwf = np.empty((self.n_rw, 14, 4), dtype=np.uint64), np.empty(self.n_rw, dtype=np.uint32)
-        check(self._lib.zk_copy_assign_read(self._h, _lib.ptr(rows), _lib.ptr(rf), _lib.ptr(table) if self.n_table else None,
-                                              _lib.ptr(rw) if self.n_rw else None, _lib.ptr(rwf) if self.n_rw else None), "zk_copy_assign_read")
+        check(self._lib.zk_copy_assign_read(self._h, ptr(rows), ptr(rf), ptr(table, self.n_table), ptr(rw, self.n_rw), ptr(rwf, self.n_rw)),
+              "zk_copy_assign_read")
         return rows, rf, table, rw, rwf
 
 
@@ -655,25 +695,9 @@ def open_copy_assign(events, flags, data, offsets, randomness, rows_dev=None, ro
     used in place and the optional *_dev tensors (sized with copy_assign_sizes) receive the outputs, ready for open_copy /
     open_evm."""
     lib = _lib.init(device)
-    randomness = _randomness_cells(randomness, events)
-    _expect(events, "copy events", 8, (None, 12, 4))
-    _expect(flags, "copy event flags", 4, (events.shape[0],))
-    _expect(data, "copy source data", 2, (None,))
-    _expect(offsets, "copy data offsets", 8, (int(events.shape[0]) + 1,))
-    n_rows, n_table, n_rw = copy_assign_sizes(events, flags, data, offsets, device)
-    _expect(rows_dev, "rows_dev", 8, (20, n_rows, 4))
-    _expect(row_flags_dev, "row_flags_dev", 4, (n_rows,))
-    _expect(table_dev, "table_dev", 8, (n_table, 14, 4))
-    _expect(rw_dev, "rw_dev", 8, (n_rw, 14, 4))
-    _expect(rw_flags_dev, "rw_flags_dev", 4, (n_rw,))
-    arrs, opts = _prep([events, flags, data, offsets, randomness, rows_dev, row_flags_dev, table_dev, rw_dev, rw_flags_dev],
-                       outputs=(5, 6, 7, 8, 9))
-    events, flags, data, offsets, randomness, rows_dev, row_flags_dev, table_dev, rw_dev, rw_flags_dev = arrs
-    t = _copy_events_struct(events, flags, data, offsets, randomness)
-    h = ctypes.c_void_p()
-    check(lib.zk_copy_assign_open(ctypes.byref(t), _lib.ptr(rows_dev), _lib.ptr(row_flags_dev), _lib.ptr(table_dev), _lib.ptr(rw_dev),
-                                  _lib.ptr(rw_flags_dev), opts, ctypes.byref(h)), "zk_copy_assign_open")
-    s = CopyAssignSession(h, n_rows, arrs, lib=lib)
+    t, opts, keep, (n_rows, n_table, n_rw) = _copy_assign_args(events, flags, data, offsets, randomness, device,
+                                                               (rows_dev, row_flags_dev, table_dev, rw_dev, rw_flags_dev))
+    s = _open(lib, lib.zk_copy_assign_open, n_rows, keep, ctypes.byref(t), *(ptr(x) for x in keep[5:]), opts, cls=CopyAssignSession)
     s.n_table, s.n_rw = n_table, n_rw
     return s
 
@@ -683,18 +707,22 @@ ECDSA_LAYOUT_TX_UNITS = 1   # uint8[n, 9, 32]: the Tx units' byte rows (open_sig
 ECDSA_LAYOUT_SIG_UNITS = 2  # the Sig units' byte rows (msg_hash big-endian; v = meta[:, 3])
 
 
+def _ecdsa_args(sig_bytes, v, layout, v_stride, out_dev=None):
+    """zk_ecdsa_open / zk_ecdsa_verify / a ZkEcdsaBatch -> ((sig_bytes, layout, v, v_stride, n), opts, kept arrays); out_dev: a
+    session's status buffer, prepared with the inputs (kept array 2)"""
+    _expect(sig_bytes, "signature bytes", 1, (None, 5 if layout == ECDSA_LAYOUT_PACKED else 9, 32))
+    keep, opts = _prep([sig_bytes, v, out_dev], outputs=(2,))
+    sig_bytes, v, _ = keep
+    return (ptr(sig_bytes), int(layout), ptr(v), int(v_stride), int(sig_bytes.shape[0])), opts, keep
+
+
 def open_ecdsa(sig_bytes, v=None, layout=ECDSA_LAYOUT_PACKED, out_dev=None, out_stride=1, device=None, v_stride=1):
     """secp256k1 ECDSA verification session: status per signature = the `ecdsa_status` column of the Tx / Sig units
     (0 verified, 1 not verified, else the exception's code; include/zkevm_hip.h).  out_dev: optional CUDA uint32
     tensor receiving status i at element i * out_stride (e.g. the units' meta tensor with stride 4)."""
     lib = _lib.init(device)
-    _expect(sig_bytes, "signature bytes", 1, (None, 5 if layout == ECDSA_LAYOUT_PACKED else 9, 32))
-    (sig_bytes, v, out_dev), opts = _prep([sig_bytes, v, out_dev], outputs=(2,))
-    n = int(sig_bytes.shape[0])
-    h = ctypes.c_void_p()
-    check(lib.zk_ecdsa_open(_lib.ptr(sig_bytes), int(layout), _lib.ptr(v), int(v_stride), n, _lib.ptr(out_dev),
-                            int(out_stride), opts, ctypes.byref(h)), "zk_ecdsa_open")
-    return Session(h, n, (sig_bytes, v, out_dev), lib=lib)
+    args, opts, keep = _ecdsa_args(sig_bytes, v, layout, v_stride, out_dev)
+    return _open(lib, lib.zk_ecdsa_open, args[4], keep, *args, ptr(keep[2]), int(out_stride), opts)
 
 
 def open_ecdsa_batches(batches, device=None):
@@ -703,19 +731,13 @@ def open_ecdsa_batches(batches, device=None):
     lib = _lib.init(device)
     keep, arr, opts_all, n_total = [], (_lib.ZkEcdsaBatch * len(batches))(), None, 0
     for k, b in enumerate(batches):
-        layout = b.get("layout", ECDSA_LAYOUT_PACKED)
-        _expect(b["sig_bytes"], "signature bytes", 1, (None, 5 if layout == ECDSA_LAYOUT_PACKED else 9, 32))
-        (sb, v, od), opts = _prep([b["sig_bytes"], b.get("v"), b.get("out_dev")], outputs=(2,))
+        args, opts, kb = _ecdsa_args(b["sig_bytes"], b.get("v"), b.get("layout", ECDSA_LAYOUT_PACKED), b.get("v_stride", 1), b.get("out_dev"))
         assert opts_all is None or opts == opts_all, "mix of host and device batches"
         opts_all = opts
-        keep += [sb, v, od]
-        n = int(sb.shape[0])
-        n_total += n
-        pv = lambda x: None if x is None else _lib.ptr(x).value  # noqa: E731
-        arr[k] = _lib.ZkEcdsaBatch(pv(sb), int(layout), pv(v), int(b.get("v_stride", 1)), n, pv(od), int(b.get("out_stride", 1)))
-    h = ctypes.c_void_p()
-    check(lib.zk_ecdsa_open_batches(arr, len(batches), opts_all, ctypes.byref(h)), "zk_ecdsa_open_batches")
-    return Session(h, n_total, tuple(keep), lib=lib)
+        keep += kb
+        n_total += args[4]
+        arr[k] = _lib.ZkEcdsaBatch(*args, ptr(kb[2]), int(b.get("out_stride", 1)))
+    return _open(lib, lib.zk_ecdsa_open_batches, n_total, tuple(keep), arr, len(batches), opts_all)
 
 
 def ecdsa_status(sig_bytes, v=None, layout=ECDSA_LAYOUT_PACKED, device=None, v_stride=1):
@@ -731,19 +753,58 @@ def fr_op(op, a, b):
     a = np.ascontiguousarray(a, dtype=np.uint64)
     b = np.ascontiguousarray(b, dtype=np.uint64)
     out = np.empty_like(a)
-    check(lib.zk_fr_op(int(op), _lib.ptr(a), _lib.ptr(b), _lib.ptr(out), a.shape[0], 0), "zk_fr_op")
+    check(lib.zk_fr_op(int(op), ptr(a), ptr(b), ptr(out), a.shape[0], 0), "zk_fr_op")
     return out
+
+
+def _ecc_ops(w, randomness):
+    """zk_ecc_assign / zk_ecc_verify over the arrays of flatten.flatten_ecc_ops (made host arrays) -> (ZkEccOps, opts 0, kept arrays)"""
+    w = {k: (_host(v) if isinstance(v, np.ndarray) else v) for k, v in w.items()}
+    randomness = _host(_randomness_cells(randomness, None))
+    pts, pair_pts, pair_off, pair_out = w["points"], w["pair_pts"], w["pair_off"], w["pair_out"]
+    _expect(pts, "ecc points", 8, (None, 6, 4))
+    _expect(pair_pts, "ecc pair_pts", 8, (None, 6, 4))
+    _expect(pair_out, "ecc pair_out", 8, (None, 4))
+    _expect(pair_off, "ecc pair_off", 4, (pair_out.shape[0] + 1,))
+    n_add, n_mul, n_pairing = int(w["n_add"]), int(w["n_mul"]), int(pair_out.shape[0])
+    if n_add + n_mul != pts.shape[0]:
+        raise ValueError("ecc points: n_add + n_mul != rows of points")
+    max_ok = w["max_ok"]
+    t = _lib.ZkEccOps(ptr(pts, pts.shape[0]), n_add, n_mul, ptr(pair_pts, pair_pts.shape[0]), ptr(pair_off), ptr(pair_out, n_pairing),
+                      n_pairing, ptr(randomness), int(max_ok[0]), int(max_ok[1]), int(max_ok[2]))
+    return t, 0, (w, randomness)
+
+
+def _withdrawal_eval_rows(w):
+    """rows a session over the wire dict `w` evaluates (withdrawal_circuit.hpp wd_eval_rows)"""
+    n_rows, base, total, m = int(w["rows"].shape[0]), int(w.get("row_base", 0)), int(w.get("total_rows", w["rows"].shape[0])), int(w["max_withdrawals"])
+    n_eval = max(1, min(m, total))
+    return 1 if n_rows == 0 else max(0, min(n_eval - base, n_rows))
+
+
+def withdrawal_arrays(w, randomness):
+    """(rows, mpt, keccak, block, randomness cell) of a withdrawal wire dict, C-contiguous uint64"""
+    return (_host(w["rows"], np.uint64), _host(w["mpt"], np.uint64), _host(w["keccak"], np.uint64), _host(w["block"], np.uint64),
+            _host(_randomness_cells(int(randomness), None)))
+
+
+def _withdrawal_witness(w, randomness):
+    """zk_withdrawal_open / zk_withdrawal_verify over the arrays of flatten.flatten_withdrawal_witness (made host arrays) ->
+    (ZkWithdrawalWitness, opts 0, kept arrays)"""
+    keep = rows, mpt, keccak, block, rc = withdrawal_arrays(w, randomness)
+    _expect(rows, "withdrawal rows", 8, (None, 8, 4))
+    _expect(mpt, "mpt", 8, (None, 12, 4))
+    _expect(keccak, "keccak", 8, (None, 5, 4))
+    _expect(block, "block", 8, (None, 4, 4))
+    n, m, k, b = (int(x.shape[0]) for x in (rows, mpt, keccak, block))
+    t = _lib.ZkWithdrawalWitness(ptr(rows, n), n, int(w.get("row_base", 0)), int(w.get("total_rows", n)), int(w["max_withdrawals"]),
+                                 ptr(mpt, m), m, ptr(keccak, k), k, ptr(block, b), b, ptr(rc))
+    return t, 0, keep
 
 
 def open_withdrawal(w, randomness, device=None):
     """Withdrawal circuit session over a wire dict (flatten.flatten_withdrawal_witness, or a shard of it: distributed.shard_rows(...,
     "withdrawal") with row_base set) -> Session; zk_set_range applies (1 row before + 1 after, include/zkevm_hip.h)"""
-    from .oneshot import _withdrawal_witness, withdrawal_arrays
-    from .withdrawal_circuit import eval_rows
-
     lib = _lib.init(device)
-    arrs = withdrawal_arrays(w, randomness)
-    ww = _withdrawal_witness(w, *arrs)
-    h = ctypes.c_void_p()
-    check(lib.zk_withdrawal_open(ctypes.byref(ww), 0, ctypes.byref(h)), "zk_withdrawal_open", lib)
-    return Session(h, eval_rows(w), (arrs, ww), lib=lib)
+    ww, opts, keep = _withdrawal_witness(w, randomness)
+    return _open(lib, lib.zk_withdrawal_open, _withdrawal_eval_rows(w), (keep, ww), ctypes.byref(ww), opts)

@@ -28,13 +28,6 @@ def _is_plain_int(x):
     return not (hasattr(x, "n") or hasattr(x, "expr"))
 
 
-def eval_rows(w):
-    """rows a session over the wire dict `w` evaluates (withdrawal_circuit.hpp wd_eval_rows)"""
-    n_rows, base, total, m = int(w["rows"].shape[0]), int(w.get("row_base", 0)), int(w.get("total_rows", w["rows"].shape[0])), int(w["max_withdrawals"])
-    n_eval = max(1, min(m, total))
-    return 1 if n_rows == 0 else max(0, min(n_eval - base, n_rows))
-
-
 def type_quirks(witness, max_withdrawals):
     """{row: status code} of the failures the types of the rows' cells raise in the reference (see the module docstring)"""
     rows, m = list(witness.rows), int(max_withdrawals)
