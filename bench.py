@@ -20,11 +20,17 @@ witness — rank 0 builds it, its arrays are replicated with broadcasts (RCCL), 
 contiguous ranges with that circuit's halo (zkevm_specs_amd/distributed.py), lookup tables stay whole on every rank.  The
 only collective in the result path is the tally exchange (one all-gather of three words per rank).
 
-`python bench.py --gpus N` with no torchrun environment starts its N ranks itself (re-exec under torch.distributed.run on
-127.0.0.1); under torchrun (RANK / WORLD_SIZE set) it is one rank.
+`python bench.py --gpus N` with no torchrun environment starts its N ranks itself (a child process running
+torch.distributed.run on 127.0.0.1); under torchrun (RANK / WORLD_SIZE set) it is one rank.
+
+A plain run does what the headline needs and nothing else: it builds the witness, warms up, times the K steps, writes
+`--dump-outputs` and prints the line (its `roofline` from the timed steps' own device spans and the committed counter profile).
+`--full` adds every side measurement listed below (the session, batch, cold-cache and fresh-witness legs, the live rocprofv3
+traffic, the CPU baselines and the marshalling sample, the block one-shot, the other configurations) and writes the nested record
+to bench_full.json; a `--no-*` option drops one of them from a `--full` run.
 
 The JSON line carries, next to the contract's fields (flat scalars inside `roofline` / `config` are the digest of everything
-below them: the driver's record keeps scalars of those two objects):
+below them: the driver's record keeps scalars of those two objects; the blocks below other than `roofline` come with `--full`):
   roofline        EVM: see above; `traffic` = HBM-side bytes per step from the committed rocprofv3 counter passes of this same
                   command (profiles/r*_evm_2p18_profile.json, tools/profile_bench.sh; FETCH_SIZE corrected as the guide
                   prescribes), null when no counter pass of this command is committed.  `resident_*`: the open-session pass.
@@ -37,7 +43,7 @@ below them: the driver's record keeps scalars of those two objects):
                   unmodified reference timed in the build container (tools/time_reference.py -> profiles/r*_cpu_reference.json;
                   the reference is Python and does not travel to the GPU box, so this leg is a CROSS-BOX figure and says so).
   host_path       marshalling (Python objects -> wire arrays, flatten.py) and H2D staging, reported separately.
-  other_configs   (default N = 1 run only) BASELINE configs[0], [1], [3], [4] measured after the headline on the same clock:
+  other_configs   (`--full` N = 1 run only) BASELINE configs[0], [1], [3], [4] measured after the headline on the same clock:
                   Bytecode 256 B (CPU backend: configs[0] is the CPU-runnable case), State 2^16 (+ cold-cache leg) and 2^20,
                   Tx + Sig 2^14, Super 2^20 — ms / pass, dominant kernel, physical and algorithmic fractions, CPU legs.
 """
@@ -88,8 +94,12 @@ def kernel_counters(profile, needle):
 
 
 def respawn_under_torchrun(n):
-    """`python bench.py --gpus N` outside torchrun: become `python -m torch.distributed.run ... bench.py <same args>` (one rank
-    per GPU, rendezvous on 127.0.0.1 — the container hostname may not resolve).  Rank 0's JSON line goes to the same stdout."""
+    """`python bench.py --gpus N` outside torchrun: run `python -m torch.distributed.run ... bench.py <same args>` as a child (one
+    rank per GPU, rendezvous on 127.0.0.1 — the container hostname may not resolve) and exit with its status.  Rank 0's JSON line
+    goes to the same stdout; SIGTERM / SIGINT are passed on to the child."""
+    import signal
+    import subprocess
+
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
         port = s.getsockname()[1]
@@ -98,7 +108,11 @@ def respawn_under_torchrun(n):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execv(sys.executable, cmd)
+    child = subprocess.Popen(cmd)
+    for sig in (signal.SIGTERM, signal.SIGINT):
+        signal.signal(sig, lambda signum, _frame: child.send_signal(signum))
+    rc = child.wait()
+    sys.exit(rc if rc >= 0 else 128 - rc)
 
 
 class Ctx:
@@ -688,7 +702,7 @@ def _sig(x, digits=6):
 def compact_line(out, full_path=None):
     """The ONE line the driver parses: the contract's fields, a `config` naming the workload, `roofline` and `cpu_baseline` as flat
     numbers — never prose.  Everything else the run measured (other_configs, the legs' sample texts, resident_session, batch,
-    fresh_witness, host_path) is in `out`, which main() writes to bench_full.json.  Keeps the line under LINE_BUDGET bytes by
+    fresh_witness, host_path) is in `out`, which main() writes to bench_full.json under --full.  Keeps the line under LINE_BUDGET bytes by
     construction: fixed key lists, short strings, 6 significant digits; a last-resort trim drops the other configurations' digests."""
     cfg_full, roof_full = out.get("config") or {}, out.get("roofline") or {}
     line = {k: out.get(k) for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "pre_ramp_steps", "ms_per_step", "higher_is_better",
@@ -794,7 +808,10 @@ def write_full(out):
     return name
 
 
-def main():
+SIDE_LEGS = ("no_session_leg", "no_batch_leg", "no_cold_leg", "no_fresh_leg", "no_live_pmc", "no_cpu_baseline", "no_oneshot_leg", "no_other_configs")
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
@@ -816,11 +833,22 @@ def main():
     ap.add_argument("--no-oneshot-leg", action="store_true", help="super: skip the block one-shot side measurement (block.BlockVerifier)")
     ap.add_argument("--no-cold-leg", action="store_true", help="skip the cold-cache kernel timing after the timed region")
     ap.add_argument("--no-fresh-leg", action="store_true", help="skip the open / pass split with explicit cache flushes")
-    ap.add_argument("--full-line", action="store_true", help="print the full nested record on stdout instead of the compact line (it is always written to bench_full.json)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs[0], [1], [3], [4] after the headline (default: run them at N = 1, evm workload)")
+    ap.add_argument("--full-line", action="store_true", help="print the full nested record on stdout instead of the compact line (--full also writes it to bench_full.json)")
+    ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs[0], [1], [3], [4] after the headline (with --full they run at N = 1, evm workload)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned to its caller (rank 0) as DIR/<name>.npy, float64")
-    args = ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (session / batch / cold-cache / fresh-witness legs, live PMC traffic, CPU baselines, block one-shot, "
+                         "other configurations) and write bench_full.json; without it a run does the headline alone and the --no-* options have nothing to drop")
+    args = ap.parse_args(argv)
+    if not args.full or args.pmc_child:  # the headline alone (the child of live_pmc_traffic: counters over the one-shot steps only)
+        for leg in SIDE_LEGS:
+            setattr(args, leg, True)
+    return args
+
+
+def main():
+    args = parse_args()
     global STATE_COMPACT
     STATE_COMPACT = bool(args.state_compact)
     global STATE_FUSED
@@ -828,9 +856,6 @@ def main():
     # what the side legs (tools/bench_legs.py) need from this file: the builders, the timing loop and the roofline blocks
     CORE = types.SimpleNamespace(BUILDERS=BUILDERS, timed_passes=timed_passes, resolve_super=resolve_super, roofline_block=roofline_block,
                                  tx_extras=tx_extras, oneshot_profile_numbers=oneshot_profile_numbers)
-    if args.pmc_child:  # counters are collected over the one-shot steps alone
-        args.no_session_leg = args.no_batch_leg = args.no_cold_leg = args.no_fresh_leg = args.no_other_configs = args.no_cpu_baseline = True
-        args.no_live_pmc = args.no_oneshot_leg = True
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         respawn_under_torchrun(args.gpus)
 
@@ -1001,7 +1026,7 @@ def main():
         out["other_configs"] = legs.other_configs(CORE, ctx, args)
         digest_other(out["roofline"], out["config"], out["other_configs"])
     if rank == 0:
-        full_path = write_full(out)
+        full_path = write_full(out) if args.full or os.environ.get("ZK_BENCH_FULL") else None
         if args.full_line:
             print(json.dumps(out))  # everything on one line (tools that want the nested blocks on stdout); NOT what the driver should parse
         else:

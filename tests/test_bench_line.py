@@ -122,3 +122,16 @@ def test_dump_outputs_writes_the_last_steps_tally(bench, tmp_path):
     got = {p.stem: float(np.load(p)[0]) for p in (tmp_path / "super").glob("*.npy")}
     assert got["block_first_fail_row"] == -1 and got["block_fail_count"] == 0 and "block_rows_evaluated" not in got
     assert got["evm_fail_count"] == 3 and not any("kernel_ms" in k for k in got)
+
+
+def test_plain_run_times_the_headline_alone(bench):
+    """a plain run drops every side leg; --full runs them all, and a --no-* option still drops one of them from it"""
+    plain = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert not plain.full and all(getattr(plain, leg) for leg in bench.SIDE_LEGS)
+    assert (plain.gpus, plain.steps, plain.warmup, plain.workload, plain.dump_outputs) == (1, 20, 5, "evm", None)
+    full = bench.parse_args(["--full", "--steps", "20", "--warmup", "5"])
+    assert full.full and not any(getattr(full, leg) for leg in bench.SIDE_LEGS)
+    some = bench.parse_args(["--full", "--no-cpu-baseline", "--no-live-pmc"])
+    assert {leg for leg in bench.SIDE_LEGS if getattr(some, leg)} == {"no_cpu_baseline", "no_live_pmc"}
+    child = bench.parse_args(["--full", "--pmc-child"])  # live_pmc_traffic's child: the one-shot steps alone whatever it is given
+    assert all(getattr(child, leg) for leg in bench.SIDE_LEGS)

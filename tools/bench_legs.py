@@ -198,7 +198,7 @@ def own_process_config(name, log_rows, steps, warmup, args, with_cpu_baseline, e
     fd, path = tempfile.mkstemp(prefix="zk_bench_child_", suffix=".json", dir="/tmp")
     os.close(fd)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", name, "--log-rows", str(log_rows), "--steps", str(steps), "--warmup", str(warmup),
-           "--no-other-configs", "--no-cold-leg", "--no-fresh-leg"] + ([] if with_cpu_baseline else ["--no-cpu-baseline"]) + list(extra)
+           "--full", "--no-other-configs", "--no-cold-leg", "--no-fresh-leg"] + ([] if with_cpu_baseline else ["--no-cpu-baseline"]) + list(extra)
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     try:
         t0 = time.perf_counter()

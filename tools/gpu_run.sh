@@ -1,7 +1,7 @@
 #!/bin/bash
 # ONE parameterised lease script (run on the GPU box through gpurun): `tools/gpu_run.sh <tag> <stage>...`, stages in the order given.
 #   tests      the -m gpu suite (PYTEST_ARGS narrows it)          smoke     __graft_entry__.smoke()
-#   bench      the driver's command: python bench.py --gpus 1 --steps 20 --warmup 5; checks that the LAST stdout line parses
+#   bench      python bench.py --full --gpus 1 --steps 20 --warmup 5 (every side measurement); checks that the LAST stdout line parses
 #   prof-evm   rocprofv3 passes of the one-shot headline           prof-session / prof-state / prof-tx / prof-super: the other configurations
 #   rows       tools/bench_row_kernels.py                          refsuite  the reference's own tests through the HIP library
 #   fuzz       differential fuzz (State, EVM pairs, EVM traces) against the oracle
@@ -16,7 +16,7 @@ for stage in "$@"; do
     case "$stage" in
     tests)    eval "timeout 2400 python -m pytest tests -m gpu -x -q ${PYTEST_ARGS:-}" > $out/pytest.log 2>&1; echo "pytest rc=$?" >> $out/pytest.log; tail -5 $out/pytest.log ;;
     smoke)    python -c "import __graft_entry__ as g; g.smoke()" > $out/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $out/smoke.log ;;
-    bench)    timeout 1200 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_stdout.txt 2> $out/bench.err; echo "bench rc=$?"
+    bench)    timeout 1200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $out/bench_stdout.txt 2> $out/bench.err; echo "bench rc=$?"
               cp -f bench_full.json $out/bench_full.json 2>/dev/null
               python - "$out" <<'PY'
 import json, sys

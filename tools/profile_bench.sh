@@ -13,7 +13,7 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/prof_$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-cmd="python $root/bench.py --no-cpu-baseline --no-cold-leg --no-fresh-leg $*"
+cmd="python $root/bench.py --full --no-cpu-baseline --no-cold-leg --no-fresh-leg $*"
 if [ -n "${PROFILE_CMD:-}" ]; then cmd="$PROFILE_CMD"; fi  # e.g. PROFILE_CMD="python tools/bench_row_kernels.py" (run from the repo root)
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- $cmd > "$out/trace.log" 2>&1
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -- $cmd > "$out/pmc_fetch.log" 2>&1

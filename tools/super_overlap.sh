@@ -10,7 +10,7 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 out=$root/gpurun_out/prof_$tag
 mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
-cmd="python $root/bench.py --workload super --no-cpu-baseline --no-cold-leg $*"
+cmd="python $root/bench.py --full --workload super --no-cpu-baseline --no-cold-leg $*"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- $cmd > "$out/trace.log" 2>&1
 python - "$out" <<'PY'
 import csv, glob, json, shutil, sys
