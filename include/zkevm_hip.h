@@ -101,6 +101,8 @@ const char* zk_last_error(void);
  * 25 the G2 scalar chain of the ECC circuit (py_ecc's multiply over Fq2, exact also off the twist): a = Q (x.c1, x.c0, y.c1, y.c0,
  * reduced mod p, all zero = None), then the scalar as a 256-bit integer, then zeros; out = affine x.c0, x.c1, y.c0, y.c1, then
  * 1 if the result is None (its coordinates 0) else 0, then zeros.
+ * 26 / 27: the secp256k1 BASE-field chains of zk_tx_assign's key recovery, a^((P + 1) / 4) (the square root when there is one) and
+ * a^(P - 2) (the inverse, 0 -> 0); residues in, b is not read but must not be null.
  * (reference: FQ.__add__/__sub__/__mul__/__neg__/__truediv__ via py_ecc and FQ.inv, util/arithmetic.py:41-60) */
 int zk_fr_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t n, uint32_t opts);
 
@@ -355,6 +357,8 @@ int zk_state_verify_from_rw(const uint64_t* rw, const uint32_t* rw_flags, uint64
  *      (the one value outside the engine's domain: eth-keys' `if not p[1]` sees it as non-zero; any other coordinate >= P is
  *      reduced mod P, as eth-keys' formulas do implicitly).  Public keys that are not on the curve are evaluated with eth-keys'
  *      Jacobian case analysis (a Y == 0 point is the point at infinity, inv(0) == 0), so their verdicts are reproducible too.
+ *      (zk_tx_assign's key recovery reports BadSignature with the same kind: site 1 as here, plus site 3 = no curve point with
+ *      x = r and site 4 = the recovered key is the point at infinity; site 2 stays this entry's.)
  *      These verdicts for keys off the curve / coordinates >= P are those of eth-keys' NATIVE backend (pure Python,
  *      eth_keys/backends/native/ecdsa.py — what the reference's pinned environment uses); an environment with `coincurve`
  *      installed makes KeyAPI use libsecp256k1, which rejects such keys up front.  Well-formed keys verify identically either way.
@@ -586,6 +590,46 @@ int zk_withdrawal_open(const zk_withdrawal_witness* w, uint32_t opts, zk_session
 int zk_withdrawal_verify(const zk_withdrawal_witness* w, uint32_t opts, uint32_t* status_out, zk_result* result);
 int zk_withdrawal_assign(const uint64_t* withdrawals, uint64_t n, uint64_t max_withdrawals, const uint64_t* randomness, uint32_t opts,
                          uint64_t* rows_out, uint64_t* keccak_out);
+
+/* ---- Tx circuit witness assignment: replaces txs2witness (src/zkevm_specs/tx_circuit.py:432-481; tx2witness :332-406, padding_tx
+ *      :315-329, the dummy chip of the padding slots :409-425).  From raw legacy transactions to the wire flatten_tx_witness makes.
+ *      Inputs (zk_tx_inputs): fields uint64[n][8][4], per tx the 256-bit words nonce, gas_price, gas, to, value, sig_v, sig_r, sig_s;
+ *      to_is_none uint32[n] (1: tx.to is None — IsCreate, rlp's empty string); calldata: the txs' data back to back with byte offsets
+ *      uint64[n + 1] (offsets[0] = 0, non-decreasing, offsets[n] <= max_calldata_bytes); chain_id; MAX_TXS (>= n) and
+ *      MAX_CALLDATA_BYTES; randomness: one cell (keccak_randomness).  `to` must be below 2^160 (the caller rejects wider values as
+ *      encode_to's OverflowError does).
+ *      Per tx: rlp([nonce, gas_price, gas, to_bytes, value, data, chain_id, 0, 0]) is hashed with keccak-256 on the device; the
+ *      sender's key is recovered from (v, r, s, hash) as eth_keys does (oracle/refshim/eth_keys/__init__.py:99-140); keccak of the
+ *      key gives the address.  Status per tx: 0, or (ZK_KIND_UNSUPPORTED << 24) | site for eth_keys' BadSignature — site 1 the
+ *      parity v - 35 - 2 chain_id outside {0, 1} or r / s outside (0, N), site 3 no curve point with x = r, site 4 Q at infinity.
+ *      The outputs of a tx whose status is not 0 are unspecified (the reference raises there).
+ *      Outputs (zk_tx_wire):
+ *        tx_rows uint64[max_txs * 12 + max_calldata_bytes][5][4] (tx_id, tag, index, value lo, hi) + tx_flags uint32[..] (is_word):
+ *          the 12 fixed rows of every tx (GasPrice, Value, TxSignHash are Words), padding_tx(i + 1) for the slots from n on
+ *          (GasPrice / Value Word(0), TxSignHash FQ(0)), the CallData rows in tx order, then (0, CallData, 0, 0) rows;
+ *        bytes uint8[max_txs][9][32], cells column-major uint64[8][max_txs][4], meta uint32[max_txs][4]: the SignVerify units in
+ *          zk_sign_units' Tx layout (padding slots: DUMMY_PUBLIC_KEY / DUMMY_SIGNATURE / DUMMY_MSG_HASH, address 0); meta[:, 0] is
+ *          0xffffffff (pending) for the ECDSA pass (zk_ecdsa_open, layout 1, out_dev = meta, out_stride 4) to fill;
+ *        keccak uint64[n + 1 capacity][5][4]: KeccakTable's rows as a set, sorted, without duplicates, the all-zero row included
+ *          (flatten_keccak_tuples); their number comes out of zk_tx_assign_read / zk_tx_assign (n_keccak).
+ *      zk_tx_assign_open: with ZK_OPT_DEVICE_PTRS every input is a device pointer and the non-null pointers of `out_dev` receive
+ *      the outputs in place (null ones: the session owns the buffer); without it `out_dev` must be null.  zk_launch (status_dev:
+ *      uint32[n]) / zk_collect (tally over the txs) / zk_read_status as for the circuits; zk_tx_assign_read copies the last pass's
+ *      outputs to the non-null HOST pointers of `host` and the keccak row count to *n_keccak_out (nullable). */
+typedef struct zk_tx_inputs {
+    const uint64_t* fields;     const uint32_t* to_is_none;  uint64_t n_txs;
+    const uint8_t* calldata;    const uint64_t* calldata_offsets;
+    uint64_t chain_id;          uint64_t max_txs;            uint64_t max_calldata_bytes;
+    const uint64_t* randomness;
+} zk_tx_inputs;
+typedef struct zk_tx_wire {
+    uint64_t* tx_rows;  uint32_t* tx_flags;
+    uint8_t* bytes;     uint64_t* cells;     uint32_t* meta;
+    uint64_t* keccak;
+} zk_tx_wire;
+int zk_tx_assign_open(const zk_tx_inputs* in, const zk_tx_wire* out_dev, uint32_t opts, zk_session** out);
+int zk_tx_assign_read(zk_session* s, const zk_tx_wire* host, uint64_t* n_keccak_out);
+int zk_tx_assign(const zk_tx_inputs* in, const zk_tx_wire* out, uint32_t opts, uint32_t* status_out, uint64_t* n_keccak_out, zk_result* result);
 
 #ifdef __cplusplus
 }

@@ -2,7 +2,8 @@
 """Throughput of the row-stencil kernels (Bytecode / Exp / Tx-Sig circuits, the ECC circuit) on synthetic witnesses:
 rows/s and algorithmic GB/s (SURVEY.md §8d bytes per unit), device-resident inputs, HIP-event kernel
 time.  bench.py carries the headline EVM / State workloads; this is the side table in DESIGN.md §3.
-`bench_row_kernels.py ecc` runs only the ECC leg, `bench_row_kernels.py withdrawal` only the Withdrawal leg."""
+`bench_row_kernels.py ecc` runs only the ECC leg, `bench_row_kernels.py withdrawal` only the Withdrawal leg, `bench_row_kernels.py
+tx_assign` only the Tx witness-assignment leg."""
 import json
 import os
 import random
@@ -99,6 +100,26 @@ def withdrawal_leg():
     print("withdrawal_assign", out["withdrawal_assign"], flush=True)
 
 
+def tx_assign_leg():
+    """Tx circuit witness assignment (zk_tx_assign_open, inputs in HBM; kernel_ms = HIP-event span of a pass: sign hashes, key
+    recovery, rows, units, keccak set) at 2^11 and 2^14 txs, with short calldata (< 40 bytes) and with mixed calldata (every fifth tx
+    up to 600 bytes).  Signatures are random (r, s) with a curve point: each recovers some key, as a signed tx's does."""
+    from tests.tx_assign_cases import random_inputs
+
+    rk = 0x5EED % P
+    for n in (1 << 11, 1 << 14):
+        for label, long_every in (("short", 0), ("mixed", 5)):
+            t = random_inputs(n, 3, chain_id=1, long_every=long_every, signed=False)
+            td = {k: (to_dev(np.ascontiguousarray(v)) if k in engine.TX_ASSIGN_INPUTS else v) for k, v in t.items()}
+            name = f"tx_assign_{n}_{label}"
+            run(name, engine.open_tx_assign(td, rk), n, 8 * 32 + int(t["offsets"][-1]) / n)
+            out[name]["calldata_bytes"] = int(t["offsets"][-1])
+
+
+if sys.argv[1:] == ["tx_assign"]:
+    tx_assign_leg()
+    print(json.dumps(out))
+    sys.exit(0)
 if sys.argv[1:] == ["withdrawal"]:
     withdrawal_leg()
     print(json.dumps(out))

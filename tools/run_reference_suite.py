@@ -9,6 +9,7 @@ A pytest plugin rebinds, inside every reference test module that imported them, 
     check_bytecode_row              zkevm_specs/bytecode_circuit.py:37      -> zkevm_specs_amd.bytecode_circuit.check_bytecode_row
     verify_copy_table               zkevm_specs/copy_circuit.py:92          -> zkevm_specs_amd.copy_circuit.verify_copy_table
     verify_exp_circuit              zkevm_specs/exp_circuit.py:88           -> zkevm_specs_amd.exp_circuit.verify_exp_circuit
+    txs2witness                     zkevm_specs/tx_circuit.py:432           -> zkevm_specs_amd.tx_circuit.txs2witness
     verify_circuit (tx / sig / pi / ecc / withdrawal)  tx_circuit.py:253, sig_circuit.py:113, pi_circuit.py:338, ecc_circuit.py:424,
                                     withdrawal_circuit.py:128 -> the five mirrors
 
@@ -38,6 +39,7 @@ REBIND = {  # name in the test module -> (module the test imported it from, mirr
     "check_bytecode_row": ("zkevm_specs.bytecode_circuit", "zkevm_specs_amd.bytecode_circuit", "check_bytecode_row"),
     "verify_copy_table": ("zkevm_specs.copy_circuit", "zkevm_specs_amd.copy_circuit", "verify_copy_table"),
     "verify_exp_circuit": ("zkevm_specs.exp_circuit", "zkevm_specs_amd.exp_circuit", "verify_exp_circuit"),
+    "txs2witness": ("zkevm_specs.tx_circuit", "zkevm_specs_amd.tx_circuit", "txs2witness"),
 }
 VERIFY_CIRCUIT = {  # `verify_circuit` exists five times: told apart by the module that defined the imported function
     "zkevm_specs.tx_circuit": ("zkevm_specs_amd.tx_circuit", "verify_circuit"),

@@ -24,6 +24,7 @@ EXPORTED_SYMBOLS = [
     "zk_state_open", "zk_state_set_range", "zk_set_range", "zk_state_verify", "zk_evm_open", "zk_evm_verify", "zk_evm_verify_batch", "zk_bytecode_open", "zk_bytecode_verify", "zk_exp_open", "zk_exp_verify", "zk_copy_open", "zk_copy_verify", "zk_sign_open", "zk_sign_verify",
     "zk_keccak_open", "zk_keccak_read_rows", "zk_keccak_table", "zk_state_assign_open", "zk_state_assign_read", "zk_state_assign", "zk_state_ops_from_rw_open", "zk_state_ops_from_rw_read", "zk_state_ops_from_rw", "zk_state_assign_from_rw_open", "zk_state_verify_from_rw_open", "zk_state_verify_from_rw", "zk_block_verify", "zk_ecdsa_open", "zk_ecdsa_open_batches", "zk_ecdsa_verify", "zk_bytecode_assign_open", "zk_bytecode_assign_read", "zk_bytecode_assign", "zk_pi_open", "zk_pi_verify", "zk_pi_copy_open", "zk_pi_copy_verify", "zk_copy_assign_sizes", "zk_copy_assign_open", "zk_copy_assign_read", "zk_copy_assign", "zk_launch", "zk_collect", "zk_read_status", "zk_close", "zk_session_timing", "zk_last_timing", "zk_timing_sums", "zk_last_host_phases", "zk_dist_unique_id", "zk_dist_init", "zk_dist_tally", "zk_dist_close",
     "zk_ecc_assign", "zk_ecc_verify", "zk_withdrawal_open", "zk_withdrawal_verify", "zk_withdrawal_assign",
+    "zk_tx_assign_open", "zk_tx_assign_read", "zk_tx_assign",
 ]
 
 OPT_DEVICE_PTRS = 1
@@ -90,6 +91,17 @@ class ZkWithdrawalWitness(ctypes.Structure):
     _fields_ = [("rows", ctypes.c_void_p), ("n_rows", ctypes.c_uint64), ("row_base", ctypes.c_uint64), ("total_rows", ctypes.c_uint64),
                 ("max_withdrawals", ctypes.c_uint64), ("mpt", ctypes.c_void_p), ("n_mpt", ctypes.c_uint64), ("keccak", ctypes.c_void_p),
                 ("n_keccak", ctypes.c_uint64), ("block", ctypes.c_void_p), ("n_block", ctypes.c_uint64), ("randomness", ctypes.c_void_p)]
+
+
+class ZkTxInputs(ctypes.Structure):
+    _fields_ = [("fields", ctypes.c_void_p), ("to_is_none", ctypes.c_void_p), ("n_txs", ctypes.c_uint64), ("calldata", ctypes.c_void_p),
+                ("calldata_offsets", ctypes.c_void_p), ("chain_id", ctypes.c_uint64), ("max_txs", ctypes.c_uint64),
+                ("max_calldata_bytes", ctypes.c_uint64), ("randomness", ctypes.c_void_p)]
+
+
+class ZkTxWire(ctypes.Structure):
+    _fields_ = [("tx_rows", ctypes.c_void_p), ("tx_flags", ctypes.c_void_p), ("bytes", ctypes.c_void_p), ("cells", ctypes.c_void_p),
+                ("meta", ctypes.c_void_p), ("keccak", ctypes.c_void_p)]
 
 
 class ZkEcdsaBatch(ctypes.Structure):
@@ -207,6 +219,9 @@ def _bind(lib):
     lib.zk_withdrawal_open.argtypes = [ctypes.POINTER(ZkWithdrawalWitness), u32, ctypes.POINTER(vp)]
     lib.zk_withdrawal_verify.argtypes = [ctypes.POINTER(ZkWithdrawalWitness), u32, vp, ctypes.POINTER(ZkResult)]
     lib.zk_withdrawal_assign.argtypes = [vp, u64, u64, vp, u32, vp, vp]
+    lib.zk_tx_assign_open.argtypes = [ctypes.POINTER(ZkTxInputs), ctypes.POINTER(ZkTxWire), u32, ctypes.POINTER(vp)]
+    lib.zk_tx_assign_read.argtypes = [vp, ctypes.POINTER(ZkTxWire), ctypes.POINTER(u64)]
+    lib.zk_tx_assign.argtypes = [ctypes.POINTER(ZkTxInputs), ctypes.POINTER(ZkTxWire), u32, vp, ctypes.POINTER(u64), ctypes.POINTER(ZkResult)]
     lib.zk_keccak_open.argtypes = [vp, u64, vp, u64, vp, u32, vp, u32, ctypes.POINTER(vp)]
     lib.zk_keccak_read_rows.argtypes = [vp, vp]
     lib.zk_keccak_table.argtypes = [vp, u64, vp, u64, vp, u32, vp, u32, vp, ctypes.POINTER(ZkResult)]

@@ -34,6 +34,7 @@
 #include "state_rekey.hpp"
 #include "ecc_circuit.hpp"
 #include "withdrawal_circuit.hpp"
+#include "tx_assign.hpp"
 
 static thread_local std::string g_err;
 #define ARG_TRY(cond, msg) do { if (!(cond)) { g_err = msg; return -1; } } while (0)
@@ -119,6 +120,10 @@ struct zk_session {
     CpaPlan cpa_plan;
     EcdsaArgs ecdsa;
     KeccakGenArgs kgen;
+    TxAssignArgs txa;
+    std::vector<u64> txa_out64[4];  // Tx assignment outputs: tx_rows, cells, keccak candidates, keccak
+    std::vector<u32> txa_out32[3];  // tx_flags, meta, the txs' status
+    u64 n_keccak = 0;
     ZkRwMeta rw_meta;
     HostCodeDir dir;
     std::vector<u64> aux64;
@@ -318,6 +323,8 @@ extern "C" int zk_fr_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* 
         case 5: r = fr_inv(x); break;
         case 6: r = fr_div(x, y); break;
         case 18: r = ecc_fq_mul_hook(x, y); break;
+        case 26: r = sp_sqrt_p(x); break;
+        case 27: r = sp_inv_p(x); break;
         case 19: case 20: case 21: case 22: case 23: case 24: case 25:
             if (i % 12 == 0 && i + 12 <= (long long)n) ecc_fq12_op_hook(op, a + 4 * i, b + 4 * i, out + 4 * i);
             continue;
@@ -1221,4 +1228,113 @@ extern "C" int zk_withdrawal_assign(const uint64_t* withdrawals, uint64_t n, uin
         wd_assign_row(a, (u64)i, m);
     }
     return 0;
+}
+
+// ---- Tx circuit witness assignment (tx_assign.hpp): the device functions in host loops; recovery in the one-lane form
+static void tx_assign_pass(zk_session* s) {
+    TxAssignArgs& a = s->txa;
+    const long long n = (long long)a.n;
+#pragma omp parallel for schedule(dynamic, 16)
+    for (long long i = 0; i < n; i++) {
+        tx_sign_hash(a, (u64)i);
+        u32 tab[15 * 24];
+        EcdsaPrep pr;
+        Fr u1, u2;
+        const u32 st = tx_recover_prepare(a, (u64)i, pr, u1, u2);
+        u32 code;
+        if (st == ECDSA_PENDING) code = tx_recover_finish(a, (u64)i, ecdsa_partial(pr, 0, 1, tab, 1, nullptr));
+        else if (st == TX_RECOVER_EXACT) code = tx_recover_finish(a, (u64)i, tx_recover_exact(pr, u1, u2));
+        else { code = st; tx_recover_fail(a, (u64)i); }
+        a.status[i] = code;
+    }
+    memcpy(s->status.data(), a.status, (size_t)a.n * sizeof(u32));
+#pragma omp parallel for schedule(dynamic, 64)
+    for (long long i = 0; i < (long long)a.max_txs; i++) tx_write_slot(a, (u64)i);
+    tx_write_zero_candidate(a);
+#pragma omp parallel for schedule(static)
+    for (long long j = 0; j < (long long)a.max_calldata; j++) tx_write_calldata_row(a, (u64)j);
+    // the keccak table as a sorted set
+    std::vector<u64> idx((size_t)a.n + 1);
+    for (u64 k = 0; k <= a.n; k++) idx[k] = k;
+    const u64* kc = a.kcand;
+    std::sort(idx.begin(), idx.end(), [kc](u64 x, u64 y) { return tx_krow_cmp(kc + x * 20, kc + y * 20) < 0; });
+    u64 m = 0;
+    for (u64 k = 0; k <= a.n; k++) {
+        if (m && tx_krow_cmp(a.keccak + (m - 1) * 20, kc + idx[k] * 20) == 0) continue;
+        memcpy(a.keccak + m * 20, kc + idx[k] * 20, 160);
+        m++;
+    }
+    s->n_keccak = m;
+}
+extern "C" int zk_tx_assign_open(const zk_tx_inputs* in, const zk_tx_wire* out_dev, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_tx_assign_open");
+    ARG_TRY(in && out && !out_dev && in->randomness && in->calldata_offsets && (in->n_txs == 0 || (in->fields && in->to_is_none)) &&
+            in->n_txs <= in->max_txs && in->max_txs < (1ull << 31) && in->max_calldata_bytes < (1ull << 34),
+            "zk_tx_assign_open: bad arguments");
+    const u64 n = in->n_txs, mt = in->max_txs, mc = in->max_calldata_bytes;
+    const u64* off = in->calldata_offsets;
+    ARG_TRY(off[0] == 0, "zk_tx_assign_open: calldata offsets must start at 0");
+    for (u64 j = 0; j < n; j++) ARG_TRY(off[j] <= off[j + 1], "zk_tx_assign_open: calldata offsets must be non-decreasing");
+    ARG_TRY(off[n] <= mc, "zk_tx_assign_open: more calldata bytes than max_calldata_bytes");
+    ARG_TRY(!off[n] || in->calldata, "zk_tx_assign_open: calldata is null");
+    zk_session* s = new_session(n, false);
+    s->a64[0].assign(in->fields, in->fields + n * TX_NFIELDS * 4);
+    s->a32[0].assign(in->to_is_none, in->to_is_none + n);
+    s->a64[1].assign(off, off + n + 1);
+    s->a8.assign((size_t)((off[n] + 15) & ~7ull), 0);  // whole aligned words for the sponge's reads
+    if (off[n]) memcpy(s->a8.data(), in->calldata, (size_t)off[n]);
+    s->a64[2].assign(KT_RPOW_ROWS * 4, 0);
+    kt_fill_rpow(cell_of(in->randomness), s->a64[2].data());
+    s->a64[3].assign((size_t)(n + 1) * 4, 0);   // hash
+    s->w64[0].assign((size_t)n + 1, 0);         // gas cost
+    s->w64[1].assign((size_t)(n + 1) * 8, 0);   // pk
+    s->txa_out32[2].assign((size_t)n + 1, 0);   // status
+    const u64 rows = mt * TX_FIXED_ROWS + mc;
+    s->txa_out64[0].assign((size_t)rows * TX_ROW_CELLS * 4 + 4, 0);
+    s->txa_out32[0].assign((size_t)rows + 1, 0);
+    s->a8b.assign((size_t)mt * TX_UNIT_BYTES + 32, 0);
+    s->txa_out64[1].assign((size_t)mt * TX_UNIT_CELLS * 4 + 4, 0);
+    s->txa_out32[1].assign((size_t)mt * 4 + 4, 0);
+    s->txa_out64[2].assign((size_t)(n + 1) * KT_NCELLS * 4, 0);
+    s->txa_out64[3].assign((size_t)(n + 1) * KT_NCELLS * 4, 0);
+    TxAssignArgs& a = s->txa;
+    memset(&a, 0, sizeof(a));
+    a.fields = s->a64[0].data(); a.to_none = s->a32[0].data(); a.data = s->a8.data(); a.off = s->a64[1].data();
+    a.n = n; a.max_txs = mt; a.max_calldata = mc; a.chain_id = in->chain_id; a.rpow = s->a64[2].data();
+    a.hash = s->a64[3].data(); a.gas_cost = s->w64[0].data(); a.pk = s->w64[1].data(); a.status = s->txa_out32[2].data();
+    a.tx_rows = s->txa_out64[0].data(); a.tx_flags = s->txa_out32[0].data(); a.bytes = s->a8b.data(); a.cells = s->txa_out64[1].data();
+    a.meta = s->txa_out32[1].data(); a.kcand = s->txa_out64[2].data(); a.keccak = s->txa_out64[3].data();
+    a.lanes_per_sig = 1;
+    s->pass = tx_assign_pass;
+    s->assign_kind = 5;
+    *out = s;
+    return 0;
+}
+extern "C" int zk_tx_assign_read(zk_session* s, const zk_tx_wire* host, uint64_t* n_keccak_out) {
+    ARG_TRY(s && s->assign_kind == 5, "zk_tx_assign_read: bad arguments");
+    const TxAssignArgs& a = s->txa;
+    const u64 rows = a.max_txs * TX_FIXED_ROWS + a.max_calldata;
+    if (host) {
+        if (host->tx_rows) memcpy(host->tx_rows, a.tx_rows, (size_t)rows * TX_ROW_CELLS * 32);
+        if (host->tx_flags) memcpy(host->tx_flags, a.tx_flags, (size_t)rows * 4);
+        if (host->bytes) memcpy(host->bytes, a.bytes, (size_t)a.max_txs * TX_UNIT_BYTES);
+        if (host->cells) memcpy(host->cells, a.cells, (size_t)a.max_txs * TX_UNIT_CELLS * 32);
+        if (host->meta) memcpy(host->meta, a.meta, (size_t)a.max_txs * 16);
+        if (host->keccak) memcpy(host->keccak, a.keccak, (size_t)s->n_keccak * KT_NCELLS * 32);
+    }
+    if (n_keccak_out) *n_keccak_out = s->n_keccak;
+    return 0;
+}
+extern "C" int zk_tx_assign(const zk_tx_inputs* in, const zk_tx_wire* out, uint32_t opts, uint32_t* status_out, uint64_t* n_keccak_out,
+                            zk_result* result) {
+    ARG_TRY(result && out, "zk_tx_assign: null output");
+    zk_session* s = nullptr;
+    int rc = zk_tx_assign_open(in, nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && status_out) rc = zk_read_status(s, status_out);
+    if (!rc) rc = zk_tx_assign_read(s, out, n_keccak_out);
+    zk_close(s);
+    return rc;
 }

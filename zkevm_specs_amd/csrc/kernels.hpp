@@ -18,6 +18,7 @@
 #include "state_rekey.hpp"
 #include "ecc_circuit.hpp"
 #include "withdrawal_circuit.hpp"
+#include "tx_assign.hpp"
 
 // The single-kernel row sessions keep two tallies and alternate between them: a pass accumulates into one and its first
 // lane clears the other for the pass after it, so that no reset kernel sits in front of every evaluation kernel (a kernel
@@ -82,3 +83,5 @@ void zk_launch_fq12_op(hipStream_t st, int op, const u64* x, const u64* y, u64* 
 // Withdrawal circuit (k_withdrawal.hip): verify held rows [lo, hi) (status / twin tally); assign rows [0, a.n_out) (+ keccak rows)
 void zk_launch_withdrawal_rows(hipStream_t st, const WithdrawalArgs& a, u64 lo, u64 hi, u32* status, ZkTally* tally);
 void zk_launch_withdrawal_assign(hipStream_t st, const WithdrawalArgs& a);
+// Tx circuit witness assignment (k_tx_assign.hip): sign hashes, key recovery (status / tally per tx), rows, units, keccak set
+void zk_launch_tx_assign(hipStream_t st, const TxAssignArgs& a, u32* status, ZkTally* tally);

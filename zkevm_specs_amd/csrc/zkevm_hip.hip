@@ -540,6 +540,8 @@ __global__ void fr_op_kernel(int op, const u64* a, const u64* b, u64* out, u64 n
     case 16: r = sp_mul_p(x, y); break;   // secp256k1 base field (unit-test hooks of csrc/secp256k1.hpp): a * b mod P, residues in and out
     case 17: r = sp_sqr_p(x); break;
     case 18: r = ecc_fq_mul_hook(x, y); break;  // BN254 base field (unit-test hook of csrc/bn254_fq.hpp)
+    case 26: r = sp_sqrt_p(x); break;      // secp256k1 base field (unit-test hooks of csrc/tx_assign.hpp): a^((P + 1) / 4)
+    case 27: r = sp_inv_p(x); break;       // a^(P - 2) = a^-1 mod P (0 -> 0)
     default: r = fr_zero();
     }
     for (int k = 0; k < 4; k++) out[4 * i + k] = (u64)r.v[2 * k] | ((u64)r.v[2 * k + 1] << 32);
@@ -568,7 +570,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -599,6 +601,7 @@ struct zk_session {
     PiArgs pi;
     PiCopyArgs picopy;
     WithdrawalArgs withdrawal;
+    TxAssignArgs txa;
     RekeyArgs rekey;
     RwkPlan rekey_plan_host;      // the compact-key plan as uploaded (host copy owned by the session: the upload needs no synchronisation of its own)
     bool assign_from_rw = false;  // SESSION_ASSIGN over an RW table: every pass starts with the re-keying and the sort (rekey)
@@ -2457,6 +2460,7 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     case SESSION_BCA: zk_launch_bytecode_assign(s->stream, s->bca, status, s->d_tally); break;
     case SESSION_PI: zk_launch_pi_rows(s->stream, s->pi, range_lo(s), range_hi(s), status, tally); break;
     case SESSION_WITHDRAWAL: zk_launch_withdrawal_rows(s->stream, s->withdrawal, range_lo(s), range_hi(s), status, tally); break;
+    case SESSION_TXA: zk_launch_tx_assign(s->stream, s->txa, status, s->d_tally); break;
     case SESSION_PICOPY: zk_launch_pi_copy(s->stream, s->picopy, status, tally); break;
     case SESSION_CPA: zk_launch_copy_assign(s->stream, s->cpa, status, s->d_tally); break;
     case SESSION_REKEY: zk_launch_state_rekey(s->stream, s->rekey, status, s->d_tally); break;
@@ -3402,4 +3406,150 @@ extern "C" int zk_withdrawal_assign(const uint64_t* withdrawals, uint64_t n, uin
     HIP_TRY(e);
     HIP_TRY(se);
     return 0;
+}
+
+// ---- Tx circuit witness assignment (tx_assign.hpp, k_tx_assign.hip)
+extern "C" int zk_tx_assign_open(const zk_tx_inputs* in, const zk_tx_wire* out_dev, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_tx_assign_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(in && out && in->randomness && in->calldata_offsets && (in->n_txs == 0 || (in->fields && in->to_is_none)) &&
+            in->n_txs <= in->max_txs && in->max_txs < (1ull << 31) && in->max_calldata_bytes < (1ull << 34),
+            "zk_tx_assign_open: bad arguments");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    ARG_TRY(dev || !out_dev, "zk_tx_assign_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    const u64 n = in->n_txs, mt = in->max_txs, mc = in->max_calldata_bytes;
+    zk_session* s = new zk_session();
+    s->kind = SESSION_TXA;
+    s->n = n;
+    TxAssignArgs& a = s->txa;
+    memset(&a, 0, sizeof(a));
+    int rc = 0;
+    const void* p = nullptr;
+    u64 rh[4];
+    Fr r;
+    std::vector<u64> h_off((size_t)n + 1, 0);
+    // the offsets are validated on the host (a device caller's are read back once)
+    if (dev) {
+        if (fetch_small(s->stream, h_off.data(), in->calldata_offsets, (n + 1) * 8)) { rc = -2; g_err = "offsets download failed"; goto fail; }
+        if (fetch_small(s->stream, rh, in->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
+    } else {
+        memcpy(h_off.data(), in->calldata_offsets, (n + 1) * 8);
+        memcpy(rh, in->randomness, 32);
+    }
+    if (h_off[0] != 0) { rc = -1; g_err = "zk_tx_assign_open: calldata offsets must start at 0"; goto fail; }
+    for (u64 j = 0; j < n; j++)
+        if (h_off[j] > h_off[j + 1]) { rc = -1; g_err = "zk_tx_assign_open: calldata offsets must be non-decreasing"; goto fail; }
+    if (h_off[n] > mc) { rc = -1; g_err = "zk_tx_assign_open: more calldata bytes than max_calldata_bytes"; goto fail; }
+    if (h_off[n] && !in->calldata) { rc = -1; g_err = "zk_tx_assign_open: calldata is null"; goto fail; }
+    for (int k = 0; k < 4; k++) { r.v[2 * k] = (u32)rh[k]; r.v[2 * k + 1] = (u32)(rh[k] >> 32); }
+    {   // the fixed-base table of G, as zk_ecdsa_open
+        std::lock_guard<std::mutex> lock(g_dev_mutex);
+        if (!g_secp_comb[s->device]) {
+            u32* tab = nullptr;
+            if (hipMalloc(&tab, (size_t)ECDSA_COMB_ENTRIES * 16 * sizeof(u32)) != hipSuccess) { rc = -2; g_err = "zk_tx_assign_open: table allocation failed"; goto fail; }
+            zk_launch_ecdsa_comb_build(s->stream, tab);
+            if (hipStreamSynchronize(s->stream) != hipSuccess) { (void)hipFree(tab); rc = -2; g_err = "zk_tx_assign_open: table build failed"; goto fail; }
+            g_secp_comb[s->device] = tab;
+        }
+        a.gcomb = g_secp_comb[s->device];
+    }
+    if ((rc = stage(s, in->fields, (size_t)n * TX_NFIELDS * 32, dev, &p))) goto fail;
+    a.fields = (const u64*)p;
+    if ((rc = stage(s, in->to_is_none, (size_t)n * 4, dev, &p))) goto fail;
+    a.to_none = (const u32*)p;
+    if ((rc = stage(s, in->calldata_offsets, (size_t)(n + 1) * 8, dev, &p))) goto fail;
+    a.off = (const u64*)p;
+    if (dev || !h_off[n]) {
+        if ((rc = stage(s, h_off[n] ? in->calldata : nullptr, (size_t)h_off[n], dev, &p))) goto fail;
+        a.data = (const uint8_t*)p;
+    } else {  // staged with its last aligned word whole (the sponge reads whole aligned words)
+        void* d = nullptr;
+        if ((rc = dev_alloc(s, &d, (size_t)((h_off[n] + 15) & ~7ull)))) goto fail;
+        HIP_TRY(hipMemcpyAsync(d, in->calldata, (size_t)h_off[n], hipMemcpyHostToDevice, s->stream));
+        a.data = (const uint8_t*)d;
+    }
+    a.n = n; a.max_txs = mt; a.max_calldata = mc; a.chain_id = in->chain_id;
+    {
+        u64* d_rpow = nullptr;
+        void* d = nullptr;
+        if ((rc = dev_alloc(s, (void**)&d_rpow, KT_RPOW_ROWS * 4 * sizeof(u64)))) goto fail;
+        zk_launch_keccak_rpow(s->stream, r, d_rpow);
+        a.rpow = d_rpow;
+        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 32))) goto fail;
+        a.hash = (u64*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 8))) goto fail;
+        a.gas_cost = (u64*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 64))) goto fail;
+        a.pk = (u64*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 4))) goto fail;
+        a.status = (u32*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * KT_NCELLS * 32))) goto fail;
+        a.kcand = (u64*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 4))) goto fail;
+        a.kfirst = (u32*)d;
+        if ((rc = dev_alloc(s, &d, 64))) goto fail;
+        a.n_keccak = (u32*)d;
+    }
+    // lane forms as zk_ecdsa_open (ZK_ECDSA_LANES overrides here too)
+    a.lanes_per_sig = n <= (1ull << 14) ? 4u : n <= (1ull << 16) ? 2u : 1u;
+    if (const char* e = getenv("ZK_ECDSA_LANES")) { const int v = atoi(e); a.lanes_per_sig = v == 4 ? 4u : v == 2 ? 2u : 1u; }
+    a.qtab_lanes = ((n * a.lanes_per_sig + 63) / 64) * 64;
+    if (a.qtab_lanes == 0) a.qtab_lanes = 64;
+    if (a.qtab_lanes > ZK_ECDSA_CHUNK_LANES) a.qtab_lanes = ZK_ECDSA_CHUNK_LANES;
+    if ((rc = dev_alloc(s, (void**)&a.qtab, (size_t)a.qtab_lanes * 15 * 24 * sizeof(u32)))) goto fail;
+    {
+        const zk_tx_wire* o = out_dev;
+        void* d = nullptr;
+        const u64 rows = mt * TX_FIXED_ROWS + mc;
+#define TXA_OUT(field, member, type, bytes)                                               \
+        if (o && o->field) a.member = (type)o->field;                                     \
+        else { if ((rc = dev_alloc(s, &d, (size_t)(bytes)))) goto fail; a.member = (type)d; }
+        TXA_OUT(tx_rows, tx_rows, u64*, rows * TX_ROW_CELLS * 32 + 32)
+        TXA_OUT(tx_flags, tx_flags, u32*, rows * 4 + 4)
+        TXA_OUT(bytes, bytes, uint8_t*, mt * TX_UNIT_BYTES + 32)
+        TXA_OUT(cells, cells, u64*, mt * TX_UNIT_CELLS * 32 + 32)
+        TXA_OUT(meta, meta, u32*, mt * 16 + 16)
+        TXA_OUT(keccak, keccak, u64*, (n + 1) * KT_NCELLS * 32)
+#undef TXA_OUT
+    }
+    if ((rc = session_common_init(s))) goto fail;
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_tx_assign_read(zk_session* s, const zk_tx_wire* host, uint64_t* n_keccak_out) {
+    ARG_TRY(s && s->kind == SESSION_TXA, "zk_tx_assign_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    const TxAssignArgs& a = s->txa;
+    const u64 rows = a.max_txs * TX_FIXED_ROWS + a.max_calldata;
+    u32 nk = 0;
+    HIP_TRY(hipMemcpyAsync(&nk, a.n_keccak, 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (host) {
+        if (host->tx_rows) HIP_TRY(hipMemcpyAsync(host->tx_rows, a.tx_rows, (size_t)rows * TX_ROW_CELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        if (host->tx_flags) HIP_TRY(hipMemcpyAsync(host->tx_flags, a.tx_flags, (size_t)rows * 4, hipMemcpyDeviceToHost, s->stream));
+        if (host->bytes) HIP_TRY(hipMemcpyAsync(host->bytes, a.bytes, (size_t)a.max_txs * TX_UNIT_BYTES, hipMemcpyDeviceToHost, s->stream));
+        if (host->cells) HIP_TRY(hipMemcpyAsync(host->cells, a.cells, (size_t)a.max_txs * TX_UNIT_CELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        if (host->meta) HIP_TRY(hipMemcpyAsync(host->meta, a.meta, (size_t)a.max_txs * 16, hipMemcpyDeviceToHost, s->stream));
+        if (host->keccak) HIP_TRY(hipMemcpyAsync(host->keccak, a.keccak, (size_t)nk * KT_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    if (n_keccak_out) *n_keccak_out = nk;
+    return 0;
+}
+extern "C" int zk_tx_assign(const zk_tx_inputs* in, const zk_tx_wire* out, uint32_t opts, uint32_t* status_out, uint64_t* n_keccak_out,
+                            zk_result* result) {
+    ARG_TRY(result && out, "zk_tx_assign: null output");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    int rc = zk_tx_assign_open(in, dev ? out : nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, dev ? status_out : nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && !dev && status_out) rc = zk_read_status(s, status_out);
+    if (!rc) rc = zk_tx_assign_read(s, dev ? nullptr : out, n_keccak_out);
+    zk_close(s);
+    return rc;
 }

@@ -808,3 +808,70 @@ def open_withdrawal(w, randomness, device=None):
     lib = _lib.init(device)
     ww, opts, keep = _withdrawal_witness(w, randomness)
     return _open(lib, lib.zk_withdrawal_open, _withdrawal_eval_rows(w), (keep, ww), ctypes.byref(ww), opts)
+
+
+# ---- Tx circuit witness assignment (zk_tx_assign*) --------------------------------------------------------------------------------
+TX_ASSIGN_INPUTS = ("fields", "to_is_none", "calldata", "offsets")
+TX_ASSIGN_OUTPUTS = ("tx_rows", "tx_flags", "bytes", "cells", "meta", "keccak")
+
+
+def tx_assign_shapes(n, max_txs, max_calldata_bytes):
+    """name -> (shape, dtype) of the outputs of zk_tx_assign* (keccak: its capacity, n + 1 rows)"""
+    rows = max_txs * 12 + max_calldata_bytes
+    return {"tx_rows": ((rows, 5, 4), np.uint64), "tx_flags": ((rows,), np.uint32), "bytes": ((max_txs, 9, 32), np.uint8),
+            "cells": ((8, max_txs, 4), np.uint64), "meta": ((max_txs, 4), np.uint32), "keccak": ((n + 1, 5, 4), np.uint64)}
+
+
+def _tx_assign_args(tx, randomness, outs=None):
+    """zk_tx_assign_open / zk_tx_assign over `tx` = dict(fields uint64[n, 8, 4], to_is_none uint32[n], calldata uint8[b], offsets
+    uint64[n + 1], chain_id, max_txs, max_calldata_bytes) -> (ZkTxInputs, ZkTxWire of the device outputs or None, opts, kept arrays).
+    `outs` (device tensors only, each optional): buffers of TX_ASSIGN_OUTPUTS the session writes in place."""
+    n = int(tx["fields"].shape[0])
+    _expect(tx["fields"], "fields", 8, (None, 8, 4))
+    _expect(tx["to_is_none"], "to_is_none", 4, (n,))
+    _expect(tx["offsets"], "offsets", 8, (n + 1,))
+    _expect(tx["calldata"], "calldata", 1, (None,))
+    mt, mc = int(tx["max_txs"]), int(tx["max_calldata_bytes"])
+    shapes = tx_assign_shapes(n, mt, mc)
+    outs = dict(outs or {})
+    for k, v in outs.items():
+        if v is not None:
+            _expect(v, k, np.dtype(shapes[k][1]).itemsize, shapes[k][0])
+    out_list = [outs.get(k) for k in TX_ASSIGN_OUTPUTS]
+    a, opts = _prep([tx[k] for k in TX_ASSIGN_INPUTS] + out_list, outputs=range(4, 4 + len(out_list)))
+    if any(v is not None for v in out_list) and not opts:
+        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
+    rc = _randomness_cells(randomness, a[0])
+    keep = a + [rc]
+    t = _lib.ZkTxInputs(ptr(a[0], n), ptr(a[1], n), n, ptr(a[2], int(a[2].shape[0])), ptr(a[3]), int(tx["chain_id"]), mt, mc, ptr(rc))
+    w = _lib.ZkTxWire(*[ptr(x) for x in a[4:]]) if opts else None
+    return t, w, opts, keep
+
+
+class TxAssignSession(Session):
+    """zk_tx_assign_open: status per tx; read() -> the wire dict of the last pass (host arrays)"""
+
+    def read(self):
+        t = self._keep[-1]
+        shapes = tx_assign_shapes(self.n, t["max_txs"], t["max_calldata_bytes"])
+        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items()}
+        nk = ctypes.c_uint64()
+        w = _lib.ZkTxWire(*[ptr(out[k]) for k in TX_ASSIGN_OUTPUTS])
+        check(self._lib.zk_tx_assign_read(self._h, ctypes.byref(w), ctypes.byref(nk)), "zk_tx_assign_read", self._lib)
+        out["keccak"] = out["keccak"][: nk.value]
+        return out
+
+    def n_keccak(self):
+        nk = ctypes.c_uint64()
+        check(self._lib.zk_tx_assign_read(self._h, None, ctypes.byref(nk)), "zk_tx_assign_read", self._lib)
+        return int(nk.value)
+
+
+def open_tx_assign(tx, randomness, outs=None, device=None):
+    """Tx circuit witness assignment session over the raw txs of `tx` (see _tx_assign_args).  With device tensors the outputs stay
+    in HBM: in `outs`' buffers where given (e.g. for zk_ecdsa_open / zk_sign_open on them), else in the session's own."""
+    lib = _lib.init(device)
+    t, w, opts, keep = _tx_assign_args(tx, randomness, outs)
+    sizes = {"max_txs": int(tx["max_txs"]), "max_calldata_bytes": int(tx["max_calldata_bytes"])}
+    return _open(lib, lib.zk_tx_assign_open, t.n_txs, (keep, t, w, sizes), ctypes.byref(t), ctypes.byref(w) if w is not None else None,
+                 opts, cls=TxAssignSession)

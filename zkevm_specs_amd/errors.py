@@ -29,6 +29,27 @@ class UnsupportedOnDevice(Exception):
     """The engine has no device implementation for this execution state / gadget."""
 
 
+class BadSignature(Exception):
+    """eth_keys' BadSignature (eth_keys.exceptions.BadSignature), raised by tx_circuit.txs2witness for a signature no public key can be
+    recovered from: status (KIND_UNSUPPORTED << 24) | site of zk_tx_assign, sites 1 / 3 / 4 (include/zkevm_hip.h).  Only that path
+    raises it; everywhere else kind 15 stays UnsupportedOnDevice."""
+
+
+TX_BAD_SIGNATURE_SITES = {1: "parity or r / s out of range", 3: "no curve point with x = r", 4: "recovered key at infinity"}
+
+
+def bad_signature(msg):
+    """A BadSignature instance: eth_keys' own class when eth_keys is loaded in this process (a caller's `except BadSignature` written
+    against it keeps catching), else this module's"""
+    import sys
+
+    for name in ("eth_keys.exceptions", "eth_keys"):
+        cls = getattr(sys.modules.get(name), "BadSignature", None)
+        if isinstance(cls, type) and issubclass(cls, BaseException):
+            return cls(msg)
+    return BadSignature(msg)
+
+
 KIND_OK, KIND_ASSERT, KIND_CONSTRAINT, KIND_LOOKUP_UNSAT, KIND_LOOKUP_AMBIGUOUS = 0, 1, 2, 3, 4
 KIND_WRONG_QUERY_KEY, KIND_NOT_IMPLEMENTED, KIND_TYPE_ERROR, KIND_OVERFLOW_ERROR = 5, 6, 7, 8
 KIND_VALUE_ERROR, KIND_ZERO_DIVISION, KIND_NAME_ERROR, KIND_INDEX_ERROR, KIND_UNSUPPORTED = 9, 10, 11, 12, 15

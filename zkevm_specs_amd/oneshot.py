@@ -184,3 +184,18 @@ def withdrawal_assign(withdrawals, max_withdrawals, randomness, keccak_rows=True
     kr = np.zeros((n, 5, 4), dtype=np.uint64) if keccak_rows else None
     check(lib.zk_withdrawal_assign(ptr(wd, n), n, m, ptr(rc), 0, ptr(rows, rows.shape[0]), ptr(kr, n)), "zk_withdrawal_assign", lib)
     return rows, kr
+
+
+def tx_assign(tx, randomness, device=None):
+    """zk_tx_assign over raw txs (engine._tx_assign_args) -> (Result, status uint32[n], wire dict: tx_rows, tx_flags, bytes, cells,
+    meta, keccak — the arrays flatten_tx_witness makes)"""
+    lib = _lib.init(device)
+    t, _, opts, keep = engine._tx_assign_args({k: (_host(v) if k in engine.TX_ASSIGN_INPUTS else v) for k, v in tx.items()}, randomness)
+    n = int(t.n_txs)
+    shapes = engine.tx_assign_shapes(n, int(t.max_txs), int(t.max_calldata_bytes))
+    out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items()}
+    w = _lib.ZkTxWire(*[ptr(out[k]) for k in engine.TX_ASSIGN_OUTPUTS])
+    status, r, nk = np.zeros(max(n, 1), dtype=np.uint32), ZkResult(), ctypes.c_uint64()
+    check(lib.zk_tx_assign(ctypes.byref(t), ctypes.byref(w), opts, ptr(status), ctypes.byref(nk), ctypes.byref(r)), "zk_tx_assign")
+    out["keccak"] = out["keccak"][: nk.value]
+    return Result(r), status[:n], out
