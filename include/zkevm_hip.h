@@ -461,6 +461,9 @@ int zk_copy_assign(const zk_copy_events* ev, uint64_t* rows_out, uint32_t* row_f
  *      table (zk_keccak_*: rows [0, n_codes) are the Bytecode circuit's table, the rest the EVM circuit's), the Bytecode circuit's rows
  *      (zk_bytecode_assign_*: the unrolled bytecodes ARE evm.bytecode, cut by code_offsets / code_lengths), the Copy circuit's rows and
  *      the EVM circuit's copy table (zk_copy_assign_*; the Copy circuit looks up evm.rw / evm.bytecode / evm.tx), the State circuit's
+ *      Exp circuit's rows and the EVM circuit's exp table when exp_events.n_events > 0 (zk_exp_assign_*: launched on the EVM chain ahead
+ *      of the open, the Exp circuit's pass on the last chain ordered behind it by an event; exp_rows / evm.exp must then be absent:
+ *      passing both forms is an error; with n_events == 0 they are taken as given, as before), the State circuit's
  *      verdict from evm.rw (zk_state_verify_from_rw_open: the State rows are evaluated where they are computed; with
  *      ZK_OPT_BLOCK_STATE_ROWS or ZK_OPT_STATE_COMPACT the witness is written and read back as zk_state_assign_from_rw_open +
  *      zk_state_open do — the same results, for comparison).  evm.copy / evm.keccak are ignored.  Four host threads drive four chains on
@@ -472,6 +475,12 @@ int zk_copy_assign(const zk_copy_events* ev, uint64_t* rows_out, uint32_t* row_f
  *      State op, ...) is an error return with the text in zk_last_error.  chain_ms (nullable, ten doubles; a measurement aid): host
  *      milliseconds from the call to the end of each chain [0..3], to its start [4..7], to the end of the last one [8] and to the
  *      return [9]. */
+/* EXP events, the input of zk_exp_assign_* (documented with those entries below): ROW-major uint64[n][5][4] — identifier, base lo,
+ * base hi, exponent lo, exponent hi */
+typedef struct zk_exp_events {
+    const uint64_t* events;     uint64_t n_events;
+    uint64_t max_exp_steps;     /* ExpCircuit(max_exp_steps): pad with dummy rows up to 7 * max_exp_steps rows; 0 = no padding */
+} zk_exp_events;
 typedef struct zk_block {
     zk_evm_tables evm;
     const uint8_t* hashed_data; uint64_t hashed_bytes; const uint64_t* hashed_offsets;  /* n_hashed + 1 offsets */
@@ -481,6 +490,7 @@ typedef struct zk_block {
     zk_copy_events copy_events;                                                          /* n_events == 0: no Copy circuit rows */
     const uint64_t* exp_rows; uint64_t n_exp_rows;                                       /* column-major uint64[21][n][4] */
     zk_sign_units tx;                                                                    /* n_units == 0: no Tx circuit */
+    zk_exp_events exp_events;                                                            /* n_events > 0: the Exp rows and evm.exp are derived */
 } zk_block;
 enum { ZK_BLOCK_EVM = 0, ZK_BLOCK_STATE = 1, ZK_BLOCK_BYTECODE = 2, ZK_BLOCK_TX = 3, ZK_BLOCK_COPY = 4, ZK_BLOCK_EXP = 5, ZK_BLOCK_NCIRCUITS = 6 };
 int zk_block_verify(const zk_block* b, uint32_t opts, zk_result* results /* [ZK_BLOCK_NCIRCUITS] */, double* chain_ms /* [10], nullable */);
@@ -630,6 +640,38 @@ typedef struct zk_tx_wire {
 int zk_tx_assign_open(const zk_tx_inputs* in, const zk_tx_wire* out_dev, uint32_t opts, zk_session** out);
 int zk_tx_assign_read(zk_session* s, const zk_tx_wire* host, uint64_t* n_keccak_out);
 int zk_tx_assign(const zk_tx_inputs* in, const zk_tx_wire* out, uint32_t opts, uint32_t* status_out, uint64_t* n_keccak_out, zk_result* result);
+
+/* ---- Exp circuit witness assignment: replaces ExpCircuit.add_event / fill_dummy_events (src/zkevm_specs/evm_circuit/typing.py:
+ *      868-994) and the exp-table rows Tables._convert_exp_circuit_to_table derives (evm_circuit/table.py:654-671).
+ *      One event = one add_event(base, exponent, identifier): events ROW-major uint64[n][5][4] — identifier, base lo, base hi,
+ *      exponent lo, exponent hi (canonical cells; the halves of the two Words below 2^128).  An event with exponent 0 or 1
+ *      contributes no rows; any other bit_length(exponent) - 1 + popcount(exponent) - 1 step rows, from the full exponent down to
+ *      base * base (exponent 2), d = base^exponent mod 2^256 on every row.
+ *      Outputs: rows COLUMN-major uint64[21][n_rows][4] (what zk_exp_open takes): the step rows of all events in event order, then
+ *      the dummy rows of fill_dummy_events while n_rows < 7 * max_exp_steps (none when the step rows reach or exceed that);
+ *      table uint64[n_table][11][4] (what zk_evm_tables.exp takes): one row per step row in the same order, plus ONE row
+ *      (1, 0, 0, 1, 0, 0, 0, 1, 0, 1, 0) for the dummy rows when there is at least one (the reference's table is a set).
+ *      zk_exp_assign_sizes: the three counts; they depend on the exponents' bits, so with ZK_OPT_DEVICE_PTRS they are computed on
+ *      the device and read back (one small read).  n_events == 0 is allowed (dummy rows only).
+ *      zk_exp_assign_open: with ZK_OPT_DEVICE_PTRS `events` is a device pointer and rows_dev / table_dev (each nullable: the
+ *      session then owns the buffer), sized with zk_exp_assign_sizes, receive the outputs, ready for zk_exp_open / zk_evm_open
+ *      without leaving the device.  zk_launch / zk_collect / zk_read_status as for the circuits (one status per row, always 0:
+ *      the domain is checked at open).  An assignment without any row (n_rows == 0) cannot be opened.
+ *      Domain, rejected at sizes / open with an error code and its text in zk_last_error, never guessed:
+ *        ZK_ERR_EXP_CELL   a cell is not canonical (identifier >= p, a lo / hi half >= 2^128);
+ *        ZK_ERR_EXP_ORDER  the identifiers of row-producing events are not strictly increasing (the reference's set would merge,
+ *                          or make ambiguous, what a plain row list cannot; a trace produces them in rw_counter order);
+ *        ZK_ERR_EXP_ROWS   2^31 rows or more. */
+#define ZK_ERR_EXP_CELL (-40)
+#define ZK_ERR_EXP_ORDER (-41)
+#define ZK_ERR_EXP_ROWS (-42)
+/* (zk_exp_events: defined in front of zk_block, which carries one) */
+int zk_exp_assign_sizes(const zk_exp_events* ev, uint32_t opts, uint64_t* n_rows, uint64_t* n_step_rows, uint64_t* n_table);
+int zk_exp_assign_open(const zk_exp_events* ev, uint64_t* rows_dev, uint64_t* table_dev, uint32_t opts, zk_session** out);
+int zk_exp_assign_read(zk_session* s, uint64_t* rows_host, uint64_t* table_host);
+int zk_exp_assign(const zk_exp_events* ev, uint64_t* rows_out, uint64_t* table_out, uint32_t opts, zk_result* result);
+/* the three counts of an open session (what zk_exp_assign_sizes returns for its events), without a second size pass */
+int zk_exp_assign_counts(zk_session* s, uint64_t* n_rows, uint64_t* n_step_rows, uint64_t* n_table);
 
 #ifdef __cplusplus
 }

@@ -3,7 +3,7 @@
 rows/s and algorithmic GB/s (SURVEY.md §8d bytes per unit), device-resident inputs, HIP-event kernel
 time.  bench.py carries the headline EVM / State workloads; this is the side table in DESIGN.md §3.
 `bench_row_kernels.py ecc` runs only the ECC leg, `bench_row_kernels.py withdrawal` only the Withdrawal leg, `bench_row_kernels.py
-tx_assign` only the Tx witness-assignment leg."""
+tx_assign` only the Tx witness-assignment leg, `bench_row_kernels.py exp_assign` only the Exp witness-assignment leg."""
 import json
 import os
 import random
@@ -116,6 +116,45 @@ def tx_assign_leg():
             out[name]["calldata_bytes"] = int(t["offsets"][-1])
 
 
+def exp_assign_leg():
+    """Exp circuit witness assignment (zk_exp_assign_open, events in HBM; kernel_ms = HIP-event span of a pass: power chain + expansion,
+    best-of-run mean of 20 passes after 3) at 2^12 events x 256-bit exponents and 2^16 events x 16-bit exponents; bytes per row = the 21
+    + 11 cells written.  Beside it, in the same process: the State assignment's rows kernel regime (zk_state_assign_open at 2^20 ops,
+    57 cells written per row) and the host path the assignment replaces (synth_block.exp_event_rows + rows_to_colmajor over the
+    first 64 events of the 256-bit set, one core, scaled to the set)."""
+    import time
+
+    from tests.exp_assign_cases import random_events_wire
+    from zkevm_specs_amd.synth_block import exp_event_rows
+    from zkevm_specs_amd.wire import cells_to_ints, rows_to_colmajor
+
+    for n, bits in ((1 << 12, 256), (1 << 16, 16)):
+        ev = random_events_wire(11 + bits, n, bits)
+        s = engine.open_exp_assign(to_dev(ev), 0)
+        name = f"exp_assign_{n}x{bits}b"
+        rows = s.n
+        run(name, s, rows, (21 + 11) * 32)
+        out[name]["events"] = n
+    ev = random_events_wire(11 + 256, 1 << 12, 256)[:64]
+    ints = cells_to_ints(ev)
+    t0 = time.perf_counter()
+    rows_h = []
+    for k in range(64):
+        c = ints[5 * k:5 * k + 5]
+        rows_h += exp_event_rows(c[1] | c[2] << 128, c[3] | c[4] << 128, c[0])[0]
+    rows_to_colmajor(rows_h, 21)
+    dt = time.perf_counter() - t0
+    out["exp_host_path_64x256b"] = {"rows": len(rows_h), "wall_ms": round(dt * 1e3, 1), "rows_per_s": round(len(rows_h) / dt),
+                                    "scaled_to_4096_events_s": round(dt * 64, 2)}
+    print("exp_host_path_64x256b", out["exp_host_path_64x256b"], flush=True)
+    ops, op_flags, *_ = synth_state_ops(1 << 20, seed=2)
+    run("state_assign_2p20", engine.open_state_assign(to_dev(ops), to_dev(op_flags)), 1 << 20, 57 * 32)
+
+
+if sys.argv[1:] == ["exp_assign"]:
+    exp_assign_leg()
+    print(json.dumps(out))
+    sys.exit(0)
 if sys.argv[1:] == ["tx_assign"]:
     tx_assign_leg()
     print(json.dumps(out))

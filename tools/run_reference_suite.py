@@ -40,6 +40,9 @@ REBIND = {  # name in the test module -> (module the test imported it from, mirr
     "verify_copy_table": ("zkevm_specs.copy_circuit", "zkevm_specs_amd.copy_circuit", "verify_copy_table"),
     "verify_exp_circuit": ("zkevm_specs.exp_circuit", "zkevm_specs_amd.exp_circuit", "verify_exp_circuit"),
     "txs2witness": ("zkevm_specs.tx_circuit", "zkevm_specs_amd.tx_circuit", "txs2witness"),
+    # the witness BUILDER of tests/evm/test_exp.py: the class itself is rebound (by identity, as the drivers are), so the reference's
+    # own EXP tests build their Exp rows and their exp table through zk_exp_assign
+    "ExpCircuit": ("zkevm_specs.evm_circuit", "zkevm_specs_amd.exp_circuit", "ExpCircuit"),
 }
 VERIFY_CIRCUIT = {  # `verify_circuit` exists five times: told apart by the module that defined the imported function
     "zkevm_specs.tx_circuit": ("zkevm_specs_amd.tx_circuit", "verify_circuit"),

@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = [
     "zk_keccak_open", "zk_keccak_read_rows", "zk_keccak_table", "zk_state_assign_open", "zk_state_assign_read", "zk_state_assign", "zk_state_ops_from_rw_open", "zk_state_ops_from_rw_read", "zk_state_ops_from_rw", "zk_state_assign_from_rw_open", "zk_state_verify_from_rw_open", "zk_state_verify_from_rw", "zk_block_verify", "zk_ecdsa_open", "zk_ecdsa_open_batches", "zk_ecdsa_verify", "zk_bytecode_assign_open", "zk_bytecode_assign_read", "zk_bytecode_assign", "zk_pi_open", "zk_pi_verify", "zk_pi_copy_open", "zk_pi_copy_verify", "zk_copy_assign_sizes", "zk_copy_assign_open", "zk_copy_assign_read", "zk_copy_assign", "zk_launch", "zk_collect", "zk_read_status", "zk_close", "zk_session_timing", "zk_last_timing", "zk_timing_sums", "zk_last_host_phases", "zk_dist_unique_id", "zk_dist_init", "zk_dist_tally", "zk_dist_close",
     "zk_ecc_assign", "zk_ecc_verify", "zk_withdrawal_open", "zk_withdrawal_verify", "zk_withdrawal_assign",
     "zk_tx_assign_open", "zk_tx_assign_read", "zk_tx_assign",
+    "zk_exp_assign_sizes", "zk_exp_assign_open", "zk_exp_assign_read", "zk_exp_assign", "zk_exp_assign_counts",
 ]
 
 OPT_DEVICE_PTRS = 1
@@ -117,6 +118,13 @@ class ZkCopyEvents(ctypes.Structure):
     ]
 
 
+class ZkExpEvents(ctypes.Structure):
+    _fields_ = [("events", ctypes.c_void_p), ("n_events", ctypes.c_uint64), ("max_exp_steps", ctypes.c_uint64)]
+
+
+ERR_EXP_CELL, ERR_EXP_ORDER, ERR_EXP_ROWS = -40, -41, -42  # ZK_ERR_EXP_* (include/zkevm_hip.h): why zk_exp_assign* rejected its events
+
+
 class ZkBlock(ctypes.Structure):
     """zk_block (include/zkevm_hip.h): the raw device-resident inputs of zk_block_verify"""
     _fields_ = [
@@ -128,6 +136,7 @@ class ZkBlock(ctypes.Structure):
         ("copy_events", ZkCopyEvents),
         ("exp_rows", ctypes.c_void_p), ("n_exp_rows", ctypes.c_uint64),
         ("tx", ZkSignUnits),
+        ("exp_events", ZkExpEvents),
     ]
 
 
@@ -141,7 +150,7 @@ OPT_BLOCK_STATE_ROWS = 64  # zk_block_verify: materialise the State witness inst
 
 
 class EngineError(RuntimeError):
-    pass
+    rc = None  # the C entry's return code, where one call failed (check)
 
 
 _lib = None
@@ -249,6 +258,11 @@ def _bind(lib):
     lib.zk_copy_assign_open.argtypes = [ctypes.POINTER(ZkCopyEvents), vp, vp, vp, vp, vp, u32, ctypes.POINTER(vp)]
     lib.zk_copy_assign_read.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.zk_copy_assign.argtypes = [ctypes.POINTER(ZkCopyEvents), vp, vp, vp, vp, vp, u32, ctypes.POINTER(ZkResult)]
+    lib.zk_exp_assign_sizes.argtypes = [ctypes.POINTER(ZkExpEvents), u32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_exp_assign_open.argtypes = [ctypes.POINTER(ZkExpEvents), vp, vp, u32, ctypes.POINTER(vp)]
+    lib.zk_exp_assign_read.argtypes = [vp, vp, vp]
+    lib.zk_exp_assign_counts.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_exp_assign.argtypes = [ctypes.POINTER(ZkExpEvents), vp, vp, u32, ctypes.POINTER(ZkResult)]
     lib.zk_launch.argtypes = [vp, vp]
     lib.zk_collect.argtypes = [vp, ctypes.POINTER(ZkResult)]
     lib.zk_read_status.argtypes = [vp, vp]
@@ -273,7 +287,9 @@ def check(rc, what, lib=None):
         msg = owner.zk_last_error().decode(errors="replace")
         if not msg and lib is None and _cpu_lib is not None and owner is not _cpu_lib:
             msg = _cpu_lib.zk_last_error().decode(errors="replace")
-        raise EngineError(f"{what} failed (rc={rc}): {msg}")
+        err = EngineError(f"{what} failed (rc={rc}): {msg}")
+        err.rc = int(rc)
+        raise err
 
 
 def init(device=None):

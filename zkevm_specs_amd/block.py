@@ -8,7 +8,7 @@ The reference has no super-circuit driver.  The inputs
   * the byte strings the block hashes — the contracts (`KeccakCircuit.add`, evm_circuit/typing.py:854-865) and the SHA3 inputs;
   * the copy events (`CopyCircuit.copy`, typing.py:1010-1091), the Exp circuit's rows, the Tx units.
 Derived here, on the device: keccak rows (zk_keccak_*), Bytecode rows (zk_bytecode_assign_*), Copy rows + copy table
-(zk_copy_assign_*), State rows from the RW table (zk_state_assign_from_rw_open: re-keying + lexicographic sort + op2row).
+(zk_copy_assign_*), with exp_from_events the Exp rows + exp table (zk_exp_assign_*), State rows from the RW table (zk_state_assign_from_rw_open: re-keying + lexicographic sort + op2row).
 
 Four host threads drive four independent chains, each on its own HIP stream (the C ABI is re-entrant per session; ctypes releases
 the GIL inside every call): the State chain (the longest), keccak -> Bytecode, copy assignment -> EVM + Copy, and Exp + Tx.
@@ -23,14 +23,16 @@ from . import _lib, engine
 from .errors import exception_for_code
 
 
-def stage_block(parts, to_device):
-    """parts (super_circuit.synth_super_block) -> the device-resident inputs verify_block takes"""
+def stage_block(parts, to_device, exp_from_events=False):
+    """parts (super_circuit.synth_super_block) -> the device-resident inputs verify_block takes.  exp_from_events says which of the
+    two forms of the EXP steps the caller hands over: False (default) the Exp circuit's rows and the exp table ready-made, True the
+    events (parts["exp_events"]) — zk_block_verify then derives rows and table on the device (zk_exp_assign_*)."""
     dev = to_device
 
     def cell(r):  # the randomness as a device-resident cell: an int would be uploaded per open, on the default stream (a device-wide wait)
         return dev(np.frombuffer(int(r).to_bytes(32, "little"), dtype="<u8").copy())
 
-    b = {"evm": {k: dev(v) for k, v in parts["evm"].items() if k not in ("keccak", "copy")}}
+    b = {"evm": {k: dev(v) for k, v in parts["evm"].items() if k not in ("keccak", "copy") and not (exp_from_events and k == "exp")}}
     data, offsets, n_codes = parts["keccak_messages"]
     b["keccak"] = (dev(data), dev(offsets), int(n_codes), int(offsets.shape[0]) - 1)
     ub_rows, ub_off, ub_len, k = parts["bytecode_unrolled"]
@@ -39,7 +41,8 @@ def stage_block(parts, to_device):
     ce = parts["copy_events"]
     b["copy_events"] = (dev(ce["events"]), dev(ce["flags"]), dev(ce["data"].view(np.int16)), dev(ce["offsets"]), cell(ce["r"]))
     b["copy_sizes"] = engine.copy_assign_sizes(ce["events"], ce["flags"], ce["data"], ce["offsets"])
-    b["exp_rows"] = dev(parts["exp_rows"])
+    b["exp_rows"] = None if exp_from_events else dev(parts["exp_rows"])
+    b["exp_events"] = dev(parts["exp_events"]) if exp_from_events else None
     tx, r_tx = parts["tx"]
     b["tx"] = ({k: dev(v) for k, v in tx.items()}, cell(r_tx))
     return b
@@ -58,9 +61,10 @@ def native_block(b):
     tx = engine._sign_struct({name: tx_w.get(name) for name in engine._SIGN_WIRE}, r_tx, False)
     ex = b["exp_rows"]
     n_exp = 0 if ex is None else int(ex.shape[1])
+    exp_events = engine._exp_events_struct(b.get("exp_events"), 0)
     return _lib.ZkBlock(evm, ptr(data, int(data.shape[0])), int(data.shape[0]), ptr(offsets), int(n_codes), int(n_msgs), ptr(b["r"]),
                         ptr(ub_off), ptr(ub_len), int(ub_len.shape[0]), int(k), 0, engine._copy_events_struct(ev, fl, da, of, r_copy),
-                        ptr(ex, n_exp), n_exp, tx)
+                        ptr(ex, n_exp), n_exp, tx, exp_events)
 
 
 def verify_block_native(b, device=0, state_compact=False, state_rows=False):
@@ -230,6 +234,8 @@ class BlockVerifier:
             self._bind("rest")
             mark("rest", "start")
             tx_w, r_tx = b["tx"]
+            if b["exp_rows"] is None:
+                raise ValueError("BlockVerifier.verify takes the Exp rows ready-made; a block staged with exp_from_events goes through verify_block_native")
             ex = engine.open_exp(b["exp_rows"], device=self.device)
             ex.launch()
             mark("rest", "exp launched")

@@ -35,6 +35,7 @@
 #include "ecc_circuit.hpp"
 #include "withdrawal_circuit.hpp"
 #include "tx_assign.hpp"
+#include "exp_assign.hpp"
 
 static thread_local std::string g_err;
 #define ARG_TRY(cond, msg) do { if (!(cond)) { g_err = msg; return -1; } } while (0)
@@ -96,7 +97,7 @@ struct zk_session {
     std::vector<u64> w64[4];              // assignment sessions: work / output buffers
     std::vector<u32> out32;
     void (*pass)(zk_session*) = nullptr;  // assignment sessions: one pass computes the outputs and fills `status`
-    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops
+    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 6 exp
     u64 n_ops = 0;                        // RW -> State ops: 1 + kept rows
     std::vector<u32> rekey_plan;          // RW -> State ops: the RwkHostPlan's plan (as words) ...
     std::vector<u32> rekey_jobs;          // ... and its rank jobs (cls, field, base, count)
@@ -121,6 +122,8 @@ struct zk_session {
     EcdsaArgs ecdsa;
     KeccakGenArgs kgen;
     TxAssignArgs txa;
+    ExaArgs exa;
+    ExaSizes exa_sizes;
     std::vector<u64> txa_out64[4];  // Tx assignment outputs: tx_rows, cells, keccak candidates, keccak
     std::vector<u32> txa_out32[3];  // tx_flags, meta, the txs' status
     u64 n_keccak = 0;
@@ -1143,6 +1146,97 @@ extern "C" int zk_copy_assign(const zk_copy_events* t, uint64_t* rows_out, uint3
     rc = zk_launch(s, nullptr);
     if (!rc) rc = zk_collect(s, result);
     if (!rc) rc = zk_copy_assign_read(s, rows_out, row_flags_out, table_out, rw_out, rw_flags_out);
+    zk_close(s);
+    return rc;
+}
+
+// ---- Exp-circuit witness assignment: the per-event / per-row functions of csrc/exp_assign.hpp in plain loops
+static void exp_assign_pass(zk_session* s) {
+    ExaArgs& a = s->exa;
+    for (u64 e = 0; e < a.n_events; e++) exa_chain(a, e);
+    for (u64 j = 0; j < a.n_rows; j++) exa_write_row(a, j);
+}
+// the size pass of an open: counts, first rows, the first rejected event (buffers owned by `s`)
+static int exa_size_pass(const zk_exp_events* t, zk_session* s, ExaSizes& z) {
+    ExaArgs& a = s->exa;
+    s->a64[0].assign(t->events, t->events + t->n_events * EXA_EV_NCELLS * 4);
+    s->a32[0].assign(t->n_events + 1, 0);
+    s->a64[1].assign(t->n_events + 1, 0);
+    a.events = s->a64[0].data(); a.n_events = t->n_events; a.count = s->a32[0].data(); a.row0 = s->a64[1].data();
+    u64 reject = EXA_NO_REJECT, run = 0;
+    for (u64 e = 0; e < a.n_events; e++) {
+        const u32 reason = exa_event_size(a, e);
+        if (reason && reject == EXA_NO_REJECT) reject = exa_reject_word(e, reason);
+        a.row0[e] = run;
+        run += a.count[e];
+    }
+    a.row0[a.n_events] = run;
+    for (u64 e = 0; e < a.n_events; e++) {
+        const u32 reason = exa_ident_check(a, e);
+        if (reason && exa_reject_word(e, reason) < reject) reject = exa_reject_word(e, reason);
+    }
+    char msg[256];
+    const int rc = exa_sizes_of(reject, run, t->max_exp_steps, z, msg, sizeof msg);
+    if (rc) { g_err = msg; return rc; }
+    a.n_step = z.n_step;
+    a.n_rows = z.n_rows;
+    return 0;
+}
+extern "C" int zk_exp_assign_sizes(const zk_exp_events* t, uint32_t opts, uint64_t* n_rows, uint64_t* n_step_rows, uint64_t* n_table) {
+    NO_DEVICE_PTRS(opts, "zk_exp_assign_sizes");
+    ARG_TRY(t && (t->events || t->n_events == 0) && t->n_events < (1ull << 31), "zk_exp_assign_sizes: bad arguments");
+    zk_session* s = new_session(1, false);
+    ExaSizes z;
+    const int rc = exa_size_pass(t, s, z);
+    delete s;
+    if (rc) return rc;
+    if (n_rows) *n_rows = z.n_rows;
+    if (n_step_rows) *n_step_rows = z.n_step;
+    if (n_table) *n_table = z.n_table;
+    return 0;
+}
+extern "C" int zk_exp_assign_open(const zk_exp_events* t, uint64_t* rows_dev, uint64_t* table_dev, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_exp_assign_open");
+    ARG_TRY(t && out && (t->events || t->n_events == 0) && t->n_events < (1ull << 31), "zk_exp_assign_open: bad arguments");
+    ARG_TRY(!rows_dev && !table_dev, "zk_exp_assign_open: output buffers need ZK_OPT_DEVICE_PTRS");
+    zk_session* s = new_session(1, false);
+    ExaSizes& z = s->exa_sizes;
+    const int rc = exa_size_pass(t, s, z);
+    if (rc) { delete s; return rc; }
+    if (z.n_rows == 0) { delete s; g_err = "zk_exp_assign_open: no rows (every exponent is 0 or 1 and max_exp_steps is 0)"; return -1; }
+    s->n = s->hi = z.n_rows;
+    s->status.assign(z.n_rows, 0u);
+    s->w64[0].assign((z.n_step + 1) * 4, 0);                     // d
+    s->w64[1].assign(z.n_rows * EXA_ROW_NCELLS * 4 + 4, 0);      // rows
+    s->w64[2].assign(z.n_table * EXA_TABLE_NCELLS * 4 + 4, 0);   // table
+    s->exa.d = s->w64[0].data(); s->exa.rows = s->w64[1].data(); s->exa.table = s->w64[2].data();
+    s->pass = exp_assign_pass;
+    s->assign_kind = 6;
+    *out = s;
+    return 0;
+}
+extern "C" int zk_exp_assign_counts(zk_session* s, uint64_t* n_rows, uint64_t* n_step_rows, uint64_t* n_table) {
+    ARG_TRY(s && s->assign_kind == 6, "zk_exp_assign_counts: bad arguments");
+    if (n_rows) *n_rows = s->exa_sizes.n_rows;
+    if (n_step_rows) *n_step_rows = s->exa_sizes.n_step;
+    if (n_table) *n_table = s->exa_sizes.n_table;
+    return 0;
+}
+extern "C" int zk_exp_assign_read(zk_session* s, uint64_t* rows_host, uint64_t* table_host) {
+    ARG_TRY(s && s->assign_kind == 6, "zk_exp_assign_read: bad arguments");
+    const ExaSizes& z = s->exa_sizes;
+    if (rows_host) memcpy(rows_host, s->w64[1].data(), (size_t)z.n_rows * EXA_ROW_NCELLS * 32);
+    if (table_host && z.n_table) memcpy(table_host, s->w64[2].data(), (size_t)z.n_table * EXA_TABLE_NCELLS * 32);
+    return 0;
+}
+extern "C" int zk_exp_assign(const zk_exp_events* t, uint64_t* rows_out, uint64_t* table_out, uint32_t opts, zk_result* result) {
+    ARG_TRY(result && rows_out, "zk_exp_assign: null output");
+    zk_session* s = nullptr;
+    int rc = zk_exp_assign_open(t, nullptr, nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc) rc = zk_exp_assign_read(s, rows_out, table_out);
     zk_close(s);
     return rc;
 }

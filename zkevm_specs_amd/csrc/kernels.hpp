@@ -19,6 +19,7 @@
 #include "ecc_circuit.hpp"
 #include "withdrawal_circuit.hpp"
 #include "tx_assign.hpp"
+#include "exp_assign.hpp"
 
 // The single-kernel row sessions keep two tallies and alternate between them: a pass accumulates into one and its first
 // lane clears the other for the pass after it, so that no reset kernel sits in front of every evaluation kernel (a kernel
@@ -85,3 +86,6 @@ void zk_launch_withdrawal_rows(hipStream_t st, const WithdrawalArgs& a, u64 lo, 
 void zk_launch_withdrawal_assign(hipStream_t st, const WithdrawalArgs& a);
 // Tx circuit witness assignment (k_tx_assign.hip): sign hashes, key recovery (status / tally per tx), rows, units, keccak set
 void zk_launch_tx_assign(hipStream_t st, const TxAssignArgs& a, u32* status, ZkTally* tally);
+// Exp circuit witness assignment (k_exp_assign.hip): the open's counts / first rows / reject word, then chain + rows per pass
+void zk_launch_exp_assign_sizes(hipStream_t st, const ExaArgs& a);
+void zk_launch_exp_assign(hipStream_t st, const ExaArgs& a, u32* status, ZkTally* tally);

@@ -570,7 +570,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -602,6 +602,8 @@ struct zk_session {
     PiCopyArgs picopy;
     WithdrawalArgs withdrawal;
     TxAssignArgs txa;
+    ExaArgs exa;
+    u64 exa_n_table = 0;
     RekeyArgs rekey;
     RwkPlan rekey_plan_host;      // the compact-key plan as uploaded (host copy owned by the session: the upload needs no synchronisation of its own)
     bool assign_from_rw = false;  // SESSION_ASSIGN over an RW table: every pass starts with the re-keying and the sort (rekey)
@@ -2138,6 +2140,106 @@ extern "C" int zk_copy_assign(const zk_copy_events* t, uint64_t* rows_out, uint3
     return rc;
 }
 
+// ---- Exp-circuit witness assignment
+// The size pass of an open: events staged, counts / first rows / reject word computed on the session's stream and the two words
+// read back (the one wait of the open).  `s` owns the buffers; on a rejected event the error code is returned with its text.
+static int exa_size_pass(const zk_exp_events* t, bool dev, zk_session* s, ExaSizes& z) {
+    ExaArgs& a = s->exa;
+    const void* p = nullptr;
+    int rc = stage(s, t->n_events ? t->events : nullptr, (size_t)t->n_events * EXA_EV_NCELLS * 32, dev, &p);
+    if (rc) return rc;
+    a.events = (const u64*)p;
+    a.n_events = t->n_events;
+    if ((rc = dev_alloc(s, (void**)&a.count, (size_t)(t->n_events + 1) * 4))) return rc;
+    if ((rc = dev_alloc(s, (void**)&a.row0, (size_t)(t->n_events + 1) * 8))) return rc;
+    if ((rc = dev_alloc(s, (void**)&a.meta, 16))) return rc;
+    u64 meta[2] = {EXA_NO_REJECT, 0};
+    HIP_TRY(hipMemcpyAsync(a.meta, meta, 16, hipMemcpyHostToDevice, s->stream));
+    HIP_TRY(hipMemsetAsync(a.row0, 0, (size_t)(t->n_events + 1) * 8, s->stream));
+    zk_launch_exp_assign_sizes(s->stream, a);
+    HIP_TRY(hipGetLastError());
+    if ((rc = d2h_now(s->stream, meta, a.meta, 16))) return rc;
+    char msg[256];
+    if ((rc = exa_sizes_of(meta[0], meta[1], t->max_exp_steps, z, msg, sizeof msg))) { g_err = msg; return rc; }
+    a.n_step = z.n_step;
+    a.n_rows = z.n_rows;
+    return 0;
+}
+extern "C" int zk_exp_assign_sizes(const zk_exp_events* t, uint32_t opts, uint64_t* n_rows, uint64_t* n_step_rows, uint64_t* n_table) {
+    ARG_TRY(t_device >= 0, "zk_exp_assign_sizes: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(t && (t->events || t->n_events == 0) && t->n_events < (1ull << 31), "zk_exp_assign_sizes: bad arguments");
+    zk_session* s = new zk_session();
+    s->kind = SESSION_EXA;
+    ExaSizes z;
+    const int rc = exa_size_pass(t, opts & ZK_OPT_DEVICE_PTRS, s, z);
+    zk_close(s);
+    if (rc) return rc;
+    if (n_rows) *n_rows = z.n_rows;
+    if (n_step_rows) *n_step_rows = z.n_step;
+    if (n_table) *n_table = z.n_table;
+    return 0;
+}
+// allow_empty: events that expand to no row at all are no error, *out stays null (zk_block_verify: a block without Exp rows)
+static int exa_open(const zk_exp_events* t, uint64_t* rows_dev, uint64_t* table_dev, uint32_t opts, zk_session** out, bool allow_empty) {
+    ARG_TRY(t_device >= 0, "zk_exp_assign_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(t && out && (t->events || t->n_events == 0) && t->n_events < (1ull << 31), "zk_exp_assign_open: bad arguments");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    ARG_TRY(dev || (!rows_dev && !table_dev), "zk_exp_assign_open: output buffers need ZK_OPT_DEVICE_PTRS");
+    zk_session* s = new zk_session();
+    s->kind = SESSION_EXA;
+    ExaArgs& a = s->exa;
+    ExaSizes z;
+    int rc = exa_size_pass(t, dev, s, z);
+    if (rc) goto fail;
+    if (z.n_rows == 0 && allow_empty) { zk_close(s); *out = nullptr; return 0; }
+    if (z.n_rows == 0) { rc = -1; g_err = "zk_exp_assign_open: no rows (every exponent is 0 or 1 and max_exp_steps is 0)"; goto fail; }
+    s->n = z.n_rows;
+    s->exa_n_table = z.n_table;
+    if ((rc = dev_alloc(s, (void**)&a.d, (size_t)(z.n_step + 1) * 32))) goto fail;
+    a.rows = rows_dev; a.table = table_dev;
+    if (!a.rows && (rc = dev_alloc(s, (void**)&a.rows, (size_t)z.n_rows * EXA_ROW_NCELLS * 32))) goto fail;
+    if (!a.table && (rc = dev_alloc(s, (void**)&a.table, (size_t)z.n_table * EXA_TABLE_NCELLS * 32))) goto fail;
+    if ((rc = session_common_init(s))) goto fail;
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_exp_assign_open(const zk_exp_events* t, uint64_t* rows_dev, uint64_t* table_dev, uint32_t opts, zk_session** out) {
+    return exa_open(t, rows_dev, table_dev, opts, out, false);
+}
+extern "C" int zk_exp_assign_counts(zk_session* s, uint64_t* n_rows, uint64_t* n_step_rows, uint64_t* n_table) {
+    ARG_TRY(s && s->kind == SESSION_EXA, "zk_exp_assign_counts: bad arguments");
+    if (n_rows) *n_rows = s->exa.n_rows;
+    if (n_step_rows) *n_step_rows = s->exa.n_step;
+    if (n_table) *n_table = s->exa_n_table;
+    return 0;
+}
+extern "C" int zk_exp_assign_read(zk_session* s, uint64_t* rows_host, uint64_t* table_host) {
+    ARG_TRY(s && s->kind == SESSION_EXA, "zk_exp_assign_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    const ExaArgs& a = s->exa;
+    if (rows_host) HIP_TRY(hipMemcpyAsync(rows_host, a.rows, (size_t)a.n_rows * EXA_ROW_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+    if (table_host && s->exa_n_table) HIP_TRY(hipMemcpyAsync(table_host, a.table, (size_t)s->exa_n_table * EXA_TABLE_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+extern "C" int zk_exp_assign(const zk_exp_events* t, uint64_t* rows_out, uint64_t* table_out, uint32_t opts, zk_result* result) {
+    ARG_TRY(result && rows_out, "zk_exp_assign: null output");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    int rc = zk_exp_assign_open(t, dev ? rows_out : nullptr, dev ? table_out : nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && !dev) rc = zk_exp_assign_read(s, rows_out, table_out);
+    zk_close(s);
+    return rc;
+}
+
 // ---- Public-inputs circuit
 extern "C" int zk_pi_open(const uint64_t* rows, uint64_t n, const uint64_t* keccak, uint64_t n_keccak, const uint64_t* gas, uint64_t n_gas,
                           uint64_t circuit_len, const uint64_t* keccak_rand, const uint64_t* byte_pow_base, uint32_t opts, zk_session** out) {
@@ -2463,6 +2565,7 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     case SESSION_TXA: zk_launch_tx_assign(s->stream, s->txa, status, s->d_tally); break;
     case SESSION_PICOPY: zk_launch_pi_copy(s->stream, s->picopy, status, tally); break;
     case SESSION_CPA: zk_launch_copy_assign(s->stream, s->cpa, status, s->d_tally); break;
+    case SESSION_EXA: zk_launch_exp_assign(s->stream, s->exa, status, s->d_tally); break;
     case SESSION_REKEY: zk_launch_state_rekey(s->stream, s->rekey, status, s->d_tally); break;
     case SESSION_EVM: {
         // the state-sorted lane mapping is derived from the step column on every pass
@@ -2908,6 +3011,8 @@ struct BlockShared {
     zk_session* keep_cpa = nullptr;  // the copy assignment session (the Copy circuit on chain 3 reads its rows)
     bool cpa_enqueued = false, cpa_failed = false;
     hipEvent_t ev_cpa = nullptr;
+    zk_session* keep_exa = nullptr;  // the Exp assignment session (the Exp circuit on chain 3 reads its rows); set before cpa_enqueued
+    hipEvent_t ev_exa = nullptr;
     hipEvent_t ev_keccak = nullptr;  // here: "the Bytecode assignment's rows are written"
     int rc[4] = {0, 0, 0, 0};
     std::string err[4];
@@ -2925,6 +3030,8 @@ extern "C" int zk_block_verify(const zk_block* b, uint32_t opts, zk_result* resu
     ARG_TRY(b && results && (opts & ZK_OPT_DEVICE_PTRS), "zk_block_verify: needs a block, a result array and ZK_OPT_DEVICE_PTRS");
     ARG_TRY(b->evm.steps && b->evm.n_steps >= 2 && b->evm.rw && b->evm.n_rw && b->randomness && b->hashed_offsets && b->n_hashed >= b->n_codes &&
             b->code_offsets && b->code_lengths && b->n_bytecodes, "zk_block_verify: bad arguments");
+    ARG_TRY(!b->exp_events.n_events || (b->exp_events.events && !b->n_exp_rows && !b->evm.n_exp),
+            "zk_block_verify: exp_events given together with exp_rows / evm.exp (hand over one of the two forms)");
     HIP_TRY(hipSetDevice(t_device));
     const int device = t_device;
     const uint32_t dev_opts = ZK_OPT_DEVICE_PTRS, st_opts = ZK_OPT_DEVICE_PTRS | (opts & ZK_OPT_STATE_COMPACT);
@@ -2952,10 +3059,11 @@ extern "C" int zk_block_verify(const zk_block* b, uint32_t opts, zk_result* resu
     bool views_ready = false, views_failed = false;
     { int erc = arena_event(device, &sh.ev_keccak); if (erc) return erc; }
     { int erc = arena_event(device, &sh.ev_cpa); if (erc) return erc; }
+    { int erc = arena_event(device, &sh.ev_exa); if (erc) return erc; }
     // Chains (each a host thread on its own stream):
     //   0  State:     RW table -> State verdict (rows evaluated where they are computed; or -> State witness -> State circuit)
     //   1  Bytecode:  keccak of the contracts (long messages: the slow pass) -> [Bytecode rows ready: event from chain 3] -> Bytecode circuit
-    //   2  EVM:       copy assignment (+ event) -> keccak of the SHA3 inputs (its own short pass: the EVM circuit's keccak table does not
+    //   2  EVM:       [Exp assignment from exp_events (+ event)] -> copy assignment (+ event) -> keccak of the SHA3 inputs (its own short pass: the EVM circuit's keccak table does not
     //                 hold the contracts' hashes, so this chain never waits for chain 1) -> EVM open + pass
     //   3  rest:      Bytecode assignment (+ event) -> Exp -> Tx -> [copy rows ready: event from chain 2] -> Copy circuit
     auto enter = [&](int chain) {
@@ -3048,12 +3156,25 @@ extern "C" int zk_block_verify(const zk_block* b, uint32_t opts, zk_result* resu
     auto chain_evm = [&] {
         const bool entered = enter(2);
         int rc = 0;
-        zk_session *ca = nullptr, *es = nullptr, *ks = nullptr;
+        zk_session *ca = nullptr, *es = nullptr, *ks = nullptr, *xa = nullptr;
         zk_result rc_assign, rk;
         zk_evm_tables t = b->evm;
         t.copy = nullptr; t.n_copy = 0; t.keccak = nullptr; t.n_keccak = 0;
         bool cpa_signalled = false;
         if (!entered) { rc = -2; g_err = "zk_block_verify: reading the block's randomness / offsets failed"; goto done; }
+        if (b->exp_events.n_events) {
+            // first on this chain: its open reads the step-row total back, a wait that must find nothing of the chain in front of it.
+            // A rejected event is this open's error return, with its text.
+            BLK_TRY(exa_open(&b->exp_events, nullptr, nullptr, dev_opts, &xa, true));
+            if (xa) {
+                BLK_TRY(zk_launch(xa, nullptr));
+                if (hipEventRecord(sh.ev_exa, xa->stream) != hipSuccess) { rc = -2; g_err = "zk_block_verify: event record failed"; goto done; }
+                sh.keep_exa = xa;
+                mark(2, "exp assignment launched");
+                t.exp = xa->exa.table;
+                t.n_exp = xa->exa_n_table;
+            }
+        }
         if (b->copy_events.n_events) {
             BLK_TRY(zk_copy_assign_open(&b->copy_events, nullptr, nullptr, nullptr, nullptr, nullptr, dev_opts, &ca));
             BLK_TRY(zk_launch(ca, nullptr));
@@ -3089,7 +3210,9 @@ extern "C" int zk_block_verify(const zk_block* b, uint32_t opts, zk_result* resu
             BLK_TRY(zk_collect(ks, &rk));
             if (rk.fail_count) { rc = -1; g_err = "zk_block_verify: a SHA3 input was rejected by the keccak table generation"; goto done; }
         }
+        if (xa) BLK_TRY(zk_collect(xa, &rc_assign));  // (no failure modes of its own: the events were checked at its open)
     done:
+        if (xa && !sh.keep_exa) zk_close(xa);
         if (!cpa_signalled) {
             { std::lock_guard<std::mutex> lock(sh.m); sh.cpa_failed = true; sh.cpa_enqueued = true; }
             sh.cv.notify_all();
@@ -3114,7 +3237,7 @@ extern "C" int zk_block_verify(const zk_block* b, uint32_t opts, zk_result* resu
         sh.cv.notify_all();
         signalled = true;
         mark(3, "bytecode assignment launched");
-        if (b->n_exp_rows) {
+        if (b->n_exp_rows && !b->exp_events.n_events) {
             BLK_TRY(zk_exp_open(b->exp_rows, b->n_exp_rows, dev_opts, &ex));
             BLK_TRY(zk_launch(ex, nullptr));
         }
@@ -3128,6 +3251,12 @@ extern "C" int zk_block_verify(const zk_block* b, uint32_t opts, zk_result* resu
             std::unique_lock<std::mutex> lock(sh.m);
             sh.cv.wait(lock, [&] { return sh.cpa_enqueued; });
             if (sh.cpa_failed) { rc = -1; g_err = "zk_block_verify: the copy assignment failed before it was enqueued"; goto done; }
+        }
+        if (sh.keep_exa) {  // (chain 2 set it before it signalled cpa_enqueued) the Exp circuit over the rows its assignment writes
+            BLK_TRY(zk_exp_open(sh.keep_exa->exa.rows, sh.keep_exa->exa.n_rows, dev_opts, &ex));
+            if (hipStreamWaitEvent(g_block_stream[device][3], sh.ev_exa, 0) != hipSuccess) { rc = -2; g_err = "zk_block_verify: stream wait failed"; goto done; }
+            BLK_TRY(zk_launch(ex, nullptr));
+            mark(3, "exp circuit launched");
         }
         if (sh.keep_cpa && sh.keep_cpa->cpa.n_rows) {
             zk_session* ca = sh.keep_cpa;
@@ -3191,9 +3320,11 @@ extern "C" int zk_block_verify(const zk_block* b, uint32_t opts, zk_result* resu
     const double joined_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - sh.t0).count();
     if (sh.keep) zk_close(sh.keep);
     if (sh.keep_cpa) zk_close(sh.keep_cpa);
+    if (sh.keep_exa) zk_close(sh.keep_exa);
     {
         DevArena& A = g_arena[device];
         std::lock_guard<std::mutex> lock(A.m);
+        A.events.push_back(sh.ev_exa);
         A.events.push_back(sh.ev_keccak);
         A.events.push_back(sh.ev_cpa);
     }

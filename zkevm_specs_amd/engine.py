@@ -875,3 +875,62 @@ def open_tx_assign(tx, randomness, outs=None, device=None):
     sizes = {"max_txs": int(tx["max_txs"]), "max_calldata_bytes": int(tx["max_calldata_bytes"])}
     return _open(lib, lib.zk_tx_assign_open, t.n_txs, (keep, t, w, sizes), ctypes.byref(t), ctypes.byref(w) if w is not None else None,
                  opts, cls=TxAssignSession)
+
+
+# ---- Exp circuit witness assignment (zk_exp_assign*) ------------------------------------------------------------------------------
+def _exp_events_struct(events, max_exp_steps):
+    """the ZkExpEvents block over a prepared event array (None or empty: a null pointer, dummy rows only)"""
+    n = _rows(events)
+    return _lib.ZkExpEvents(ptr(events, n), n, int(max_exp_steps))
+
+
+def exp_assign_sizes(events, max_exp_steps=0, device=None):
+    """(n_rows, n_step_rows, n_table) a list of EXP events expands to; with device tensors the counts come back from the device.
+    Raises EngineError (rc = _lib.ERR_EXP_*) for events outside the wire's domain."""
+    lib = _lib.init(device)
+    _expect(events, "exp events", 8, (None, 5, 4))
+    (events,), opts = _prep([events])
+    t = _exp_events_struct(events, max_exp_steps)
+    a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    check(lib.zk_exp_assign_sizes(ctypes.byref(t), opts, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "zk_exp_assign_sizes", lib)
+    return int(a.value), int(b.value), int(c.value)
+
+
+def _exp_assign_args(events, max_exp_steps, device, outs=(None, None)):
+    """zk_exp_assign_open / zk_exp_assign -> (ZkExpEvents, opts, kept arrays, sizes or None); outs: (rows_out, table_out), checked
+    against the sizes (one size pass of their own: zk_exp_assign_sizes) and prepared with the input (kept arrays 1..2).  Without
+    output buffers nothing is sized here: the open's own size pass is the only one (ExpAssignSession reads its counts back)."""
+    _expect(events, "exp events", 8, (None, 5, 4))
+    sizes = None
+    if any(o is not None for o in outs):
+        sizes = n_rows, _, n_table = exp_assign_sizes(events, max_exp_steps, device)
+        _expect(outs[0], "rows", 8, (21, n_rows, 4))
+        _expect(outs[1], "table", 8, (n_table, 11, 4))
+    keep, opts = _prep([events, *outs], outputs=(1, 2))
+    return _exp_events_struct(keep[0], max_exp_steps), opts, keep, sizes
+
+
+class ExpAssignSession(Session):
+    """Exp-circuit witness assignment session: launch()/collect() like the circuits; read() for the outputs."""
+
+    def read(self):
+        """-> (rows uint64[21, n, 4], table uint64[m, 11, 4]) on the host"""
+        rows, table = np.empty((21, self.n, 4), dtype=np.uint64), np.empty((self.n_table, 11, 4), dtype=np.uint64)
+        check(self._lib.zk_exp_assign_read(self._h, ptr(rows), ptr(table, self.n_table)), "zk_exp_assign_read", self._lib)
+        return rows, table
+
+
+def open_exp_assign(events, max_exp_steps=0, rows_dev=None, table_dev=None, device=None):
+    """events uint64[n, 5, 4] (row-major EXP events: identifier, base lo / hi, exponent lo / hi; include/zkevm_hip.h) ->
+    ExpAssignSession over the n_rows circuit rows (n, n_step, n_table: the open's counts).  numpy inputs are staged to HBM; torch CUDA
+    tensors are used in place and the optional rows_dev uint64[21, n_rows, 4] / table_dev uint64[n_table, 11, 4] (sized with
+    exp_assign_sizes) receive the outputs, ready for open_exp / open_evm."""
+    lib = _lib.init(device)
+    t, opts, keep, _ = _exp_assign_args(events, max_exp_steps, device, (rows_dev, table_dev))
+    if (rows_dev is not None or table_dev is not None) and not opts:
+        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
+    s = _open(lib, lib.zk_exp_assign_open, 0, keep, ctypes.byref(t), ptr(keep[1]), ptr(keep[2]), opts, cls=ExpAssignSession)
+    a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    check(lib.zk_exp_assign_counts(s._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "zk_exp_assign_counts", lib)
+    s.n, s.n_step, s.n_table = int(a.value), int(b.value), int(c.value)
+    return s

@@ -27,6 +27,13 @@ class FQ:
     def __int__(self):
         return self.n
 
+    def __eq__(self, other):  # by value, as py_ecc's FQ: rows built from these go into the reference's table SETS
+        n = getattr(other, "n", other)
+        return isinstance(n, int) and n == self.n
+
+    def __hash__(self):
+        return hash(self.n)
+
     def __repr__(self):
         return f"FQ({self.n})"
 
@@ -40,6 +47,23 @@ class Word:
         if hi is None:  # Word(int)
             lo, hi = int(lo) & ((1 << 128) - 1), int(lo) >> 128
         self.lo, self.hi = FQ(lo), FQ(hi)
+
+    def int_value(self):
+        return self.lo.n + (self.hi.n << 128)
+
+    def to_64s(self):
+        """the four 64-bit limbs, little-endian (util/arithmetic.py Word.to_64s)"""
+        v = self.int_value()
+        return tuple(FQ((v >> (64 * k)) & ((1 << 64) - 1)) for k in range(4))
+
+    def __eq__(self, other):
+        return hasattr(other, "lo") and hasattr(other, "hi") and self.lo == other.lo and self.hi == other.hi
+
+    def __hash__(self):
+        return hash((self.lo.n, self.hi.n))
+
+    def __repr__(self):
+        return f"Word({self.int_value()})"
 
 
 class WordOrValue(Word):

@@ -132,6 +132,21 @@ def copy_assign(events, flags, data, offsets, randomness, device=None):
     return Result(r), rows, rf, table, rw, rwf
 
 
+def exp_assign(events, max_exp_steps=0, device=None):
+    """zk_exp_assign over EXP events uint64[n, 5, 4] -> (Result or None, rows uint64[21, n_rows, 4], table uint64[n_table, 11, 4]);
+    events that expand to no row at all give empty arrays without a pass (Result None).  The host buffers of a one-shot have to be
+    sized before the call (zk_exp_assign_sizes); a session (engine.open_exp_assign) sizes once."""
+    lib = _lib.init(device)
+    events = _host(events, np.uint64)
+    n_rows, _, n_table = engine.exp_assign_sizes(events, max_exp_steps, device)
+    rows, table, r = np.zeros((21, n_rows, 4), dtype=np.uint64), np.zeros((n_table, 11, 4), dtype=np.uint64), ZkResult()
+    if n_rows == 0:
+        return None, rows, table
+    t, opts, keep, _ = engine._exp_assign_args(events, max_exp_steps, device)
+    check(lib.zk_exp_assign(ctypes.byref(t), ptr(rows), ptr(table, n_table), opts, ctypes.byref(r)), "zk_exp_assign", lib)
+    return Result(r), rows, table
+
+
 def pi_verify(rows, keccak, gas, circuit_len, keccak_rand=255, byte_pow_base=255, device=None):
     """zk_pi_verify -> (Result, status uint32[n])"""
     lib = _lib.init(device)

@@ -128,6 +128,7 @@ def synth_super_block(log_total=20, seed=5, keccak_rows_of=None, block_ops=None,
     meta = evm.pop("meta")
     copy_ev = evm.pop("copy_events")
     exp_rows = evm.pop("exp_rows")
+    exp_events = evm.pop("exp_events")  # the EXP steps as events (zk_exp_assign's input); the rows above stay what the block evaluates
     evm.pop("sha3_inputs")
     evm["keccak"] = sha3_rows  # the EVM circuit's keccak table: the SHA3 steps' rows (execution/sha3.py:31)
     # evm["exp"] (the exp table of the EXP steps) came with the trace; evm["copy"] is produced by the copy assignment (SuperCircuit)
@@ -146,7 +147,7 @@ def synth_super_block(log_total=20, seed=5, keccak_rows_of=None, block_ops=None,
     n_exp = int(exp_rows.shape[1])
     rows = {"evm": n_steps - 1, "state": n_state, "bytecode": 1 << k, "tx": n_tx, "copy": int(copy_ev["n_rows"]), "exp": n_exp}
     return {"codes": codes, "evm": evm, "state_ops": None, "bytecode": (bc_rows, keccak, r), "bytecode_unrolled": (bt, offsets, lengths, k),
-            "tx": (tx, r), "copy_events": copy_ev, "exp_rows": exp_rows, "rows": rows, "keccak_messages": (k_data, k_offsets, len(codes)),
+            "tx": (tx, r), "copy_events": copy_ev, "exp_rows": exp_rows, "exp_events": exp_events, "rows": rows, "keccak_messages": (k_data, k_offsets, len(codes)),
             "meta": dict(meta, n_contracts=n_contracts, code_rows=n_code_rows, state_rows_from_rw_table=True, copy_exp_rows_from_trace=True)}
 
 
@@ -158,7 +159,7 @@ class SuperCircuit:
     """Sessions of the four circuits over one witness set; launch() enqueues one pass of each, collect() returns
     ({circuit: Result}, total fail_count, first failing (circuit, row, code))."""
 
-    def __init__(self, parts, device=None, to_device=None, shard=None, state_compact=False, state_fused=False):
+    def __init__(self, parts, device=None, to_device=None, shard=None, state_compact=False, state_fused=False, exp_from_events=False):
         """shard = (rank, world): ONE global block, every circuit's rows cut into `world` contiguous ranges with that
         circuit's halo (distributed.HALO), all tables whole on every rank (BASELINE configs[4]).  The
         witness assignment (State / Bytecode / Copy rows from ops / unrolled codes / copy events) runs over the whole
@@ -173,6 +174,24 @@ class SuperCircuit:
         self._keep = []
         evm_w = {k: dev(v) for k, v in parts["evm"].items()}
         on_dev = hasattr(evm_w["steps"], "is_cuda")
+        exp_assigned = None
+        if exp_from_events:  # the caller hands over the EXP steps as events: rows and exp table are derived (zk_exp_assign_*)
+            ev = dev(parts["exp_events"])
+            if on_dev:
+                import torch
+
+                n_rows, _, n_table = engine.exp_assign_sizes(ev, 0, device)
+                e_rows_b = torch.empty((21, n_rows, 4), dtype=torch.int64, device=ev.device)
+                e_table_b = torch.empty((n_table, 11, 4), dtype=torch.int64, device=ev.device)
+                if n_rows:
+                    with engine.open_exp_assign(ev, 0, e_rows_b, e_table_b, device=device) as a:
+                        a.run()
+                exp_assigned = (e_rows_b, e_table_b)
+            else:
+                from . import oneshot
+
+                exp_assigned = oneshot.exp_assign(ev, 0, device=device)[1:]
+            evm_w["exp"] = exp_assigned[1]
         odev = evm_w["steps"].device if on_dev else None
         self.state_from_rw = parts.get("state_ops") is None
         # state_compact: the State rows are assigned and evaluated without their limb / byte columns (ZK_OPT_STATE_COMPACT: 15 of the 57
@@ -313,8 +332,8 @@ class SuperCircuit:
             else:
                 self.sessions["copy"] = engine.open_copy(c_rows, c_rf, ce["r"], c_rw, c_rwf, dev(ce["bytecode"]), dev(ce["tx"]), dev(ce["tx_flags"]),
                                                          device=device)
-        if "exp_rows" in parts and int(parts["exp_rows"].shape[1]) > 0:
-            e_rows = dev(parts["exp_rows"])
+        if (int(exp_assigned[0].shape[1]) > 0) if exp_assigned is not None else ("exp_rows" in parts and int(parts["exp_rows"].shape[1]) > 0):
+            e_rows = exp_assigned[0] if exp_assigned is not None else dev(parts["exp_rows"])
             self.global_rows["exp"], self.row_lo["exp"] = int(e_rows.shape[1]), 0
             if world > 1:
                 e_rows, _, lo_, hi_, self.row_lo["exp"] = distributed.shard_rows(e_rows, None, rank, world, "exp")

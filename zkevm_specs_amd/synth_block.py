@@ -211,7 +211,8 @@ def synth_block_trace(n_steps, seed=5, seg_len=640, n_contracts=16, code_hashes=
     block_ops=True: the programs also hash, copy code and exponentiate (SHA3 / CODECOPY / EXP); the dict then carries what the
     other circuits and tables of the block are derived from — `copy_events` (the events of those steps in zk_copy_events form,
     rw_counters absolute: zk_copy_assign expands them to the Copy circuit's rows and the EVM circuit's copy table; their Memory
-    rows are ALREADY in `rw`), `exp_rows` / `exp` (Exp circuit rows, column-major, and the EVM circuit's exp table), `sha3_inputs`
+    rows are ALREADY in `rw`), `exp_rows` / `exp` (Exp circuit rows, column-major, and the EVM circuit's exp table), `exp_events` (the same EXP steps as events in
+    zk_exp_events form: zk_exp_assign derives both from them), `sha3_inputs`
     (the keccak table's messages).  digest_of(list of bytes) -> list of 32-byte keccak-256 digests (the pushed hashes must be the
     real ones: the keccak table is built from the inputs); randomness: the block's keccak randomness (copy-table RLCs)."""
     rng = random.Random(seed)
@@ -222,7 +223,7 @@ def synth_block_trace(n_steps, seed=5, seg_len=640, n_contracts=16, code_hashes=
         msgs = [m for c in contracts for m in c.sha3_inputs]
         digest = dict(zip(msgs, digest_of(msgs)))
     copy_events, copy_flags, copy_data, copy_offsets = [], [], [], [0]
-    exp_rows, exp_table = [], []
+    exp_rows, exp_table, exp_events = [], [], []
     fixups = []  # (list, index, column): rw_counter-valued cells recorded relative to the prelude, shifted with the rows at the end
     if code_hashes is not None:
         for c, h in zip(contracts, code_hashes):
@@ -429,6 +430,8 @@ def synth_block_trace(n_steps, seed=5, seg_len=640, n_contracts=16, code_hashes=
                 push(pow(base, exponent, 1 << 256), 1)
                 sp += 1
                 rows_, table_ = exp_event_rows(base, exponent, rwc)  # identifier = the rw_counter after the three stack rows (exp.py:31)
+                fixups.append((exp_events, len(exp_events), 0))  # the same step as zk_exp_events takes it: identifier, base, exponent
+                exp_events.append([rwc, base & M128, base >> 128, exponent & M128, exponent >> 128])
                 for r_ in rows_:
                     fixups.append((exp_rows, len(exp_rows), 2))
                     exp_rows.append(r_)
@@ -483,5 +486,6 @@ def synth_block_trace(n_steps, seed=5, seg_len=640, n_contracts=16, code_hashes=
                               "n_rows": 2 * sum(e[9] for e in copy_events)}
         out["exp_rows"] = rows_to_colmajor(exp_rows, 21)
         out["exp"] = rows_to_rowmajor(exp_table, 11)
+        out["exp_events"] = rows_to_rowmajor(exp_events, 5)
         out["sha3_inputs"] = [m for c in contracts for m in c.sha3_inputs]
     return out
