@@ -124,6 +124,7 @@ class Ins:
         self.next = w.steps[idx + 1]
         self.is_first, self.is_last = is_first, is_last
         self.seq = 0
+        self.required = None  # a list: collects the ordinals of the checkpoints reached through require() (verify_step's `trace`)
         self.rw_off = self.pc_off = self.sp_off = 0
 
     # ---- checkpoints --------------------------------------------------------------------
@@ -135,6 +136,8 @@ class Ins:
 
     def require(self, cond, kind=ASSERT):
         self.cp()
+        if self.required is not None:
+            self.required.append(self.seq)
         if not cond:
             self.fail(kind)
 
@@ -1713,7 +1716,7 @@ def g_end_block(i):  # end_block.py
     invalid_rows = [k for k, r in enumerate(w.tx) if r[1] == TXC.TxInvalid]
     i.require(not any(w.tx_flags[k] & 1 for k in invalid_rows))  # `.value.value()` on every TxInvalid row (:70-78)
     total_valid_txs = total_txs - sum(1 for k in invalid_rows if w.tx[k][3] == 1)
-    max_rws, max_wds = len(w.rw), len(w.withdrawals)
+    max_rws, max_wds = len(set(w.rw)), len(w.withdrawals)  # len(rw_table): the reference's table is a set, equal rows count once
     total_wds = sum(1 for r in w.withdrawals if r[3] != 0)
     is_empty = int((i.curr[S_RWC] - 1) % P == 0)
     total_rws = (1 - is_empty) * (i.curr[S_RWC] - 1 + 2) % P
@@ -2261,9 +2264,7 @@ def g_create(i):  # create.py (CREATE and CREATE2)
                 next_hash = (i.next[S_CH_LO], i.next[S_CH_HI])
                 inc, _ = i.copy_lookup((i.curr[S_CALL_ID], 0), CDT_MEMORY, next_hash, CDT_BYTECODE, offset, offset + size, 0, size,
                                        i.curr[S_RWC] + i.rw_off)
-                if inc >= 1 << 62:
-                    raise Fail(UNSUPPORTED, i.seq)  # rw_counter_offset += int(copy_rwc_inc): kept in 64 bits on the device
-                i.rw_off += inc
+                i.rw_off += inc  # rw_counter_offset += int(copy_rwc_inc): any cell value (the counters below are taken in the field)
                 code_size = i.bytecode_length(next_hash)
                 i.constrain_equal(code_size, size)
                 for tag, want in ((CC.ProgramCounter, i.curr[S_PC] + 1), (CC.StackPointer, i.curr[S_SP] + sp_delta),
@@ -2605,7 +2606,13 @@ GADGETS = {
 SUPPORTED_STATES = sorted(int(s) for s in GADGETS)
 
 
+_STATE_VALUES = frozenset(int(s) for s in ES)
+_HALTS = frozenset(int(s) for s in ES if T.halts(s))
+
+
 def _state_transition_ok(curr, nxt):  # instruction.py:189-204
+    """Total over plain integers: a value that is no ExecutionState member halts nothing and equals no state.  (verify_step
+    never asks about one: such a pair has its verdict before checkpoint 1, see there.)"""
     E = ES
     if curr == E.EndTx and nxt not in (E.BeginTx, E.EndBlock):
         return False
@@ -2614,17 +2621,36 @@ def _state_transition_ok(curr, nxt):  # instruction.py:189-204
     if nxt == E.BeginTx:
         return curr == E.EndTx
     if nxt == E.EndTx:
-        return T.halts(curr) or curr == E.BeginTx
+        return curr in _HALTS or curr == E.BeginTx
     if nxt == E.EndBlock:
         return curr in (E.EndTx, E.EndBlock)
     return True
 
 
-def verify_step(w, idx, is_first=False, is_last=False):
-    """Status code of the step pair (idx, idx+1) — main.py:47-63."""
+def verify_step(w, idx, is_first=False, is_last=False, trace=None):
+    """Status code of the step pair (idx, idx+1) — main.py:47-63.  `trace`, a dict, receives the accounting the checkpoint census
+    needs (tests/checkpoint_cases.py): "count", the number of checkpoints evaluated, and "required", the ordinals of those that were
+    reached through require() — a condition of the circuit, as opposed to a lookup or a dispatch."""
     i = Ins(w, idx, is_first, is_last)
+    if trace is not None:
+        i.required = trace["required"] = []
+    try:
+        return _verify_step(i, is_first, is_last)
+    finally:
+        if trace is not None:
+            trace["count"] = i.seq
+
+
+def _verify_step(i, is_first, is_last):
     try:
         state = i.curr[S_STATE]
+        # An execution_state cell that is no ExecutionState member (0, above the last member, 2^64, P - 1, ...), as curr or as
+        # next: the reference's steps hold enum members, so the wire value has no counterpart there — the only thing the
+        # reference can do with it is `ExecutionState(v)`, which raises ValueError.  That is the pair's verdict, outside every
+        # checkpoint (seq 0) and before is_first / is_last are looked at: VALUE_ERROR << 24.  csrc/evm_circuit.hpp
+        # (evm_check_step) returns the same code.
+        if state not in _STATE_VALUES or i.next[S_STATE] not in _STATE_VALUES:
+            raise Fail(VALUE_ERROR, 0)
         if is_first:
             i.require(state in (ES.BeginTx, ES.EndBlock))
             i.constrain_equal(i.curr[S_RWC], 1)

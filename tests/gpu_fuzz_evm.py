@@ -36,6 +36,7 @@ def step_fuzz(w):
 
 
 tot = fail = bad = 0
+sites = set()  # distinct (execution_state cell, failing checkpoint) pairs: what this run adds to the directed cases of tests/golden/checkpoint_cases.npz
 gd = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 for fn in golden_files(gd):
     cases = [c for c in load_cases(fn) if "#fuzz" not in c[0]][:10]
@@ -48,8 +49,9 @@ for fn in golden_files(gd):
                 got = s.read_status().tolist()
             tot += len(exp)
             fail += sum(1 for e in exp if e)
+            sites.update((int.from_bytes(fw["steps"][j, 0].tobytes(), "little"), e & 0xFFFFFF) for j, e in enumerate(exp) if e)
             if got != exp:
                 bad += 1
                 if bad <= 10:
                     print("MISMATCH", os.path.basename(fn), name, got, exp, flush=True)
-print(f"fuzzed step pairs: {tot}, failing in the oracle: {fail}, mismatching cases: {bad}")
+print(f"fuzzed step pairs: {tot}, failing in the oracle: {fail}, distinct (state, seq) failing sites: {len(sites)}, mismatching cases: {bad}")

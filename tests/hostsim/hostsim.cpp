@@ -117,6 +117,7 @@ extern "C" int sim_evm_verify(const u64* steps, u64 n_steps, const u64* rw, cons
         const HostEvmAgg g = evm_aggregates_host(tx, tx_flags, n_tx, wds, n_wds);
         a.agg_max_txs = g.max_txs; a.agg_total_txs = g.total_txs; a.agg_invalid_txs = g.invalid_txs;
         a.agg_bad_invalid_rows = g.bad_invalid_rows; a.agg_total_wds = g.total_wds;
+        a.agg_rw_dups = rw_duplicate_rows_host(rw, n_rw);
     }
     a.copy = tcopy.t;
     a.keccak = tkeccak.t;

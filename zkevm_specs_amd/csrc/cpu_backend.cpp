@@ -407,6 +407,7 @@ extern "C" int zk_evm_open(const zk_evm_tables* t, uint32_t opts, zk_session** o
         const HostEvmAgg g = evm_aggregates_host(t->tx, t->tx_flags, t->n_tx, t->withdrawals, t->n_withdrawals);
         a.agg_max_txs = g.max_txs; a.agg_total_txs = g.total_txs; a.agg_invalid_txs = g.invalid_txs;
         a.agg_bad_invalid_rows = g.bad_invalid_rows; a.agg_total_wds = g.total_wds;
+        a.agg_rw_dups = rw_duplicate_rows_host(t->rw, t->n_rw);
     }
     a.aux = nullptr;
     a.aux_kind = nullptr;

@@ -20,6 +20,9 @@
 // Status code of a step = (kind << 24) | seq: `seq` is the ordinal of the failing *checkpoint*
 // (every primitive that can raise counts one, in the reference's evaluation order) — the same
 // numbering oracle/evm_oracle.py uses, so complete codes are comparable in the parity tests.
+// One code lies before every checkpoint: a pair whose curr or next execution_state cell is no ExecutionState member (0, a value
+// above the last member, anything wider than 32 bits) is ZK_VALUE_ERROR with seq 0 — what the reference's enum constructor raises
+// for such a value, the only thing it can do with it (its steps hold enum members).  See evm_check_step.
 #pragma once
 #include "common.hpp"
 #include "evm_tables.h"
@@ -52,6 +55,7 @@ struct EvmDyn {
     u32 agg_max_txs, agg_total_txs, agg_invalid_txs, agg_bad_invalid_rows, agg_total_wds;
     u32 dir_entries;    // directory build: groups counted so far (may exceed the capacity; then codes_n stays 0)
     u32 n_deferred;     // pairs the fast (hot) kernel handed to the general build this pass (reset at the start of every pass)
+    u32 agg_rw_dups;    // RW rows that equal an earlier row (counted while the generic RW index is built; dense rows have none)
 };
 
 struct EvmArgs {
@@ -65,6 +69,7 @@ struct EvmArgs {
     ZkTable withdrawals;        // optional WithdrawalTableRow rows (id, validator_id, address, amount), sorted by id
     // whole-table aggregates EndBlock's last step needs (end_block.py:55-91), computed once per session on the host
     u32 agg_max_txs, agg_total_txs, agg_invalid_txs, agg_bad_invalid_rows, agg_total_wds;
+    u32 agg_rw_dups;            // RW rows equal to an earlier row: the reference's rw_table is a set, len() counts them once
     const u64* aux;             // optional StepState.aux_data: [n_steps][aux_cells][4] cells ...
     const u32* aux_kind;        // ... and kinds (0 none, 1 Word, 2 int, 3 pair, 4 not representable, 5-8 precompile inputs)
     u32 aux_cells;              // cells per step in `aux` (2, or 12 when a precompile state is present)
@@ -94,6 +99,7 @@ ZK_HD void evm_args_resolve(EvmArgs& a) {
         a.codes.mask = d.codes_mask;
         a.agg_max_txs = d.agg_max_txs; a.agg_total_txs = d.agg_total_txs; a.agg_invalid_txs = d.agg_invalid_txs;
         a.agg_bad_invalid_rows = d.agg_bad_invalid_rows; a.agg_total_wds = d.agg_total_wds;
+        a.agg_rw_dups = d.agg_rw_dups;
     }
 }
 
@@ -3249,7 +3255,8 @@ ZK_HD void g_end_block(Ins& I, Tail& T, bool is_last) {  // end_block.py
         rw_lookup(I, Q, &one); if (I.err) return;
         RwQ R;
         rwq_init(R, 0, TG_Start);
-        Fr c2 = fr_sub(fr_sub(fr_u(a.rw.n), total_rws), fr_u(a.agg_total_wds));
+        // max_rws = len(rw_table), a set in the reference: rows of the wire table that equal an earlier one count once
+        Fr c2 = fr_sub(fr_sub(fr_u(a.rw.n - a.agg_rw_dups), total_rws), fr_u(a.agg_total_wds));
         rw_lookup(I, R, &c2);
     }
 }
@@ -3796,8 +3803,16 @@ ZK_HD void g_error_oog_sload_sstore(Ins& I, Tail& T) {  // error_oog_sload_sstor
         u32 r; r = rw_lookup(I, Q); if (I.err) return;
         const Word value_prev = rw_word(I, r, R_VAL_LO);
         if (aux_kind(I) != 2u) { if (I.err == 0u) I.err = ZK_CODE(ZK_UNSUPPORTED, I.seq); return; }  // Word(curr.aux_data)
-        I.seq++;
-        const Word orig = aux_word(I);
+        // Word(curr.aux_data) (util/arithmetic.py:115-122): the wire carries the int as cell0 | cell1 << 128 (flatten_step_aux), and an
+        // int of 2^256 or more fails Word's assert; cell0's own bits above 2^128 are part of the int's high half
+        const Fr a0 = aux_cell(I, 0), a1 = aux_cell(I, 1);
+        ev_require(I, fr_fits128(a1));
+        if (I.err) return;
+        Word orig = word_of(a0, a1);
+        for (int k = 0; k < 4; k++) {
+            orig.hi.v[k] |= a0.v[4 + k];
+            orig.lo.v[4 + k] = 0u;
+        }
         if (word_eq(value, value_prev)) gas_cost = 100;
         else if (word_eq(value_prev, orig)) { I.seq++; gas_cost = (fr_is_zero(orig.lo) && fr_is_zero(orig.hi)) ? 20000 : 2900; }
         else gas_cost = 100;
@@ -3941,8 +3956,11 @@ ZK_HD void g_create(Ins& I, Tail& T) {
                 CopyRes cr;
                 EV_TRY(cr = copy_lookup(I, word_value(I.call_id), CDT_Memory, next_hash, CDT_Bytecode, offset, fr_add(offset, size), fr_zero(),
                                         size, fr_add_u64(I.rwc, I.rw_off)));
-                if (!(fr_fits64(cr.rwc_inc) && fr_lo64(cr.rwc_inc) < (1ull << 62))) { if (I.err == 0u) I.err = ZK_CODE(ZK_UNSUPPORTED, I.seq); return; }
-                I.rw_off += fr_lo64(cr.rwc_inc);
+                // rw_counter_offset += int(copy_rwc_inc): an increment beyond the 64-bit offset (malformed copy rows only) moves the
+                // base the counters below are taken from, in the field like the reference's FQ sums, and is added back to the delta
+                Fr wide_inc = fr_zero();
+                if (fr_fits64(cr.rwc_inc) && fr_lo64(cr.rwc_inc) < (1ull << 62)) I.rw_off += fr_lo64(cr.rwc_inc);
+                else { wide_inc = cr.rwc_inc; I.rwc = fr_add(I.rwc, wide_inc); }
                 Fr code_size; code_size = bytecode_length(I, next_hash, true);
                 constrain_equal(I, code_size, size); if (I.err) return;
                 {
@@ -3980,7 +3998,7 @@ ZK_HD void g_create(Ins& I, Tail& T) {
                         constrain_equal_word(I, got.w, want); if (I.err) return;
                     }
                 }
-                transition(I, S_RWC, t_delta(fr_u(I.rw_off)));
+                transition(I, S_RWC, t_delta(fr_add(fr_u(I.rw_off), wide_inc)));
                 transition(I, S_CALL_ID, t_to(callee_call_id));
                 transition(I, S_IS_ROOT, t_to(fr_zero()));
                 transition(I, S_IS_CREATE, t_to(fr_u(1)));
@@ -4309,6 +4327,7 @@ ZK_HD void g_error_oog_precompile(Ins& I, Tail& T) {
 ZK_HD bool state_bit(u64 lo, u64 hi, u32 state) {  // bit `state` of a 128-bit immediate
     return state < 64 ? ((lo >> state) & 1ull) : (state < 128 ? ((hi >> (state - 64)) & 1ull) : 0ull);
 }
+ZK_HD bool es_is_member(const Fr& cell) { return fr_fits32(cell) && cell.v[0] - 1u < (u32)ES_COUNT - 1u; }  // the enum is 1 .. ES_COUNT - 1
 ZK_HD bool state_transition_ok(u32 curr, u32 next) {
     if (curr == ES_EndTx && !(next == ES_BeginTx || next == ES_EndBlock)) return false;
     if (curr == ES_EndBlock && next != ES_EndBlock) return false;
@@ -4665,6 +4684,15 @@ ZK_HD u32 evm_check_step(const EvmArgs& a, u64 idx, EVM_LDS32_PTR stage = nullpt
 #if !defined(ZK_HOSTSIM)
     if (EV_PROF_ON(a)) a.prof[EV_PROF_WAVE * 8 + 4] = state;
 #endif
+    // An execution_state cell that is no ExecutionState member (0, >= ES_COUNT, wider than 32 bits), in curr or in next: the
+    // reference's steps hold enum members, so such a wire value only exists where its constructor `ExecutionState(v)` raised
+    // ValueError.  That is the pair's verdict, before every checkpoint (seq 0), whatever the other state is and with or without
+    // is_first / is_last.  The whole cell is compared: `state` / `next_state` above are its low word, which decides nothing
+    // but the instantiation that owns the pair (the sort bins are taken from that word too).
+    if (!es_is_member(statef) || !es_is_member(next_statef)) {
+        ev_fail(I, ZK_VALUE_ERROR);
+        return I.err;
+    }
     if (is_first) {
         ev_require(I, state == ES_BeginTx || state == ES_EndBlock);
         constrain_equal(I, ev_curr(I, S_RWC), fr_u(1));

@@ -3,6 +3,7 @@
 #pragma once
 #include <stdint.h>
 #include <string.h>
+#include <algorithm>
 #include <map>
 #include <array>
 #include <vector>
@@ -118,6 +119,23 @@ static inline ZkRwMeta rw_dense_meta_host(const u64* rows, u64 n) {
     m.dense = ok ? 1u : 0u;
     m.base = base;
     return m;
+}
+
+// RW rows [n][14][4] that equal an earlier row: the reference's rw_table is a set, so EndBlock's len(rw_table) counts them once.
+static inline u32 rw_duplicate_rows_host(const u64* rw, u64 n) {
+    const size_t row_bytes = 14 * 4 * sizeof(u64);
+    bool increasing = true;  // strictly increasing 64-bit rw_counters (every well-formed table): no two rows are equal
+    for (u64 r = 0; r < n && increasing; r++) {
+        const u64* c = rw + r * 14 * 4;
+        increasing = (c[1] | c[2] | c[3]) == 0 && (r == 0 || c[0] > (c - 14 * 4)[0]);
+    }
+    if (increasing) return 0;
+    std::vector<u64> order(n);
+    for (u64 r = 0; r < n; r++) order[r] = r;
+    std::sort(order.begin(), order.end(), [&](u64 x, u64 y) { return memcmp(rw + x * 14 * 4, rw + y * 14 * 4, row_bytes) < 0; });
+    u32 dups = 0;
+    for (u64 k = 1; k < n; k++) dups += memcmp(rw + order[k - 1] * 14 * 4, rw + order[k] * 14 * 4, row_bytes) == 0;
+    return dups;
 }
 
 // Whole-table aggregates of EndBlock's last step (end_block.py:55-91) from the wire tables:

@@ -520,8 +520,21 @@ __global__ __launch_bounds__(1024) void evm_open_phase2_kernel(EvmOpenTables o, 
     u32* slots = const_cast<u32*>(o.rw.slots);
     const u32 stride = (gridDim.x - scatter_blocks - dir_blocks) * blockDim.x;
     for (u32 r = (b - dir_blocks) * blockDim.x + threadIdx.x; r < o.rw.n; r += stride) {
+        // a row that equals a row already on its probe path (equal rows hash alike, slots are never freed: of m equal rows every
+        // one but the first to land sees one) is a duplicate: EvmDyn::agg_rw_dups, for EndBlock's len(rw_table)
         u32 s = (u32)rw_key_hash(o.rw, r) & o.rw.mask;
-        while (atomicCAS(&slots[s], ZK_EMPTY_SLOT, r) != ZK_EMPTY_SLOT) s = (s + 1) & o.rw.mask;
+        bool dup = false;
+        for (;;) {
+            const u32 q = atomicCAS(&slots[s], ZK_EMPTY_SLOT, r);
+            if (q == ZK_EMPTY_SLOT) break;
+            if (!dup && q < o.rw.n) {
+                bool same = true;
+                for (int c = 0; c < RW_NCELLS && same; c++) same = fr_eq(zk_table_cell(o.rw, q, c), zk_table_cell(o.rw, r, c));
+                dup = same;
+            }
+            s = (s + 1) & o.rw.mask;
+        }
+        if (dup) atomicAdd(&o.dyn->agg_rw_dups, 1u);
     }
 }
 
@@ -1053,7 +1066,7 @@ extern "C" int zk_evm_open(const zk_evm_tables* t, uint32_t opts, zk_session** o
         E.codes.packed = nullptr;
         E.codes.entries = nullptr;
         E.codes.slots = nullptr;
-        E.agg_max_txs = E.agg_total_txs = E.agg_invalid_txs = E.agg_bad_invalid_rows = E.agg_total_wds = 0;
+        E.agg_max_txs = E.agg_total_txs = E.agg_invalid_txs = E.agg_bad_invalid_rows = E.agg_total_wds = E.agg_rw_dups = 0;
         EvmOpenTables o;
         memset(&o, 0, sizeof o);
         u32 blk = 0;
