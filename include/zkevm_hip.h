@@ -673,6 +673,67 @@ int zk_exp_assign(const zk_exp_events* ev, uint64_t* rows_out, uint64_t* table_o
 /* the three counts of an open session (what zk_exp_assign_sizes returns for its events), without a second size pass */
 int zk_exp_assign_counts(zk_session* s, uint64_t* n_rows, uint64_t* n_step_rows, uint64_t* n_table);
 
+/* ---- PI circuit witness assignment: replaces public_data2witness (src/zkevm_specs/pi_circuit.py:839-1073) — from the block header,
+ *      its transactions and its withdrawals to everything zk_pi_open and zk_pi_copy_open take, and to the small tables of the Witness.
+ *      Inputs (zk_pi_inputs), 256-bit words as 4 x u64 little-endian:
+ *        chain_id; block uint64[9][4]: hash, coinbase, state_root, prev_randao, number, gas_limit, time, base_fee, withdrawals_root
+ *        (the fields public_data2witness reads); state_root_prev uint64[4]; block_hashes uint64[256][4];
+ *        tx_fields uint64[n_txs][7][4]: nonce, gas_price, gas, from_addr, to_addr (0 when None), value, tx_sign_hash; to_is_none uint32[n_txs];
+ *        calldata: the txs' data back to back with byte offsets uint64[n_txs + 1] (offsets[0] = 0, non-decreasing), as zk_tx_inputs;
+ *        withdrawals uint64[n_withdrawals][4][4]: id (a canonical cell: the table's FQ(id)), validator_id, address, amount;
+ *        max_txs, max_calldata_bytes, max_withdrawals; keccak_rand, byte_pow_base: one cell each (the module constants, :834-836).
+ *      Outputs (zk_pi_wire), circuit_len = 8454 + 336 max_txs + max_calldata_bytes + 56 max_withdrawals rows:
+ *        rows          uint64[24][circuit_len][4] column-major: flatten_pi_rows, what zk_pi_open takes;
+ *        gas           uint64[1 + calldata bytes][3][4]: the (0, 0, 0) row, then one row per calldata byte in tx / index order
+ *                      (the reference's set, sorted: flatten_pi_gas_table);
+ *        keccak        uint64[2][5][4]: the all-zero row, then (1, input RLC, circuit_len, digest lo, hi);
+ *        cc_cells uint64[n][4], cc_bytes uint8[n][32], cc_lens uint32[n]: the copy constraints in verify_circuit's statement order
+ *                      (:355-445), what zk_pi_copy_open takes; n = 538 + 4 (10 max_txs + 1) + 2 max_calldata_bytes + 5 max_withdrawals;
+ *        block_table   uint64[268][2][4] (lo, hi) + block_flags uint32[268] (is_word): the 265 entries of the value column, then block hash,
+ *                      state root, previous state root;
+ *        tx_table      uint64[10 max_txs + 1 + max_calldata_bytes][5][4] (tx_id, tag, index, value lo, hi) + tx_flags uint32[..] (is_word);
+ *        wd_table      uint64[max_withdrawals][5][4]: id, validator_id, address lo, hi, amount;
+ *        public_inputs uint64[4][2][4]: pi_keccak, block_hash, state_root, state_root_prev as lo, hi;
+ *        raw_bytes uint8[circuit_len] + raw_lens uint32[n_values]: Witness.copy_constrains, its byte strings back to back and their
+ *                      lengths; n_values = 533 + 33 max_txs + max_calldata_bytes + 5 max_withdrawals.
+ *      zk_pi_assign_open: with ZK_OPT_DEVICE_PTRS every input is a device pointer and the non-null pointers of `out_dev` receive the
+ *      outputs in place (null ones, or a null out_dev: the session owns the buffer); without it out_dev must be null.  zk_launch /
+ *      zk_collect / zk_read_status as for the circuits (one status per row, always 0: the domain is checked at open); zk_pi_assign_read
+ *      copies the last pass's outputs to the non-null HOST pointers of `host`.
+ *      Domain, rejected at sizes / open with an error code and its text in zk_last_error:
+ *        ZK_ERR_PI_TXS          no tx, or more than max_txs (the reference's asserts);
+ *        ZK_ERR_PI_WITHDRAWALS  no withdrawal, or more than max_withdrawals;
+ *        ZK_ERR_PI_CALLDATA     more calldata bytes than max_calldata_bytes;
+ *        ZK_ERR_PI_FIELD        a field wider than the bytes to_bytes gives it (coinbase / from_addr / to_addr 20; number, gas_limit, time,
+ *                               nonce, gas, validator_id, amount 8), a withdrawal id that is no canonical cell, offsets that decrease;
+ *        ZK_ERR_PI_ROWS         2^31 rows or more. */
+#define ZK_ERR_PI_TXS (-50)
+#define ZK_ERR_PI_WITHDRAWALS (-51)
+#define ZK_ERR_PI_CALLDATA (-52)
+#define ZK_ERR_PI_FIELD (-53)
+#define ZK_ERR_PI_ROWS (-54)
+typedef struct zk_pi_inputs {
+    uint64_t chain_id;
+    const uint64_t* block;      const uint64_t* state_root_prev;   const uint64_t* block_hashes;
+    const uint64_t* tx_fields;  const uint32_t* to_is_none;        uint64_t n_txs;
+    const uint8_t* calldata;    const uint64_t* calldata_offsets;
+    const uint64_t* withdrawals; uint64_t n_withdrawals;
+    uint64_t max_txs;           uint64_t max_calldata_bytes;       uint64_t max_withdrawals;
+    const uint64_t* keccak_rand; const uint64_t* byte_pow_base;
+} zk_pi_inputs;
+typedef struct zk_pi_wire {
+    uint64_t* rows;         uint64_t* gas;          uint64_t* keccak;
+    uint64_t* cc_cells;     uint8_t* cc_bytes;      uint32_t* cc_lens;
+    uint64_t* block_table;  uint32_t* block_flags;
+    uint64_t* tx_table;     uint32_t* tx_flags;
+    uint64_t* wd_table;     uint64_t* public_inputs;
+    uint8_t* raw_bytes;     uint32_t* raw_lens;
+} zk_pi_wire;
+int zk_pi_assign_sizes(const zk_pi_inputs* in, uint32_t opts, uint64_t* circuit_len, uint64_t* n_gas, uint64_t* n_constraints);
+int zk_pi_assign_open(const zk_pi_inputs* in, const zk_pi_wire* out_dev, uint32_t opts, zk_session** out);
+int zk_pi_assign_read(zk_session* s, const zk_pi_wire* host);
+int zk_pi_assign(const zk_pi_inputs* in, const zk_pi_wire* out, uint32_t opts, zk_result* result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,8 @@
 rows/s and algorithmic GB/s (SURVEY.md §8d bytes per unit), device-resident inputs, HIP-event kernel
 time.  bench.py carries the headline EVM / State workloads; this is the side table in DESIGN.md §3.
 `bench_row_kernels.py ecc` runs only the ECC leg, `bench_row_kernels.py withdrawal` only the Withdrawal leg, `bench_row_kernels.py
-tx_assign` only the Tx witness-assignment leg, `bench_row_kernels.py exp_assign` only the Exp witness-assignment leg."""
+tx_assign` only the Tx witness-assignment leg, `bench_row_kernels.py exp_assign` only the Exp witness-assignment leg,
+`bench_row_kernels.py pi_assign` only the PI witness-assignment leg."""
 import json
 import os
 import random
@@ -151,6 +152,44 @@ def exp_assign_leg():
     run("state_assign_2p20", engine.open_state_assign(to_dev(ops), to_dev(op_flags)), 1 << 20, 57 * 32)
 
 
+def pi_assign_leg():
+    """PI circuit witness assignment (zk_pi_assign_open, public data in HBM) at MAX_TXS 2^11 / MAX_CALLDATA_BYTES 2^20 / MAX_WITHDRAWALS
+    2^10 and at 2^9 / 2^17 / 2^8: open_ms = wall time of the open (staging-free: the inputs are device tensors; the domain check's
+    read-back is its one wait), kernel_ms = HIP-event span of a pass (gas scan, inverses, bytes, digest beside scans + row writer,
+    patch; mean of 20 passes after 3); bytes per row = the 24 cells written (768 B: the row writer's share of HBM; tables and
+    constraints come on top).  Per-kernel times: one `rocprofv3 --kernel-trace --stats -- python3 tools/bench_row_kernels.py pi_assign`."""
+    import time
+
+    g = np.random.default_rng(8)
+    words = lambda n, bits: (g.integers(0, 1 << 62, size=(n, 4), dtype=np.uint64)  # noqa: E731
+                             & np.array([(1 << min(max(bits - 64 * k, 0), 62)) - 1 for k in range(4)], dtype=np.uint64))
+    for mt, mc, mw in ((1 << 11, 1 << 20, 1 << 10), (1 << 9, 1 << 17, 1 << 8)):
+        cuts = np.sort(g.integers(0, mc + 1, size=mt - 1)).astype(np.uint64)
+        offsets = np.concatenate([[0], cuts, [mc]]).astype(np.uint64)
+        calldata = g.integers(0, 256, size=mc, dtype=np.uint8) * (g.integers(0, 3, size=mc, dtype=np.uint8) == 0)
+        txf = np.stack([words(mt, b) for b in (64, 256, 64, 160, 160, 256, 256)], axis=1)
+        wd = np.stack([words(mw, b) for b in (0, 64, 160, 62)], axis=1)
+        wd[:, 0, 0] = np.arange(mw, dtype=np.uint64)
+        wd[:, 3, 0] |= np.uint64(1)
+        block = np.stack([words(1, b)[0] for b in (256, 160, 256, 256, 64, 64, 64, 256, 256)])
+        pd = {"chain_id": 1, "block": block, "state_root_prev": words(1, 256)[0], "block_hashes": words(256, 256), "tx_fields": txf,
+              "to_is_none": np.zeros(mt, dtype=np.uint32), "calldata": calldata, "offsets": offsets, "withdrawals": wd,
+              "max_txs": mt, "max_calldata_bytes": mc, "max_withdrawals": mw}
+        pdd = {k: (to_dev(np.ascontiguousarray(v)) if k in engine.PI_ASSIGN_INPUTS else v) for k, v in pd.items()}
+        engine.open_pi_assign(pdd).close()  # (warm-up: arena, side stream)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        s = engine.open_pi_assign(pdd)
+        open_ms = (time.perf_counter() - t0) * 1e3
+        name = f"pi_assign_{mt}x{mc}x{mw}"
+        run(name, s, s.n, 24 * 32)
+        out[name]["open_wall_ms"] = round(open_ms, 3)
+
+
+if sys.argv[1:] == ["pi_assign"]:
+    pi_assign_leg()
+    print(json.dumps(out))
+    sys.exit(0)
 if sys.argv[1:] == ["exp_assign"]:
     exp_assign_leg()
     print(json.dumps(out))

@@ -10,6 +10,7 @@ A pytest plugin rebinds, inside every reference test module that imported them, 
     verify_copy_table               zkevm_specs/copy_circuit.py:92          -> zkevm_specs_amd.copy_circuit.verify_copy_table
     verify_exp_circuit              zkevm_specs/exp_circuit.py:88           -> zkevm_specs_amd.exp_circuit.verify_exp_circuit
     txs2witness                     zkevm_specs/tx_circuit.py:432           -> zkevm_specs_amd.tx_circuit.txs2witness
+    public_data2witness             zkevm_specs/pi_circuit.py:839           -> zkevm_specs_amd.pi_circuit.public_data2witness_reference
     verify_circuit (tx / sig / pi / ecc / withdrawal)  tx_circuit.py:253, sig_circuit.py:113, pi_circuit.py:338, ecc_circuit.py:424,
                                     withdrawal_circuit.py:128 -> the five mirrors
 
@@ -40,6 +41,7 @@ REBIND = {  # name in the test module -> (module the test imported it from, mirr
     "verify_copy_table": ("zkevm_specs.copy_circuit", "zkevm_specs_amd.copy_circuit", "verify_copy_table"),
     "verify_exp_circuit": ("zkevm_specs.exp_circuit", "zkevm_specs_amd.exp_circuit", "verify_exp_circuit"),
     "txs2witness": ("zkevm_specs.tx_circuit", "zkevm_specs_amd.tx_circuit", "txs2witness"),
+    "public_data2witness": ("zkevm_specs.pi_circuit", "zkevm_specs_amd.pi_circuit", "public_data2witness_reference"),
     # the witness BUILDER of tests/evm/test_exp.py: the class itself is rebound (by identity, as the drivers are), so the reference's
     # own EXP tests build their Exp rows and their exp table through zk_exp_assign
     "ExpCircuit": ("zkevm_specs.evm_circuit", "zkevm_specs_amd.exp_circuit", "ExpCircuit"),

@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = [
     "zk_ecc_assign", "zk_ecc_verify", "zk_withdrawal_open", "zk_withdrawal_verify", "zk_withdrawal_assign",
     "zk_tx_assign_open", "zk_tx_assign_read", "zk_tx_assign",
     "zk_exp_assign_sizes", "zk_exp_assign_open", "zk_exp_assign_read", "zk_exp_assign", "zk_exp_assign_counts",
+    "zk_pi_assign_sizes", "zk_pi_assign_open", "zk_pi_assign_read", "zk_pi_assign",
 ]
 
 OPT_DEVICE_PTRS = 1
@@ -122,6 +123,21 @@ class ZkExpEvents(ctypes.Structure):
     _fields_ = [("events", ctypes.c_void_p), ("n_events", ctypes.c_uint64), ("max_exp_steps", ctypes.c_uint64)]
 
 
+class ZkPiInputs(ctypes.Structure):
+    _fields_ = [("chain_id", ctypes.c_uint64), ("block", ctypes.c_void_p), ("state_root_prev", ctypes.c_void_p), ("block_hashes", ctypes.c_void_p),
+                ("tx_fields", ctypes.c_void_p), ("to_is_none", ctypes.c_void_p), ("n_txs", ctypes.c_uint64), ("calldata", ctypes.c_void_p),
+                ("calldata_offsets", ctypes.c_void_p), ("withdrawals", ctypes.c_void_p), ("n_withdrawals", ctypes.c_uint64),
+                ("max_txs", ctypes.c_uint64), ("max_calldata_bytes", ctypes.c_uint64), ("max_withdrawals", ctypes.c_uint64),
+                ("keccak_rand", ctypes.c_void_p), ("byte_pow_base", ctypes.c_void_p)]
+
+
+class ZkPiWire(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("rows", "gas", "keccak", "cc_cells", "cc_bytes", "cc_lens", "block_table", "block_flags",
+                                               "tx_table", "tx_flags", "wd_table", "public_inputs", "raw_bytes", "raw_lens")]
+
+
+# ZK_ERR_PI_* (include/zkevm_hip.h): why zk_pi_assign* rejected its inputs
+ERR_PI_TXS, ERR_PI_WITHDRAWALS, ERR_PI_CALLDATA, ERR_PI_FIELD, ERR_PI_ROWS = -50, -51, -52, -53, -54
 ERR_EXP_CELL, ERR_EXP_ORDER, ERR_EXP_ROWS = -40, -41, -42  # ZK_ERR_EXP_* (include/zkevm_hip.h): why zk_exp_assign* rejected its events
 
 
@@ -263,6 +279,10 @@ def _bind(lib):
     lib.zk_exp_assign_read.argtypes = [vp, vp, vp]
     lib.zk_exp_assign_counts.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.zk_exp_assign.argtypes = [ctypes.POINTER(ZkExpEvents), vp, vp, u32, ctypes.POINTER(ZkResult)]
+    lib.zk_pi_assign_sizes.argtypes = [ctypes.POINTER(ZkPiInputs), u32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_pi_assign_open.argtypes = [ctypes.POINTER(ZkPiInputs), ctypes.POINTER(ZkPiWire), u32, ctypes.POINTER(vp)]
+    lib.zk_pi_assign_read.argtypes = [vp, ctypes.POINTER(ZkPiWire)]
+    lib.zk_pi_assign.argtypes = [ctypes.POINTER(ZkPiInputs), ctypes.POINTER(ZkPiWire), u32, ctypes.POINTER(ZkResult)]
     lib.zk_launch.argtypes = [vp, vp]
     lib.zk_collect.argtypes = [vp, ctypes.POINTER(ZkResult)]
     lib.zk_read_status.argtypes = [vp, vp]

@@ -36,6 +36,7 @@
 #include "withdrawal_circuit.hpp"
 #include "tx_assign.hpp"
 #include "exp_assign.hpp"
+#include "pi_assign.hpp"
 
 static thread_local std::string g_err;
 #define ARG_TRY(cond, msg) do { if (!(cond)) { g_err = msg; return -1; } } while (0)
@@ -97,7 +98,7 @@ struct zk_session {
     std::vector<u64> w64[4];              // assignment sessions: work / output buffers
     std::vector<u32> out32;
     void (*pass)(zk_session*) = nullptr;  // assignment sessions: one pass computes the outputs and fills `status`
-    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 6 exp
+    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 6 exp, 7 PI
     u64 n_ops = 0;                        // RW -> State ops: 1 + kept rows
     std::vector<u32> rekey_plan;          // RW -> State ops: the RwkHostPlan's plan (as words) ...
     std::vector<u32> rekey_jobs;          // ... and its rank jobs (cls, field, base, count)
@@ -124,6 +125,12 @@ struct zk_session {
     TxAssignArgs txa;
     ExaArgs exa;
     ExaSizes exa_sizes;
+    PiaArgs pia;
+    PiaSizes pia_sizes;
+    KeccakGenArgs pia_kgen;
+    std::vector<u64> pia64[20];     // PI assignment: inputs, work buffers and outputs of 64-bit words
+    std::vector<u32> pia32[6];
+    std::vector<uint8_t> pia8[4];
     std::vector<u64> txa_out64[4];  // Tx assignment outputs: tx_rows, cells, keccak candidates, keccak
     std::vector<u32> txa_out32[3];  // tx_flags, meta, the txs' status
     u64 n_keccak = 0;
@@ -1238,6 +1245,174 @@ extern "C" int zk_exp_assign(const zk_exp_events* t, uint64_t* rows_out, uint64_
     rc = zk_launch(s, nullptr);
     if (!rc) rc = zk_collect(s, result);
     if (!rc) rc = zk_exp_assign_read(s, rows_out, table_out);
+    zk_close(s);
+    return rc;
+}
+
+// ---- PI-circuit witness assignment: the per-row functions of csrc/pi_assign.hpp in plain loops
+static void pi_assign_pass(zk_session* s) {
+    PiaArgs& a = s->pia;
+    {   // calldata gas: the prefix inside each tile, the tile bases
+        u64 base = 0;
+        u32 run = 0;
+        for (u64 c = 0; c < a.total_cd; c++) {
+            if (c % PIA_GAS_TILE == 0) { base += run; run = 0; a.gas_tile[c / PIA_GAS_TILE] = base; }
+            run += a.calldata[c] ? 16u : 4u;
+            a.gas_local[c] = run;
+        }
+    }
+    for (u64 r = 0; r < PIA_TX_LEN * a.max_txs; r++) {  // (one Fermat chain per distinct value: the padding slots share theirs)
+        const Fr lo = pia_tx_value_lo(a, r);
+        if (fr_is_zero(lo)) pia_store_fr(a.inv_txlo + 4 * r, lo); else pia_tx_inverse(a, r);
+    }
+#pragma omp parallel for schedule(static)
+    for (long long i = 0; i < (long long)a.n; i++) pia_row_byte(a, (u64)i);
+    keccak_table_row(s->pia_kgen, 0);
+    {   // suffix RLC: one walk from the last row of the last tile, keeping the tile's own sum beside the whole one
+        const Fr rand_m = fr_to_mont(a.rand);
+        Fr all = fr_zero(), tile = fr_zero();
+        pia_store_fr(a.carry + 4 * a.n_tiles, all);
+        for (u64 i = a.n_tiles * PIA_TILE; i-- > 0;) {
+            const u32 b = pia_byte_at(a, i);
+            all = fr_add_u64(fr_mulc(all, rand_m), b);
+            tile = fr_add_u64(fr_mulc(tile, rand_m), b);
+            if (i % PIA_SLICE == 0) pia_store_fr(a.slice_acc + 4 * (i / PIA_SLICE), tile);
+            if (i % PIA_TILE == 0) {
+                pia_store_fr(a.tile_acc + 4 * (i / PIA_TILE), tile);
+                pia_store_fr(a.carry + 4 * (i / PIA_TILE), all);
+                tile = fr_zero();
+            }
+        }
+    }
+#pragma omp parallel for schedule(static)
+    for (long long i = 0; i < (long long)a.n; i++) pia_write_row(a, (u64)i);
+    pia_patch(a);
+}
+static int pia_prepare(const zk_pi_inputs* t, zk_session* s, PiaSizes& z) {
+    PiaArgs& a = s->pia;
+    char msg[256];
+    const u64 total = t->calldata_offsets[t->n_txs];
+    int rc = pia_sizes_of(t->n_txs, t->n_withdrawals, total, t->max_txs, t->max_calldata_bytes, t->max_withdrawals, z, msg, sizeof msg);
+    if (rc) { g_err = msg; return rc; }
+    s->pia64[0].assign(t->block, t->block + PIA_NBLOCK_FIELDS * 4);
+    s->pia64[1].assign(t->state_root_prev, t->state_root_prev + 4);
+    s->pia64[2].assign(t->block_hashes, t->block_hashes + 256 * 4);
+    s->pia64[3].assign(t->tx_fields, t->tx_fields + t->n_txs * PIA_NTX_FIELDS * 4);
+    s->pia64[4].assign(t->calldata_offsets, t->calldata_offsets + t->n_txs + 1);
+    s->pia64[5].assign(t->withdrawals, t->withdrawals + t->n_withdrawals * PIA_NWD_FIELDS * 4);
+    s->pia32[0].assign(t->to_is_none, t->to_is_none + t->n_txs);
+    s->pia8[0].assign(t->calldata, t->calldata + total);
+    s->pia8[0].push_back(0);
+    a.chain_id = t->chain_id;
+    a.block = s->pia64[0].data(); a.srp = s->pia64[1].data(); a.hashes = s->pia64[2].data(); a.txf = s->pia64[3].data();
+    a.offs = s->pia64[4].data(); a.wd = s->pia64[5].data(); a.to_none = s->pia32[0].data(); a.calldata = s->pia8[0].data();
+    a.n_txs = t->n_txs; a.n_wd = t->n_withdrawals; a.max_txs = t->max_txs; a.max_cd = t->max_calldata_bytes; a.max_wd = t->max_withdrawals;
+    a.total_cd = total;
+    pia_set_layout(a, z);
+    a.rand = cell_of(t->keccak_rand);
+    a.base = cell_of(t->byte_pow_base);
+    for (u64 k = 0; k < PIA_N_CHECKS(a); k++)
+        if (!pia_check(a, k)) { rc = pia_reject_text(k, msg, sizeof msg); g_err = msg; return rc; }
+    return 0;
+}
+#define PIA_ARGS_OK(t) ((t) && (t)->block && (t)->state_root_prev && (t)->block_hashes && (t)->calldata_offsets && (t)->keccak_rand && (t)->byte_pow_base && \
+                        ((t)->n_txs == 0 || ((t)->tx_fields && (t)->to_is_none)) && ((t)->n_withdrawals == 0 || (t)->withdrawals) && (t)->n_txs < (1ull << 31) && \
+                        (t)->n_withdrawals < (1ull << 31) && ((t)->calldata || (t)->calldata_offsets[(t)->n_txs] == 0))
+extern "C" int zk_pi_assign_sizes(const zk_pi_inputs* t, uint32_t opts, uint64_t* circuit_len, uint64_t* n_gas, uint64_t* n_constraints) {
+    NO_DEVICE_PTRS(opts, "zk_pi_assign_sizes");
+    ARG_TRY(PIA_ARGS_OK(t), "zk_pi_assign_sizes: bad arguments");
+    zk_session* s = new_session(1, false);
+    PiaSizes z;
+    const int rc = pia_prepare(t, s, z);
+    delete s;
+    if (rc) return rc;
+    if (circuit_len) *circuit_len = z.n;
+    if (n_gas) *n_gas = z.n_gas;
+    if (n_constraints) *n_constraints = z.n_cc;
+    return 0;
+}
+extern "C" int zk_pi_assign_open(const zk_pi_inputs* t, const zk_pi_wire* out_dev, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_pi_assign_open");
+    ARG_TRY(PIA_ARGS_OK(t) && out, "zk_pi_assign_open: bad arguments");
+    ARG_TRY(!out_dev, "zk_pi_assign_open: output buffers need ZK_OPT_DEVICE_PTRS");
+    zk_session* s = new_session(1, false);
+    PiaSizes& z = s->pia_sizes;
+    const int rc = pia_prepare(t, s, z);
+    if (rc) { delete s; return rc; }
+    PiaArgs& a = s->pia;
+    s->n = s->hi = z.n;
+    s->status.assign(z.n, 0u);
+    s->pia32[1].assign(a.total_cd + 1, 0);                         a.gas_local = s->pia32[1].data();
+    s->pia64[6].assign(a.n_gas_tiles + 1, 0);                      a.gas_tile = s->pia64[6].data();
+    s->pia64[7].assign(a.n_inv * 4, 0);                            a.inv_small = s->pia64[7].data();
+    s->pia64[8].assign(PIA_TX_LEN * a.max_txs * 4 + 4, 0);         a.inv_txlo = s->pia64[8].data();
+    s->pia8[1].assign(z.n, 0);                                     a.gen = s->pia8[1].data();
+    s->pia64[9].assign(((size_t)PIA_TILE + 1) * 4, 0);             a.rpow = s->pia64[9].data();
+    s->pia64[10].assign(a.n_tiles * 256 * 4, 0);                   a.slice_acc = s->pia64[10].data();
+    s->pia64[11].assign((a.n_tiles + 1) * 4, 0);                   a.tile_acc = s->pia64[11].data();
+    s->pia64[12].assign((a.n_tiles + 1) * 4, 0);                   a.carry = s->pia64[12].data();
+    s->pia64[13].assign(KT_NCELLS * 4 + (size_t)KT_RPOW_ROWS * 4 + 2, 0);  a.krow = s->pia64[13].data();
+    s->pia64[14].assign(z.n * PI_NCELLS * 4, 0);                   a.rows = s->pia64[14].data();
+    s->pia64[15].assign(z.n_gas * PI_GAS_NCELLS * 4, 0);           a.gas = s->pia64[15].data();
+    s->pia64[16].assign(2 * 5 * 4 + 4 * 2 * 4, 0);                 a.keccak = s->pia64[16].data(); a.public_inputs = a.keccak + 2 * 5 * 4;
+    s->pia64[17].assign(z.n_cc * 4, 0);                            a.cc_cells = s->pia64[17].data();
+    s->pia8[2].assign(z.n_cc * 32, 0);                             a.cc_bytes = s->pia8[2].data();
+    s->pia32[2].assign(z.n_cc, 0);                                 a.cc_lens = s->pia32[2].data();
+    s->pia64[18].assign((size_t)PIA_BLOCK_ENTRIES * 2 * 4, 0);     a.block_table = s->pia64[18].data();
+    s->pia32[3].assign(PIA_BLOCK_ENTRIES, 0);                      a.block_flags = s->pia32[3].data();
+    s->pia64[19].assign(z.tx_table_rows * 5 * 4 + a.max_wd * 5 * 4, 0);  a.tx_table = s->pia64[19].data(); a.wd_table = a.tx_table + z.tx_table_rows * 5 * 4;
+    s->pia32[4].assign(z.tx_table_rows, 0);                        a.tx_flags = s->pia32[4].data();
+    s->pia8[3].assign(z.n, 0);                                     a.raw_bytes = s->pia8[3].data();
+    s->pia32[5].assign(z.n_values, 0);                             a.raw_lens = s->pia32[5].data();
+    for (u64 k = 0; k <= (u64)PIA_TILE; k++) pia_store_fr(a.rpow + 4 * k, pia_pow_mont(fr_to_mont(a.rand), k));
+    {   // k^-1 from one Fermat chain: the inverse of (n_inv - 1)!, walked down
+        std::vector<Fr> fact(a.n_inv, fr_from_u64(1));
+        for (u64 k = 2; k < a.n_inv; k++) fact[k] = fr_mul(fact[k - 1], fr_from_u64(k));
+        Fr finv = fr_inv(fact[a.n_inv - 1]);  // 1 / (n_inv - 1)!
+        for (u64 k = a.n_inv; k-- > 1;) {
+            pia_store_fr(a.inv_small + 4 * k, fr_mul(finv, fact[k - 1]));  // (k - 1)! / k!
+            finv = fr_mul(finv, fr_from_u64(k));
+        }
+    }
+    KeccakGenArgs& g = s->pia_kgen;
+    u64* offs = a.krow + KT_NCELLS * 4 + (size_t)KT_RPOW_ROWS * 4;
+    offs[0] = 0; offs[1] = z.n;
+    kt_fill_rpow(cell_of(t->keccak_rand), a.krow + KT_NCELLS * 4);
+    g.data = a.gen; g.offsets = offs; g.n = 1; g.rpow = a.krow + KT_NCELLS * 4; g.rows = a.krow; g.mode = KT_MODE_CIRCUIT; g.long_list = nullptr; g.long_count = nullptr;
+    s->pass = pi_assign_pass;
+    s->assign_kind = 7;
+    *out = s;
+    return 0;
+}
+#define PIA_COPY(dst, src, bytes) do { if (dst) memcpy(dst, src, bytes); } while (0)
+extern "C" int zk_pi_assign_read(zk_session* s, const zk_pi_wire* h) {
+    ARG_TRY(s && h && s->assign_kind == 7, "zk_pi_assign_read: bad arguments");
+    const PiaArgs& a = s->pia;
+    const PiaSizes& z = s->pia_sizes;
+    PIA_COPY(h->rows, a.rows, (size_t)z.n * PI_NCELLS * 32);
+    PIA_COPY(h->gas, a.gas, (size_t)z.n_gas * PI_GAS_NCELLS * 32);
+    PIA_COPY(h->keccak, a.keccak, 2 * 5 * 32);
+    PIA_COPY(h->cc_cells, a.cc_cells, (size_t)z.n_cc * 32);
+    PIA_COPY(h->cc_bytes, a.cc_bytes, (size_t)z.n_cc * 32);
+    PIA_COPY(h->cc_lens, a.cc_lens, (size_t)z.n_cc * 4);
+    PIA_COPY(h->block_table, a.block_table, (size_t)PIA_BLOCK_ENTRIES * 2 * 32);
+    PIA_COPY(h->block_flags, a.block_flags, (size_t)PIA_BLOCK_ENTRIES * 4);
+    PIA_COPY(h->tx_table, a.tx_table, (size_t)z.tx_table_rows * 5 * 32);
+    PIA_COPY(h->tx_flags, a.tx_flags, (size_t)z.tx_table_rows * 4);
+    PIA_COPY(h->wd_table, a.wd_table, (size_t)a.max_wd * 5 * 32);
+    PIA_COPY(h->public_inputs, a.public_inputs, 4 * 2 * 32);
+    PIA_COPY(h->raw_bytes, a.raw_bytes, (size_t)z.n);
+    PIA_COPY(h->raw_lens, a.raw_lens, (size_t)z.n_values * 4);
+    return 0;
+}
+extern "C" int zk_pi_assign(const zk_pi_inputs* t, const zk_pi_wire* out_wire, uint32_t opts, zk_result* result) {
+    ARG_TRY(result && out_wire && out_wire->rows, "zk_pi_assign: null output");
+    zk_session* s = nullptr;
+    int rc = zk_pi_assign_open(t, nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc) rc = zk_pi_assign_read(s, out_wire);
     zk_close(s);
     return rc;
 }

@@ -20,6 +20,7 @@
 #include "withdrawal_circuit.hpp"
 #include "tx_assign.hpp"
 #include "exp_assign.hpp"
+#include "pi_assign.hpp"
 
 // The single-kernel row sessions keep two tallies and alternate between them: a pass accumulates into one and its first
 // lane clears the other for the pass after it, so that no reset kernel sits in front of every evaluation kernel (a kernel
@@ -89,3 +90,10 @@ void zk_launch_tx_assign(hipStream_t st, const TxAssignArgs& a, u32* status, ZkT
 // Exp circuit witness assignment (k_exp_assign.hip): the open's counts / first rows / reject word, then chain + rows per pass
 void zk_launch_exp_assign_sizes(hipStream_t st, const ExaArgs& a);
 void zk_launch_exp_assign(hipStream_t st, const ExaArgs& a, u32* status, ZkTally* tally);
+// PI circuit witness assignment (k_pi_assign.hip): the reject word of sizes / open; the open's power table and small inverses; one pass
+// (g: the keccak kernels' arguments over the generation-order byte buffer; side: a second stream of the device for them, forked and
+// joined with the two events, or null: everything on st)
+void zk_launch_pi_assign_check(hipStream_t st, const PiaArgs& a);
+void zk_launch_pi_assign_tables(hipStream_t st, const PiaArgs& a);
+void zk_launch_pi_assign(hipStream_t st, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join, const PiaArgs& a, const KeccakGenArgs& g,
+                         u32* status, ZkTally* tally);

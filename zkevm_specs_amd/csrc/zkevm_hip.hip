@@ -583,7 +583,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -617,6 +617,10 @@ struct zk_session {
     TxAssignArgs txa;
     ExaArgs exa;
     u64 exa_n_table = 0;
+    PiaArgs pia;
+    PiaSizes pia_sizes;
+    KeccakGenArgs pia_kgen;
+    u64 pia_host[4] = {0, 0, 0, 0};  // small host words the open uploads (their source must outlive the asynchronous copy)
     RekeyArgs rekey;
     RwkPlan rekey_plan_host;      // the compact-key plan as uploaded (host copy owned by the session: the upload needs no synchronisation of its own)
     bool assign_from_rw = false;  // SESSION_ASSIGN over an RW table: every pass starts with the re-keying and the sort (rekey)
@@ -2253,6 +2257,185 @@ extern "C" int zk_exp_assign(const zk_exp_events* t, uint64_t* rows_out, uint64_
     return rc;
 }
 
+// ---- PI-circuit witness assignment
+#define PIA_ARGS_OK(t) ((t) && (t)->block && (t)->state_root_prev && (t)->block_hashes && (t)->calldata_offsets && (t)->keccak_rand && (t)->byte_pow_base && \
+                        ((t)->n_txs == 0 || ((t)->tx_fields && (t)->to_is_none)) && ((t)->n_withdrawals == 0 || (t)->withdrawals) && (t)->n_txs < (1ull << 31) && \
+                        (t)->n_withdrawals < (1ull << 31))
+// The inputs staged, the sizes, and the open's kernels with the one wait for their reject word.  `s` owns the buffers.
+static int pia_prepare(const zk_pi_inputs* t, bool dev, zk_session* s, PiaSizes& z) {
+    PiaArgs& a = s->pia;
+    char msg[256];
+    u64 total = 0, rh[8];
+    int rc = 0;
+    if (dev) { if ((rc = fetch_small(s->stream, &total, t->calldata_offsets + t->n_txs, 8))) return rc; }
+    else total = t->calldata_offsets[t->n_txs];
+    if ((rc = pia_sizes_of(t->n_txs, t->n_withdrawals, total, t->max_txs, t->max_calldata_bytes, t->max_withdrawals, z, msg, sizeof msg))) { g_err = msg; return rc; }
+    ARG_TRY(t->calldata || total == 0, "zk_pi_assign: calldata is null");
+    const void* p = nullptr;
+    if ((rc = stage(s, t->block, PIA_NBLOCK_FIELDS * 32, dev, &p))) return rc;
+    a.block = (const u64*)p;
+    if ((rc = stage(s, t->state_root_prev, 32, dev, &p))) return rc;
+    a.srp = (const u64*)p;
+    if ((rc = stage(s, t->block_hashes, 256 * 32, dev, &p))) return rc;
+    a.hashes = (const u64*)p;
+    if ((rc = stage(s, t->tx_fields, (size_t)t->n_txs * PIA_NTX_FIELDS * 32, dev, &p))) return rc;
+    a.txf = (const u64*)p;
+    if ((rc = stage(s, t->to_is_none, (size_t)t->n_txs * 4, dev, &p))) return rc;
+    a.to_none = (const u32*)p;
+    if ((rc = stage(s, t->calldata, (size_t)total, dev, &p))) return rc;
+    a.calldata = (const uint8_t*)p;
+    if ((rc = stage(s, t->calldata_offsets, (size_t)(t->n_txs + 1) * 8, dev, &p))) return rc;
+    a.offs = (const u64*)p;
+    if ((rc = stage(s, t->withdrawals, (size_t)t->n_withdrawals * PIA_NWD_FIELDS * 32, dev, &p))) return rc;
+    a.wd = (const u64*)p;
+    a.chain_id = t->chain_id;
+    a.n_txs = t->n_txs; a.n_wd = t->n_withdrawals; a.max_txs = t->max_txs; a.max_cd = t->max_calldata_bytes; a.max_wd = t->max_withdrawals;
+    a.total_cd = total;
+    pia_set_layout(a, z);
+    if (dev) {
+        if (fetch_small(s->stream, rh, t->keccak_rand, 32) || fetch_small(s->stream, rh + 4, t->byte_pow_base, 32)) { g_err = "zk_pi_assign: randomness download failed"; return -2; }
+    } else {
+        memcpy(rh, t->keccak_rand, 32);
+        memcpy(rh + 4, t->byte_pow_base, 32);
+    }
+    Fr r, b;
+    for (int q = 0; q < 4; q++) { r.v[2 * q] = (u32)rh[q]; r.v[2 * q + 1] = (u32)(rh[q] >> 32); b.v[2 * q] = (u32)rh[4 + q]; b.v[2 * q + 1] = (u32)(rh[4 + q] >> 32); }
+    a.rand = r;
+    a.base = b;
+    if ((rc = dev_alloc(s, (void**)&a.meta, 32))) return rc;
+    s->pia_host[0] = PIA_NO_REJECT;
+    HIP_TRY(hipMemcpyAsync(a.meta, s->pia_host, 8, hipMemcpyHostToDevice, s->stream));
+    zk_launch_pi_assign_check(s->stream, a);
+    HIP_TRY(hipGetLastError());
+    u64 meta = PIA_NO_REJECT;
+    if ((rc = d2h_now(s->stream, &meta, a.meta, 8))) return rc;  // the one wait of sizes / open
+    if (meta != PIA_NO_REJECT) { rc = pia_reject_text(meta, msg, sizeof msg); g_err = msg; return rc; }
+    return 0;
+}
+// what only an open needs: the power table, the small inverses, and the keccak kernels' arguments (one message: the generation-order buffer)
+static int pia_tables(zk_session* s, const PiaSizes& z) {
+    PiaArgs& a = s->pia;
+    int rc = 0;
+    if ((rc = dev_alloc(s, (void**)&a.rpow, ((size_t)PIA_TILE + 1) * 32))) return rc;
+    if ((rc = dev_alloc(s, (void**)&a.inv_small, (size_t)a.n_inv * 32))) return rc;
+    zk_launch_pi_assign_tables(s->stream, a);
+    u64* kbuf = nullptr;
+    if ((rc = dev_alloc(s, (void**)&kbuf, (KT_NCELLS * 4 + (size_t)KT_RPOW_ROWS * 4 + 4) * 8))) return rc;
+    if ((rc = dev_alloc(s, (void**)&a.gen, (size_t)z.n + 8))) return rc;
+    a.krow = kbuf;
+    KeccakGenArgs& g = s->pia_kgen;
+    u64* offs = kbuf + KT_NCELLS * 4 + (size_t)KT_RPOW_ROWS * 4;
+    // offsets[2], then the long-message list (one index) and its counter; the source lives as long as the session
+    s->pia_host[0] = 0; s->pia_host[1] = z.n; s->pia_host[2] = 0; s->pia_host[3] = 0;
+    HIP_TRY(hipMemcpyAsync(offs, s->pia_host, 32, hipMemcpyHostToDevice, s->stream));
+    zk_launch_keccak_rpow(s->stream, a.rand, kbuf + KT_NCELLS * 4);
+    HIP_TRY(hipGetLastError());
+    g.data = a.gen; g.offsets = offs; g.n = 1; g.rpow = kbuf + KT_NCELLS * 4; g.rows = kbuf; g.mode = KT_MODE_CIRCUIT;
+    g.long_list = (u32*)(offs + 2); g.long_count = (u32*)(offs + 3);
+    return 0;
+}
+extern "C" int zk_pi_assign_sizes(const zk_pi_inputs* t, uint32_t opts, uint64_t* circuit_len, uint64_t* n_gas, uint64_t* n_constraints) {
+    ARG_TRY(t_device >= 0, "zk_pi_assign_sizes: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(PIA_ARGS_OK(t), "zk_pi_assign_sizes: bad arguments");
+    zk_session* s = new zk_session();
+    s->kind = SESSION_PIA;
+    PiaSizes z;
+    const int rc = pia_prepare(t, opts & ZK_OPT_DEVICE_PTRS, s, z);
+    zk_close(s);
+    if (rc) return rc;
+    if (circuit_len) *circuit_len = z.n;
+    if (n_gas) *n_gas = z.n_gas;
+    if (n_constraints) *n_constraints = z.n_cc;
+    return 0;
+}
+extern "C" int zk_pi_assign_open(const zk_pi_inputs* t, const zk_pi_wire* out_dev, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_pi_assign_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(PIA_ARGS_OK(t) && out, "zk_pi_assign_open: bad arguments");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    ARG_TRY(dev || !out_dev, "zk_pi_assign_open: output buffers need ZK_OPT_DEVICE_PTRS");
+    zk_session* s = new zk_session();
+    s->kind = SESSION_PIA;
+    PiaArgs& a = s->pia;
+    PiaSizes& z = s->pia_sizes;
+    int rc = pia_prepare(t, dev, s, z);
+    if (rc) goto fail;
+    if ((rc = pia_tables(s, z))) goto fail;
+    s->n = z.n;
+    if ((rc = dev_alloc(s, (void**)&a.gas_local, ((size_t)a.total_cd + 1) * 4))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&a.gas_tile, ((size_t)a.n_gas_tiles + 1) * 8))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&a.inv_txlo, ((size_t)PIA_TX_LEN * a.max_txs + 1) * 32))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&a.slice_acc, (size_t)a.n_tiles * 256 * 32))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&a.tile_acc, ((size_t)a.n_tiles + 1) * 32))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&a.carry, ((size_t)a.n_tiles + 1) * 32))) goto fail;
+    if (out_dev) {
+        a.rows = out_dev->rows; a.gas = out_dev->gas; a.keccak = out_dev->keccak; a.cc_cells = out_dev->cc_cells; a.cc_bytes = out_dev->cc_bytes;
+        a.cc_lens = out_dev->cc_lens; a.block_table = out_dev->block_table; a.block_flags = out_dev->block_flags; a.tx_table = out_dev->tx_table;
+        a.tx_flags = out_dev->tx_flags; a.wd_table = out_dev->wd_table; a.public_inputs = out_dev->public_inputs; a.raw_bytes = out_dev->raw_bytes;
+        a.raw_lens = out_dev->raw_lens;
+    } else {
+        a.rows = a.gas = a.keccak = a.cc_cells = a.block_table = a.tx_table = a.wd_table = a.public_inputs = nullptr;
+        a.cc_bytes = a.raw_bytes = nullptr;
+        a.cc_lens = a.block_flags = a.tx_flags = a.raw_lens = nullptr;
+    }
+    if (!a.rows && (rc = dev_alloc(s, (void**)&a.rows, (size_t)z.n * PI_NCELLS * 32))) goto fail;
+    if (!a.gas && (rc = dev_alloc(s, (void**)&a.gas, (size_t)z.n_gas * PI_GAS_NCELLS * 32))) goto fail;
+    if (!a.keccak && (rc = dev_alloc(s, (void**)&a.keccak, 2 * 5 * 32))) goto fail;
+    if (!a.cc_cells && (rc = dev_alloc(s, (void**)&a.cc_cells, (size_t)z.n_cc * 32))) goto fail;
+    if (!a.cc_bytes && (rc = dev_alloc(s, (void**)&a.cc_bytes, (size_t)z.n_cc * 32))) goto fail;
+    if (!a.cc_lens && (rc = dev_alloc(s, (void**)&a.cc_lens, (size_t)z.n_cc * 4))) goto fail;
+    if (!a.block_table && (rc = dev_alloc(s, (void**)&a.block_table, (size_t)PIA_BLOCK_ENTRIES * 2 * 32))) goto fail;
+    if (!a.block_flags && (rc = dev_alloc(s, (void**)&a.block_flags, (size_t)PIA_BLOCK_ENTRIES * 4))) goto fail;
+    if (!a.tx_table && (rc = dev_alloc(s, (void**)&a.tx_table, (size_t)z.tx_table_rows * 5 * 32))) goto fail;
+    if (!a.tx_flags && (rc = dev_alloc(s, (void**)&a.tx_flags, (size_t)z.tx_table_rows * 4))) goto fail;
+    if (!a.wd_table && (rc = dev_alloc(s, (void**)&a.wd_table, (size_t)a.max_wd * 5 * 32))) goto fail;
+    if (!a.public_inputs && (rc = dev_alloc(s, (void**)&a.public_inputs, 4 * 2 * 32))) goto fail;
+    if (!a.raw_bytes && (rc = dev_alloc(s, (void**)&a.raw_bytes, (size_t)z.n))) goto fail;
+    if (!a.raw_lens && (rc = dev_alloc(s, (void**)&a.raw_lens, (size_t)z.n_values * 4))) goto fail;
+    if ((rc = session_common_init(s))) goto fail;
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+#define PIA_D2H(dst, src, bytes) do { if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s->stream)); } while (0)
+extern "C" int zk_pi_assign_read(zk_session* s, const zk_pi_wire* h) {
+    ARG_TRY(s && h && s->kind == SESSION_PIA, "zk_pi_assign_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    const PiaArgs& a = s->pia;
+    const PiaSizes& z = s->pia_sizes;
+    PIA_D2H(h->rows, a.rows, (size_t)z.n * PI_NCELLS * 32);
+    PIA_D2H(h->gas, a.gas, (size_t)z.n_gas * PI_GAS_NCELLS * 32);
+    PIA_D2H(h->keccak, a.keccak, 2 * 5 * 32);
+    PIA_D2H(h->cc_cells, a.cc_cells, (size_t)z.n_cc * 32);
+    PIA_D2H(h->cc_bytes, a.cc_bytes, (size_t)z.n_cc * 32);
+    PIA_D2H(h->cc_lens, a.cc_lens, (size_t)z.n_cc * 4);
+    PIA_D2H(h->block_table, a.block_table, (size_t)PIA_BLOCK_ENTRIES * 2 * 32);
+    PIA_D2H(h->block_flags, a.block_flags, (size_t)PIA_BLOCK_ENTRIES * 4);
+    PIA_D2H(h->tx_table, a.tx_table, (size_t)z.tx_table_rows * 5 * 32);
+    PIA_D2H(h->tx_flags, a.tx_flags, (size_t)z.tx_table_rows * 4);
+    PIA_D2H(h->wd_table, a.wd_table, (size_t)a.max_wd * 5 * 32);
+    PIA_D2H(h->public_inputs, a.public_inputs, 4 * 2 * 32);
+    PIA_D2H(h->raw_bytes, a.raw_bytes, (size_t)z.n);
+    PIA_D2H(h->raw_lens, a.raw_lens, (size_t)z.n_values * 4);
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+extern "C" int zk_pi_assign(const zk_pi_inputs* t, const zk_pi_wire* out_wire, uint32_t opts, zk_result* result) {
+    ARG_TRY(result && out_wire && out_wire->rows, "zk_pi_assign: null output");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    int rc = zk_pi_assign_open(t, dev ? out_wire : nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && !dev) rc = zk_pi_assign_read(s, out_wire);
+    zk_close(s);
+    return rc;
+}
+
 // ---- Public-inputs circuit
 extern "C" int zk_pi_open(const uint64_t* rows, uint64_t n, const uint64_t* keccak, uint64_t n_keccak, const uint64_t* gas, uint64_t n_gas,
                           uint64_t circuit_len, const uint64_t* keccak_rand, const uint64_t* byte_pow_base, uint32_t opts, zk_session** out) {
@@ -2579,6 +2762,23 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     case SESSION_PICOPY: zk_launch_pi_copy(s->stream, s->picopy, status, tally); break;
     case SESSION_CPA: zk_launch_copy_assign(s->stream, s->cpa, status, s->d_tally); break;
     case SESSION_EXA: zk_launch_exp_assign(s->stream, s->exa, status, s->d_tally); break;
+    case SESSION_PIA: {
+        // the digest (one message: a serial sponge) runs on the device's side stream beside the scans and the row writer; only the patch
+        // kernel waits for it
+        {
+            std::lock_guard<std::mutex> lock(g_dev_mutex);
+            if (!g_side_stream[s->device]) HIP_TRY(hipStreamCreateWithFlags(&g_side_stream[s->device], hipStreamNonBlocking));
+        }
+        if (!s->ev_fork) {
+            int erc = arena_event(s->device, &s->ev_fork);
+            if (!erc) erc = arena_event(s->device, &s->ev_join);
+            if (erc) return erc;
+        }
+        hipStream_t pside = g_side_stream[s->device];
+        if (pside == s->stream) pside = nullptr;
+        zk_launch_pi_assign(s->stream, pside, s->ev_fork, s->ev_join, s->pia, s->pia_kgen, status, s->d_tally);
+        break;
+    }
     case SESSION_REKEY: zk_launch_state_rekey(s->stream, s->rekey, status, s->d_tally); break;
     case SESSION_EVM: {
         // the state-sorted lane mapping is derived from the step column on every pass

@@ -934,3 +934,86 @@ def open_exp_assign(events, max_exp_steps=0, rows_dev=None, table_dev=None, devi
     check(lib.zk_exp_assign_counts(s._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "zk_exp_assign_counts", lib)
     s.n, s.n_step, s.n_table = int(a.value), int(b.value), int(c.value)
     return s
+
+
+# ---- PI circuit witness assignment (zk_pi_assign*) ----------------------------------------------------------------------------------
+PI_ASSIGN_INPUTS = ("block", "state_root_prev", "block_hashes", "tx_fields", "to_is_none", "calldata", "offsets", "withdrawals")
+PI_ASSIGN_OUTPUTS = ("rows", "gas", "keccak", "cc_cells", "cc_bytes", "cc_lens", "block_table", "block_flags", "tx_table", "tx_flags",
+                     "wd_table", "public_inputs", "raw_bytes", "raw_lens")
+
+
+def pi_assign_shapes(max_txs, max_calldata_bytes, max_withdrawals, calldata_bytes):
+    """name -> (shape, dtype) of the outputs of zk_pi_assign* (include/zkevm_hip.h)"""
+    mt, mc, mw = int(max_txs), int(max_calldata_bytes), int(max_withdrawals)
+    n = 8454 + 336 * mt + mc + 56 * mw
+    n_cc = 538 + 4 * (10 * mt + 1) + 2 * mc + 5 * mw
+    t = 10 * mt + 1 + mc
+    return {"rows": ((24, n, 4), np.uint64), "gas": ((1 + int(calldata_bytes), 3, 4), np.uint64), "keccak": ((2, 5, 4), np.uint64),
+            "cc_cells": ((n_cc, 4), np.uint64), "cc_bytes": ((n_cc, 32), np.uint8), "cc_lens": ((n_cc,), np.uint32),
+            "block_table": ((268, 2, 4), np.uint64), "block_flags": ((268,), np.uint32), "tx_table": ((t, 5, 4), np.uint64),
+            "tx_flags": ((t,), np.uint32), "wd_table": ((mw, 5, 4), np.uint64), "public_inputs": ((4, 2, 4), np.uint64),
+            "raw_bytes": ((n,), np.uint8), "raw_lens": ((533 + 33 * mt + mc + 5 * mw,), np.uint32)}
+
+
+def _pi_assign_args(pd, keccak_rand=255, byte_pow_base=255, outs=None):
+    """zk_pi_assign_open / zk_pi_assign over `pd` = dict(chain_id, block uint64[9, 4], state_root_prev uint64[4], block_hashes
+    uint64[256, 4], tx_fields uint64[n, 7, 4], to_is_none uint32[n], calldata uint8[b], offsets uint64[n + 1], withdrawals
+    uint64[m, 4, 4], max_txs, max_calldata_bytes, max_withdrawals) -> (ZkPiInputs, ZkPiWire of the device outputs or None, opts, kept
+    arrays).  `outs` (device tensors only, each optional): buffers of PI_ASSIGN_OUTPUTS the session writes in place; they are sized
+    from pd["calldata"], so its extent must be the offsets' last entry."""
+    n, m = _rows(pd["tx_fields"]), _rows(pd["withdrawals"])
+    _expect(pd["block"], "block", 8, (9, 4))
+    _expect(pd["state_root_prev"], "state_root_prev", 8, (4,))
+    _expect(pd["block_hashes"], "block_hashes", 8, (256, 4))
+    _expect(pd["tx_fields"], "tx_fields", 8, (None, 7, 4))
+    _expect(pd["to_is_none"], "to_is_none", 4, (n,))
+    _expect(pd["offsets"], "offsets", 8, (n + 1,))
+    _expect(pd["calldata"], "calldata", 1, (None,))
+    _expect(pd["withdrawals"], "withdrawals", 8, (None, 4, 4))
+    shapes = pi_assign_shapes(pd["max_txs"], pd["max_calldata_bytes"], pd["max_withdrawals"], pd["calldata"].shape[0])
+    outs = dict(outs or {})
+    for k, v in outs.items():
+        if v is not None:
+            _expect(v, k, np.dtype(shapes[k][1]).itemsize, shapes[k][0])
+    out_list = [outs.get(k) for k in PI_ASSIGN_OUTPUTS]
+    a, opts = _prep([pd[k] for k in PI_ASSIGN_INPUTS] + out_list, outputs=range(8, 8 + len(out_list)))
+    if any(v is not None for v in out_list) and not opts:
+        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
+    kr, bp = _randomness_cells(int(keccak_rand), a[0]), _randomness_cells(int(byte_pow_base), a[0])
+    keep = a + [kr, bp]
+    t = _lib.ZkPiInputs(int(pd["chain_id"]), ptr(a[0]), ptr(a[1]), ptr(a[2]), ptr(a[3], n), ptr(a[4], n), n, ptr(a[5], int(a[5].shape[0])),
+                        ptr(a[6]), ptr(a[7], m), m, int(pd["max_txs"]), int(pd["max_calldata_bytes"]), int(pd["max_withdrawals"]), ptr(kr), ptr(bp))
+    w = _lib.ZkPiWire(*[ptr(x) for x in a[8:]]) if opts else None
+    return t, w, opts, keep, shapes
+
+
+def pi_assign_sizes(pd, device=None):
+    """(circuit_len, gas-table rows, copy constraints) of the public data `pd`; raises EngineError (rc = _lib.ERR_PI_*) for inputs
+    outside the circuit's domain"""
+    lib = _lib.init(device)
+    t, _, opts, keep, _ = _pi_assign_args(pd)
+    a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    check(lib.zk_pi_assign_sizes(ctypes.byref(t), opts, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "zk_pi_assign_sizes", lib)
+    return int(a.value), int(b.value), int(c.value)
+
+
+class PiAssignSession(Session):
+    """zk_pi_assign_open: one status per row; read() -> the wire dict of the last pass (host arrays)"""
+
+    def read(self, names=PI_ASSIGN_OUTPUTS):
+        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in self.shapes.items() if k in names}
+        w = _lib.ZkPiWire(*[ptr(out[k]) if k in out else None for k in PI_ASSIGN_OUTPUTS])
+        check(self._lib.zk_pi_assign_read(self._h, ctypes.byref(w)), "zk_pi_assign_read", self._lib)
+        return out
+
+
+def open_pi_assign(pd, keccak_rand=255, byte_pow_base=255, outs=None, device=None):
+    """PI circuit witness assignment session over the public data `pd` (see _pi_assign_args).  With device tensors the outputs stay in
+    HBM: in `outs`' buffers where given (rows / keccak / gas for open_pi, cc_cells / cc_bytes / cc_lens for zk_pi_copy_open), else in
+    the session's own."""
+    lib = _lib.init(device)
+    t, w, opts, keep, shapes = _pi_assign_args(pd, keccak_rand, byte_pow_base, outs)
+    s = _open(lib, lib.zk_pi_assign_open, shapes["rows"][0][1], (keep, t, w), ctypes.byref(t), ctypes.byref(w) if w is not None else None,
+              opts, cls=PiAssignSession)
+    s.shapes = shapes
+    return s

@@ -214,3 +214,15 @@ def tx_assign(tx, randomness, device=None):
     check(lib.zk_tx_assign(ctypes.byref(t), ctypes.byref(w), opts, ptr(status), ctypes.byref(nk), ctypes.byref(r)), "zk_tx_assign")
     out["keccak"] = out["keccak"][: nk.value]
     return Result(r), status[:n], out
+
+
+def pi_assign(pd, keccak_rand=255, byte_pow_base=255, device=None):
+    """zk_pi_assign over raw public data (engine._pi_assign_args) -> (Result, wire dict of engine.PI_ASSIGN_OUTPUTS)"""
+    lib = _lib.init(device)
+    t, _, opts, keep, shapes = engine._pi_assign_args({k: (_host(v) if k in engine.PI_ASSIGN_INPUTS else v) for k, v in pd.items()},
+                                                      keccak_rand, byte_pow_base)
+    out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items()}
+    w = _lib.ZkPiWire(*[ptr(out[k]) for k in engine.PI_ASSIGN_OUTPUTS])
+    r = ZkResult()
+    check(lib.zk_pi_assign(ctypes.byref(t), ctypes.byref(w), opts, ctypes.byref(r)), "zk_pi_assign", lib)
+    return Result(r), out
