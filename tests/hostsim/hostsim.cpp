@@ -2,6 +2,7 @@
 // the HIP kernels call (csrc/*.hpp) with g++ -DZK_HOSTSIM and runs them in a plain loop, so
 // the kernels' constraint logic can be checked against the oracle in the GPU-less build
 // container.  It is NOT a CPU backend: the package never loads this library.
+#include <cstring>
 #include <vector>
 #include "../../zkevm_specs_amd/csrc/state_circuit.hpp"
 
@@ -488,4 +489,26 @@ extern "C" int sim_pi_copy_verify(const u64* cells, const uint8_t* bytes, const 
     a.cells = cells; a.bytes = bytes; a.lens = lens; a.n = n;
     for (u64 i = 0; i < n; i++) status[i] = pi_copy_check(a, i);
     return 0;
+}
+
+// ---- Tx witness assignment: the key recovery through the plain chains (tx_recover_exact), which inputs cannot reach: the GLV split
+// never fails for a scalar below N.  tx_sign_hash and tx_recover_prepare run as they do in the library; whatever the split says,
+// Q = u1 G + u2 R comes from the plain chains.  pk: [n][8] (x, y), status: [n]
+#include "../../zkevm_specs_amd/csrc/tx_assign.hpp"
+extern "C" void sim_tx_recover_exact(const u64* fields, const u32* to_none, const uint8_t* calldata, const u64* offsets, u64 n,
+                                    u64 chain_id, u64* pk, u32* status) {
+    std::vector<u64> words((size_t)(offsets[n] / 8 + 2), 0);  // whole aligned words for the sponge's reads
+    if (offsets[n]) memcpy(words.data(), calldata, (size_t)offsets[n]);
+    std::vector<u64> hash((size_t)(n + 1) * 4, 0), gas_cost((size_t)n + 1, 0);
+    TxAssignArgs a = {};
+    a.fields = fields; a.to_none = to_none; a.data = (const uint8_t*)words.data(); a.off = offsets; a.n = n; a.chain_id = chain_id;
+    a.hash = hash.data(); a.gas_cost = gas_cost.data(); a.pk = pk; a.status = status;
+    for (u64 i = 0; i < n; i++) {
+        tx_sign_hash(a, i);
+        EcdsaPrep pr;
+        Fr u1, u2;
+        const u32 st = tx_recover_prepare(a, i, pr, u1, u2);
+        if (st == ECDSA_PENDING || st == TX_RECOVER_EXACT) status[i] = tx_recover_finish(a, i, tx_recover_exact(pr, u1, u2));
+        else { status[i] = st; tx_recover_fail(a, i); }
+    }
 }

@@ -392,3 +392,25 @@ def test_two_batches_in_one_launch():
     assert out0.cpu().numpy().view(np.uint32).tolist() == exp0
     m = meta.cpu().numpy().view(np.uint32)
     assert m[:, 0].tolist() == exp1 and (m[:, 1:] == 0xFFFFFFFF).all()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("lanes,n", [("4", (1 << 15) + 67), ("2", (1 << 16) + 67)])
+def test_chunked_launches_match_tiled_openssl_verdicts(golden_dir, lanes, n, monkeypatch):
+    """above 2^17 lanes zk_launch_ecdsa runs consecutive launches over one set of key tables: the smallest batch that chunks in the
+    four-lane and in the lane-pair form, OpenSSL's vectors tiled (320 does not divide 2^15: the later launch starts inside the
+    pattern), every status and the tally against OpenSSL's verdicts"""
+    from zkevm_specs_amd import engine
+
+    monkeypatch.setenv("ZK_ECDSA_LANES", lanes)
+    sigs, verdict = _openssl(golden_dir)
+    idx = np.arange(n) % len(verdict)
+    want = np.asarray(verdict, dtype=np.uint32)[idx]
+    # (the lane form is the requested one as long as zk_ecdsa_open has the comb of G, which it builds before it chooses: without
+    # the comb it would drop four lanes to two, and the first case would fit one launch and still pass)
+    assert n * int(lanes) > 1 << 17 and (n - 67) % len(verdict) != 0
+    with engine.open_ecdsa(np.ascontiguousarray(sigs[idx])) as s:
+        res = s.run()
+        got = s.read_status()
+    assert np.array_equal(got, want)
+    assert res.fail_count == int(np.count_nonzero(want)) and res.first_fail_row == int(np.flatnonzero(want)[0])
