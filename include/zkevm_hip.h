@@ -573,6 +573,26 @@ typedef struct zk_ecc_ops {
 } zk_ecc_ops;
 int zk_ecc_assign(const zk_ecc_ops* ops, uint32_t opts, uint64_t* rows_out);
 int zk_ecc_verify(const zk_ecc_ops* ops, const uint64_t* rows, uint32_t opts, uint32_t* status_out, zk_result* result);
+/* ECC sessions: the ops stay resident and the rows are evaluated pass after pass (zk_launch / zk_collect / zk_read_status /
+ * zk_session_set_stream / zk_close as for every row circuit; twin tally; status_dev or the session's own buffer, uint32[n]).
+ * zk_ecc_open: host pointers are staged once at open; with ZK_OPT_DEVICE_PTRS the arrays of `ops` (the struct itself is host memory),
+ *      `rows` and `randomness` are device pointers used in place.  pair_off (4 B per op) is read back at open to validate it
+ *      (pair_off[0] = 0, non-decreasing) and to size the per-pair work, the randomness cell to check that it is canonical; points and
+ *      rows are never read back.  Status codes are those of zk_ecc_verify, bit for bit, including which check of a row fails first.
+ *      zk_set_range(s, lo, hi) evaluates rows [lo, hi) of the n_add + n_mul + n_pairing rows (circuit2rows order; ops and rows are
+ *      replicated on every rank, only the range differs).  The range may cut through the adds, the muls or the pairings and — for this
+ *      circuit only — may be empty (lo == hi).  rows_evaluated == hi - lo, first_fail_row is a global row, statuses outside the range
+ *      are zero after zk_set_range.
+ *      A pass is three launches in stream order: the add / mul rows of the range (one lane per row), then the pairing rows in two
+ *      stages — one lane per (op, pair) computes the pair's subgroup / on-curve / infinity flags and its Miller value into a record the
+ *      session owns, then one lane per op runs the row's checks in their order over the records, multiplies the Miller values and does
+ *      the final exponentiation.  status_dev is final in stream order.
+ * zk_ecc_assign_open / zk_ecc_assign_read: circuit2rows over resident ops.  The 13-cell rows go to rows_dev (a device buffer
+ *      uint64[n][13][4]; needs ZK_OPT_DEVICE_PTRS) or, when it is null, to the session's own buffer, which zk_ecc_assign_read copies
+ *      to the host.  The output is what zk_ecc_open takes as `rows`. */
+int zk_ecc_open(const zk_ecc_ops* ops, const uint64_t* rows, uint32_t opts, zk_session** out);
+int zk_ecc_assign_open(const zk_ecc_ops* ops, uint64_t* rows_dev, uint32_t opts, zk_session** out);
+int zk_ecc_assign_read(zk_session* s, uint64_t* rows_host);
 
 /* ---- Withdrawal circuit: replaces the row loop of withdrawal_circuit.verify_circuit (src/zkevm_specs/withdrawal_circuit.py:128-201)
  *      and the reference test's withdrawals2witness (tests/test_withdrawal_circuit.py).

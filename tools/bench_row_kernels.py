@@ -2,7 +2,7 @@
 """Throughput of the row-stencil kernels (Bytecode / Exp / Tx-Sig circuits, the ECC circuit) on synthetic witnesses:
 rows/s and algorithmic GB/s (SURVEY.md §8d bytes per unit), device-resident inputs, HIP-event kernel
 time.  bench.py carries the headline EVM / State workloads; this is the side table in DESIGN.md §3.
-`bench_row_kernels.py ecc` runs only the ECC leg, `bench_row_kernels.py withdrawal` only the Withdrawal leg, `bench_row_kernels.py
+`bench_row_kernels.py ecc` runs only the ECC legs (one-shot, then the resident session), `bench_row_kernels.py withdrawal` only the Withdrawal leg, `bench_row_kernels.py
 tx_assign` only the Tx witness-assignment leg, `bench_row_kernels.py exp_assign` only the Exp witness-assignment leg,
 `bench_row_kernels.py pi_assign` only the PI witness-assignment leg."""
 import json
@@ -76,6 +76,49 @@ def ecc_leg():
         out[name] = {"rows": n, "hip_kernel_ms": round(kms, 3), "hip_rows_per_s": round(n / kms * 1e3),
                      "cpu_wall_ms": round(cpu_s * 1e3, 1), "cpu_rows_per_s": round(n / cpu_s), "cpu_threads": os.cpu_count()}
         print(name, out[name], flush=True)
+
+
+def ecc_pairing_ops(n_ops, n_pairs):
+    """n_ops pairing ops of n_pairs pairs each whose product is 1 (n_pairs / 2 cancelling couples e(aG1, G2) e(-G1, aG2)) -> ops wire"""
+    from tests import bn254_ref as b
+    from zkevm_specs_amd.flatten import flatten_ecc_ops
+
+    g = random.Random(4)
+    a = g.randrange(1, b.R)
+    qa = b.multiply(b.G2, a, b.Fq2)
+    q1, qa_w = (b.G2[0][1], b.G2[0][0], b.G2[1][1], b.G2[1][0]), (qa[0][1], qa[0][0], qa[1][1], qa[1][0])
+    pairing = ([b.multiply(b.G1, a, b.Fq), b.neg(b.G1, b.Fq)] * (n_pairs // 2), [q1, qa_w] * (n_pairs // 2), 1)
+    return flatten_ecc_ops([], [], [pairing] * n_ops)
+
+
+def ecc_session_leg():
+    """ECC circuit in a resident session (zk_ecc_open, ops and rows in HBM; kernel_ms = HIP-event span of a pass: point rows, stage 1
+    — one lane per (op, pair) —, stage 2 — one lane per op; mean of 10 passes after 2) beside the one-shot zk_ecc_verify on the same ops:
+    2^10 ops of two pairs, and 8 ops of 16 pairs (a rank's handful of ops, the shape the per-pair split exists for)."""
+    from zkevm_specs_amd import oneshot
+
+    rk = 0x5EED % P
+    for name, n_ops, n_pairs in (("ecc_pairing_2pairs", 1 << 10, 2), ("ecc_pairing_8x16pairs", 8, 16)):
+        w = ecc_pairing_ops(n_ops, n_pairs)
+        rows = oneshot.ecc_assign(w, rk)
+        one = []
+        for _ in range(4):
+            res, _ = oneshot.ecc_verify(w, rows, rk)
+            assert res.fail_count == 0, (name, res.first_fail_code)
+            one.append(round(res.kernel_ms, 3))
+        wd = {k: (to_dev(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) and k != "max_ok" else v) for k, v in w.items()}
+        with engine.open_ecc(wd, to_dev(rows), rk) as s:
+            for _ in range(2):
+                s.launch()
+            s.collect()
+            for _ in range(10):
+                s.launch()
+            r = s.collect()
+            assert r.ok, (name, r)
+        out[name + "_session"] = {"ops": n_ops, "pairs_per_op": n_pairs, "session_kernel_ms": round(r.kernel_ms, 3),
+                                  "oneshot_kernel_ms": one[1:], "session_over_oneshot": round(r.kernel_ms / min(one[1:]), 3),
+                                  "ops_per_s": round(n_ops / r.kernel_ms * 1e3)}
+        print(name + "_session", out[name + "_session"], flush=True)
 
 
 def withdrawal_leg():
@@ -204,6 +247,7 @@ if sys.argv[1:] == ["withdrawal"]:
     sys.exit(0)
 if sys.argv[1:] == ["ecc"]:
     ecc_leg()
+    ecc_session_leg()
     print(json.dumps(out))
     sys.exit(0)
 
@@ -298,4 +342,5 @@ for reps in (1, 2, 4, 8):
     d = torch.from_numpy(np.tile(packed, (reps, 1, 1))).cuda()
     run(f"ecdsa_verify_{n_sig * reps}", engine.open_ecdsa(d), n_sig * reps, 160 + 4)
 ecc_leg()
+ecc_session_leg()
 print(json.dumps(out))

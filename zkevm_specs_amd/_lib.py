@@ -23,7 +23,7 @@ EXPORTED_SYMBOLS = [
     "zk_init", "zk_shutdown", "zk_set_stream", "zk_session_set_stream", "zk_last_error", "zk_fr_op",
     "zk_state_open", "zk_state_set_range", "zk_set_range", "zk_state_verify", "zk_evm_open", "zk_evm_verify", "zk_evm_verify_batch", "zk_bytecode_open", "zk_bytecode_verify", "zk_exp_open", "zk_exp_verify", "zk_copy_open", "zk_copy_verify", "zk_sign_open", "zk_sign_verify",
     "zk_keccak_open", "zk_keccak_read_rows", "zk_keccak_table", "zk_state_assign_open", "zk_state_assign_read", "zk_state_assign", "zk_state_ops_from_rw_open", "zk_state_ops_from_rw_read", "zk_state_ops_from_rw", "zk_state_assign_from_rw_open", "zk_state_verify_from_rw_open", "zk_state_verify_from_rw", "zk_block_verify", "zk_ecdsa_open", "zk_ecdsa_open_batches", "zk_ecdsa_verify", "zk_bytecode_assign_open", "zk_bytecode_assign_read", "zk_bytecode_assign", "zk_pi_open", "zk_pi_verify", "zk_pi_copy_open", "zk_pi_copy_verify", "zk_copy_assign_sizes", "zk_copy_assign_open", "zk_copy_assign_read", "zk_copy_assign", "zk_launch", "zk_collect", "zk_read_status", "zk_close", "zk_session_timing", "zk_last_timing", "zk_timing_sums", "zk_last_host_phases", "zk_dist_unique_id", "zk_dist_init", "zk_dist_tally", "zk_dist_close",
-    "zk_ecc_assign", "zk_ecc_verify", "zk_withdrawal_open", "zk_withdrawal_verify", "zk_withdrawal_assign",
+    "zk_ecc_assign", "zk_ecc_verify", "zk_ecc_open", "zk_ecc_assign_open", "zk_ecc_assign_read", "zk_withdrawal_open", "zk_withdrawal_verify", "zk_withdrawal_assign",
     "zk_tx_assign_open", "zk_tx_assign_read", "zk_tx_assign",
     "zk_exp_assign_sizes", "zk_exp_assign_open", "zk_exp_assign_read", "zk_exp_assign", "zk_exp_assign_counts",
     "zk_pi_assign_sizes", "zk_pi_assign_open", "zk_pi_assign_read", "zk_pi_assign",
@@ -241,6 +241,9 @@ def _bind(lib):
     lib.zk_sign_verify.argtypes = [ctypes.POINTER(ZkSignUnits), u32, vp, ctypes.POINTER(ZkResult)]
     lib.zk_ecc_assign.argtypes = [ctypes.POINTER(ZkEccOps), u32, vp]
     lib.zk_ecc_verify.argtypes = [ctypes.POINTER(ZkEccOps), vp, u32, vp, ctypes.POINTER(ZkResult)]
+    lib.zk_ecc_open.argtypes = [ctypes.POINTER(ZkEccOps), vp, u32, ctypes.POINTER(vp)]
+    lib.zk_ecc_assign_open.argtypes = [ctypes.POINTER(ZkEccOps), vp, u32, ctypes.POINTER(vp)]
+    lib.zk_ecc_assign_read.argtypes = [vp, vp]
     lib.zk_withdrawal_open.argtypes = [ctypes.POINTER(ZkWithdrawalWitness), u32, ctypes.POINTER(vp)]
     lib.zk_withdrawal_verify.argtypes = [ctypes.POINTER(ZkWithdrawalWitness), u32, vp, ctypes.POINTER(ZkResult)]
     lib.zk_withdrawal_assign.argtypes = [vp, u64, u64, vp, u32, vp, vp]

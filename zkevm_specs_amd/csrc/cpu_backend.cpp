@@ -90,6 +90,7 @@ struct zk_session {
     u64 fail_count = 0, first_row = ~0ull;
     u32 first_code = 0;
     bool range_ok = false;                // zk_set_range applies (row circuits)
+    bool range_may_be_empty = false;      // ... and takes lo == hi (ECC sessions)
     // owned inputs (kept alive for `row`)
     std::vector<u64> a64[4];
     std::vector<u32> a32[4];
@@ -98,7 +99,7 @@ struct zk_session {
     std::vector<u64> w64[4];              // assignment sessions: work / output buffers
     std::vector<u32> out32;
     void (*pass)(zk_session*) = nullptr;  // assignment sessions: one pass computes the outputs and fills `status`
-    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 6 exp, 7 PI
+    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 6 exp, 7 PI, 8 ECC
     u64 n_ops = 0;                        // RW -> State ops: 1 + kept rows
     std::vector<u32> rekey_plan;          // RW -> State ops: the RwkHostPlan's plan (as words) ...
     std::vector<u32> rekey_jobs;          // ... and its rank jobs (cls, field, base, count)
@@ -128,6 +129,7 @@ struct zk_session {
     PiaArgs pia;
     PiaSizes pia_sizes;
     KeccakGenArgs pia_kgen;
+    EccArgs ecc_assign;             // ECC assignment session (the verify session's args live in its `row` closure)
     std::vector<u64> pia64[20];     // PI assignment: inputs, work buffers and outputs of 64-bit words
     std::vector<u32> pia32[6];
     std::vector<uint8_t> pia8[4];
@@ -286,7 +288,7 @@ extern "C" int zk_last_timing(double* open_ms, double* pass_ms, double* span_ms)
 }
 extern "C" int zk_set_range(zk_session* s, uint64_t row_lo, uint64_t row_hi) {
     ARG_TRY(s && s->range_ok, "zk_set_range: not a row-circuit session");
-    ARG_TRY(row_lo < row_hi && row_hi <= s->n, "zk_set_range: bad range");
+    ARG_TRY((row_lo < row_hi || (s->range_may_be_empty && row_lo == row_hi)) && row_hi <= s->n, "zk_set_range: bad range");
     s->lo = row_lo;
     s->hi = row_hi;
     std::fill(s->status.begin(), s->status.end(), 0u);
@@ -1443,6 +1445,68 @@ extern "C" int zk_ecc_verify(const zk_ecc_ops* ops, const uint64_t* rows, uint32
     zk_session* s = new_session(a.n_add + a.n_mul + a.n_pairing, true);
     s->row = [a](u64 i) { return ecc_verify_row(a, i); };
     return one_shot(s, status_out, result);
+}
+
+// ECC sessions: a private copy of the ops (and rows); per-row evaluation by ecc_verify_row / ecc_assign_*_row over the range
+static int ecc_session_ops(zk_session* s, const zk_ecc_ops* ops, EccArgs& a, const char* name) {
+    const char* err = ecc_args_from_ops(ops, a);
+    if (err) { g_err = std::string(name) + ": " + err; return -1; }
+    const u64 np = a.n_add + a.n_mul, n_pp = a.n_pairing ? a.pair_off[a.n_pairing] : 0;
+    if (np) s->a64[0].assign(a.pts, a.pts + np * 24);
+    if (n_pp) s->a64[1].assign(a.pair_pts, a.pair_pts + n_pp * 24);
+    if (a.n_pairing) s->a64[2].assign(a.pair_out, a.pair_out + a.n_pairing * 4);
+    s->a32[0].assign(a.n_pairing + 1, 0u);
+    if (a.n_pairing) memcpy(s->a32[0].data(), a.pair_off, (a.n_pairing + 1) * 4);
+    a.pts = s->a64[0].data(); a.pair_pts = s->a64[1].data(); a.pair_out = s->a64[2].data(); a.pair_off = s->a32[0].data();
+    return 0;
+}
+extern "C" int zk_ecc_open(const zk_ecc_ops* ops, const uint64_t* rows, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_ecc_open");
+    ARG_TRY(out, "zk_ecc_open: out is null");
+    ARG_TRY(rows, "zk_ecc_open: rows is null");
+    zk_session* s = new zk_session();
+    EccArgs a;
+    if (int rc = ecc_session_ops(s, ops, a, "zk_ecc_open")) { delete s; return rc; }
+    const u64 n = a.n_add + a.n_mul + a.n_pairing;
+    s->n = n; s->lo = 0; s->hi = n;
+    s->status.assign(n, 0u);
+    s->range_ok = s->range_may_be_empty = true;
+    s->a64[3].assign(rows, rows + n * ECC_NCELLS * 4);
+    a.rows = s->a64[3].data();
+    s->row = [a](u64 i) { return ecc_verify_row(a, i); };
+    *out = s;
+    return 0;
+}
+static void ecc_assign_pass(zk_session* s) {
+    const EccArgs a = s->ecc_assign;
+    const u64 np = a.n_add + a.n_mul;
+#pragma omp parallel for schedule(dynamic, 16)
+    for (long long i = 0; i < (long long)s->n; i++) {
+        u64* row = a.rows_out + (u64)i * ECC_NCELLS * 4;
+        if ((u64)i < np) ecc_assign_point_row(a, (u64)i, row);
+        else ecc_assign_pairing_row(a, (u64)i - np, row);
+    }
+}
+extern "C" int zk_ecc_assign_open(const zk_ecc_ops* ops, uint64_t* rows_dev, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_ecc_assign_open");
+    ARG_TRY(out && !rows_dev, "zk_ecc_assign_open: bad arguments (rows_dev needs ZK_OPT_DEVICE_PTRS)");
+    zk_session* s = new zk_session();
+    EccArgs& a = s->ecc_assign;
+    if (int rc = ecc_session_ops(s, ops, a, "zk_ecc_assign_open")) { delete s; return rc; }
+    const u64 n = a.n_add + a.n_mul + a.n_pairing;
+    s->n = n; s->lo = 0; s->hi = n;
+    s->status.assign(n, 0u);
+    s->w64[0].assign(n * ECC_NCELLS * 4, 0);
+    a.rows_out = s->w64[0].data();
+    s->pass = ecc_assign_pass;
+    s->assign_kind = 8;
+    *out = s;
+    return 0;
+}
+extern "C" int zk_ecc_assign_read(zk_session* s, uint64_t* rows_host) {
+    ARG_TRY(s && rows_host && s->assign_kind == 8, "zk_ecc_assign_read: bad arguments");
+    memcpy(rows_host, s->w64[0].data(), s->w64[0].size() * 8);
+    return 0;
 }
 
 // ---- Withdrawal circuit -----------------------------------------------------------------------------------------------

@@ -301,6 +301,82 @@ ZK_HD u32 ecc_verify_row(const EccArgs& a, u64 i) {
     return i < a.n_add + a.n_mul ? ecc_verify_point_row(a, i) : ecc_verify_pairing_row(a, i);
 }
 
+// ---- verification of a session's pairing rows in two stages (zk_ecc_open) ----------------------------------------------------------
+// Stage 1, one call per pair of the points array: everything of ecc_verify_pairing_op that depends on one pair alone — the flags its
+// three loops test and the pair's Miller value — into the session's per-pair record.  Stage 2, one call per pairing row: the checks
+// of ecc_verify_pairing_op in their order, over the records.  Both run the functions the one-lane form runs, on the same values, so
+// the code of a row is the same bit for bit.
+enum EccPairFlag : u32 {
+    ECC_PF_VALID_P = 1u,      // on_curve(p) || [r]P == None
+    ECC_PF_VALID_Q = 2u,      // [r]Q == None
+    ECC_PF_Q_ON_CURVE = 4u,
+    ECC_PF_P_ON_CURVE = 8u,
+    ECC_PF_INF = 16u,         // p or q is None: the pair is left out of the product
+    ECC_PF_MILLER = 32u,      // the record's Fq12 holds miller_loop(p, q)
+};
+struct EccPairArgs {
+    EccArgs a;
+    u32* pair_flags;       // uint32[n_pair_pts]
+    bn::Fq12* pair_f;      // [n_pair_pts] (Montgomery form, tower order)
+};
+
+ZK_HD void ecc_pair_stage1(const EccPairArgs& s, u32 t) {
+    using namespace bn;
+    Fq c[6];
+    ecc_pair_words(s.a.pair_pts + (u64)t * 24, c);
+    for (int e = 0; e < 6; e++) c[e] = fq_reduce(c[e]);
+    Aff<Fq> p;
+    Aff<Fq2> q;
+    ecc_pair_points(c, p, q);
+    const bool p_on = on_curve(p), q_on = on_curve(q);
+    u32 fl = (p_on ? ECC_PF_P_ON_CURVE : 0u) | (q_on ? ECC_PF_Q_ON_CURVE : 0u) | ((p.inf || q.inf) ? ECC_PF_INF : 0u);
+    if (p_on || mul_by_r_is_inf(p)) fl |= ECC_PF_VALID_P;
+    if (mul_by_r_is_inf(q)) fl |= ECC_PF_VALID_Q;
+    // the Miller value is read only by an op that got past its subgroup and on-curve loops: a pair that fails either on its own, or
+    // that the product skips, needs none (what OTHER pairs of the op do is stage 2's business)
+    const u32 need = ECC_PF_VALID_P | ECC_PF_VALID_Q | ECC_PF_P_ON_CURVE | ECC_PF_Q_ON_CURVE;
+    if ((fl & need) == need && !(fl & ECC_PF_INF)) {
+        s.pair_f[t] = miller_loop(p.x, p.y, q.x, q.y);
+        fl |= ECC_PF_MILLER;
+    }
+    s.pair_flags[t] = fl;
+}
+
+// pairing row i (>= n_add + n_mul) of the session: ecc_verify_pairing_row with the per-pair work read from the records
+ZK_HD u32 ecc_pair_stage2(const EccPairArgs& s, u64 i) {
+    using namespace bn;
+    const EccArgs& a = s.a;
+    const u64* row = a.rows + i * (ECC_NCELLS * 4);
+    int kind;
+    const u32 st = ecc_verify_common(a, i, row, &kind);
+    if (st) return st;
+    if (!ecc_cell_zero(row + 40)) return ECC_CODE(ECC_PAIR_OUT_X);
+    const u64 k = i - a.n_add - a.n_mul;
+    const u64* out = a.pair_out + 4 * k;
+    if (!(row[44] == out[0] && row[45] == out[1] && (row[46] | row[47]) == 0)) return ECC_CODE(ECC_PAIR_OUT_Y);
+    const u32 t0 = a.pair_off[k], t1 = a.pair_off[k + 1];
+    for (u32 t = t0; t < t1; t++) {
+        const u32 fl = s.pair_flags[t];
+        if (!((fl & ECC_PF_VALID_P) && (fl & ECC_PF_VALID_Q))) return ECC_CODE(ECC_PAIR_SUBGROUP);
+    }
+    const Fr rM = fr_to_mont(a.randomness);
+    Fr rlc = fr_zero();
+    for (u32 t = t0; t < t1; t++) {
+        Fq c[6];
+        ecc_pair_words(a.pair_pts + (u64)t * 24, c);
+        for (int e = 0; e < 6; e++) rlc = ecc_rlc_step(rlc, rM, fq_reduce(c[e]));
+    }
+    if (!fr_eq(rlc, fr_load(row + 36))) return ECC_CODE(ECC_PAIR_RLC);
+    Fq12 f = fq12_one();
+    for (u32 t = t0; t < t1; t++) {
+        const u32 fl = s.pair_flags[t];
+        if (!(fl & ECC_PF_Q_ON_CURVE) || !(fl & ECC_PF_P_ON_CURVE)) return ECC_CODE(ECC_PAIR_ON_CURVE);
+        if (!(fl & ECC_PF_INF)) f = fq12_mul(f, s.pair_f[t]);  // (ECC_PF_MILLER is set: the pair passed both loops)
+    }
+    const bool one = fq12_is_one(final_exp(f));
+    return ecc_cell_is(row + 44, one ? 1 : 0) ? 0 : ECC_CODE(ECC_PAIR_RESULT);
+}
+
 // zk_fr_op known-answer hooks (ops 18 .. 25): Fq product, Fq12 operations of residues (words are reduced first), the pairing of one
 // pair and the G2 scalar chain
 ZK_HD Fr ecc_fq_mul_hook(const Fr& x, const Fr& y) {

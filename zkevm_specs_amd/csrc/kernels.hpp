@@ -81,6 +81,9 @@ void zk_launch_ecdsa(hipStream_t st, const EcdsaArgs& a, u32* status, ZkTally* t
 void zk_launch_ecdsa_comb_build(hipStream_t st, u32* table);  // the device's 8-bit fixed-base table of G (522 KB), built once
 // ECC circuit (k_ecc.hip): assign = circuit2rows into a.rows_out, else verify a.rows (status / tally)
 void zk_launch_ecc(hipStream_t st, const EccArgs& a, bool assign, u32* status, ZkTally* tally);
+// rows [lo, hi) of an ECC session: add / mul rows, then the pairs [t_lo, t_hi) of the pairing ops in range (stage 1) and those ops'
+// rows (stage 2), three launches in stream order (twin tally; status is never null)
+void zk_launch_ecc_range(hipStream_t st, const EccPairArgs& s, u64 lo, u64 hi, u32 t_lo, u32 t_hi, u32* status, ZkTally* tally);
 void zk_launch_fq12_op(hipStream_t st, int op, const u64* x, const u64* y, u64* out, u64 n12);  // zk_fr_op 19..25
 // Withdrawal circuit (k_withdrawal.hip): verify held rows [lo, hi) (status / twin tally); assign rows [0, a.n_out) (+ keccak rows)
 void zk_launch_withdrawal_rows(hipStream_t st, const WithdrawalArgs& a, u64 lo, u64 hi, u32* status, ZkTally* tally);

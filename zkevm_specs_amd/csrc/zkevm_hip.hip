@@ -583,7 +583,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -591,6 +591,7 @@ struct zk_session {
     hipStream_t stream = t_stream;
     u64 n = 0;                      // rows per pass
     u64 eval_lo = 0, eval_hi = 0;   // row sessions: rows [eval_lo, eval_hi) are evaluated (zk_set_range); 0, 0 = all n
+    bool eval_empty = false;        // ECC sessions: zk_set_range(lo, lo) — no row is evaluated (a rank without rows)
     std::vector<void*> owned;       // device buffers (arena) returned at close
     std::vector<int> owned_class;   // their arena size classes
     ZkTally* d_tally = nullptr;
@@ -617,6 +618,8 @@ struct zk_session {
     TxAssignArgs txa;
     ExaArgs exa;
     u64 exa_n_table = 0;
+    EccPairArgs ecc;                // SESSION_ECC (with the per-pair records) / SESSION_ECC_ASSIGN (ecc.a alone)
+    std::vector<u32> ecc_pair_off;  // ... pair_off on the host (validated at open): sizes the per-pair launch of every range
     PiaArgs pia;
     PiaSizes pia_sizes;
     KeccakGenArgs pia_kgen;
@@ -2571,16 +2574,18 @@ extern "C" int zk_exp_verify(const uint64_t* rows, uint64_t n, uint32_t opts, ui
     return one_shot(s, opts & ZK_OPT_DEVICE_PTRS, status_out, result);
 }
 
-static inline u64 range_lo(const zk_session* s) { return s->eval_hi ? s->eval_lo : 0; }
-static inline u64 range_hi(const zk_session* s) { return s->eval_hi ? s->eval_hi : s->n; }
+static inline u64 range_lo(const zk_session* s) { return (s->eval_hi || s->eval_empty) ? s->eval_lo : 0; }
+static inline u64 range_hi(const zk_session* s) { return s->eval_empty ? s->eval_lo : s->eval_hi ? s->eval_hi : s->n; }
 extern "C" int zk_set_range(zk_session* s, uint64_t row_lo, uint64_t row_hi) {
     ARG_TRY(s && (s->kind == SESSION_STATE || s->kind == SESSION_BYTECODE || s->kind == SESSION_COPY || s->kind == SESSION_EXP ||
-                  s->kind == SESSION_SIGN || s->kind == SESSION_PI || s->kind == SESSION_WITHDRAWAL),
+                  s->kind == SESSION_SIGN || s->kind == SESSION_PI || s->kind == SESSION_WITHDRAWAL || s->kind == SESSION_ECC),
             "zk_set_range: not a row-circuit session (EVM sessions shard by the steps they are opened over)");
-    ARG_TRY(row_lo < row_hi && row_hi <= s->n, "zk_set_range: bad range");
+    // (an ECC range may be empty: shard_ecc balances cost, not rows, and a rank may be left without any)
+    ARG_TRY((row_lo < row_hi || (s->kind == SESSION_ECC && row_lo == row_hi)) && row_hi <= s->n, "zk_set_range: bad range");
     HIP_TRY(hipSetDevice(s->device));
     s->eval_lo = row_lo;
     s->eval_hi = row_hi;
+    s->eval_empty = row_lo == row_hi;
     if (s->kind == SESSION_STATE) {
         s->state.eval_lo = row_lo;
         s->state.eval_hi = row_hi;
@@ -2704,7 +2709,7 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     }
     const bool twin_tally = s->kind == SESSION_STATE || s->kind == SESSION_BYTECODE || s->kind == SESSION_COPY ||
                             s->kind == SESSION_SIGN || s->kind == SESSION_EXP || s->kind == SESSION_PI || s->kind == SESSION_PICOPY ||
-                            s->kind == SESSION_WITHDRAWAL;
+                            s->kind == SESSION_WITHDRAWAL || s->kind == SESSION_ECC;
     ZkTally* const tally = twin_tally ? s->d_tally + (s->tally_pass++ & 1u) : s->d_tally;
     s->tally_last = tally;
     if (!twin_tally && !(s->kind == SESSION_EVM && s->evm.perm))
@@ -2758,6 +2763,15 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     case SESSION_BCA: zk_launch_bytecode_assign(s->stream, s->bca, status, s->d_tally); break;
     case SESSION_PI: zk_launch_pi_rows(s->stream, s->pi, range_lo(s), range_hi(s), status, tally); break;
     case SESSION_WITHDRAWAL: zk_launch_withdrawal_rows(s->stream, s->withdrawal, range_lo(s), range_hi(s), status, tally); break;
+    case SESSION_ECC: {
+        // pairing ops [k_lo, k_hi) of the range own the pairs [pair_off[k_lo], pair_off[k_hi]): stage 1's lanes
+        const u64 np = s->ecc.a.n_add + s->ecc.a.n_mul, lo = range_lo(s), hi = range_hi(s);
+        const u64 k_lo = lo > np ? lo - np : 0, k_hi = hi > np ? hi - np : 0;
+        const bool pairs = k_hi > k_lo;
+        zk_launch_ecc_range(s->stream, s->ecc, lo, hi, pairs ? s->ecc_pair_off[k_lo] : 0u, pairs ? s->ecc_pair_off[k_hi] : 0u, status, tally);
+        break;
+    }
+    case SESSION_ECC_ASSIGN: zk_launch_ecc(s->stream, s->ecc.a, true, nullptr, s->d_tally); break;
     case SESSION_TXA: zk_launch_tx_assign(s->stream, s->txa, status, s->d_tally); break;
     case SESSION_PICOPY: zk_launch_pi_copy(s->stream, s->picopy, status, tally); break;
     case SESSION_CPA: zk_launch_copy_assign(s->stream, s->cpa, status, s->d_tally); break;
@@ -3640,6 +3654,96 @@ extern "C" int zk_ecc_verify(const zk_ecc_ops* ops, const uint64_t* rows, uint32
     ARG_TRY(!(opts & ZK_OPT_DEVICE_PTRS), "zk_ecc_verify: ZK_OPT_DEVICE_PTRS is not supported (the ops are read on the host)");
     ARG_TRY(rows && result, "zk_ecc_verify: rows / result is null");
     return ecc_run(ops, rows, false, nullptr, status_out, result, "zk_ecc_verify");
+}
+
+// ---- ECC sessions: the ops resident (zk_ecc_open verifies rows over them, zk_ecc_assign_open assigns the rows) -------------------------
+// Brings the ops to the device (or takes them in place), validates them as the one-shots do — pair_off and the randomness cell are
+// the only parts the host looks at — and fills s->ecc.a / s->ecc_pair_off.
+static int ecc_session_ops(zk_session* s, const zk_ecc_ops* ops, bool dev, const char* name) {
+    auto fail = [&](const char* what) { g_err = std::string(name) + ": " + what; return -1; };
+    if (!ops || !ops->randomness) return fail("null ops / randomness");
+    if (ops->n_pairing >= (1ull << 32)) return fail("bad row count");
+    if (ops->n_pairing && !ops->pair_off) return fail("pair_off / pair_out is null");
+    u64 rh[4];
+    s->ecc_pair_off.assign(ops->n_pairing + 1, 0u);
+    if (dev) {
+        if (fetch_small(s->stream, rh, ops->randomness, 32)) return fail("randomness download failed");
+        if (ops->n_pairing && d2h_now(s->stream, s->ecc_pair_off.data(), ops->pair_off, (ops->n_pairing + 1) * 4)) return fail("pair_off download failed");
+    } else {
+        memcpy(rh, ops->randomness, 32);
+        if (ops->n_pairing) memcpy(s->ecc_pair_off.data(), ops->pair_off, (ops->n_pairing + 1) * 4);
+    }
+    zk_ecc_ops h = *ops;  // what the host-side check reads, on the host
+    h.randomness = rh;
+    h.pair_off = ops->n_pairing ? s->ecc_pair_off.data() : nullptr;
+    EccArgs& a = s->ecc.a;
+    if (const char* err = ecc_args_from_ops(&h, a)) return fail(err);
+    const u64 np = a.n_add + a.n_mul, n_pp = s->ecc_pair_off[a.n_pairing];
+    int rc;
+    const void* p = nullptr;
+    if ((rc = stage(s, ops->points, (size_t)np * 192, dev, &p))) return rc;
+    a.pts = (const u64*)p;
+    if ((rc = stage(s, ops->pair_pts, (size_t)n_pp * 192, dev, &p))) return rc;
+    a.pair_pts = (const u64*)p;
+    if ((rc = stage(s, ops->pair_out, (size_t)a.n_pairing * 32, dev, &p))) return rc;
+    a.pair_out = (const u64*)p;
+    if ((rc = stage(s, ops->pair_off, a.n_pairing ? (size_t)(a.n_pairing + 1) * 4 : 0, dev, &p))) return rc;
+    a.pair_off = (const u32*)p;
+    s->n = np + a.n_pairing;
+    return 0;
+}
+extern "C" int zk_ecc_open(const zk_ecc_ops* ops, const uint64_t* rows, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_ecc_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(out, "zk_ecc_open: out is null");
+    ARG_TRY(rows, "zk_ecc_open: rows is null");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = new zk_session();
+    s->kind = SESSION_ECC;
+    int rc = ecc_session_ops(s, ops, dev, "zk_ecc_open");
+    const void* p = nullptr;
+    if (rc) goto fail;
+    if ((rc = stage(s, rows, (size_t)s->n * ECC_NCELLS * 32, dev, &p))) goto fail;
+    s->ecc.a.rows = (const u64*)p;
+    {   // the per-pair records of the two-stage pairing pass (written by stage 1 of every pass before stage 2 reads them)
+        const u64 n_pp = s->ecc_pair_off[s->ecc.a.n_pairing];
+        if ((rc = dev_alloc(s, (void**)&s->ecc.pair_flags, (size_t)(n_pp ? n_pp : 1) * sizeof(u32)))) goto fail;
+        if ((rc = dev_alloc(s, (void**)&s->ecc.pair_f, (size_t)(n_pp ? n_pp : 1) * sizeof(bn::Fq12)))) goto fail;
+    }
+    if ((rc = session_common_init(s))) goto fail;
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_ecc_assign_open(const zk_ecc_ops* ops, uint64_t* rows_dev, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_ecc_assign_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(out, "zk_ecc_assign_open: out is null");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    ARG_TRY(dev || !rows_dev, "zk_ecc_assign_open: rows_dev needs ZK_OPT_DEVICE_PTRS");
+    zk_session* s = new zk_session();
+    s->kind = SESSION_ECC_ASSIGN;
+    int rc = ecc_session_ops(s, ops, dev, "zk_ecc_assign_open");
+    if (rc) goto fail;
+    s->ecc.a.rows_out = rows_dev;
+    if (!rows_dev && (rc = dev_alloc(s, (void**)&s->ecc.a.rows_out, (size_t)s->n * ECC_NCELLS * 32))) goto fail;
+    s->ecc.pair_flags = nullptr;
+    s->ecc.pair_f = nullptr;
+    if ((rc = session_common_init(s))) goto fail;
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_ecc_assign_read(zk_session* s, uint64_t* rows_host) {
+    ARG_TRY(s && rows_host && s->kind == SESSION_ECC_ASSIGN, "zk_ecc_assign_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipMemcpyAsync(rows_host, s->ecc.a.rows_out, (size_t)s->n * ECC_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------

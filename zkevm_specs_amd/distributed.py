@@ -61,6 +61,39 @@ def shard_rows(cols, flags, rank, world, circuit, max_withdrawals=None, total_ro
     return _take(cols, idx, 1), (None if flags is None else _take(flags, idx, 0)), before, before + (hi - lo), lo
 
 
+# Cost weights of the ECC circuit's rows, for shard_ecc, in units of 1e-5 ms of device time per row.  Derived from the one-lane
+# row-kernel figures of DESIGN.md §3.ECC (MI355X, device time of a pass divided by its rows):
+#   add rows      2^14 rows in 0.44 ms  -> 2.7e-5 ms per row
+#   mul rows      2^12 rows in 7.67 ms  -> 1.9e-3 ms per row (one 254-step Jacobian chain in Fq)
+#   pairing ops   2^10 ops of two pairs in 79.3 ms -> 7.7e-2 ms per op.  Split per pair and per op by the work inside: a pair's [r]Q
+#                 chain is the mul row's chain over Fq2 (3 Fq products per product: ~3 x 7.67 = 23 of the 79.3 ms per pair); the remaining
+#                 79.3 - 2 x 23 = 33 ms are two Miller loops (per pair) and one final exponentiation (per op), taken as thirds, 11 ms each.
+#                 So a pair is (23 + 11) / 79.3 and the op 11 / 79.3 of 7.7e-2 ms: 3.3e-2 and 1.1e-2 ms.
+# A balance heuristic only: the figures are those of the one-lane kernels at their benchmark sizes, nobody has measured the weights on
+# sharded runs, and no test asserts anything about the balance they give.
+ECC_COST_ADD = 3
+ECC_COST_MUL = 190
+ECC_COST_PAIR = 3300
+ECC_COST_PAIRING_OP = 1100
+
+
+def shard_ecc(n_add, n_mul, pair_off, rank, world):
+    """[lo, hi) of the ECC circuit's n_add + n_mul + n_pairing rows (circuit2rows order) that rank `rank` evaluates: contiguous,
+    tiling [0, n) without gap or overlap over the ranks, cut at equal shares of the prefix sum of the rows' cost weights (ECC_COST_*).
+    Ops and rows are replicated on every rank; only the range differs (Session.set_range; a range may be empty)."""
+    off = np.asarray(pair_off.cpu() if hasattr(pair_off, "is_cuda") else pair_off).astype(np.int64)
+    n_add, n_mul = int(n_add), int(n_mul)
+    cost = np.concatenate([np.full(n_add, ECC_COST_ADD, dtype=np.int64), np.full(n_mul, ECC_COST_MUL, dtype=np.int64),
+                           ECC_COST_PAIRING_OP + ECC_COST_PAIR * (off[1:] - off[:-1])])
+    ends = np.cumsum(cost)  # ends[i]: cost of rows [0, i]
+    total = int(ends[-1]) if ends.size else 0
+
+    def cut(r):  # the first row whose prefix cost reaches r / world of the total
+        return int(ends.size) if r >= world else int(np.searchsorted(ends, -(-total * r // world), side="left")) if r > 0 else 0
+
+    return cut(rank), cut(rank + 1)
+
+
 def shard_units(wire, rank, world):
     """Tx / Sig units shard (no halo: units are independent, tx_circuit.py:253-291): bytes[n, 9, 32], cells[8, n, 4],
     meta[n, 4] and the units' twelve fixed tx-table rows are cut to the rank's units, the keccak table stays whole (replicated).  Returns (wire_local, lo)."""

@@ -775,6 +775,56 @@ def _ecc_ops(w, randomness):
     return t, 0, (w, randomness)
 
 
+def _ecc_session_ops(w, randomness, rows=None, rows_out=None):
+    """zk_ecc_open / zk_ecc_assign_open over the arrays of flatten.flatten_ecc_ops, numpy (staged at open) or device tensors (used in
+    place; all of them then, `rows` / `rows_out` included) -> (ZkEccOps, rows, rows_out, n, opts, kept arrays)"""
+    pts, pair_pts, pair_off, pair_out = w["points"], w["pair_pts"], w["pair_off"], w["pair_out"]
+    randomness = _randomness_cells(randomness, pts)
+    n_add, n_mul, n_pairing = int(w["n_add"]), int(w["n_mul"]), int(pair_out.shape[0])
+    n = n_add + n_mul + n_pairing
+    _expect(pts, "ecc points", 8, (n_add + n_mul, 6, 4))
+    _expect(pair_pts, "ecc pair_pts", 8, (None, 6, 4))
+    _expect(pair_out, "ecc pair_out", 8, (None, 4))
+    _expect(pair_off, "ecc pair_off", 4, (n_pairing + 1,))
+    _expect(randomness, "randomness", 8, (4,))
+    _expect(rows, "ecc rows", 8, (n, 13, 4))
+    _expect(rows_out, "rows_dev", 8, (n, 13, 4))
+    keep, opts = _prep([pts, pair_pts, pair_off, pair_out, randomness, rows, rows_out], outputs=(6,))
+    pts, pair_pts, pair_off, pair_out, randomness, rows, rows_out = keep
+    max_ok = w["max_ok"]
+    max_ok = max_ok.cpu().tolist() if hasattr(max_ok, "is_cuda") else max_ok
+    t = _lib.ZkEccOps(ptr(pts, n_add + n_mul), n_add, n_mul, ptr(pair_pts, _rows(pair_pts)), ptr(pair_off), ptr(pair_out, n_pairing),
+                      n_pairing, ptr(randomness), int(max_ok[0]), int(max_ok[1]), int(max_ok[2]))
+    return t, rows, rows_out, n, opts, keep
+
+
+def open_ecc(w, rows, randomness, device=None):
+    """ECC circuit session: w = the ops wire of flatten.flatten_ecc_ops, rows uint64[n, 13, 4] (EccTableRow cells: ecc_assign's or an
+    EccAssignSession's output), randomness (int or uint64[4]) -> Session over the n_add + n_mul + n_pairing rows.  numpy arrays are
+    staged at open, device tensors used in place.  set_range(lo, hi) evaluates rows [lo, hi) (distributed.shard_ecc; lo == hi is
+    allowed); first_fail_row is always a row of the whole circuit."""
+    lib = _lib.init(device)
+    t, rows, _, n, opts, keep = _ecc_session_ops(w, randomness, rows=rows)
+    return _open(lib, lib.zk_ecc_open, n, (keep, t), ctypes.byref(t), ptr(rows), opts)
+
+
+class EccAssignSession(Session):
+    """ECC witness-assignment session (circuit2rows): launch()/collect() like the circuits; rows() for the EccTableRow cells."""
+
+    def rows(self):
+        out = np.empty((self.n, 13, 4), dtype=np.uint64)
+        check(self._lib.zk_ecc_assign_read(self._h, ptr(out)), "zk_ecc_assign_read", self._lib)
+        return out
+
+
+def open_ecc_assign(w, randomness, rows_dev=None, device=None):
+    """ECC circuit2rows over resident ops (the wire of flatten.flatten_ecc_ops, numpy or device tensors) -> EccAssignSession;
+    rows_dev: optional CUDA tensor uint64[n, 13, 4] receiving the rows in place (ready for open_ecc)."""
+    lib = _lib.init(device)
+    t, _, rows_dev, n, opts, keep = _ecc_session_ops(w, randomness, rows_out=rows_dev)
+    return _open(lib, lib.zk_ecc_assign_open, n, (keep, t), ctypes.byref(t), ptr(rows_dev), opts, cls=EccAssignSession)
+
+
 def _withdrawal_eval_rows(w):
     """rows a session over the wire dict `w` evaluates (withdrawal_circuit.hpp wd_eval_rows)"""
     n_rows, base, total, m = int(w["rows"].shape[0]), int(w.get("row_base", 0)), int(w.get("total_rows", w["rows"].shape[0])), int(w["max_withdrawals"])

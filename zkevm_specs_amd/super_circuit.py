@@ -339,10 +339,21 @@ class SuperCircuit:
                 e_rows, _, lo_, hi_, self.row_lo["exp"] = distributed.shard_rows(e_rows, None, rank, world, "exp")
                 ranges["exp"] = (lo_, hi_)
             self.sessions["exp"] = engine.open_exp(e_rows, device=device)
+        if "ecc" in parts:
+            # ECC circuit: parts["ecc"] = (ops wire of flatten.flatten_ecc_ops, rows uint64[n, 13, 4], randomness).  Ops and rows are
+            # whole on every rank (as tables are); a rank evaluates its shard_ecc range, and the session reports rows of the whole circuit.
+            e_w, e_rows, e_r = parts["ecc"]
+            e_w = {k: (dev(v) if hasattr(v, "shape") and k != "max_ok" else v) for k, v in e_w.items()}
+            self.sessions["ecc"] = engine.open_ecc(e_w, dev(e_rows), e_r, device=device)
+            self.global_rows["ecc"], self.row_lo["ecc"] = self.sessions["ecc"].n, 0
+            if world > 1:
+                ranges["ecc"] = distributed.shard_ecc(e_w["n_add"], e_w["n_mul"], parts["ecc"][0]["pair_off"], rank, world)
         for k, (lo_, hi_) in ranges.items():
             self.sessions[k].set_range(lo_, hi_)
         self.rows = {k: (ranges[k][1] - ranges[k][0] if k in ranges else s.n) for k, s in self.sessions.items()}
         self.eval_lo = {k: ranges.get(k, (0, 0))[0] for k in self.sessions}
+        if "ecc" in self.sessions:
+            self.eval_lo["ecc"] = 0  # (an ECC session reports rows of the whole circuit whatever its range)
         # one HIP stream per circuit: the kernels are independent and bound by different things (the State kernel streams
         # HBM, the EVM kernel is latency / issue bound), so their passes overlap on the device
         self._streams = None
@@ -358,7 +369,7 @@ class SuperCircuit:
             prio = os.environ.get("ZK_SUPER_PRIO", "1") == "1"
             hi = tuple(os.environ.get("ZK_SUPER_PRIO_SET", "exp,tx,copy,bytecode").split(","))  # which sessions get the high-priority streams
             self._streams = {k: (torch.cuda.Stream(priority=-1) if prio and k in hi else torch.cuda.Stream()) for k in self.sessions}
-            order = os.environ.get("ZK_SUPER_ORDER", "exp,tx,copy,bytecode,evm,state" if prio else "").split(",")
+            order = os.environ.get("ZK_SUPER_ORDER", "exp,tx,copy,bytecode,evm,state" if prio else "").split(",")  # (an "ecc" session goes last)
             self._launch_order = [k for k in order if k in self.sessions] + [k for k in self.sessions if k not in order]
             for k, s in self.sessions.items():
                 s.set_stream(self._streams[k])
