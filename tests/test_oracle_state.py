@@ -73,3 +73,21 @@ def test_kernel_logic_on_tampered_synthetic(hostsim):
     got = _hostsim_state(hostsim, cols, flags, mpt)
     assert got.tolist() == exp
     assert sum(1 for e in exp if e) > 100
+
+
+def test_oracle_reproduces_the_stored_site_cases(golden_dir):
+    """tests/golden/state_site_cases.npz: this copy of the oracle gives every case the failing rows and codes the generator's copy gave
+    (full pass over the patched base, no shortcut), and the helper's neighbourhood-only expectation equals the full pass"""
+    from tests import state_site_cases as ssc
+
+    data = ssc.load(golden_dir)
+    for k, c in enumerate(data.cases):
+        _, flags, _, rows, mpt_rows, t, affected = ssc.build(data, c, 0, 0)
+        exp = state_oracle.verify_rows(rows, flags, mpt_rows)
+        assert exp[t] == c.code and codes.site_of(c.code) == c.site and codes.kind_of(c.code) == c.ref_kind, k
+        assert [(j, e) for j, e in enumerate(exp) if e] == c.fails, k
+        assert ssc.expected(rows, flags, mpt_rows, affected) == exp, k
+        if c.compact_code != ssc.EXCLUDED:
+            _, flags, _, rows, mpt_rows, t, _ = ssc.build(data, c, 0, 0, compact=True)
+            assert state_oracle.check_row(rows, flags, t, set(tuple(m) for m in mpt_rows)) == c.compact_code, k
+    assert len(data.cases) >= 300

@@ -124,3 +124,184 @@ def test_gpu_fused_state_verify_fuzz():
         n = rng.choice([3, 17, 64, 200, 511, 1300])
         rows, flags = rand_rw_table(rng, n, 0.0, 0.0, dup=rng.choice([0.0, 0.3, 0.8]))
         check_case(rows, flags, None, with_oracle=n <= 200)
+
+
+# ---- Directed RW-level cases: one RW row of a consistent trace damaged at a time (value, previous value, is_write, counter, id, address /
+# field tag, committed value, rw_flags), on the first and the last access of a key group of every State tag; for Storage and Account the
+# damaged row is also moved — by Stack rows that sort in front of it, or by dropping what sorts behind it — to the first evaluated lane of
+# a 63-row wavefront, to its last lane, and to row n - 1 of the sorted State rows.  Each case: fused == two steps == the three checkers.
+A_ACC, A_STO = 0x1234567890ABCDEF1234567890ABCDEF12345678, 0xFEDCBA9876543210FEDCBA9876543210FEDCBA98
+DIRECTED_TAGS = (2, 3, 4, 5, 6, 7, 8, 9, 10, 11)
+PLACED_TAGS = (4, 6)
+# State sites the directed RW cases make a failing site of some row, per State tag of the damaged row: measured with the three checkers
+# (oracle_statuses), not with the library.  Decomposition checks (4..7, 9) cannot fail on this path — op2row derives limbs and bytes —
+# and a damaged row is re-sorted, so many per-tag "unused key is zero" checks are out of reach as well.
+FUSED_REACHED = {
+    2: [11, 13, 40, 42, 44, 45, 47, 48],
+    3: [11, 13, 60, 62, 64],
+    4: [10, 11, 12, 13, 70, 71],
+    5: [11, 13, 83, 84],
+    6: [11, 12, 13, 93, 94, 95],
+    7: [13, 100, 101],
+    8: [11, 13, 110, 112, 115, 116],
+    9: [13, 120, 121, 125],
+    10: [13, 130, 132],
+    11: [11, 13, 140, 142, 144, 145, 148, 150],
+}
+
+
+def directed_rw_base():
+    """the 150-step block's RW table plus accesses the block generator does not make: Storage and Account key groups with several
+    accesses (the last access carries the first's value: the mock MPT updates are made from a key's first op), TxAccessListAccount,
+    TxLog and TxReceipt rows"""
+    rows, flags = _valid_block_rw(150)
+    rows, flags = [list(r) for r in rows], list(flags)
+    c = max(r[0] for r in rows)
+
+    def add(target, id_, addr, ft, key, is_write, value, committed=0, word=0):
+        nonlocal c
+        c += 1
+        rows.append([c, is_write, target, id_, addr, ft, key & ((1 << 128) - 1), key >> 128, value & ((1 << 128) - 1), value >> 128, 0, 0,
+                     committed & ((1 << 128) - 1), committed >> 128])
+        flags.append(word)
+
+    add(9, 9000, 64, 0, 0, 0, 0), add(9, 9000, 64, 0, 0, 1, 42), add(9, 9000, 64, 0, 0, 0, 42)  # Memory: read 0, write, read back
+    for key in (0x99, (7 << 128) | 5):
+        v = (1 << 130) + key % 1000
+        add(6, 1, A_STO, 0, key, 1, v, 55, 1), add(6, 1, A_STO, 0, key, 1, 5, 55, 1), add(6, 1, A_STO, 0, key, 1, v, 55, 1), add(6, 1, A_STO, 0, key, 0, v, 55, 1)
+    for addr in (A_ACC, 0x77):
+        add(5, 0, addr, 1, 0, 1, 1, 0, 0), add(5, 0, addr, 1, 0, 0, 1, 0, 0)
+        add(5, 0, addr, 2, 0, 1, (1 << 128) + 3, 1 << 64, 1), add(5, 0, addr, 2, 0, 1, 9, 1 << 64, 1), add(5, 0, addr, 2, 0, 1, (1 << 128) + 3, 1 << 64, 1)
+        h = (1 << 250) + addr % 1000  # (an existing code hash: the mock MPT updates have no non-existing proof for a 0 -> 0 leaf)
+        add(5, 0, addr, 3, 0, 0, h, h, 1), add(5, 0, addr, 3, 0, 0, h, h, 1)
+    for tx in (1, 2):
+        add(2, tx, A_ACC, 0, 0, 0, 0), add(2, tx, A_ACC, 0, 0, 1, 1), add(2, tx, A_ACC, 0, 0, 0, 1)
+        for log in (1, 2):
+            add(10, tx, (log << 48) | (0 << 32), 0, 0, 1, 124), add(10, tx, (log << 48) | (2 << 32) | 1, 0, 0, 1, (1 << 255) + 7, 0, 1), add(10, tx, (log << 48) | (3 << 32), 0, 0, 1, 10)
+    gas = 0
+    for tx in (1, 2, 3):
+        if tx != 2:
+            add(11, tx, 0, 1, 0, 0, 1)
+        gas += 21000
+        add(11, tx, 0, 2, 0, 0, gas)
+    return rows, flags
+
+
+def _state_keys(rows, flags):
+    """[(State key tuple with rw_counter, RW row index)] of the rows that become State ops, in the State circuit's order"""
+    out = []
+    for i, (r, f) in enumerate(zip(rows, flags)):
+        op = rw_state_oracle.rekey_row(r, int(f))
+        if op is not None:
+            o = op[0]
+            out.append(((o[2], o[3], o[4], o[5], o[6], o[0]), i))
+    return sorted(out)
+
+
+def _damages(r, f):
+    """(name, row, flags, moves) — `moves`: the damage changes a key cell or the counter, so the row sorts elsewhere"""
+    def w(j, v):
+        x = list(r)
+        x[j] = v
+        return x
+    yield "value+1", w(8, r[8] + 1), f, False
+    yield "value=256", w(8, 256), f, False
+    yield "value hi", w(9, r[9] ^ (1 << 64)), f, False
+    yield "previous value", w(10, r[10] + 1), f, False
+    yield "is_write", w(1, r[1] ^ 1), f, False
+    yield "committed+1", w(12, r[12] + 1), f, False
+    yield "committed hi", w(13, r[13] ^ (1 << 64)), f, False
+    yield "value is_word", r, f ^ 1, False
+    yield "previous is_word", r, f ^ 2, False
+    yield "counter=0", w(0, 0), f, True
+    yield "id+1", w(3, r[3] + 1), f, True
+    yield "id=0", w(3, 0), f, True
+    yield "field tag+1", w(5, r[5] + 1), f, True
+    yield "field tag=5", w(5, 5), f, True
+    yield "address+1", w(4, r[4] + 1), f, True
+
+
+def _placed(rows, flags, i, want):
+    """the table with RW row i's State row moved: want = 0 / 62: Stack writes of call id 0 (they sort behind the Memory rows and in front of
+    everything else) until its State row index is want modulo 63; want = "last": every row that sorts behind its key group dropped"""
+    keys = _state_keys(rows, flags)
+    pos = 1 + [j for _, j in keys].index(i)  # (the Start row is State row 0)
+    if want == "last":
+        mine = keys[pos - 1][0][:5]
+        keep = {j for k, j in keys if k[:5] <= mine}
+        assert keys[pos - 1][0] == max(k for k, j in keys if j in keep)  # the last access of the last group
+        out = [(rows[j], flags[j]) for j in range(len(rows)) if j in keep]
+        return [r for r, _ in out], [f for _, f in out], len(out)
+    assert rows[i][2] not in (9, 8) and not any(r[2] == 8 and r[3] == 0 for r in rows)
+    k = (want - pos) % 63
+    c = max(r[0] for r in rows)
+    pad = [[c + 1 + j, 1, 8, 0, 1023, 0, 0, 0, 7, 0, 0, 0, 0, 0] for j in range(k)]
+    return rows + pad, flags + [1] * k, pos + k
+
+
+def directed_variants(tag):
+    """(damaged RW rows, flags) of every directed case of one State tag, placements included"""
+    rows, flags = directed_rw_base()
+    groups = {}
+    for k, i in _state_keys(rows, flags):
+        if k[0] == tag:
+            groups.setdefault(k[:5], []).append(i)
+    multi = [g for g in groups.values() if len(g) > 1]
+    single = [g for g in groups.values() if len(g) == 1]
+    # the first and the last access of a key group with several, and up to two rows that are their group's only access
+    targets = ([multi[0][0], multi[0][-1]] if multi else []) + [g[0] for g in single[:2]]
+    assert len(targets) >= 2, tag
+    for i in targets:
+        for name, r, f, moves in _damages(rows[i], flags[i]):
+            hurt, hf = [list(x) for x in rows], list(flags)
+            hurt[i], hf[i] = r, f
+            yield hurt, hf
+            if tag in PLACED_TAGS and not moves and multi and i in (multi[0][0], multi[0][-1]):
+                for want in (0, 62):
+                    pr, pf, pos = _placed(hurt, hf, i, want)
+                    assert pos % 63 == want and [j for _, j in _state_keys(pr, pf)].index(i) + 1 == pos
+                    yield pr, pf
+                if i == multi[0][-1]:  # the last access: its next row is row 0 through the wrap-around
+                    pr, pf, m = _placed(hurt, hf, i, "last")
+                    assert len(_state_keys(pr, pf)) == m
+                    yield pr, pf
+
+
+def directed_census(tag, device=None, run=False):
+    """State sites the cases of one tag make a failing site, by the three checkers; with `run`, each case also goes through check_case"""
+    sites, n, refused = set(), 0, 0
+    for vr, vf in directed_variants(tag):
+        ops, op_flags, _ = rw_state_oracle.rw_to_state_ops(vr, vf, strict=True)
+        if any(assign_oracle.assign(ops, op_flags)[3]):  # no witness (an Account field tag op2row has no proof type for): refused
+            if run:
+                with pytest.raises(EngineError, match="State witness assignment"):
+                    fused(vr, vf, device)
+            refused += 1
+            continue
+        if run:
+            check_case(vr, vf, device)
+        sites |= {c & 0xFFFFFF for c in oracle_statuses(vr, vf) if c}
+        n += 1
+    assert n >= 2 * 13 and refused <= 4, (n, refused)
+    return sorted(sites)
+
+
+def run_directed(device, tag):
+    assert directed_census(tag, device, run=True) == FUSED_REACHED[tag]
+
+
+@pytest.mark.parametrize("tag", DIRECTED_TAGS)
+def test_cpu_backend_fused_directed_rw_cases(tag):
+    run_directed("cpu", tag)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("tag", DIRECTED_TAGS)
+def test_gpu_fused_directed_rw_cases(tag):
+    run_directed(None, tag)
+
+
+def test_directed_rw_base_is_a_valid_witness():
+    rows, flags = directed_rw_base()
+    assert not any(oracle_statuses(rows, flags))
+    assert {k[0] for k, _ in _state_keys(rows, flags)} == set(DIRECTED_TAGS)
