@@ -754,6 +754,56 @@ int zk_pi_assign_open(const zk_pi_inputs* in, const zk_pi_wire* out_dev, uint32_
 int zk_pi_assign_read(zk_session* s, const zk_pi_wire* host);
 int zk_pi_assign(const zk_pi_inputs* in, const zk_pi_wire* out, uint32_t opts, zk_result* result);
 
+/* ---- Sig circuit witness assignment: from signed data (msg_hash, v, r, s) to the Sig circuit's witness — what the reference's
+ *      tests build in signedData2witness (tests/test_sig_circuit.py:40-67) — and, from the same key recovery, the EVM circuit's sig
+ *      table and the aux cells of the ecRecover precompile (tests/evm/precompiles/test_ecRecover.py:78-112).
+ *      Inputs (zk_sig_inputs): fields uint64[n][4][4], per signature the 256-bit words msg_hash (the word of the hash's 32 bytes,
+ *      little-endian: Word(msg_hash_bytes); z is the same bytes read big-endian), sig_v, sig_r, sig_s; addr (nullable) the CLAIMED
+ *      address per signature; expect_valid (nullable); v_offset: 0 where v is the parity (SignedData), 27 where it is the
+ *      precompile's input word; randomness: one cell (keccak_randomness).
+ *      Status per signature: 0, or (ZK_KIND_UNSUPPORTED << 24) | site as zk_tx_assign's key recovery — site 1 the parity
+ *      v - v_offset outside {0, 1} (a v above 2^64 included) or r / s outside (0, N), site 3 no curve point with x = r, site 4 Q at
+ *      infinity.
+ *      Outputs (zk_sig_wire), n rows each unless said otherwise:
+ *        bytes uint8[n][9][32], cells column-major uint64[8][n][4], meta uint32[n][4]: the units in zk_sign_units' Sig layout.
+ *          Byte rows: key x, y, x, y (little-endian), the hash's 32 bytes twice, keccak256(x BE || y BE), r, s (little-endian).
+ *          Cells: the claimed address (addr null: the recovered one), msg_hash lo, hi, FQ(v.lo) - FQ(v_offset) (the parity), r lo, hi,
+ *          s lo, hi.  Meta: (0xffffffff pending, expect_valid or 1, 0, v - v_offset — 0xffffffff where that does not fit 32 bits), ready
+ *          for zk_ecdsa_open (layout 2, v = meta + 3 with stride 4, out_dev = meta, out_stride 4);
+ *        keccak uint64[n + 1 capacity][5][4]: KeccakTable.add's row of every recovered key, as a set, sorted, without duplicates, the
+ *          all-zero row included (flatten_keccak_tuples); their number in n_keccak;
+ *        sig_table uint64[n capacity][9][4]: (msg_hash lo, hi, FQ(v.lo) - FQ(v_offset), r lo, hi, s lo, hi, recovered_addr, is_valid)
+ *          per signature — the recovered address (never the claimed one) and 1, or 0 and 0 — the first occurrence of every distinct
+ *          row, in input order; their number in n_sig_rows (zk_evm_tables.sig / n_sig);
+ *        aux uint64[n][12][4], row i for signature i (zk_evm_tables.aux, kind 5): msg_hash, v as given, r, s as lo / hi, the recovered
+ *          address, input_rlc (Horner over msg_hash || v || r || s, each 32 bytes as in `fields`, first byte highest power),
+ *          output_rlc (the same over the address's 32 little-endian bytes), randomness.
+ *      A signature whose status is not 0 has defined outputs: key rows and key hash zero, the rest of its unit as given, cell 0 the
+ *      claimed address or 0, no keccak row, recovered address / is_valid / output_rlc 0.
+ *      The session protocol is zk_tx_assign's: zk_sig_assign_open with ZK_OPT_DEVICE_PTRS takes device inputs and writes the non-null
+ *      pointers of `out_dev` in place (null ones: the session owns the buffer); zk_launch (status_dev: uint32[n]) / zk_collect
+ *      (tally over the signatures) / zk_read_status; zk_sig_assign_read copies the last pass's outputs to the non-null HOST pointers
+ *      of `host` and the two row counts out (each nullable). */
+typedef struct zk_sig_inputs {
+    const uint64_t* fields;        /* uint64[n][4][4]: msg_hash, sig_v, sig_r, sig_s as 256-bit words */
+    const uint64_t* addr;          /* nullable uint64[n][4]: the CLAIMED address -> cells[0]; NULL: the recovered one */
+    const uint32_t* expect_valid;  /* nullable uint32[n] -> meta[:, 1]; NULL: 1 */
+    uint64_t n;
+    uint32_t v_offset;             /* 0: v is the parity (SignedData); 27: v is the precompile's input word */
+    uint32_t reserved;
+    const uint64_t* randomness;    /* one cell: keccak_randomness */
+} zk_sig_inputs;
+typedef struct zk_sig_wire {
+    uint8_t* bytes; uint64_t* cells; uint32_t* meta;   /* the units, zk_sign_units' Sig layout */
+    uint64_t* keccak;                                  /* capacity n + 1 rows */
+    uint64_t* sig_table;                               /* uint64[n capacity][9][4] */
+    uint64_t* aux;                                     /* uint64[n][12][4], aux kind 5, input order */
+} zk_sig_wire;
+int zk_sig_assign_open(const zk_sig_inputs* in, const zk_sig_wire* out_dev, uint32_t opts, zk_session** out);
+int zk_sig_assign_read(zk_session* s, const zk_sig_wire* host, uint64_t* n_keccak_out, uint64_t* n_sig_rows_out);
+int zk_sig_assign(const zk_sig_inputs* in, const zk_sig_wire* out, uint32_t opts, uint32_t* status_out,
+                  uint64_t* n_keccak_out, uint64_t* n_sig_rows_out, zk_result* result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,7 @@
 rows/s and algorithmic GB/s (SURVEY.md §8d bytes per unit), device-resident inputs, HIP-event kernel
 time.  bench.py carries the headline EVM / State workloads; this is the side table in DESIGN.md §3.
 `bench_row_kernels.py ecc` runs only the ECC legs (one-shot, then the resident session), `bench_row_kernels.py withdrawal` only the Withdrawal leg, `bench_row_kernels.py
-tx_assign` only the Tx witness-assignment leg, `bench_row_kernels.py exp_assign` only the Exp witness-assignment leg,
+tx_assign` only the Tx witness-assignment leg, `bench_row_kernels.py sig_assign` only the Sig witness-assignment leg, `bench_row_kernels.py exp_assign` only the Exp witness-assignment leg,
 `bench_row_kernels.py pi_assign` only the PI witness-assignment leg."""
 import json
 import os
@@ -160,6 +160,40 @@ def tx_assign_leg():
             out[name]["calldata_bytes"] = int(t["offsets"][-1])
 
 
+def sig_assign_leg():
+    """Sig circuit witness assignment (zk_sig_assign_open, inputs in HBM; kernel_ms = HIP-event span of a pass: key recovery, units,
+    keccak set, sig table, aux rows) at 2^11, 2^14 and 2^17 signatures — random (r, s) with a curve point, as the Tx leg's.  Then, in
+    the same process, five alternating rounds of the 2^14 pass and the Tx assignment's 2^14 short-calldata pass (10 passes each after
+    a warm-up): the Sig pass does strictly less work, so its median must not exceed the Tx pass's by more than the Tx pass's own
+    spread over the rounds."""
+    from tests.sig_assign_cases import random_curve_point_inputs
+    from tests.tx_assign_cases import random_inputs
+
+    rk = 0x5EED % P
+    dev = lambda d, keys: {k: (to_dev(np.ascontiguousarray(v)) if k in keys and v is not None else v) for k, v in d.items()}  # noqa: E731
+    for n in (1 << 11, 1 << 14, 1 << 17):
+        sg = random_curve_point_inputs(n, 3)
+        run(f"sig_assign_{n}", engine.open_sig_assign(dev(sg, engine.SIG_ASSIGN_INPUTS), rk), n, 4 * 32)
+    n = 1 << 14
+    sg, tx = random_curve_point_inputs(n, 3), random_inputs(n, 3, chain_id=1, long_every=0, signed=False)
+    ms = {"sig_assign": [], "tx_assign": []}
+    with engine.open_sig_assign(dev(sg, engine.SIG_ASSIGN_INPUTS), rk) as ss, engine.open_tx_assign(dev(tx, engine.TX_ASSIGN_INPUTS), rk) as ts:
+        for rnd in range(6):
+            for name, s in (("sig_assign", ss), ("tx_assign", ts)):
+                for _ in range(10):
+                    s.launch()
+                r = s.collect()
+                assert r.ok, (name, r)
+                if rnd:  # round 0 warms up
+                    ms[name].append(round(r.kernel_ms, 4))
+    med = {k: sorted(v)[len(v) // 2] for k, v in ms.items()}
+    spread = max(ms["tx_assign"]) - min(ms["tx_assign"])
+    out["sig_vs_tx_assign_16384"] = {"sig_assign_kernel_ms": ms["sig_assign"], "tx_assign_kernel_ms": ms["tx_assign"], "sig_median_ms": med["sig_assign"],
+                                     "tx_median_ms": med["tx_assign"], "tx_spread_ms": round(spread, 4),
+                                     "sig_not_slower": bool(med["sig_assign"] <= med["tx_assign"] + spread)}
+    print("sig_vs_tx_assign_16384", out["sig_vs_tx_assign_16384"], flush=True)
+
+
 def exp_assign_leg():
     """Exp circuit witness assignment (zk_exp_assign_open, events in HBM; kernel_ms = HIP-event span of a pass: power chain + expansion,
     best-of-run mean of 20 passes after 3) at 2^12 events x 256-bit exponents and 2^16 events x 16-bit exponents; bytes per row = the 21
@@ -235,6 +269,10 @@ if sys.argv[1:] == ["pi_assign"]:
     sys.exit(0)
 if sys.argv[1:] == ["exp_assign"]:
     exp_assign_leg()
+    print(json.dumps(out))
+    sys.exit(0)
+if sys.argv[1:] == ["sig_assign"]:
+    sig_assign_leg()
     print(json.dumps(out))
     sys.exit(0)
 if sys.argv[1:] == ["tx_assign"]:

@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = [
     "zk_tx_assign_open", "zk_tx_assign_read", "zk_tx_assign",
     "zk_exp_assign_sizes", "zk_exp_assign_open", "zk_exp_assign_read", "zk_exp_assign", "zk_exp_assign_counts",
     "zk_pi_assign_sizes", "zk_pi_assign_open", "zk_pi_assign_read", "zk_pi_assign",
+    "zk_sig_assign_open", "zk_sig_assign_read", "zk_sig_assign",
 ]
 
 OPT_DEVICE_PTRS = 1
@@ -104,6 +105,15 @@ class ZkTxInputs(ctypes.Structure):
 class ZkTxWire(ctypes.Structure):
     _fields_ = [("tx_rows", ctypes.c_void_p), ("tx_flags", ctypes.c_void_p), ("bytes", ctypes.c_void_p), ("cells", ctypes.c_void_p),
                 ("meta", ctypes.c_void_p), ("keccak", ctypes.c_void_p)]
+
+
+class ZkSigInputs(ctypes.Structure):
+    _fields_ = [("fields", ctypes.c_void_p), ("addr", ctypes.c_void_p), ("expect_valid", ctypes.c_void_p), ("n", ctypes.c_uint64),
+                ("v_offset", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("randomness", ctypes.c_void_p)]
+
+
+class ZkSigWire(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("bytes", "cells", "meta", "keccak", "sig_table", "aux")]
 
 
 class ZkEcdsaBatch(ctypes.Structure):
@@ -286,6 +296,10 @@ def _bind(lib):
     lib.zk_pi_assign_open.argtypes = [ctypes.POINTER(ZkPiInputs), ctypes.POINTER(ZkPiWire), u32, ctypes.POINTER(vp)]
     lib.zk_pi_assign_read.argtypes = [vp, ctypes.POINTER(ZkPiWire)]
     lib.zk_pi_assign.argtypes = [ctypes.POINTER(ZkPiInputs), ctypes.POINTER(ZkPiWire), u32, ctypes.POINTER(ZkResult)]
+    lib.zk_sig_assign_open.argtypes = [ctypes.POINTER(ZkSigInputs), ctypes.POINTER(ZkSigWire), u32, ctypes.POINTER(vp)]
+    lib.zk_sig_assign_read.argtypes = [vp, ctypes.POINTER(ZkSigWire), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_sig_assign.argtypes = [ctypes.POINTER(ZkSigInputs), ctypes.POINTER(ZkSigWire), u32, vp, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                  ctypes.POINTER(ZkResult)]
     lib.zk_launch.argtypes = [vp, vp]
     lib.zk_collect.argtypes = [vp, ctypes.POINTER(ZkResult)]
     lib.zk_read_status.argtypes = [vp, vp]

@@ -35,6 +35,7 @@
 #include "ecc_circuit.hpp"
 #include "withdrawal_circuit.hpp"
 #include "tx_assign.hpp"
+#include "sig_assign.hpp"
 #include "exp_assign.hpp"
 #include "pi_assign.hpp"
 
@@ -99,7 +100,7 @@ struct zk_session {
     std::vector<u64> w64[4];              // assignment sessions: work / output buffers
     std::vector<u32> out32;
     void (*pass)(zk_session*) = nullptr;  // assignment sessions: one pass computes the outputs and fills `status`
-    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 6 exp, 7 PI, 8 ECC
+    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig
     u64 n_ops = 0;                        // RW -> State ops: 1 + kept rows
     std::vector<u32> rekey_plan;          // RW -> State ops: the RwkHostPlan's plan (as words) ...
     std::vector<u32> rekey_jobs;          // ... and its rank jobs (cls, field, base, count)
@@ -124,6 +125,10 @@ struct zk_session {
     EcdsaArgs ecdsa;
     KeccakGenArgs kgen;
     TxAssignArgs txa;
+    SigAssignArgs sga;
+    std::vector<u64> sga64[8];      // Sig assignment: fields, addr, rpow, pk, cells, keccak candidates / table, sig candidates / table, aux
+    std::vector<u32> sga32[3];      // expect_valid, meta, the signatures' status
+    u64 n_sig_rows = 0;
     ExaArgs exa;
     ExaSizes exa_sizes;
     PiaArgs pia;
@@ -1669,6 +1674,118 @@ extern "C" int zk_tx_assign(const zk_tx_inputs* in, const zk_tx_wire* out, uint3
     if (!rc) rc = zk_collect(s, result);
     if (!rc && status_out) rc = zk_read_status(s, status_out);
     if (!rc) rc = zk_tx_assign_read(s, out, n_keccak_out);
+    zk_close(s);
+    return rc;
+}
+
+// ---- Sig circuit witness assignment (sig_assign.hpp): the device functions in host loops; recovery in the one-lane form
+static void sig_assign_pass(zk_session* s) {
+    SigAssignArgs& a = s->sga;
+    const long long n = (long long)a.n;
+#pragma omp parallel for schedule(dynamic, 16)
+    for (long long i = 0; i < n; i++) {
+        u32 tab[15 * 24];
+        EcdsaPrep pr;
+        Fr u1, u2;
+        const u32 st = sig_recover_prepare(a, (u64)i, pr, u1, u2);
+        u32 code;
+        if (st == ECDSA_PENDING) code = tx_recover_finish_to(a.pk + i * 8, ecdsa_partial(pr, 0, 1, tab, 1, nullptr));
+        else if (st == TX_RECOVER_EXACT) code = tx_recover_finish_to(a.pk + i * 8, tx_recover_exact(pr, u1, u2));
+        else { code = st; tx_recover_fail_to(a.pk + i * 8); }
+        a.status[i] = code;
+    }
+    memcpy(s->status.data(), a.status, (size_t)a.n * sizeof(u32));
+#pragma omp parallel for schedule(dynamic, 64)
+    for (long long i = 0; i < n; i++) sig_write_unit(a, (u64)i);
+    sig_write_zero_candidate(a);
+    // the keccak table as a sorted set
+    std::vector<u64> idx((size_t)a.n + 1);
+    for (u64 k = 0; k <= a.n; k++) idx[k] = k;
+    const u64* kc = a.kcand;
+    std::sort(idx.begin(), idx.end(), [kc](u64 x, u64 y) { return tx_krow_cmp(kc + x * 20, kc + y * 20) < 0; });
+    u64 m = 0;
+    for (u64 k = 0; k <= a.n; k++) {
+        if (m && tx_krow_cmp(a.keccak + (m - 1) * 20, kc + idx[k] * 20) == 0) continue;
+        memcpy(a.keccak + m * 20, kc + idx[k] * 20, 160);
+        m++;
+    }
+    s->n_keccak = m;
+    // the sig table: first occurrences in input order (equal rows are adjacent once sorted by (row, index))
+    const u64* sc = a.scand;
+    idx.resize((size_t)a.n);
+    for (u64 k = 0; k < a.n; k++) idx[k] = k;
+    std::sort(idx.begin(), idx.end(), [sc](u64 x, u64 y) {
+        const int c = memcmp(sc + x * SIG_TABLE_WORDS, sc + y * SIG_TABLE_WORDS, SIG_TABLE_WORDS * 8);
+        return c ? c < 0 : x < y;
+    });
+    for (u64 k = 0; k < a.n; k++) a.sdup[idx[k]] = k && sig_row_eq(sc + idx[k - 1] * SIG_TABLE_WORDS, sc + idx[k] * SIG_TABLE_WORDS);
+    m = 0;
+    for (u64 k = 0; k < a.n; k++)
+        if (!a.sdup[k]) memcpy(a.sig_table + m++ * SIG_TABLE_WORDS, sc + k * SIG_TABLE_WORDS, SIG_TABLE_WORDS * 8);
+    s->n_sig_rows = m;
+}
+extern "C" int zk_sig_assign_open(const zk_sig_inputs* in, const zk_sig_wire* out_dev, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_sig_assign_open");
+    ARG_TRY(in && out && !out_dev && in->randomness && (in->n == 0 || in->fields) && in->n < (1ull << 31), "zk_sig_assign_open: bad arguments");
+    const u64 n = in->n;
+    zk_session* s = new_session(n, false);
+    if (n) s->sga64[0].assign(in->fields, in->fields + n * SIG_NFIELDS * 4);
+    if (n && in->addr) s->sga64[1].assign(in->addr, in->addr + n * 4);
+    if (n && in->expect_valid) s->sga32[0].assign(in->expect_valid, in->expect_valid + n);
+    s->sga64[2].assign(KT_RPOW_ROWS * 4, 0);
+    kt_fill_rpow(cell_of(in->randomness), s->sga64[2].data());
+    s->sga64[3].assign((size_t)(n + 1) * 8, 0);                                        // pk
+    s->sga32[2].assign((size_t)n + 1, 0);                                              // status
+    s->a8b.assign((size_t)n * TX_UNIT_BYTES + 32, 0);
+    s->sga64[4].assign((size_t)n * TX_UNIT_CELLS * 4 + 4, 0);
+    s->sga32[1].assign((size_t)n * 4 + 4, 0);
+    s->sga64[5].assign((size_t)(n + 1) * KT_NCELLS * 4 * 2, 0);                        // keccak candidates, then the table
+    s->sga64[6].assign((size_t)(n + 1) * SIG_TABLE_WORDS * 2, 0);                      // sig candidates, then the table
+    s->sga64[7].assign((size_t)n * SIG_AUX_CELLS * 4 + 4, 0);
+    s->a32[0].assign((size_t)n + 1, 0);                                                // sdup
+    SigAssignArgs& a = s->sga;
+    memset(&a, 0, sizeof(a));
+    a.fields = s->sga64[0].data();
+    a.addr = (n && in->addr) ? s->sga64[1].data() : nullptr;
+    a.expect_valid = (n && in->expect_valid) ? s->sga32[0].data() : nullptr;
+    a.n = n; a.v_offset = in->v_offset;
+    memcpy(a.rand, in->randomness, 32);
+    a.rpow = s->sga64[2].data(); a.pk = s->sga64[3].data(); a.status = s->sga32[2].data();
+    a.bytes = s->a8b.data(); a.cells = s->sga64[4].data(); a.meta = s->sga32[1].data();
+    a.kcand = s->sga64[5].data(); a.keccak = a.kcand + (n + 1) * KT_NCELLS * 4;
+    a.scand = s->sga64[6].data(); a.sig_table = a.scand + (n + 1) * SIG_TABLE_WORDS; a.sdup = s->a32[0].data();
+    a.aux = s->sga64[7].data();
+    a.lanes_per_sig = 1;
+    s->pass = sig_assign_pass;
+    s->assign_kind = 9;
+    *out = s;
+    return 0;
+}
+extern "C" int zk_sig_assign_read(zk_session* s, const zk_sig_wire* host, uint64_t* n_keccak_out, uint64_t* n_sig_rows_out) {
+    ARG_TRY(s && s->assign_kind == 9, "zk_sig_assign_read: bad arguments");
+    const SigAssignArgs& a = s->sga;
+    if (host) {
+        if (host->bytes) memcpy(host->bytes, a.bytes, (size_t)a.n * TX_UNIT_BYTES);
+        if (host->cells) memcpy(host->cells, a.cells, (size_t)a.n * TX_UNIT_CELLS * 32);
+        if (host->meta) memcpy(host->meta, a.meta, (size_t)a.n * 16);
+        if (host->keccak) memcpy(host->keccak, a.keccak, (size_t)s->n_keccak * KT_NCELLS * 32);
+        if (host->sig_table) memcpy(host->sig_table, a.sig_table, (size_t)s->n_sig_rows * SIG_TABLE_CELLS * 32);
+        if (host->aux) memcpy(host->aux, a.aux, (size_t)a.n * SIG_AUX_CELLS * 32);
+    }
+    if (n_keccak_out) *n_keccak_out = s->n_keccak;
+    if (n_sig_rows_out) *n_sig_rows_out = s->n_sig_rows;
+    return 0;
+}
+extern "C" int zk_sig_assign(const zk_sig_inputs* in, const zk_sig_wire* out, uint32_t opts, uint32_t* status_out, uint64_t* n_keccak_out,
+                             uint64_t* n_sig_rows_out, zk_result* result) {
+    ARG_TRY(result && out, "zk_sig_assign: null output");
+    zk_session* s = nullptr;
+    int rc = zk_sig_assign_open(in, nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && status_out) rc = zk_read_status(s, status_out);
+    if (!rc) rc = zk_sig_assign_read(s, out, n_keccak_out, n_sig_rows_out);
     zk_close(s);
     return rc;
 }

@@ -19,6 +19,7 @@
 #include "ecc_circuit.hpp"
 #include "withdrawal_circuit.hpp"
 #include "tx_assign.hpp"
+#include "sig_assign.hpp"
 #include "exp_assign.hpp"
 #include "pi_assign.hpp"
 
@@ -90,6 +91,8 @@ void zk_launch_withdrawal_rows(hipStream_t st, const WithdrawalArgs& a, u64 lo, 
 void zk_launch_withdrawal_assign(hipStream_t st, const WithdrawalArgs& a);
 // Tx circuit witness assignment (k_tx_assign.hip): sign hashes, key recovery (status / tally per tx), rows, units, keccak set
 void zk_launch_tx_assign(hipStream_t st, const TxAssignArgs& a, u32* status, ZkTally* tally);
+// Sig circuit witness assignment (k_sig_assign.hip): key recovery (status / tally per signature), units, keccak set, sig table, aux rows
+void zk_launch_sig_assign(hipStream_t st, const SigAssignArgs& a, u32* status, ZkTally* tally);
 // Exp circuit witness assignment (k_exp_assign.hip): the open's counts / first rows / reject word, then chain + rows per pass
 void zk_launch_exp_assign_sizes(hipStream_t st, const ExaArgs& a);
 void zk_launch_exp_assign(hipStream_t st, const ExaArgs& a, u32* status, ZkTally* tally);

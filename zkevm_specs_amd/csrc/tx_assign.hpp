@@ -60,6 +60,15 @@ struct TxAssignArgs {
 
 ZK_HD u64 tx_limb64(const Fr& x, int q) { return (u64)x.v[2 * q] | ((u64)x.v[2 * q + 1] << 32); }
 ZK_HD Fr tx_from_limbs(const u64* p) { return fr_load(p); }
+ZK_HD Fr tx_bswap256(const Fr& x) {  // the 32 bytes of x in reverse order
+    Fr r;
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const u64 w = kt_bswap64(tx_limb64(x, 3 - q));
+        r.v[2 * q] = (u32)w; r.v[2 * q + 1] = (u32)(w >> 32);
+    }
+    return r;
+}
 ZK_HD Fr tx_mod_fr(Fr x) {  // a 256-bit integer mod the BN254 scalar field (FQ(x))
     const Fr p = fr_modulus();
 #pragma unroll
@@ -269,14 +278,12 @@ ZK_NOINLINE Fr sp_inv_p(Fr a) {
 // Validation, the lift of R and the two scalars.  ECDSA_PENDING: `pr` is ready for ecdsa_partial / ecdsa_partial4 (R in pr.qx / qy,
 // the GLV halves of u2 = s / r, the halves of u1 = -z / r); TX_RECOVER_EXACT: the plain chains over u1 / u2 (tx_recover_exact);
 // anything else is the tx's status.
-ZK_HD u32 tx_recover_prepare(const TxAssignArgs& a, u64 i, EcdsaPrep& pr, Fr& u1, Fr& u2) {
-    const u64* f = a.fields + i * (TX_NFIELDS * 4);
-    const Fr v = fr_load(f + 20), r = fr_load(f + 24), s = fr_load(f + 28);
-    Fr c2, par;
-    const Fr c = fr_from_u64(a.chain_id);
-    u256_add(c2, c, c);
-    u256_add(c2, c2, fr_from_u64(35));  // < 2^66
-    const u32 bw = u256_sub(par, v, c2);
+// (the core over the signature's words: `v_base` is what v exceeds by the parity, `hash` the message hash as a 256-bit integer —
+// HASH_BYTES: as the word of its 32 bytes instead, which the core reads big-endian; sig_assign.hpp recovers through it too)
+template <bool HASH_BYTES>
+ZK_HD u32 tx_recover_prepare_vrs(const Fr& v, const Fr& v_base, const Fr& r, const Fr& s, const u64* hash, EcdsaPrep& pr, Fr& u1, Fr& u2) {
+    Fr par;
+    const u32 bw = u256_sub(par, v, v_base);
     if (bw || !fr_fits32(par) || par.v[0] > 1u) return TX_BAD_SIGNATURE;
     const Fr n = SecpN::mod();
     if (!fr_lt(r, n) || !fr_lt(s, n) || fr_is_zero(r) || fr_is_zero(s)) return TX_BAD_SIGNATURE;
@@ -286,7 +293,7 @@ ZK_HD u32 tx_recover_prepare(const TxAssignArgs& a, u64 i, EcdsaPrep& pr, Fr& u1
     Fr y = sp_sqrt_p(y2);
     if (!fr_eq(spf_sqr(y), y2)) return TX_NO_CURVE_POINT;
     if ((y.v[0] & 1u) != par.v[0]) y = spf_sub(fr_zero(), y);  // (y != 0: the group order is odd)
-    const Fr z = sp_reduce_once<SecpN>(fr_load(a.hash + i * 4));
+    const Fr z = sp_reduce_once<SecpN>(HASH_BYTES ? tx_bswap256(fr_load(hash)) : fr_load(hash));
     const Fr rinvM = sp_to_mont<SecpN>(sp_inv_n_safegcd(r));
     u2 = sp_mont<SecpN>(s, rinvM);
     u1 = sp_sub<SecpN>(fr_zero(), sp_mont<SecpN>(z, rinvM));
@@ -299,6 +306,15 @@ ZK_HD u32 tx_recover_prepare(const TxAssignArgs& a, u64 i, EcdsaPrep& pr, Fr& u1
     }
     return TX_RECOVER_EXACT;
 }
+ZK_HD u32 tx_recover_prepare(const TxAssignArgs& a, u64 i, EcdsaPrep& pr, Fr& u1, Fr& u2) {
+    const u64* f = a.fields + i * (TX_NFIELDS * 4);
+    const Fr v = fr_load(f + 20), r = fr_load(f + 24), s = fr_load(f + 28);
+    Fr c2;
+    const Fr c = fr_from_u64(a.chain_id);
+    u256_add(c2, c, c);
+    u256_add(c2, c2, fr_from_u64(35));  // < 2^66
+    return tx_recover_prepare_vrs<false>(v, c2, r, s, a.hash + i * 4, pr, u1, u2);
+}
 ZK_HD SpPoint tx_recover_exact(const EcdsaPrep& pr, const Fr& u1, const Fr& u2) {
     SpPoint R;
     R.X = pr.qx; R.Y = pr.qy; R.Z = SecpP::one();
@@ -306,9 +322,8 @@ ZK_HD SpPoint tx_recover_exact(const EcdsaPrep& pr, const Fr& u1, const Fr& u2) 
     sp_add_ip(C, sp_scalar_mul(R, u2));
     return C;
 }
-// Q (Jacobian) -> affine into a.pk; the tx's status
-ZK_HD u32 tx_recover_finish(const TxAssignArgs& a, u64 i, const SpPoint& C) {
-    u64* out = a.pk + i * 8;
+// Q (Jacobian) -> affine into out[8] (x, y); the signature's status
+ZK_HD u32 tx_recover_finish_to(u64* out, const SpPoint& C) {
     if (fr_is_zero(C.Y) || fr_is_zero(C.Z)) {
 #pragma unroll
         for (int q = 0; q < 8; q++) out[q] = 0;
@@ -320,10 +335,12 @@ ZK_HD u32 tx_recover_finish(const TxAssignArgs& a, u64 i, const SpPoint& C) {
     kt_store(out + 4, y);
     return 0;
 }
-ZK_HD void tx_recover_fail(const TxAssignArgs& a, u64 i) {
+ZK_HD u32 tx_recover_finish(const TxAssignArgs& a, u64 i, const SpPoint& C) { return tx_recover_finish_to(a.pk + i * 8, C); }
+ZK_HD void tx_recover_fail_to(u64* out) {
 #pragma unroll
-    for (int q = 0; q < 8; q++) a.pk[i * 8 + q] = 0;
+    for (int q = 0; q < 8; q++) out[q] = 0;
 }
+ZK_HD void tx_recover_fail(const TxAssignArgs& a, u64 i) { tx_recover_fail_to(a.pk + i * 8); }
 
 // ---- stage 3: rows, units, keccak rows -------------------------------------------------------------------------------------
 ZK_HD void tx_put_row(u64* row, u64 tx_id, u64 tag, u64 index, const Fr& lo, const Fr& hi) {

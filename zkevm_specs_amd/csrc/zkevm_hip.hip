@@ -583,7 +583,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -616,6 +616,7 @@ struct zk_session {
     PiCopyArgs picopy;
     WithdrawalArgs withdrawal;
     TxAssignArgs txa;
+    SigAssignArgs sga;
     ExaArgs exa;
     u64 exa_n_table = 0;
     EccPairArgs ecc;                // SESSION_ECC (with the per-pair records) / SESSION_ECC_ASSIGN (ecc.a alone)
@@ -2773,6 +2774,7 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     }
     case SESSION_ECC_ASSIGN: zk_launch_ecc(s->stream, s->ecc.a, true, nullptr, s->d_tally); break;
     case SESSION_TXA: zk_launch_tx_assign(s->stream, s->txa, status, s->d_tally); break;
+    case SESSION_SGA: zk_launch_sig_assign(s->stream, s->sga, status, s->d_tally); break;
     case SESSION_PICOPY: zk_launch_pi_copy(s->stream, s->picopy, status, tally); break;
     case SESSION_CPA: zk_launch_copy_assign(s->stream, s->cpa, status, s->d_tally); break;
     case SESSION_EXA: zk_launch_exp_assign(s->stream, s->exa, status, s->d_tally); break;
@@ -3998,6 +4000,136 @@ extern "C" int zk_tx_assign(const zk_tx_inputs* in, const zk_tx_wire* out, uint3
     if (!rc) rc = zk_collect(s, result);
     if (!rc && !dev && status_out) rc = zk_read_status(s, status_out);
     if (!rc) rc = zk_tx_assign_read(s, dev ? nullptr : out, n_keccak_out);
+    zk_close(s);
+    return rc;
+}
+
+// ---- Sig circuit witness assignment (sig_assign.hpp, k_sig_assign.hip)
+extern "C" int zk_sig_assign_open(const zk_sig_inputs* in, const zk_sig_wire* out_dev, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_sig_assign_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(in && out && in->randomness && (in->n == 0 || in->fields) && in->n < (1ull << 31), "zk_sig_assign_open: bad arguments");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    ARG_TRY(dev || !out_dev, "zk_sig_assign_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    const u64 n = in->n;
+    zk_session* s = new zk_session();
+    s->kind = SESSION_SGA;
+    s->n = n;
+    SigAssignArgs& a = s->sga;
+    memset(&a, 0, sizeof(a));
+    int rc = 0;
+    const void* p = nullptr;
+    Fr r;
+    if (dev) {
+        if (fetch_small(s->stream, a.rand, in->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
+    } else {
+        memcpy(a.rand, in->randomness, 32);
+    }
+    for (int k = 0; k < 4; k++) { r.v[2 * k] = (u32)a.rand[k]; r.v[2 * k + 1] = (u32)(a.rand[k] >> 32); }
+    {   // the fixed-base table of G, as zk_ecdsa_open
+        std::lock_guard<std::mutex> lock(g_dev_mutex);
+        if (!g_secp_comb[s->device]) {
+            u32* tab = nullptr;
+            if (hipMalloc(&tab, (size_t)ECDSA_COMB_ENTRIES * 16 * sizeof(u32)) != hipSuccess) { rc = -2; g_err = "zk_sig_assign_open: table allocation failed"; goto fail; }
+            zk_launch_ecdsa_comb_build(s->stream, tab);
+            if (hipStreamSynchronize(s->stream) != hipSuccess) { (void)hipFree(tab); rc = -2; g_err = "zk_sig_assign_open: table build failed"; goto fail; }
+            g_secp_comb[s->device] = tab;
+        }
+        a.gcomb = g_secp_comb[s->device];
+    }
+    if ((rc = stage(s, in->fields, (size_t)n * SIG_NFIELDS * 32, dev, &p))) goto fail;
+    a.fields = (const u64*)p;
+    if (in->addr && n) {
+        if ((rc = stage(s, in->addr, (size_t)n * 32, dev, &p))) goto fail;
+        a.addr = (const u64*)p;
+    }
+    if (in->expect_valid && n) {
+        if ((rc = stage(s, in->expect_valid, (size_t)n * 4, dev, &p))) goto fail;
+        a.expect_valid = (const u32*)p;
+    }
+    a.n = n; a.v_offset = in->v_offset;
+    {
+        u64* d_rpow = nullptr;
+        void* d = nullptr;
+        if ((rc = dev_alloc(s, (void**)&d_rpow, KT_RPOW_ROWS * 4 * sizeof(u64)))) goto fail;
+        zk_launch_keccak_rpow(s->stream, r, d_rpow);
+        a.rpow = d_rpow;
+        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 64))) goto fail;
+        a.pk = (u64*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 4))) goto fail;
+        a.status = (u32*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * KT_NCELLS * 32))) goto fail;
+        a.kcand = (u64*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 4))) goto fail;
+        a.kfirst = (u32*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * SIG_TABLE_CELLS * 32))) goto fail;
+        a.scand = (u64*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 4))) goto fail;
+        a.sdup = (u32*)d;
+        if ((rc = dev_alloc(s, &d, 64))) goto fail;
+        a.n_keccak = (u32*)d;
+        a.n_sig_rows = (u32*)d + 1;
+        if (hipMemsetAsync(d, 0, 64, s->stream) != hipSuccess) { rc = -2; g_err = "zk_sig_assign_open: counter reset failed"; goto fail; }  // (a read before any pass: no rows)
+    }
+    // lane forms as zk_ecdsa_open (ZK_ECDSA_LANES overrides here too)
+    a.lanes_per_sig = n <= (1ull << 14) ? 4u : n <= (1ull << 16) ? 2u : 1u;
+    if (const char* e = getenv("ZK_ECDSA_LANES")) { const int v = atoi(e); a.lanes_per_sig = v == 4 ? 4u : v == 2 ? 2u : 1u; }
+    a.qtab_lanes = ((n * a.lanes_per_sig + 63) / 64) * 64;
+    if (a.qtab_lanes == 0) a.qtab_lanes = 64;
+    if (a.qtab_lanes > ZK_ECDSA_CHUNK_LANES) a.qtab_lanes = ZK_ECDSA_CHUNK_LANES;
+    if ((rc = dev_alloc(s, (void**)&a.qtab, (size_t)a.qtab_lanes * 15 * 24 * sizeof(u32)))) goto fail;
+    {
+        const zk_sig_wire* o = out_dev;
+        void* d = nullptr;
+#define SGA_OUT(field, type, bytes)                                                       \
+        if (o && o->field) a.field = (type)o->field;                                      \
+        else { if ((rc = dev_alloc(s, &d, (size_t)(bytes)))) goto fail; a.field = (type)d; }
+        SGA_OUT(bytes, uint8_t*, n * TX_UNIT_BYTES + 32)
+        SGA_OUT(cells, u64*, n * TX_UNIT_CELLS * 32 + 32)
+        SGA_OUT(meta, u32*, n * 16 + 16)
+        SGA_OUT(keccak, u64*, (n + 1) * KT_NCELLS * 32)
+        SGA_OUT(sig_table, u64*, n * SIG_TABLE_CELLS * 32 + 32)
+        SGA_OUT(aux, u64*, n * SIG_AUX_CELLS * 32 + 32)
+#undef SGA_OUT
+    }
+    if ((rc = session_common_init(s))) goto fail;
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_sig_assign_read(zk_session* s, const zk_sig_wire* host, uint64_t* n_keccak_out, uint64_t* n_sig_rows_out) {
+    ARG_TRY(s && s->kind == SESSION_SGA, "zk_sig_assign_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    const SigAssignArgs& a = s->sga;
+    u32 cnt[2] = {0, 0};  // n_keccak, n_sig_rows: adjacent words
+    HIP_TRY(hipMemcpyAsync(cnt, a.n_keccak, 8, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (host) {
+        if (host->bytes) HIP_TRY(hipMemcpyAsync(host->bytes, a.bytes, (size_t)a.n * TX_UNIT_BYTES, hipMemcpyDeviceToHost, s->stream));
+        if (host->cells) HIP_TRY(hipMemcpyAsync(host->cells, a.cells, (size_t)a.n * TX_UNIT_CELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        if (host->meta) HIP_TRY(hipMemcpyAsync(host->meta, a.meta, (size_t)a.n * 16, hipMemcpyDeviceToHost, s->stream));
+        if (host->keccak) HIP_TRY(hipMemcpyAsync(host->keccak, a.keccak, (size_t)cnt[0] * KT_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        if (host->sig_table) HIP_TRY(hipMemcpyAsync(host->sig_table, a.sig_table, (size_t)cnt[1] * SIG_TABLE_CELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        if (host->aux) HIP_TRY(hipMemcpyAsync(host->aux, a.aux, (size_t)a.n * SIG_AUX_CELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    if (n_keccak_out) *n_keccak_out = cnt[0];
+    if (n_sig_rows_out) *n_sig_rows_out = cnt[1];
+    return 0;
+}
+extern "C" int zk_sig_assign(const zk_sig_inputs* in, const zk_sig_wire* out, uint32_t opts, uint32_t* status_out, uint64_t* n_keccak_out,
+                             uint64_t* n_sig_rows_out, zk_result* result) {
+    ARG_TRY(result && out, "zk_sig_assign: null output");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    int rc = zk_sig_assign_open(in, dev ? out : nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, dev ? status_out : nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && !dev && status_out) rc = zk_read_status(s, status_out);
+    if (!rc) rc = zk_sig_assign_read(s, dev ? nullptr : out, n_keccak_out, n_sig_rows_out);
     zk_close(s);
     return rc;
 }

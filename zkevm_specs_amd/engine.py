@@ -927,6 +927,73 @@ def open_tx_assign(tx, randomness, outs=None, device=None):
                  opts, cls=TxAssignSession)
 
 
+# ---- Sig circuit witness assignment (zk_sig_assign*) ------------------------------------------------------------------------------
+SIG_ASSIGN_INPUTS = ("fields", "addr", "expect_valid")
+SIG_ASSIGN_OUTPUTS = ("bytes", "cells", "meta", "keccak", "sig_table", "aux")
+
+
+def sig_assign_shapes(n):
+    """name -> (shape, dtype) of the outputs of zk_sig_assign* (keccak, sig_table: their capacities, n + 1 and n rows)"""
+    return {"bytes": ((n, 9, 32), np.uint8), "cells": ((8, n, 4), np.uint64), "meta": ((n, 4), np.uint32),
+            "keccak": ((n + 1, 5, 4), np.uint64), "sig_table": ((n, 9, 4), np.uint64), "aux": ((n, 12, 4), np.uint64)}
+
+
+def _sig_assign_args(sig, randomness, outs=None):
+    """zk_sig_assign_open / zk_sig_assign over `sig` = dict(fields uint64[n, 4, 4]: msg_hash, sig_v, sig_r, sig_s; addr uint64[n, 4] or
+    None: the claimed addresses; expect_valid uint32[n] or None; v_offset: 0 (v is the parity) or 27 (the precompile's input word))
+    -> (ZkSigInputs, ZkSigWire of the device outputs or None, opts, kept arrays).
+    `outs` (device tensors only, each optional): buffers of SIG_ASSIGN_OUTPUTS the session writes in place."""
+    n = int(sig["fields"].shape[0])
+    _expect(sig["fields"], "fields", 8, (None, 4, 4))
+    _expect(sig.get("addr"), "addr", 8, (n, 4))
+    _expect(sig.get("expect_valid"), "expect_valid", 4, (n,))
+    shapes = sig_assign_shapes(n)
+    outs = dict(outs or {})
+    for k, v in outs.items():
+        if v is not None:
+            _expect(v, k, np.dtype(shapes[k][1]).itemsize, shapes[k][0])
+    out_list = [outs.get(k) for k in SIG_ASSIGN_OUTPUTS]
+    a, opts = _prep([sig.get(k) for k in SIG_ASSIGN_INPUTS] + out_list, outputs=range(3, 3 + len(out_list)))
+    if any(v is not None for v in out_list) and not opts:
+        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
+    rc = _randomness_cells(randomness, a[0])
+    keep = a + [rc]
+    t = _lib.ZkSigInputs(ptr(a[0], n), ptr(a[1], n), ptr(a[2], n), n, int(sig.get("v_offset", 0)), 0, ptr(rc))
+    w = _lib.ZkSigWire(*[ptr(x) for x in a[3:]]) if opts else None
+    return t, w, opts, keep
+
+
+class SigAssignSession(Session):
+    """zk_sig_assign_open: status per signature; read() -> the wire dict of the last pass (host arrays)"""
+
+    def _counts(self, w=None):
+        nk, ns = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._lib.zk_sig_assign_read(self._h, ctypes.byref(w) if w is not None else None, ctypes.byref(nk), ctypes.byref(ns)),
+              "zk_sig_assign_read", self._lib)
+        return int(nk.value), int(ns.value)
+
+    def read(self):
+        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in sig_assign_shapes(self.n).items()}
+        nk, ns = self._counts(_lib.ZkSigWire(*[ptr(out[k]) for k in SIG_ASSIGN_OUTPUTS]))
+        out["keccak"], out["sig_table"] = out["keccak"][:nk], out["sig_table"][:ns]
+        return out
+
+    def n_keccak(self):
+        return self._counts()[0]
+
+    def n_sig_rows(self):
+        return self._counts()[1]
+
+
+def open_sig_assign(sig, randomness, outs=None, device=None):
+    """Sig circuit witness assignment session over the signed data of `sig` (see _sig_assign_args).  With device tensors the outputs
+    stay in HBM: in `outs`' buffers where given (e.g. for zk_ecdsa_open / zk_sign_open on them), else in the session's own."""
+    lib = _lib.init(device)
+    t, w, opts, keep = _sig_assign_args(sig, randomness, outs)
+    return _open(lib, lib.zk_sig_assign_open, t.n, (keep, t, w), ctypes.byref(t), ctypes.byref(w) if w is not None else None, opts,
+                 cls=SigAssignSession)
+
+
 # ---- Exp circuit witness assignment (zk_exp_assign*) ------------------------------------------------------------------------------
 def _exp_events_struct(events, max_exp_steps):
     """the ZkExpEvents block over a prepared event array (None or empty: a null pointer, dummy rows only)"""

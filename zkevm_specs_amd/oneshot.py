@@ -216,6 +216,21 @@ def tx_assign(tx, randomness, device=None):
     return Result(r), status[:n], out
 
 
+def sig_assign(sig, randomness, device=None):
+    """zk_sig_assign over signed data (engine._sig_assign_args) -> (Result, status uint32[n], wire dict: bytes, cells, meta, keccak,
+    sig_table, aux — the units as flatten_sig_witness makes them, the EVM circuit's sig table and its aux rows of kind 5)"""
+    lib = _lib.init(device)
+    t, _, opts, keep = engine._sig_assign_args({k: (_host(v) if k in engine.SIG_ASSIGN_INPUTS else v) for k, v in sig.items()}, randomness)
+    n = int(t.n)
+    out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in engine.sig_assign_shapes(n).items()}
+    w = _lib.ZkSigWire(*[ptr(out[k]) for k in engine.SIG_ASSIGN_OUTPUTS])
+    status, r, nk, ns = np.zeros(max(n, 1), dtype=np.uint32), ZkResult(), ctypes.c_uint64(), ctypes.c_uint64()
+    check(lib.zk_sig_assign(ctypes.byref(t), ctypes.byref(w), opts, ptr(status), ctypes.byref(nk), ctypes.byref(ns), ctypes.byref(r)),
+          "zk_sig_assign", lib)
+    out["keccak"], out["sig_table"] = out["keccak"][: nk.value], out["sig_table"][: ns.value]
+    return Result(r), status[:n], out
+
+
 def pi_assign(pd, keccak_rand=255, byte_pow_base=255, device=None):
     """zk_pi_assign over raw public data (engine._pi_assign_args) -> (Result, wire dict of engine.PI_ASSIGN_OUTPUTS)"""
     lib = _lib.init(device)
