@@ -52,6 +52,17 @@ def test_oracle_reference_and_kernel_logic(golden_dir, hostsim):
         n_fail += sum(1 for e in exp if e)
         sites |= {codes.site_of(e) for e in exp if e}
     assert n > 100000 and n_fail > 40 and len(sites) >= 8, (n, n_fail, sorted(sites))
+    # with the directed corpus (tests/pi_sign_site_cases.py) added in, the failing sites reached are exactly its census: every site of
+    # pi_check_row but the ones the file lists as unreached
+    from tests import pi_sign_site_cases as psc
+
+    data = psc.load_pi(golden_dir)
+    for c in data.cases:
+        b = psc.pi_build(data, c, 0)
+        exp = psc.pi_expected(data, b._replace(affected=None))
+        assert psc.pi_sim(hostsim, data, b) == exp and exp[c.target] == c.code, c
+        sites |= {codes.site_of(e) for e in exp if e}
+    assert sorted(sites) == psc.census(data.cases, psc.PI_SITES)[0] == sorted(set(psc.PI_SITES) - set(data.unreached)), sorted(sites)
 
 
 @pytest.mark.gpu

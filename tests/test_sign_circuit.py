@@ -40,13 +40,27 @@ def _sim(lib, c, r_cells, is_sig):
 
 def test_oracle_reference_and_kernel_logic(golden_dir, hostsim):
     n = n_fail = 0
+    sites = {0: set(), 1: set()}
     for name, c in _cases(golden_dir):
         exp = _oracle(c)
         assert [codes.kind_of(e) for e in exp] == c["ref_kind"].tolist(), name
         assert _sim(hostsim, c, c["r"], int(c["is_sig"][0])) == exp, name
         n += len(exp)
         n_fail += sum(1 for e in exp if e)
+        sites[int(c["is_sig"][0])] |= {codes.site_of(e) for e in exp if e}
     assert n > 300 and n_fail > 80
+    # with the directed corpus (tests/pi_sign_site_cases.py) added in, the failing sites reached are exactly its census: every site of
+    # sign_check_unit, for the Tx and for the Sig circuit
+    from tests import pi_sign_site_cases as psc
+
+    for is_sig, all_sites in ((0, psc.TX_SITES), (1, psc.SIG_SITES)):
+        data = psc.load_sign(golden_dir, bool(is_sig))
+        for c in data.cases:
+            w, _ = psc.sign_build(data, c, None)
+            exp = psc.sign_expected(data, w, c.r)
+            assert psc.sign_sim(hostsim, data, w, c.r) == exp == [c.code], c.name
+            sites[is_sig] |= {codes.site_of(e) for e in exp if e}
+        assert sorted(sites[is_sig]) == psc.census(data.cases, all_sites)[0] == sorted(set(all_sites) - set(data.unreached)), (is_sig, sorted(sites[is_sig]))
 
 
 def _tamper(w, rng, k):
