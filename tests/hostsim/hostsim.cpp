@@ -512,3 +512,19 @@ extern "C" void sim_tx_recover_exact(const u64* fields, const u32* to_none, cons
         else { status[i] = st; tx_recover_fail(a, i); }
     }
 }
+
+// ---- the secp256k1 lane forms' host-side rules (csrc/secp_lanes.hpp): the form of a batch, and the launches of a batch
+extern "C" void sim_secp_lane_form(u64 n, u32 have_comb, const char* forced, u32* lanes_per_sig, u64* qtab_lanes) {
+    const SecpLaneForm f = secp_lane_form(n, have_comb != 0u, forced);
+    *lanes_per_sig = f.lanes_per_sig;
+    *qtab_lanes = f.qtab_lanes;
+}
+// out: [cap][4] = first, count, grid, block per launch; returns the number of launches (which may exceed cap)
+extern "C" u64 sim_secp_chunks(u64 n, u64 qtab_lanes, u32 lanes_per_sig, u64* out, u64 cap) {
+    SecpLanes l = {};
+    l.qtab_lanes = qtab_lanes; l.lanes_per_sig = lanes_per_sig;
+    u64 k = 0;
+    for (SecpChunk c = secp_chunk(n, l, 0); c.count; c = secp_chunk(n, l, c.first + c.count), k++)
+        if (k < cap) { out[4 * k] = c.first; out[4 * k + 1] = c.count; out[4 * k + 2] = c.grid; out[4 * k + 3] = c.block; }
+    return k;
+}

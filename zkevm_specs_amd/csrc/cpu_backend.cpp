@@ -731,12 +731,9 @@ extern "C" int zk_ecdsa_open_batches(const zk_ecdsa_batch* bt, uint32_t n_batche
             for (int c = 0; c < 5; c++) a.off1[c] = OFF[bt[k].layout ? 1 : 0][c];
         }
     }
-    a.first = 0;
     a.out = nullptr;
     a.out_stride = 0;
-    a.qtab = nullptr;
-    a.qtab_lanes = 1;
-    a.lanes_per_sig = 1;
+    a.lanes = SecpLanes{nullptr, 1, 1, nullptr, 0};
     s->row = [s](u64 i) {
         u32 tab[15 * 24];  // the key's multiples: per call on the CPU
         return ecdsa_verify_one(s->ecdsa, i, tab, 1);
@@ -1569,22 +1566,42 @@ extern "C" int zk_withdrawal_assign(const uint64_t* withdrawals, uint64_t n, uin
     return 0;
 }
 
+// ---- what the Tx and the Sig witness assignment share
+// signature i of a recovery batch in the one-lane form: its key and its status
+static void secp_recover_one(const SecpRecoverArgs& q, u64 i) {
+    u32 tab[15 * 24];
+    EcdsaPrep pr;
+    Fr u1, u2;
+    const u32 st = tx_recover_prepare(q, i, pr, u1, u2);
+    u32 code;
+    if (st == ECDSA_PENDING) code = tx_recover_finish_to(q.pk + i * 8, ecdsa_partial(pr, 0, 1, tab, 1, nullptr));
+    else if (st == TX_RECOVER_EXACT) code = tx_recover_finish_to(q.pk + i * 8, tx_recover_exact(pr, u1, u2));
+    else { code = st; tx_recover_fail_to(q.pk + i * 8); }
+    q.status[i] = code;
+}
+// the m keccak candidates as a sorted set in `keccak`; returns its size
+static u64 keccak_sorted_set(const u64* kc, u64 m, u64* keccak) {
+    std::vector<u64> idx((size_t)m);
+    for (u64 k = 0; k < m; k++) idx[k] = k;
+    std::sort(idx.begin(), idx.end(), [kc](u64 x, u64 y) { return tx_krow_cmp(kc + x * 20, kc + y * 20) < 0; });
+    u64 cnt = 0;
+    for (u64 k = 0; k < m; k++) {
+        if (cnt && tx_krow_cmp(keccak + (cnt - 1) * 20, kc + idx[k] * 20) == 0) continue;
+        memcpy(keccak + cnt * 20, kc + idx[k] * 20, 160);
+        cnt++;
+    }
+    return cnt;
+}
+
 // ---- Tx circuit witness assignment (tx_assign.hpp): the device functions in host loops; recovery in the one-lane form
 static void tx_assign_pass(zk_session* s) {
     TxAssignArgs& a = s->txa;
+    const SecpRecoverArgs q = tx_recover_args(a);
     const long long n = (long long)a.n;
 #pragma omp parallel for schedule(dynamic, 16)
     for (long long i = 0; i < n; i++) {
         tx_sign_hash(a, (u64)i);
-        u32 tab[15 * 24];
-        EcdsaPrep pr;
-        Fr u1, u2;
-        const u32 st = tx_recover_prepare(a, (u64)i, pr, u1, u2);
-        u32 code;
-        if (st == ECDSA_PENDING) code = tx_recover_finish(a, (u64)i, ecdsa_partial(pr, 0, 1, tab, 1, nullptr));
-        else if (st == TX_RECOVER_EXACT) code = tx_recover_finish(a, (u64)i, tx_recover_exact(pr, u1, u2));
-        else { code = st; tx_recover_fail(a, (u64)i); }
-        a.status[i] = code;
+        secp_recover_one(q, (u64)i);
     }
     memcpy(s->status.data(), a.status, (size_t)a.n * sizeof(u32));
 #pragma omp parallel for schedule(dynamic, 64)
@@ -1592,18 +1609,7 @@ static void tx_assign_pass(zk_session* s) {
     tx_write_zero_candidate(a);
 #pragma omp parallel for schedule(static)
     for (long long j = 0; j < (long long)a.max_calldata; j++) tx_write_calldata_row(a, (u64)j);
-    // the keccak table as a sorted set
-    std::vector<u64> idx((size_t)a.n + 1);
-    for (u64 k = 0; k <= a.n; k++) idx[k] = k;
-    const u64* kc = a.kcand;
-    std::sort(idx.begin(), idx.end(), [kc](u64 x, u64 y) { return tx_krow_cmp(kc + x * 20, kc + y * 20) < 0; });
-    u64 m = 0;
-    for (u64 k = 0; k <= a.n; k++) {
-        if (m && tx_krow_cmp(a.keccak + (m - 1) * 20, kc + idx[k] * 20) == 0) continue;
-        memcpy(a.keccak + m * 20, kc + idx[k] * 20, 160);
-        m++;
-    }
-    s->n_keccak = m;
+    s->n_keccak = keccak_sorted_set(a.kcand, a.n + 1, a.keccak);
 }
 extern "C" int zk_tx_assign_open(const zk_tx_inputs* in, const zk_tx_wire* out_dev, uint32_t opts, zk_session** out) {
     NO_DEVICE_PTRS(opts, "zk_tx_assign_open");
@@ -1643,7 +1649,7 @@ extern "C" int zk_tx_assign_open(const zk_tx_inputs* in, const zk_tx_wire* out_d
     a.hash = s->a64[3].data(); a.gas_cost = s->w64[0].data(); a.pk = s->w64[1].data(); a.status = s->txa_out32[2].data();
     a.tx_rows = s->txa_out64[0].data(); a.tx_flags = s->txa_out32[0].data(); a.bytes = s->a8b.data(); a.cells = s->txa_out64[1].data();
     a.meta = s->txa_out32[1].data(); a.kcand = s->txa_out64[2].data(); a.keccak = s->txa_out64[3].data();
-    a.lanes_per_sig = 1;
+    a.lanes.lanes_per_sig = 1;
     s->pass = tx_assign_pass;
     s->assign_kind = 5;
     *out = s;
@@ -1681,45 +1687,25 @@ extern "C" int zk_tx_assign(const zk_tx_inputs* in, const zk_tx_wire* out, uint3
 // ---- Sig circuit witness assignment (sig_assign.hpp): the device functions in host loops; recovery in the one-lane form
 static void sig_assign_pass(zk_session* s) {
     SigAssignArgs& a = s->sga;
+    const SecpRecoverArgs q = sig_recover_args(a);
     const long long n = (long long)a.n;
 #pragma omp parallel for schedule(dynamic, 16)
-    for (long long i = 0; i < n; i++) {
-        u32 tab[15 * 24];
-        EcdsaPrep pr;
-        Fr u1, u2;
-        const u32 st = sig_recover_prepare(a, (u64)i, pr, u1, u2);
-        u32 code;
-        if (st == ECDSA_PENDING) code = tx_recover_finish_to(a.pk + i * 8, ecdsa_partial(pr, 0, 1, tab, 1, nullptr));
-        else if (st == TX_RECOVER_EXACT) code = tx_recover_finish_to(a.pk + i * 8, tx_recover_exact(pr, u1, u2));
-        else { code = st; tx_recover_fail_to(a.pk + i * 8); }
-        a.status[i] = code;
-    }
+    for (long long i = 0; i < n; i++) secp_recover_one(q, (u64)i);
     memcpy(s->status.data(), a.status, (size_t)a.n * sizeof(u32));
 #pragma omp parallel for schedule(dynamic, 64)
     for (long long i = 0; i < n; i++) sig_write_unit(a, (u64)i);
     sig_write_zero_candidate(a);
-    // the keccak table as a sorted set
-    std::vector<u64> idx((size_t)a.n + 1);
-    for (u64 k = 0; k <= a.n; k++) idx[k] = k;
-    const u64* kc = a.kcand;
-    std::sort(idx.begin(), idx.end(), [kc](u64 x, u64 y) { return tx_krow_cmp(kc + x * 20, kc + y * 20) < 0; });
-    u64 m = 0;
-    for (u64 k = 0; k <= a.n; k++) {
-        if (m && tx_krow_cmp(a.keccak + (m - 1) * 20, kc + idx[k] * 20) == 0) continue;
-        memcpy(a.keccak + m * 20, kc + idx[k] * 20, 160);
-        m++;
-    }
-    s->n_keccak = m;
+    s->n_keccak = keccak_sorted_set(a.kcand, a.n + 1, a.keccak);
     // the sig table: first occurrences in input order (equal rows are adjacent once sorted by (row, index))
     const u64* sc = a.scand;
-    idx.resize((size_t)a.n);
+    std::vector<u64> idx((size_t)a.n);
     for (u64 k = 0; k < a.n; k++) idx[k] = k;
     std::sort(idx.begin(), idx.end(), [sc](u64 x, u64 y) {
         const int c = memcmp(sc + x * SIG_TABLE_WORDS, sc + y * SIG_TABLE_WORDS, SIG_TABLE_WORDS * 8);
         return c ? c < 0 : x < y;
     });
     for (u64 k = 0; k < a.n; k++) a.sdup[idx[k]] = k && sig_row_eq(sc + idx[k - 1] * SIG_TABLE_WORDS, sc + idx[k] * SIG_TABLE_WORDS);
-    m = 0;
+    u64 m = 0;
     for (u64 k = 0; k < a.n; k++)
         if (!a.sdup[k]) memcpy(a.sig_table + m++ * SIG_TABLE_WORDS, sc + k * SIG_TABLE_WORDS, SIG_TABLE_WORDS * 8);
     s->n_sig_rows = m;
@@ -1755,7 +1741,7 @@ extern "C" int zk_sig_assign_open(const zk_sig_inputs* in, const zk_sig_wire* ou
     a.kcand = s->sga64[5].data(); a.keccak = a.kcand + (n + 1) * KT_NCELLS * 4;
     a.scand = s->sga64[6].data(); a.sig_table = a.scand + (n + 1) * SIG_TABLE_WORDS; a.sdup = s->a32[0].data();
     a.aux = s->sga64[7].data();
-    a.lanes_per_sig = 1;
+    a.lanes.lanes_per_sig = 1;
     s->pass = sig_assign_pass;
     s->assign_kind = 9;
     *out = s;

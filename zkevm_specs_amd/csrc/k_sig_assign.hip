@@ -1,63 +1,10 @@
-// Sig circuit witness assignment kernels (sig_assign.hpp), all on the session's stream:
-//   sig_recover_kernel   public-key recovery in the ECDSA kernel's lane forms (L = 1, 2, 4 lanes per signature), as tx_recover_kernel
+// Sig circuit witness assignment kernels (sig_assign.hpp), all on the session's stream; the key recovery is the Tx assignment's
+// (zk_launch_secp_recover, k_tx_assign.hip):
 //   sig_unit_kernel      one lane per signature: unit, keccak candidate row, sig-table candidate row, aux row
 //   sig_keccak_first / sig_keccak_rank   the keccak table as a sorted set (keccak_set.hpp, shared with the Tx assignment)
 //   sig_table_dup / sig_table_place      the sig table: rows with an equal row before them, then every other row at the count of such rows before it
 #include "kernels.hpp"
 #include "keccak_set.hpp"
-
-// As tx_recover_kernel (k_tx_assign.hip): the roles of a signature's lanes run the halves of the joint multiplication and meet through
-// cross-lane exchanges; role 0 converts Q to affine and writes the status.
-template <int L>
-__global__ __launch_bounds__(L == 4 ? 256 : 64) void sig_recover_kernel(SigAssignArgs a, u32* status, ZkTally* tally) {
-    const u64 gid = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const u64 i = a.first + gid / L;
-    const int role = (int)(gid % L);
-    const bool valid = i < a.n;
-    u32* tab = a.qtab + gid * (15u * 24u);
-    EcdsaPrep pr;
-    Fr u1, u2;
-    u32 st = TX_BAD_SIGNATURE;
-    SpPoint part = sp_infinity();
-    if (valid) {
-        st = sig_recover_prepare(a, i, pr, u1, u2);
-        if (st == ECDSA_PENDING) part = L == 4 ? ecdsa_partial4(pr, role, tab, 1, a.gcomb)
-                                               : ecdsa_partial(pr, L == 1 ? 0 : role, L == 1 ? 1 : role, tab, 1, a.gcomb);
-        else if (st == TX_RECOVER_EXACT && role == 0) part = tx_recover_exact(pr, u1, u2);
-    }
-    if (L >= 2) {
-        SpPoint other;
-#pragma unroll
-        for (int w = 0; w < 8; w++) {
-            other.X.v[w] = (u32)__shfl_xor((int)part.X.v[w], 1);
-            other.Y.v[w] = (u32)__shfl_xor((int)part.Y.v[w], 1);
-            other.Z.v[w] = (u32)__shfl_xor((int)part.Z.v[w], 1);
-        }
-        if (valid && (role & 1) == 0 && st == ECDSA_PENDING) sp_add_ip(part, other);
-    }
-    if (L == 4) {
-        SpPoint other;
-#pragma unroll
-        for (int w = 0; w < 8; w++) {
-            other.X.v[w] = (u32)__shfl_xor((int)part.X.v[w], 2);
-            other.Y.v[w] = (u32)__shfl_xor((int)part.Y.v[w], 2);
-            other.Z.v[w] = (u32)__shfl_xor((int)part.Z.v[w], 2);
-        }
-        if (valid && role == 0 && st == ECDSA_PENDING) sp_add_ip(part, other);
-    }
-    u32 code = 0;
-    if (valid && role == 0) {
-        if (st == ECDSA_PENDING || st == TX_RECOVER_EXACT) {
-            code = tx_recover_finish_to(a.pk + i * 8, part);
-        } else {
-            code = st;
-            tx_recover_fail_to(a.pk + i * 8);
-        }
-        a.status[i] = code;
-        if (status && status != a.status) status[i] = code;
-    }
-    tally_commit(tally, i, code);
-}
 
 __global__ __launch_bounds__(64) void sig_unit_kernel(SigAssignArgs a) {
     const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
@@ -141,17 +88,8 @@ __global__ __launch_bounds__(SGT_TILE) void sig_table_place_kernel(SigAssignArgs
     if (blockIdx.x == gridDim.x - 1 && t == SGT_TILE - 1) *a.n_sig_rows = base + scan[t];
 }
 
-void zk_launch_sig_assign(hipStream_t st, const SigAssignArgs& a0, u32* status, ZkTally* tally) {
-    SigAssignArgs a = a0;
-    const u64 per_chunk = a.qtab_lanes / a.lanes_per_sig;
-    for (a.first = 0; a.first < a.n; a.first += per_chunk) {
-        const u64 m = a.n - a.first < per_chunk ? a.n - a.first : per_chunk;
-        const u32 grid = (u32)((m * a.lanes_per_sig + 63) / 64);
-        if (a.lanes_per_sig == 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(sig_recover_kernel<4>), dim3((grid + 3) / 4), dim3(256), 0, st, a, status, tally);
-        else if (a.lanes_per_sig == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(sig_recover_kernel<2>), dim3(grid), dim3(64), 0, st, a, status, tally);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(sig_recover_kernel<1>), dim3(grid), dim3(64), 0, st, a, status, tally);
-    }
-    a.first = 0;
+void zk_launch_sig_assign(hipStream_t st, const SigAssignArgs& a, u32* status, ZkTally* tally) {
+    zk_launch_secp_recover(st, sig_recover_args(a), status, tally);
     hipLaunchKernelGGL(sig_unit_kernel, dim3((u32)((a.n + 63) / 64 ? (a.n + 63) / 64 : 1)), dim3(64), 0, st, a);
     const u64 m = a.n + 1;
     (void)hipMemsetAsync(a.n_keccak, 0, sizeof(u32), st);

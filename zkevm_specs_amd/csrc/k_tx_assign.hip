@@ -1,8 +1,8 @@
 // Tx circuit witness assignment kernels (tx_assign.hpp), all on the session's stream:
-//   tx_hash_kernel      one lane per tx: RLP + keccak of the signing payload, calldata gas cost
-//   tx_recover_kernel   public-key recovery in the ECDSA kernel's lane forms (L = 1, 2, 4 lanes per signature)
-//   tx_slot_kernel      one lane per tx slot: fixed rows, SignVerify unit, keccak candidate row
-//   tx_calldata_kernel  one lane per CallData row
+//   tx_hash_kernel       one lane per tx: RLP + keccak of the signing payload, calldata gas cost
+//   secp_recover_kernel  public-key recovery in the lane forms (secp_lanes.hpp: L = 1, 2, 4 lanes per signature); the Sig assignment's too
+//   tx_slot_kernel       one lane per tx slot: fixed rows, SignVerify unit, keccak candidate row
+//   tx_calldata_kernel   one lane per CallData row
 //   tx_keccak_first / tx_keccak_rank   the keccak table as a sorted set: first occurrences, then each one's rank among them
 #include "kernels.hpp"
 #include "keccak_set.hpp"
@@ -13,56 +13,46 @@ __global__ __launch_bounds__(64) void tx_hash_kernel(TxAssignArgs a) {
 }
 
 // As ecdsa_verify_kernel (k_ecdsa.hip): the roles of a signature's lanes run the halves of the joint multiplication and meet through
-// cross-lane exchanges; role 0 converts Q to affine and writes the status.
+// cross-lane exchanges; role 0 converts Q to affine and writes the key and the status.
 template <int L>
-__global__ __launch_bounds__(L == 4 ? 256 : 64) void tx_recover_kernel(TxAssignArgs a, u32* status, ZkTally* tally) {
+__global__ __launch_bounds__(L == 4 ? 256 : 64) void secp_recover_kernel(SecpRecoverArgs a, u32* status, ZkTally* tally) {
     const u64 gid = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const u64 i = a.first + gid / L;
+    const u64 i = a.lanes.first + gid / L;
     const int role = (int)(gid % L);
     const bool valid = i < a.n;
-    u32* tab = a.qtab + gid * (15u * 24u);
+    u32* tab = a.lanes.qtab + gid * (15u * 24u);
     EcdsaPrep pr;
     Fr u1, u2;
     u32 st = TX_BAD_SIGNATURE;
     SpPoint part = sp_infinity();
     if (valid) {
         st = tx_recover_prepare(a, i, pr, u1, u2);
-        if (st == ECDSA_PENDING) part = L == 4 ? ecdsa_partial4(pr, role, tab, 1, a.gcomb)
-                                               : ecdsa_partial(pr, L == 1 ? 0 : role, L == 1 ? 1 : role, tab, 1, a.gcomb);
+        if (st == ECDSA_PENDING) part = L == 4 ? ecdsa_partial4(pr, role, tab, 1, a.lanes.gcomb)
+                                               : ecdsa_partial(pr, L == 1 ? 0 : role, L == 1 ? 1 : role, tab, 1, a.lanes.gcomb);
         else if (st == TX_RECOVER_EXACT && role == 0) part = tx_recover_exact(pr, u1, u2);
     }
-    if (L >= 2) {
-        SpPoint other;
-#pragma unroll
-        for (int w = 0; w < 8; w++) {
-            other.X.v[w] = (u32)__shfl_xor((int)part.X.v[w], 1);
-            other.Y.v[w] = (u32)__shfl_xor((int)part.Y.v[w], 1);
-            other.Z.v[w] = (u32)__shfl_xor((int)part.Z.v[w], 1);
-        }
-        if (valid && (role & 1) == 0 && st == ECDSA_PENDING) sp_add_ip(part, other);
-    }
-    if (L == 4) {
-        SpPoint other;
-#pragma unroll
-        for (int w = 0; w < 8; w++) {
-            other.X.v[w] = (u32)__shfl_xor((int)part.X.v[w], 2);
-            other.Y.v[w] = (u32)__shfl_xor((int)part.Y.v[w], 2);
-            other.Z.v[w] = (u32)__shfl_xor((int)part.Z.v[w], 2);
-        }
-        if (valid && role == 0 && st == ECDSA_PENDING) sp_add_ip(part, other);
-    }
+    secp_lanes_meet<L>(part, valid && st == ECDSA_PENDING, role);
     u32 code = 0;
     if (valid && role == 0) {
         if (st == ECDSA_PENDING || st == TX_RECOVER_EXACT) {
-            code = tx_recover_finish(a, i, part);
+            code = tx_recover_finish_to(a.pk + i * 8, part);
         } else {
             code = st;
-            tx_recover_fail(a, i);
+            tx_recover_fail_to(a.pk + i * 8);
         }
         a.status[i] = code;
         if (status && status != a.status) status[i] = code;
     }
     tally_commit(tally, i, code);
+}
+void zk_launch_secp_recover(hipStream_t st, const SecpRecoverArgs& a0, u32* status, ZkTally* tally) {
+    SecpRecoverArgs a = a0;
+    const u32 L = a.lanes.lanes_per_sig;
+    const auto kernel = L == 4 ? secp_recover_kernel<4> : L == 2 ? secp_recover_kernel<2> : secp_recover_kernel<1>;
+    for (SecpChunk c = secp_chunk(a.n, a.lanes, 0); c.count; c = secp_chunk(a.n, a.lanes, c.first + c.count)) {
+        a.lanes.first = c.first;
+        hipLaunchKernelGGL(kernel, dim3(c.grid), dim3(c.block), 0, st, a, status, tally);
+    }
 }
 
 __global__ __launch_bounds__(64) void tx_slot_kernel(TxAssignArgs a) {
@@ -79,18 +69,9 @@ __global__ __launch_bounds__(256) void tx_calldata_kernel(TxAssignArgs a) {
 __global__ __launch_bounds__(256) void tx_keccak_first_kernel(TxAssignArgs a, u64 m) { txk_first_pass(a.kcand, a.kfirst, a.n_keccak, m); }
 __global__ __launch_bounds__(256) void tx_keccak_rank_kernel(TxAssignArgs a, u64 m) { txk_rank_pass(a.kcand, a.kfirst, a.keccak, m); }
 
-void zk_launch_tx_assign(hipStream_t st, const TxAssignArgs& a0, u32* status, ZkTally* tally) {
-    TxAssignArgs a = a0;
+void zk_launch_tx_assign(hipStream_t st, const TxAssignArgs& a, u32* status, ZkTally* tally) {
     if (a.n) hipLaunchKernelGGL(tx_hash_kernel, dim3((u32)((a.n + 63) / 64)), dim3(64), 0, st, a);
-    const u64 per_chunk = a.qtab_lanes / a.lanes_per_sig;
-    for (a.first = 0; a.first < a.n; a.first += per_chunk) {
-        const u64 m = a.n - a.first < per_chunk ? a.n - a.first : per_chunk;
-        const u32 grid = (u32)((m * a.lanes_per_sig + 63) / 64);
-        if (a.lanes_per_sig == 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(tx_recover_kernel<4>), dim3((grid + 3) / 4), dim3(256), 0, st, a, status, tally);
-        else if (a.lanes_per_sig == 2) hipLaunchKernelGGL(HIP_KERNEL_NAME(tx_recover_kernel<2>), dim3(grid), dim3(64), 0, st, a, status, tally);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(tx_recover_kernel<1>), dim3(grid), dim3(64), 0, st, a, status, tally);
-    }
-    a.first = 0;
+    zk_launch_secp_recover(st, tx_recover_args(a), status, tally);
     const u64 slots = a.max_txs ? a.max_txs : 1;
     hipLaunchKernelGGL(tx_slot_kernel, dim3((u32)((slots + 63) / 64)), dim3(64), 0, st, a);
     if (a.max_calldata) hipLaunchKernelGGL(tx_calldata_kernel, dim3((u32)((a.max_calldata + 255) / 256)), dim3(256), 0, st, a);

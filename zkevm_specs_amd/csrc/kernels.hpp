@@ -89,6 +89,8 @@ void zk_launch_fq12_op(hipStream_t st, int op, const u64* x, const u64* y, u64* 
 // Withdrawal circuit (k_withdrawal.hip): verify held rows [lo, hi) (status / twin tally); assign rows [0, a.n_out) (+ keccak rows)
 void zk_launch_withdrawal_rows(hipStream_t st, const WithdrawalArgs& a, u64 lo, u64 hi, u32* status, ZkTally* tally);
 void zk_launch_withdrawal_assign(hipStream_t st, const WithdrawalArgs& a);
+// secp256k1 key recovery in the lane forms (k_tx_assign.hip): pk and status (+ status / tally) per signature of the batch
+void zk_launch_secp_recover(hipStream_t st, const SecpRecoverArgs& a, u32* status, ZkTally* tally);
 // Tx circuit witness assignment (k_tx_assign.hip): sign hashes, key recovery (status / tally per tx), rows, units, keccak set
 void zk_launch_tx_assign(hipStream_t st, const TxAssignArgs& a, u32* status, ZkTally* tally);
 // Sig circuit witness assignment (k_sig_assign.hip): key recovery (status / tally per signature), units, keccak set, sig table, aux rows

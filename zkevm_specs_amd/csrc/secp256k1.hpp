@@ -19,6 +19,7 @@
 #include "common.hpp"
 #include "secp_constants.h"
 #include "secp_g_table.h"
+#include "secp_lanes.hpp"
 
 #if defined(ZK_HOSTSIM)
 #define SP_MEMBER static inline
@@ -562,6 +563,25 @@ ZK_HD void sp_add_ip(SpPoint& p, const SpPoint& q) {
     p.Y = spf_sub(spf_mul(rr, spf_sub(v, p.X)), spf_mul(s1, hhh));
     p.Z = spf_mul(zz, h);
 }
+#if !defined(ZK_HOSTSIM)
+// The meeting of a signature's lanes (the lane forms of secp_lanes.hpp).  Every lane of the wavefront takes part in the exchanges:
+// lane 2i receives the partial sum of lane 2i + 1, then (L = 4) lane 4i the sum of lanes 4i + 2, 4i + 3.  `pending`: this lane's
+// signature is in range and its point comes out of the joint multiplication.
+template <int L>
+__device__ __forceinline__ void secp_lanes_meet(SpPoint& part, bool pending, int role) {
+#pragma unroll
+    for (int d = 1; d < L; d <<= 1) {
+        SpPoint other;
+#pragma unroll
+        for (int w = 0; w < 8; w++) {
+            other.X.v[w] = (u32)__shfl_xor((int)part.X.v[w], d);
+            other.Y.v[w] = (u32)__shfl_xor((int)part.Y.v[w], d);
+            other.Z.v[w] = (u32)__shfl_xor((int)part.Z.v[w], d);
+        }
+        if (pending && (role & (2 * d - 1)) == 0) sp_add_ip(part, other);
+    }
+}
+#endif
 // p + (x2, y2, 1), y2 != 0: the fixed-base tables' addition (8M + 3S); same case analysis
 ZK_HD void sp_add_affine_ip(SpPoint& p, const Fr& x2, const Fr& y2) {
     if (fr_is_zero(p.Y)) {
@@ -641,6 +661,13 @@ enum { ECDSA_OK = 0, ECDSA_NOT_VERIFIED = 1 };
 #define ECDSA_KEY_RANGE ZK_CODE(ZK_UNSUPPORTED, 2)       // public key with y == P exactly: outside the engine's domain (see ecdsa_prepare)
 #define ECDSA_PENDING 0xfffffffeu                        // internal: the verdict comes out of the joint multiplication
 
+// argument-block helpers that host code calls (ZK_HD is device code only)
+#if defined(ZK_HOSTSIM)
+#define SECP_HOST_DEVICE static inline
+#else
+#define SECP_HOST_DEVICE __host__ __device__ inline
+#endif
+
 struct EcdsaArgs {
     const uint8_t* bytes;  // per signature: pk_x LE, pk_y LE, msg_hash (BE or LE), sig_r LE, sig_s LE (32 bytes each)
     u64 stride;            // bytes between signatures
@@ -649,13 +676,12 @@ struct EcdsaArgs {
     const u32* v;          // optional recovery ids, v[i * v_stride] (Sig circuit): outside {0, 1} -> BadSignature
     u32 v_stride;
     u64 n;
-    u64 first;             // first signature of this launch (large batches run in chunks that share one key table, zk_launch_ecdsa)
     u32* out;              // optional: out[i * out_stride] = status (e.g. the sign units' meta column)
     u32 out_stride;
-    u32* qtab;             // per-lane tables of the key's multiples, word w of entry e of lane l at qtab[(e * 24 + w) * qtab_lanes + l]
-    u64 qtab_lanes;
-    u32 lanes_per_sig;     // 1: one lane runs both halves of the GLV split; 2: a lane pair, one half each; 4: two more lanes for the halves of u1 G (ecdsa_partial4)
-    const u32* gcomb;      // optional: the 8-bit fixed-base table of G built on the device (ecdsa_comb_entry), nullptr: 4-bit constant table
+    union {                // the lane form, its key tables and the launch's first signature (secp_lanes.hpp) ...
+        SecpLanes lanes;
+        struct { u32* qtab; u64 qtab_lanes; u32 lanes_per_sig; const u32* gcomb; u64 first; };  // ... and SecpLanes' fields by their own names, as the host harness sets them
+    };
     // A second batch in the same launch (zk_ecdsa_open_batches): signatures [n0, n) come from these arrays (the Tx circuit's and
     // the Sig circuit's chips of one block: two launches of 2^14 signatures each ran 1.9 ms side by side where one launch of
     // 2^15 takes 1.4 ms — 1,024 wavefronts placed one per SIMD by ONE dispatch).  n0 == n: a single batch.
@@ -669,14 +695,9 @@ struct EcdsaArgs {
     u32* out1;
     u32 out_stride1;
 };
-#if defined(ZK_HOSTSIM)
-static inline
-#else
-__host__ __device__ inline
-#endif
-void ecdsa_single_batch(EcdsaArgs& a) {  // callers that fill the first batch only (host code)
+SECP_HOST_DEVICE void ecdsa_single_batch(EcdsaArgs& a) {  // callers that fill the first batch only (host code)
     a.n0 = a.n;
-    a.gcomb = nullptr;
+    a.lanes.gcomb = nullptr;
     a.bytes1 = nullptr; a.stride1 = 0; a.msg_be1 = 0; a.v1 = nullptr; a.v_stride1 = 0; a.out1 = nullptr; a.out_stride1 = 0;
     for (int k = 0; k < 5; k++) a.off1[k] = 0;
 }
@@ -1125,5 +1146,5 @@ ZK_HD u32 ecdsa_verify_one(const EcdsaArgs& a, u64 i, u32* tab, u64 stride) {
     EcdsaPrep pr;
     const u32 st = ecdsa_prepare(a, i, pr, true);
     if (st != ECDSA_PENDING) return st;
-    return ecdsa_verdict(pr, ecdsa_partial(pr, 0, 1, tab, stride, a.gcomb));
+    return ecdsa_verdict(pr, ecdsa_partial(pr, 0, 1, tab, stride, a.lanes.gcomb));
 }

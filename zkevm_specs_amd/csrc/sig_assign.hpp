@@ -5,7 +5,7 @@
 //
 // Per signature:
 //   1. the key is recovered as eth_keys does it, through the Tx assignment's preparation and finish (tx_assign.hpp
-//      tx_recover_prepare_vrs / tx_recover_exact / tx_recover_finish_to) and the ECDSA kernel's joint multiplication: parity =
+//      tx_recover_prepare / tx_recover_exact / tx_recover_finish_to) and the ECDSA kernel's joint multiplication: parity =
 //      v - v_offset in {0, 1} and 0 < r, s < N (else site 1), a curve point with x = r (else site 3), Q not at infinity (else site 4).
 //      msg_hash is the word of the hash's 32 bytes (little-endian); z is the same bytes read big-endian;
 //   2. keccak(Q) gives the recovered address; the unit's nine byte rows, eight cells and four meta words, its KeccakTable.add row,
@@ -33,8 +33,7 @@ struct SigAssignArgs {
     // work
     u64* pk;                  // [n][8]: Q.x, Q.y
     u32* status;              // [n]
-    // recovery lane forms (as EcdsaArgs)
-    u32* qtab; u64 qtab_lanes; u32 lanes_per_sig; const u32* gcomb; u64 first;
+    SecpLanes lanes;          // the recovery's lane form (secp_lanes.hpp)
     // outputs
     uint8_t* bytes;           // [n][9][32]
     u64* cells;               // column-major [8][n][4]
@@ -50,10 +49,15 @@ struct SigAssignArgs {
     u64* aux;                 // [n][12][4]
 };
 
-ZK_HD u32 sig_recover_prepare(const SigAssignArgs& a, u64 i, EcdsaPrep& pr, Fr& u1, Fr& u2) {
-    const u64* f = a.fields + i * (SIG_NFIELDS * 4);
-    const Fr v = fr_load(f + 4), r = fr_load(f + 8), s = fr_load(f + 12);
-    return tx_recover_prepare_vrs<true>(v, fr_from_u64(a.v_offset), r, s, f, pr, u1, u2);
+SECP_HOST_DEVICE SecpRecoverArgs sig_recover_args(const SigAssignArgs& a) {  // (host code: the launcher's)
+    SecpRecoverArgs q;
+    q.lanes = a.lanes; q.n = a.n;
+    q.vrs = a.fields + 4; q.vrs_stride = SIG_NFIELDS * 4;
+    for (int k = 0; k < 8; k++) q.v_base.v[k] = 0u;
+    q.v_base.v[0] = (u32)a.v_offset; q.v_base.v[1] = (u32)(a.v_offset >> 32);
+    q.hash = a.fields; q.hash_stride = SIG_NFIELDS * 4; q.hash_bytes = 1;
+    q.pk = a.pk; q.status = a.status;
+    return q;
 }
 
 // acc += sum over the 8 bytes of w (first byte lowest) of byte_k * r^(top - k), top >= 7: lazily reduced, as kt_chunk / tx_pk_rlc

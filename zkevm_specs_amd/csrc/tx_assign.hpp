@@ -44,8 +44,7 @@ struct TxAssignArgs {
     u64* gas_cost;          // [n]
     u64* pk;                // [n][8]: Q.x, Q.y (256-bit integers)
     u32* status;            // [n]
-    // recovery lane forms (as EcdsaArgs)
-    u32* qtab; u64 qtab_lanes; u32 lanes_per_sig; const u32* gcomb; u64 first;
+    SecpLanes lanes;        // the recovery's lane form (secp_lanes.hpp)
     // outputs (the wire of flatten_tx_witness)
     u64* tx_rows;           // [max_txs * 12 + max_calldata][5][4]
     u32* tx_flags;          // [...]: is_word
@@ -275,15 +274,38 @@ ZK_NOINLINE Fr sp_inv_p(Fr a) {
     return spf_mul(tx_sqr_n(t, 2), a);
 }
 
+// What the recovery of a batch reads and writes: the Tx and the Sig assignment (sig_assign.hpp) differ only in where the words lie
+struct SecpRecoverArgs {
+    SecpLanes lanes;
+    u64 n;
+    const u64* vrs;     // signature i: v, r, s as three consecutive 256-bit words at vrs + i * vrs_stride
+    u64 vrs_stride;
+    Fr v_base;          // what v exceeds by the parity
+    const u64* hash;    // the message hash of signature i: the 256-bit word at hash + i * hash_stride ...
+    u64 hash_stride;
+    u32 hash_bytes;     // ... 0: as an integer, 1: the word of its 32 bytes
+    u64* pk;            // [n][8]: Q.x, Q.y (zero where the status is not)
+    u32* status;        // [n]
+};
+SECP_HOST_DEVICE SecpRecoverArgs tx_recover_args(const TxAssignArgs& a) {  // (host code: the launcher's)
+    SecpRecoverArgs q;
+    q.lanes = a.lanes; q.n = a.n;
+    q.vrs = a.fields + 20; q.vrs_stride = TX_NFIELDS * 4;
+    const u64 lo = (a.chain_id << 1) + 35u, hi = (a.chain_id >> 63) + (lo < 35u ? 1u : 0u);  // 35 + 2 chain_id < 2^66
+    for (int k = 0; k < 8; k++) q.v_base.v[k] = 0u;
+    q.v_base.v[0] = (u32)lo; q.v_base.v[1] = (u32)(lo >> 32); q.v_base.v[2] = (u32)hi;
+    q.hash = a.hash; q.hash_stride = 4; q.hash_bytes = 0;
+    q.pk = a.pk; q.status = a.status;
+    return q;
+}
 // Validation, the lift of R and the two scalars.  ECDSA_PENDING: `pr` is ready for ecdsa_partial / ecdsa_partial4 (R in pr.qx / qy,
 // the GLV halves of u2 = s / r, the halves of u1 = -z / r); TX_RECOVER_EXACT: the plain chains over u1 / u2 (tx_recover_exact);
-// anything else is the tx's status.
-// (the core over the signature's words: `v_base` is what v exceeds by the parity, `hash` the message hash as a 256-bit integer —
-// HASH_BYTES: as the word of its 32 bytes instead, which the core reads big-endian; sig_assign.hpp recovers through it too)
-template <bool HASH_BYTES>
-ZK_HD u32 tx_recover_prepare_vrs(const Fr& v, const Fr& v_base, const Fr& r, const Fr& s, const u64* hash, EcdsaPrep& pr, Fr& u1, Fr& u2) {
+// anything else is the signature's status.
+ZK_HD u32 tx_recover_prepare(const SecpRecoverArgs& q, u64 i, EcdsaPrep& pr, Fr& u1, Fr& u2) {
+    const u64* f = q.vrs + i * q.vrs_stride;
+    const Fr v = fr_load(f), r = fr_load(f + 4), s = fr_load(f + 8);
     Fr par;
-    const u32 bw = u256_sub(par, v, v_base);
+    const u32 bw = u256_sub(par, v, q.v_base);
     if (bw || !fr_fits32(par) || par.v[0] > 1u) return TX_BAD_SIGNATURE;
     const Fr n = SecpN::mod();
     if (!fr_lt(r, n) || !fr_lt(s, n) || fr_is_zero(r) || fr_is_zero(s)) return TX_BAD_SIGNATURE;
@@ -293,7 +315,8 @@ ZK_HD u32 tx_recover_prepare_vrs(const Fr& v, const Fr& v_base, const Fr& r, con
     Fr y = sp_sqrt_p(y2);
     if (!fr_eq(spf_sqr(y), y2)) return TX_NO_CURVE_POINT;
     if ((y.v[0] & 1u) != par.v[0]) y = spf_sub(fr_zero(), y);  // (y != 0: the group order is odd)
-    const Fr z = sp_reduce_once<SecpN>(HASH_BYTES ? tx_bswap256(fr_load(hash)) : fr_load(hash));
+    const Fr h = fr_load(q.hash + i * q.hash_stride);
+    const Fr z = sp_reduce_once<SecpN>(q.hash_bytes ? tx_bswap256(h) : h);  // (the bytes read big-endian)
     const Fr rinvM = sp_to_mont<SecpN>(sp_inv_n_safegcd(r));
     u2 = sp_mont<SecpN>(s, rinvM);
     u1 = sp_sub<SecpN>(fr_zero(), sp_mont<SecpN>(z, rinvM));
@@ -301,20 +324,13 @@ ZK_HD u32 tx_recover_prepare_vrs(const Fr& v, const Fr& v_base, const Fr& r, con
     if (sp_glv_split(u2, pr.kq[0], pr.neg[0], pr.kq[1], pr.neg[1])) {
         pr.kg[0] = fr_zero(); pr.kg[1] = fr_zero();
 #pragma unroll
-        for (int q = 0; q < 4; q++) { pr.kg[0].v[q] = u1.v[q]; pr.kg[1].v[q] = u1.v[4 + q]; }
+        for (int k = 0; k < 4; k++) { pr.kg[0].v[k] = u1.v[k]; pr.kg[1].v[k] = u1.v[4 + k]; }
         return ECDSA_PENDING;
     }
     return TX_RECOVER_EXACT;
 }
-ZK_HD u32 tx_recover_prepare(const TxAssignArgs& a, u64 i, EcdsaPrep& pr, Fr& u1, Fr& u2) {
-    const u64* f = a.fields + i * (TX_NFIELDS * 4);
-    const Fr v = fr_load(f + 20), r = fr_load(f + 24), s = fr_load(f + 28);
-    Fr c2;
-    const Fr c = fr_from_u64(a.chain_id);
-    u256_add(c2, c, c);
-    u256_add(c2, c2, fr_from_u64(35));  // < 2^66
-    return tx_recover_prepare_vrs<false>(v, c2, r, s, a.hash + i * 4, pr, u1, u2);
-}
+// (the forms over the Tx block, which the host harness calls)
+ZK_HD u32 tx_recover_prepare(const TxAssignArgs& a, u64 i, EcdsaPrep& pr, Fr& u1, Fr& u2) { return tx_recover_prepare(tx_recover_args(a), i, pr, u1, u2); }
 ZK_HD SpPoint tx_recover_exact(const EcdsaPrep& pr, const Fr& u1, const Fr& u2) {
     SpPoint R;
     R.X = pr.qx; R.Y = pr.qy; R.Z = SecpP::one();

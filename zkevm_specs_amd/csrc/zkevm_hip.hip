@@ -25,7 +25,6 @@
 // per thread (the "current" device / stream that zk_*_open captures, the error text) or per session (device, stream,
 // buffers, events): sessions are independent contexts, calls on different sessions may come from different threads.
 #define ZK_MAX_DEVICES 64
-#define ZK_ECDSA_CHUNK_LANES (1ull << 17)  // lanes per ECDSA launch (x 1,440 B of key tables = 189 MB); a multiple of 64
 static std::mutex g_dev_mutex;
 static hipStream_t g_own_stream[ZK_MAX_DEVICES] = {nullptr};
 static hipStream_t g_batch_stream[ZK_MAX_DEVICES][2] = {{nullptr}};
@@ -822,6 +821,38 @@ static int stage(zk_session* s, const void* src, size_t bytes, bool device_ptrs,
     *out = d;
     return 0;
 }
+// The powers of a keccak randomness (its four words, on the host) on the device: KT_RPOW_ROWS rows (keccak_table.hpp)
+static int keccak_rpow_open(zk_session* s, const u64* rand, const u64** out) {
+    u64* d_rpow = nullptr;
+    const int rc = dev_alloc(s, (void**)&d_rpow, KT_RPOW_ROWS * 4 * sizeof(u64));
+    if (rc) return rc;
+    Fr r;  // (fr_load is device code)
+    for (int k = 0; k < 4; k++) { r.v[2 * k] = (u32)rand[k]; r.v[2 * k + 1] = (u32)(rand[k] >> 32); }
+    zk_launch_keccak_rpow(s->stream, r, d_rpow);
+    *out = d_rpow;
+    return 0;
+}
+// The secp256k1 lane forms of a session over n signatures (secp_lanes.hpp): the device's fixed-base table of G, built once per device
+// (ordered before the session's first pass: same stream + a synchronisation), the form (ZK_ECDSA_LANES overrides), the key tables.
+// `entry` names the caller in the error texts.
+static int secp_lanes_open(zk_session* s, u64 n, const char* entry, SecpLanes& l) {
+    {
+        std::lock_guard<std::mutex> lock(g_dev_mutex);
+        if (!g_secp_comb[s->device]) {
+            u32* tab = nullptr;
+            if (hipMalloc(&tab, (size_t)ECDSA_COMB_ENTRIES * 16 * sizeof(u32)) != hipSuccess) { g_err = std::string(entry) + ": table allocation failed"; return -2; }
+            zk_launch_ecdsa_comb_build(s->stream, tab);
+            if (hipStreamSynchronize(s->stream) != hipSuccess) { (void)hipFree(tab); g_err = std::string(entry) + ": table build failed"; return -2; }
+            g_secp_comb[s->device] = tab;
+        }
+        l.gcomb = g_secp_comb[s->device];
+    }
+    const SecpLaneForm f = secp_lane_form(n, l.gcomb != nullptr, getenv("ZK_ECDSA_LANES"));
+    l.lanes_per_sig = f.lanes_per_sig;
+    l.qtab_lanes = f.qtab_lanes;
+    l.first = 0;
+    return dev_alloc(s, (void**)&l.qtab, (size_t)l.qtab_lanes * 15 * 24 * sizeof(u32));
+}
 
 // Small device -> host read on the SESSION's stream.  (A plain hipMemcpy runs on the legacy default stream and waits for every
 // other stream's work first: with several sessions being opened concurrently — block.py's chains — each open then queued behind
@@ -1456,7 +1487,6 @@ extern "C" int zk_keccak_open(const uint8_t* data, uint64_t n_bytes, const uint6
     int rc = 0;
     const void* p = nullptr;
     u64 rh[4];
-    Fr r;
     if ((rc = stage(s, data, (size_t)n_bytes, dev, &p))) goto fail;
     s->keccak_gen.data = (const uint8_t*)p;
     if ((rc = stage(s, offsets, (size_t)(n_msgs + 1) * 8, dev, &p))) goto fail;
@@ -1476,13 +1506,7 @@ extern "C" int zk_keccak_open(const uint8_t* data, uint64_t n_bytes, const uint6
     } else {
         memcpy(rh, randomness, 32);
     }
-    for (int k = 0; k < 4; k++) { r.v[2 * k] = (u32)rh[k]; r.v[2 * k + 1] = (u32)(rh[k] >> 32); }
-    {
-        u64* d_rpow = nullptr;
-        if ((rc = dev_alloc(s, (void**)&d_rpow, KT_RPOW_ROWS * 4 * sizeof(u64)))) goto fail;
-        zk_launch_keccak_rpow(s->stream, r, d_rpow);
-        s->keccak_gen.rpow = d_rpow;
-    }
+    if ((rc = keccak_rpow_open(s, rh, &s->keccak_gen.rpow))) goto fail;
     if (rows_dev) {
         s->keccak_gen.rows = rows_dev;
     } else {
@@ -1852,17 +1876,6 @@ extern "C" int zk_ecdsa_open_batches(const zk_ecdsa_batch* bt, uint32_t n_batche
     a.n = n;
     ecdsa_single_batch(a);
     a.n0 = bt[0].n;
-    {   // the fixed-base table of G: built once per device (ordered before this session's first pass: same stream + a synchronisation)
-        std::lock_guard<std::mutex> lock(g_dev_mutex);
-        if (!g_secp_comb[s->device]) {
-            u32* tab = nullptr;
-            if (hipMalloc(&tab, (size_t)ECDSA_COMB_ENTRIES * 16 * sizeof(u32)) != hipSuccess) { rc = -2; g_err = "zk_ecdsa_open: table allocation failed"; goto fail; }
-            zk_launch_ecdsa_comb_build(s->stream, tab);
-            if (hipStreamSynchronize(s->stream) != hipSuccess) { (void)hipFree(tab); rc = -2; g_err = "zk_ecdsa_open: table build failed"; goto fail; }
-            g_secp_comb[s->device] = tab;
-        }
-        a.gcomb = g_secp_comb[s->device];
-    }
     for (u32 k = 0; k < n_batches; k++) {
         const u64 stride = bt[k].layout ? 288 : 160;
         const uint8_t* d_bytes;
@@ -1883,17 +1896,7 @@ extern "C" int zk_ecdsa_open_batches(const zk_ecdsa_batch* bt, uint32_t n_batche
             for (int c = 0; c < 5; c++) a.off1[c] = OFF[bt[k].layout ? 1 : 0][c];
         }
     }
-    // lane pairs while the batch cannot fill the chip anyway (the pass is then bound by one lane's dependent chain: halve it);
-    // one lane per signature beyond that (less total work); lane quads up to 2^14 signatures — one wavefront per SIMD at most —, where the
-    // two extra lanes take u1 G off the pair's chain (secp256k1.hpp ecdsa_partial4: 1.09-1.11 -> 0.99-1.02 ms; 2^15 signatures as quads
-    // are two wavefronts per SIMD: 1.67 ms against 1.13).  ZK_ECDSA_LANES=1|2|4 overrides (tuning / tests).
-    a.lanes_per_sig = n <= (1ull << 14) ? 4u : n <= (1ull << 16) ? 2u : 1u;
-    if (const char* e = getenv("ZK_ECDSA_LANES")) { const int v = atoi(e); a.lanes_per_sig = v == 4 ? 4u : v == 2 ? 2u : 1u; }
-    if (a.lanes_per_sig == 4u && !a.gcomb) a.lanes_per_sig = 2u;  // (the four-lane form takes u1 G from the comb table)
-    a.first = 0;
-    a.qtab_lanes = ((n * a.lanes_per_sig + 63) / 64) * 64;
-    if (a.qtab_lanes > ZK_ECDSA_CHUNK_LANES) a.qtab_lanes = ZK_ECDSA_CHUNK_LANES;  // larger batches: chunked launches over one set of tables
-    if ((rc = dev_alloc(s, (void**)&a.qtab, (size_t)a.qtab_lanes * 15 * 24 * sizeof(u32)))) goto fail;
+    if ((rc = secp_lanes_open(s, n, "zk_ecdsa_open", a.lanes))) goto fail;
     if ((rc = session_common_init(s))) goto fail;
     *out = s;
     return 0;
@@ -3876,7 +3879,6 @@ extern "C" int zk_tx_assign_open(const zk_tx_inputs* in, const zk_tx_wire* out_d
     int rc = 0;
     const void* p = nullptr;
     u64 rh[4];
-    Fr r;
     std::vector<u64> h_off((size_t)n + 1, 0);
     // the offsets are validated on the host (a device caller's are read back once)
     if (dev) {
@@ -3891,18 +3893,6 @@ extern "C" int zk_tx_assign_open(const zk_tx_inputs* in, const zk_tx_wire* out_d
         if (h_off[j] > h_off[j + 1]) { rc = -1; g_err = "zk_tx_assign_open: calldata offsets must be non-decreasing"; goto fail; }
     if (h_off[n] > mc) { rc = -1; g_err = "zk_tx_assign_open: more calldata bytes than max_calldata_bytes"; goto fail; }
     if (h_off[n] && !in->calldata) { rc = -1; g_err = "zk_tx_assign_open: calldata is null"; goto fail; }
-    for (int k = 0; k < 4; k++) { r.v[2 * k] = (u32)rh[k]; r.v[2 * k + 1] = (u32)(rh[k] >> 32); }
-    {   // the fixed-base table of G, as zk_ecdsa_open
-        std::lock_guard<std::mutex> lock(g_dev_mutex);
-        if (!g_secp_comb[s->device]) {
-            u32* tab = nullptr;
-            if (hipMalloc(&tab, (size_t)ECDSA_COMB_ENTRIES * 16 * sizeof(u32)) != hipSuccess) { rc = -2; g_err = "zk_tx_assign_open: table allocation failed"; goto fail; }
-            zk_launch_ecdsa_comb_build(s->stream, tab);
-            if (hipStreamSynchronize(s->stream) != hipSuccess) { (void)hipFree(tab); rc = -2; g_err = "zk_tx_assign_open: table build failed"; goto fail; }
-            g_secp_comb[s->device] = tab;
-        }
-        a.gcomb = g_secp_comb[s->device];
-    }
     if ((rc = stage(s, in->fields, (size_t)n * TX_NFIELDS * 32, dev, &p))) goto fail;
     a.fields = (const u64*)p;
     if ((rc = stage(s, in->to_is_none, (size_t)n * 4, dev, &p))) goto fail;
@@ -3915,16 +3905,13 @@ extern "C" int zk_tx_assign_open(const zk_tx_inputs* in, const zk_tx_wire* out_d
     } else {  // staged with its last aligned word whole (the sponge reads whole aligned words)
         void* d = nullptr;
         if ((rc = dev_alloc(s, &d, (size_t)((h_off[n] + 15) & ~7ull)))) goto fail;
-        HIP_TRY(hipMemcpyAsync(d, in->calldata, (size_t)h_off[n], hipMemcpyHostToDevice, s->stream));
+        if (hipMemcpyAsync(d, in->calldata, (size_t)h_off[n], hipMemcpyHostToDevice, s->stream) != hipSuccess) { rc = -2; g_err = "zk_tx_assign_open: calldata upload failed"; goto fail; }
         a.data = (const uint8_t*)d;
     }
     a.n = n; a.max_txs = mt; a.max_calldata = mc; a.chain_id = in->chain_id;
+    if ((rc = keccak_rpow_open(s, rh, &a.rpow))) goto fail;
     {
-        u64* d_rpow = nullptr;
         void* d = nullptr;
-        if ((rc = dev_alloc(s, (void**)&d_rpow, KT_RPOW_ROWS * 4 * sizeof(u64)))) goto fail;
-        zk_launch_keccak_rpow(s->stream, r, d_rpow);
-        a.rpow = d_rpow;
         if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 32))) goto fail;
         a.hash = (u64*)d;
         if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 8))) goto fail;
@@ -3940,13 +3927,7 @@ extern "C" int zk_tx_assign_open(const zk_tx_inputs* in, const zk_tx_wire* out_d
         if ((rc = dev_alloc(s, &d, 64))) goto fail;
         a.n_keccak = (u32*)d;
     }
-    // lane forms as zk_ecdsa_open (ZK_ECDSA_LANES overrides here too)
-    a.lanes_per_sig = n <= (1ull << 14) ? 4u : n <= (1ull << 16) ? 2u : 1u;
-    if (const char* e = getenv("ZK_ECDSA_LANES")) { const int v = atoi(e); a.lanes_per_sig = v == 4 ? 4u : v == 2 ? 2u : 1u; }
-    a.qtab_lanes = ((n * a.lanes_per_sig + 63) / 64) * 64;
-    if (a.qtab_lanes == 0) a.qtab_lanes = 64;
-    if (a.qtab_lanes > ZK_ECDSA_CHUNK_LANES) a.qtab_lanes = ZK_ECDSA_CHUNK_LANES;
-    if ((rc = dev_alloc(s, (void**)&a.qtab, (size_t)a.qtab_lanes * 15 * 24 * sizeof(u32)))) goto fail;
+    if ((rc = secp_lanes_open(s, n, "zk_tx_assign_open", a.lanes))) goto fail;
     {
         const zk_tx_wire* o = out_dev;
         void* d = nullptr;
@@ -4019,23 +4000,10 @@ extern "C" int zk_sig_assign_open(const zk_sig_inputs* in, const zk_sig_wire* ou
     memset(&a, 0, sizeof(a));
     int rc = 0;
     const void* p = nullptr;
-    Fr r;
     if (dev) {
         if (fetch_small(s->stream, a.rand, in->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
     } else {
         memcpy(a.rand, in->randomness, 32);
-    }
-    for (int k = 0; k < 4; k++) { r.v[2 * k] = (u32)a.rand[k]; r.v[2 * k + 1] = (u32)(a.rand[k] >> 32); }
-    {   // the fixed-base table of G, as zk_ecdsa_open
-        std::lock_guard<std::mutex> lock(g_dev_mutex);
-        if (!g_secp_comb[s->device]) {
-            u32* tab = nullptr;
-            if (hipMalloc(&tab, (size_t)ECDSA_COMB_ENTRIES * 16 * sizeof(u32)) != hipSuccess) { rc = -2; g_err = "zk_sig_assign_open: table allocation failed"; goto fail; }
-            zk_launch_ecdsa_comb_build(s->stream, tab);
-            if (hipStreamSynchronize(s->stream) != hipSuccess) { (void)hipFree(tab); rc = -2; g_err = "zk_sig_assign_open: table build failed"; goto fail; }
-            g_secp_comb[s->device] = tab;
-        }
-        a.gcomb = g_secp_comb[s->device];
     }
     if ((rc = stage(s, in->fields, (size_t)n * SIG_NFIELDS * 32, dev, &p))) goto fail;
     a.fields = (const u64*)p;
@@ -4048,12 +4016,9 @@ extern "C" int zk_sig_assign_open(const zk_sig_inputs* in, const zk_sig_wire* ou
         a.expect_valid = (const u32*)p;
     }
     a.n = n; a.v_offset = in->v_offset;
+    if ((rc = keccak_rpow_open(s, a.rand, &a.rpow))) goto fail;
     {
-        u64* d_rpow = nullptr;
         void* d = nullptr;
-        if ((rc = dev_alloc(s, (void**)&d_rpow, KT_RPOW_ROWS * 4 * sizeof(u64)))) goto fail;
-        zk_launch_keccak_rpow(s->stream, r, d_rpow);
-        a.rpow = d_rpow;
         if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 64))) goto fail;
         a.pk = (u64*)d;
         if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 4))) goto fail;
@@ -4071,13 +4036,7 @@ extern "C" int zk_sig_assign_open(const zk_sig_inputs* in, const zk_sig_wire* ou
         a.n_sig_rows = (u32*)d + 1;
         if (hipMemsetAsync(d, 0, 64, s->stream) != hipSuccess) { rc = -2; g_err = "zk_sig_assign_open: counter reset failed"; goto fail; }  // (a read before any pass: no rows)
     }
-    // lane forms as zk_ecdsa_open (ZK_ECDSA_LANES overrides here too)
-    a.lanes_per_sig = n <= (1ull << 14) ? 4u : n <= (1ull << 16) ? 2u : 1u;
-    if (const char* e = getenv("ZK_ECDSA_LANES")) { const int v = atoi(e); a.lanes_per_sig = v == 4 ? 4u : v == 2 ? 2u : 1u; }
-    a.qtab_lanes = ((n * a.lanes_per_sig + 63) / 64) * 64;
-    if (a.qtab_lanes == 0) a.qtab_lanes = 64;
-    if (a.qtab_lanes > ZK_ECDSA_CHUNK_LANES) a.qtab_lanes = ZK_ECDSA_CHUNK_LANES;
-    if ((rc = dev_alloc(s, (void**)&a.qtab, (size_t)a.qtab_lanes * 15 * 24 * sizeof(u32)))) goto fail;
+    if ((rc = secp_lanes_open(s, n, "zk_sig_assign_open", a.lanes))) goto fail;
     {
         const zk_sig_wire* o = out_dev;
         void* d = nullptr;
