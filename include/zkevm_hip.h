@@ -804,6 +804,42 @@ int zk_sig_assign_read(zk_session* s, const zk_sig_wire* host, uint64_t* n_kecca
 int zk_sig_assign(const zk_sig_inputs* in, const zk_sig_wire* out, uint32_t opts, uint32_t* status_out,
                   uint64_t* n_keccak_out, uint64_t* n_sig_rows_out, zk_result* result);
 
+/* ---- Bytecode table and Bytecode-circuit witness from raw contract code: replaces Bytecode(code).table_assignments()
+ *      (src/zkevm_specs/evm_circuit/typing.py:317-324 init_is_code, :387-427) for a set of contracts, then assign_bytecode_circuit
+ *      (src/zkevm_specs/bytecode_circuit.py:104-167) over those rows and assign_keccak_table (:182-186) over the same codes — from the
+ *      contracts' BYTES (1 byte per byte of code in, where zk_bytecode_assign takes the 192-byte unrolled row).
+ *      Inputs (zk_code_set): the codes back to back with their byte offsets; k (0: no circuit rows); randomness: one cell.
+ *      Outputs (zk_code_wire), T = n_bytes + n_codes table rows:
+ *        table uint64[T][6][4] row-major (hash lo, hi, tag, index, is_code, value): per code in input order a Header row
+ *          (hash, 1, 0, 0, len) and a Byte row (hash, 2, i, is_code_i, byte_i) per byte — zk_evm_tables.bytecode, and zk_bytecode_assign's
+ *          in_rows.  hash = keccak-256 of the code as Word lo / hi.  is_code as init_is_code: the push-data counter starts at 0 per
+ *          code, PUSH1..PUSH32 set it to 1..32, every other byte (0x5f included) to 0.  Duplicate codes are not removed.
+ *        rows uint64[12][2^k][4] column-major (k > 0): cell for cell zk_bytecode_assign's output for (table, row offsets, lengths, k,
+ *          randomness), truncation at 2^k rows and EMPTY_HASH padding included; n_codes == 0: padding only.
+ *        keccak uint64[n_codes][5][4]: zk_keccak_table's rows of the codes (mode 0, KeccakCircuit.add), input order.
+ *      zk_bytecode_from_code_open: with ZK_OPT_DEVICE_PTRS every input is a device pointer and the non-null pointers of `out_dev`
+ *      receive the outputs in place (null: the session owns that buffer); without the flag out_dev must be NULL.  The offsets are read
+ *      at open and fixed for the session; the code bytes are read by every pass.  zk_launch / zk_collect / zk_close as for the other
+ *      assignments: the assignment has no failing case (the tally is always clean; rows_evaluated = T, status uint32[T] all 0).
+ *      zk_bytecode_from_code_read copies the last pass's outputs to the non-null HOST pointers of `host`.
+ *      Errors (never a guess): offsets that decrease, offsets[0] != 0, offsets[n_codes] != n_bytes, n_bytes + n_codes >= 2^31,
+ *      k > 28, `rows` asked for with k == 0. */
+typedef struct zk_code_set {
+    const uint8_t* code;  uint64_t n_bytes;   /* the contracts' bytes back to back */
+    const uint64_t* offsets;                  /* uint64[n_codes + 1]: offsets[0] = 0, non-decreasing, offsets[n_codes] = n_bytes */
+    uint64_t n_codes;
+    uint32_t k;  uint32_t reserved;           /* Bytecode circuit of 2^k rows (1..28); 0 = no circuit rows */
+    const uint64_t* randomness;               /* one cell: keccak_randomness */
+} zk_code_set;
+typedef struct zk_code_wire {                 /* each pointer nullable */
+    uint64_t* table;   /* uint64[n_bytes + n_codes][6][4] row-major */
+    uint64_t* rows;    /* uint64[12][2^k][4] column-major: what zk_bytecode_open takes (k > 0 only) */
+    uint64_t* keccak;  /* uint64[n_codes][5][4] */
+} zk_code_wire;
+int zk_bytecode_from_code_open(const zk_code_set* in, const zk_code_wire* out_dev, uint32_t opts, zk_session** out);
+int zk_bytecode_from_code_read(zk_session* s, const zk_code_wire* host);
+int zk_bytecode_from_code(const zk_code_set* in, const zk_code_wire* out, uint32_t opts, zk_result* result);
+
 #ifdef __cplusplus
 }
 #endif

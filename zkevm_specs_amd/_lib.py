@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = [
     "zk_exp_assign_sizes", "zk_exp_assign_open", "zk_exp_assign_read", "zk_exp_assign", "zk_exp_assign_counts",
     "zk_pi_assign_sizes", "zk_pi_assign_open", "zk_pi_assign_read", "zk_pi_assign",
     "zk_sig_assign_open", "zk_sig_assign_read", "zk_sig_assign",
+    "zk_bytecode_from_code_open", "zk_bytecode_from_code_read", "zk_bytecode_from_code",
 ]
 
 OPT_DEVICE_PTRS = 1
@@ -114,6 +115,15 @@ class ZkSigInputs(ctypes.Structure):
 
 class ZkSigWire(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("bytes", "cells", "meta", "keccak", "sig_table", "aux")]
+
+
+class ZkCodeSet(ctypes.Structure):
+    _fields_ = [("code", ctypes.c_void_p), ("n_bytes", ctypes.c_uint64), ("offsets", ctypes.c_void_p), ("n_codes", ctypes.c_uint64),
+                ("k", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("randomness", ctypes.c_void_p)]
+
+
+class ZkCodeWire(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("table", "rows", "keccak")]
 
 
 class ZkEcdsaBatch(ctypes.Structure):
@@ -300,6 +310,9 @@ def _bind(lib):
     lib.zk_sig_assign_read.argtypes = [vp, ctypes.POINTER(ZkSigWire), ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.zk_sig_assign.argtypes = [ctypes.POINTER(ZkSigInputs), ctypes.POINTER(ZkSigWire), u32, vp, ctypes.POINTER(u64), ctypes.POINTER(u64),
                                   ctypes.POINTER(ZkResult)]
+    lib.zk_bytecode_from_code_open.argtypes = [ctypes.POINTER(ZkCodeSet), ctypes.POINTER(ZkCodeWire), u32, ctypes.POINTER(vp)]
+    lib.zk_bytecode_from_code_read.argtypes = [vp, ctypes.POINTER(ZkCodeWire)]
+    lib.zk_bytecode_from_code.argtypes = [ctypes.POINTER(ZkCodeSet), ctypes.POINTER(ZkCodeWire), u32, ctypes.POINTER(ZkResult)]
     lib.zk_launch.argtypes = [vp, vp]
     lib.zk_collect.argtypes = [vp, ctypes.POINTER(ZkResult)]
     lib.zk_read_status.argtypes = [vp, vp]

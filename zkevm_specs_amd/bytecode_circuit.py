@@ -26,12 +26,32 @@ def assign_keccak_table(bytecodes, keccak_randomness):
     return rows
 
 
-def assign_bytecode_circuit(k, bytecodes, keccak_randomness):
+def _is_raw_codes(bytecodes):
+    return not isinstance(bytecodes, tuple) and len(bytecodes) > 0 and all(isinstance(b, (bytes, bytearray)) for b in bytecodes)
+
+
+def bytecode_table(bytecodes, device=None):
+    """`Bytecode(code).table_assignments()` (evm_circuit/typing.py:387-427) of every code of `bytecodes` (a sequence of bytes or
+    bytearray), on the device from the raw bytes (zk_bytecode_from_code): -> the (rows uint64[n, 6, 4], row offsets uint64[m + 1],
+    byte lengths uint64[m]) wire tuple that assign_bytecode_circuit and zk_evm_tables.bytecode accept."""
+    import numpy as np
+
+    codes = [bytes(b) for b in bytecodes]
+    data, offsets = engine.pack_messages(codes)
+    table = oneshot.bytecode_from_code(data, offsets, 0, 0, device=device)[1]
+    return table, offsets + np.arange(len(codes) + 1, dtype=np.uint64), np.array([len(c) for c in codes], dtype=np.uint64)
+
+
+def assign_bytecode_circuit(k, bytecodes, keccak_randomness, device=None):
     """`assign_bytecode_circuit(k, bytecodes, keccak_randomness)` (bytecode_circuit.py:104-167) on the device: bytecodes =
     sequence of reference-style UnrolledBytecode (or the (rows, offsets, lengths) wire arrays) -> the 2^k circuit rows
-    in wire form uint64[12, 2^k, 4] (what verify_bytecode_rows / engine.open_bytecode take)."""
+    in wire form uint64[12, 2^k, 4] (what verify_bytecode_rows / engine.open_bytecode take).  A sequence of raw `bytes` /
+    `bytearray` is unrolled on the device as well (zk_bytecode_from_code: table rows and circuit rows from the code bytes)."""
+    if _is_raw_codes(bytecodes):
+        data, offsets = engine.pack_messages([bytes(b) for b in bytecodes])
+        return oneshot.bytecode_from_code(data, offsets, k, _n(keccak_randomness), device=device)[2]  # zk_bytecode_from_code
     in_rows, offsets, lengths = bytecodes if isinstance(bytecodes, tuple) else flatten_unrolled_bytecodes(bytecodes)
-    return oneshot.bytecode_assign(in_rows, offsets, lengths, k, _n(keccak_randomness))[1]  # zk_bytecode_assign
+    return oneshot.bytecode_assign(in_rows, offsets, lengths, k, _n(keccak_randomness), device=device)[1]  # zk_bytecode_assign
 
 
 def verify_bytecode_rows(rows, keccak_table, keccak_randomness, success=True):

@@ -31,6 +31,7 @@
 #include "pi_circuit.hpp"
 #include "state_assign.hpp"
 #include "bytecode_assign.hpp"
+#include "bytecode_code.hpp"
 #include "state_rekey.hpp"
 #include "ecc_circuit.hpp"
 #include "withdrawal_circuit.hpp"
@@ -100,7 +101,7 @@ struct zk_session {
     std::vector<u64> w64[4];              // assignment sessions: work / output buffers
     std::vector<u32> out32;
     void (*pass)(zk_session*) = nullptr;  // assignment sessions: one pass computes the outputs and fills `status`
-    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig
+    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code
     u64 n_ops = 0;                        // RW -> State ops: 1 + kept rows
     std::vector<u32> rekey_plan;          // RW -> State ops: the RwkHostPlan's plan (as words) ...
     std::vector<u32> rekey_jobs;          // ... and its rank jobs (cls, field, base, count)
@@ -120,6 +121,10 @@ struct zk_session {
     BcaArgs bca;
     std::vector<BcaChunk> bca_chunks;
     std::vector<uint8_t> bca_map;
+    BccArgs bcc;                    // Bytecode table / rows / keccak rows from raw code (its chunk tables live in bca_chunks, bca_map)
+    KeccakGenArgs bcc_kgen;
+    std::vector<u64> bcc64[8];      // offsets, rpow, chunk_acc, chunk_in, part, table, rows, keccak rpow
+    std::vector<u32> bcc32[4];      // row_off, code_chunk0, chunk_m, chunk_state
     CpaArgs cpa;
     CpaPlan cpa_plan;
     EcdsaArgs ecdsa;
@@ -1083,6 +1088,99 @@ extern "C" int zk_bytecode_assign(const uint64_t* in_rows, uint64_t n_rows, cons
     rc = zk_launch(s, nullptr);
     if (!rc) rc = zk_collect(s, result);
     if (!rc) rc = zk_bytecode_assign_read(s, rows_out);
+    zk_close(s);
+    return rc;
+}
+
+// ---- Bytecode table + Bytecode-circuit witness + keccak rows from raw contract code (bytecode_code.hpp): the device functions in host loops
+static void bytecode_from_code_pass(zk_session* s) {
+    BccArgs& a = s->bcc;
+    for (u64 c = 0; c < a.p.n_chunks; c++) bcc_chunk(a, c);
+    for (u64 j = 0; j < a.n_codes; j++) bca_prefix_code(a.p, j);
+    for (u64 j = 0; j < a.n_codes; j++) keccak_table_row(s->bcc_kgen, j);
+    const u64 n_lanes = a.n_rows > a.n_out ? a.n_rows : a.n_out;
+    for (u64 i = 0; i < n_lanes; i++) bcc_write_row(a, i);
+}
+extern "C" int zk_bytecode_from_code_open(const zk_code_set* in, const zk_code_wire* out_dev, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_bytecode_from_code_open");
+    ARG_TRY(in && out && in->randomness && in->offsets && (in->code || in->n_bytes == 0) && !out_dev, "zk_bytecode_from_code_open: bad arguments");
+    ARG_TRY(in->k <= 28, "zk_bytecode_from_code_open: k must be at most 28");
+    ARG_TRY(in->n_bytes < (1ull << 31) && in->n_codes < (1ull << 31) && in->n_bytes + in->n_codes < (1ull << 31),
+            "zk_bytecode_from_code_open: n_bytes + n_codes must be below 2^31");
+    const u64 n_codes = in->n_codes, n_bytes = in->n_bytes, n_rows = n_bytes + n_codes, n_out = in->k ? 1ull << in->k : 0;
+    const u64* off = in->offsets;
+    ARG_TRY(off[0] == 0, "zk_bytecode_from_code_open: offsets must start at 0");
+    for (u64 j = 0; j < n_codes; j++) ARG_TRY(off[j] <= off[j + 1], "zk_bytecode_from_code_open: offsets must be non-decreasing");
+    ARG_TRY(off[n_codes] == n_bytes, "zk_bytecode_from_code_open: offsets must end at n_bytes");
+    zk_session* s = new_session(n_rows, false);
+    s->a8.assign((n_bytes + 15) & ~7ull, 0);  // (the sponge reads whole aligned words)
+    if (n_bytes) memcpy(s->a8.data(), in->code, n_bytes);
+    s->bcc64[0].assign(off, off + n_codes + 1);
+    std::vector<BcaChunk>& chunks = s->bca_chunks;
+    s->bcc32[0].assign(n_codes + 1, 0);  // row_off
+    s->bcc32[1].assign(n_codes + 1, 0);  // code_chunk0
+    for (u64 j = 0; j < n_codes; j++) {
+        s->bcc32[0][j] = (u32)(off[j] + j);
+        s->bcc32[1][j] = (u32)chunks.size();
+        for (u64 b = off[j]; b < off[j + 1]; b += BCA_CHUNK) {
+            BcaChunk c;
+            c.code = (u32)j; c.start = (u32)b;
+            c.count = (u32)((off[j + 1] - b < BCA_CHUNK) ? off[j + 1] - b : BCA_CHUNK);
+            c.first = 0;
+            chunks.push_back(c);
+        }
+    }
+    s->bcc32[0][n_codes] = (u32)n_rows;
+    s->bcc32[1][n_codes] = (u32)chunks.size();
+    s->bcc64[1].assign(BCA_RPOW_ROWS * 4, 0);
+    bca_fill_rpow(cell_of(in->randomness), s->bcc64[1].data());
+    s->bcc64[2].assign(chunks.size() * 4 + 4, 0);  // chunk_acc
+    s->bcc64[3].assign(chunks.size() * 4 + 4, 0);  // chunk_in
+    s->bcc64[4].assign(n_bytes * 4 + 4, 0);        // part
+    s->bcc64[5].assign(n_rows * BCC_TABLE_NCELLS * 4 + 4, 0);  // table
+    s->bcc64[6].assign(n_out * BCA_OUT_NCELLS * 4 + 4, 0);     // rows
+    s->bcc64[7].assign(KT_RPOW_ROWS * 4, 0);
+    kt_fill_rpow(cell_of(in->randomness), s->bcc64[7].data());
+    s->bcc32[2].assign(chunks.size() + 1, 0);      // chunk_m
+    s->bcc32[3].assign(chunks.size() + 1, 0);      // chunk_state
+    s->bca_map.assign((chunks.size() + 1) * BCA_MAP_STRIDE, 0);
+    s->keccak_rows.assign(n_codes * KT_NCELLS * 4 + 4, 0);
+    KeccakGenArgs& g = s->bcc_kgen;
+    g.data = s->a8.data(); g.offsets = s->bcc64[0].data(); g.n = n_codes; g.rpow = s->bcc64[7].data(); g.rows = s->keccak_rows.data();
+    g.mode = KT_MODE_CIRCUIT; g.long_list = nullptr; g.long_count = nullptr;
+    BccArgs& a = s->bcc;
+    memset(&a, 0, sizeof(a));
+    a.code = s->a8.data(); a.offsets = s->bcc64[0].data(); a.row_off = s->bcc32[0].data();
+    a.n_bytes = n_bytes; a.n_codes = n_codes; a.n_rows = n_rows; a.n_out = n_out;
+    a.p.chunks = chunks.data(); a.p.code_chunk0 = s->bcc32[1].data(); a.p.n_chunks = chunks.size(); a.p.n_codes = n_codes;
+    a.p.rpow = s->bcc64[1].data(); a.p.chunk_acc = s->bcc64[2].data(); a.p.chunk_in = s->bcc64[3].data(); a.p.chunk_m = s->bcc32[2].data();
+    a.p.chunk_state = s->bcc32[3].data(); a.p.chunk_map = s->bca_map.data();
+    a.part = s->bcc64[4].data(); a.keccak = g.rows; a.table = s->bcc64[5].data(); a.rows = s->bcc64[6].data();
+    s->pass = bytecode_from_code_pass;
+    s->assign_kind = 10;
+    *out = s;
+    return 0;
+}
+extern "C" int zk_bytecode_from_code_read(zk_session* s, const zk_code_wire* host) {
+    ARG_TRY(s && s->assign_kind == 10, "zk_bytecode_from_code_read: bad arguments");
+    const BccArgs& a = s->bcc;
+    ARG_TRY(!(host && host->rows) || a.n_out, "zk_bytecode_from_code_read: rows asked for with k == 0");
+    if (host) {
+        if (host->table) memcpy(host->table, a.table, a.n_rows * BCC_TABLE_NCELLS * 32);
+        if (host->rows) memcpy(host->rows, a.rows, a.n_out * BCA_OUT_NCELLS * 32);
+        if (host->keccak) memcpy(host->keccak, a.keccak, a.n_codes * KT_NCELLS * 32);
+    }
+    return 0;
+}
+extern "C" int zk_bytecode_from_code(const zk_code_set* in, const zk_code_wire* out, uint32_t opts, zk_result* result) {
+    ARG_TRY(result && out && in, "zk_bytecode_from_code: null argument");
+    ARG_TRY(in->k > 0 || !out->rows, "zk_bytecode_from_code: rows asked for with k == 0");
+    zk_session* s = nullptr;
+    int rc = zk_bytecode_from_code_open(in, nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc) rc = zk_bytecode_from_code_read(s, out);
     zk_close(s);
     return rc;
 }

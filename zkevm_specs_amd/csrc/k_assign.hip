@@ -387,6 +387,10 @@ void zk_launch_bytecode_assign(hipStream_t st, const BcaArgs& a, u32* status, Zk
     }
     hipLaunchKernelGGL(bca_rows_wave_kernel, dim3((u32)((a.n_out + 255) / 256)), dim3(256), 0, st, a, status, tally);
 }
+// the prefix pass alone, over chunk tables a caller filled itself (k_bytecode_code.hip: chunks of bytes)
+void zk_launch_bca_prefix(hipStream_t st, const BcaArgs& a) {
+    if (a.n_codes) hipLaunchKernelGGL(bca_prefix_wave_kernel, dim3((u32)a.n_codes), dim3(64 * BCA_ROUND_WAVES), 0, st, a);
+}
 // Copy-circuit witness assignment (copy_assign.hpp)
 __global__ void cpa_rpow_kernel(Fr r, u64* out) {  // entry m = Mont(r^m), one lane each (cpa_fill_rpow is the host form)
     if (blockIdx.x == 0 && threadIdx.x < CPA_RPOW_ROWS) cpa_store(out + 4 * threadIdx.x, fr_pow_small_mont(fr_to_mont(r), threadIdx.x));

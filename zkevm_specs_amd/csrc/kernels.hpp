@@ -13,6 +13,7 @@
 #include "state_assign.hpp"
 #include "secp256k1.hpp"
 #include "bytecode_assign.hpp"
+#include "bytecode_code.hpp"
 #include "copy_assign.hpp"
 #include "pi_circuit.hpp"
 #include "state_rekey.hpp"
@@ -74,6 +75,10 @@ void zk_launch_rekey_scan(hipStream_t st, const RekeyArgs& a);  // open-time cla
 void zk_launch_state_rekey(hipStream_t st, const RekeyArgs& a, u32* status, ZkTally* tally);
 void zk_launch_bca_rpow(hipStream_t st, const Fr& r, u64* out);
 void zk_launch_bytecode_assign(hipStream_t st, const BcaArgs& a, u32* status, ZkTally* tally);
+void zk_launch_bca_prefix(hipStream_t st, const BcaArgs& a);  // its prefix pass alone (value_rlc and counter entering every chunk)
+// Bytecode table + circuit rows + keccak rows from raw code (k_bytecode_code.hip); side / ev_fork / ev_join as zk_launch_pi_assign
+void zk_launch_bytecode_from_code(hipStream_t st, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join, const BccArgs& a,
+                                  const KeccakGenArgs& g, u32* status, ZkTally* tally);
 void zk_launch_pi_rows(hipStream_t st, const PiArgs& a, u64 lo, u64 hi, u32* status, ZkTally* tally);
 void zk_launch_pi_copy(hipStream_t st, const PiCopyArgs& a, u32* status, ZkTally* tally);
 void zk_launch_cpa_rpow(hipStream_t st, const Fr& r, u64* out);

@@ -582,7 +582,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -623,6 +623,8 @@ struct zk_session {
     PiaArgs pia;
     PiaSizes pia_sizes;
     KeccakGenArgs pia_kgen;
+    BccArgs bcc;                    // SESSION_BCC (zk_bytecode_from_code*): the chunk tables sit in bcc.p, the keccak pass's arguments in bcc_kgen
+    KeccakGenArgs bcc_kgen;
     u64 pia_host[4] = {0, 0, 0, 0};  // small host words the open uploads (their source must outlive the asynchronous copy)
     RekeyArgs rekey;
     RwkPlan rekey_plan_host;      // the compact-key plan as uploaded (host copy owned by the session: the upload needs no synchronisation of its own)
@@ -2798,6 +2800,22 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
         zk_launch_pi_assign(s->stream, pside, s->ev_fork, s->ev_join, s->pia, s->pia_kgen, status, s->d_tally);
         break;
     }
+    case SESSION_BCC: {
+        // the keccak kernels (the code hashes: only the row writer needs them) run on the device's side stream beside the byte scans
+        {
+            std::lock_guard<std::mutex> lock(g_dev_mutex);
+            if (!g_side_stream[s->device]) HIP_TRY(hipStreamCreateWithFlags(&g_side_stream[s->device], hipStreamNonBlocking));
+        }
+        if (!s->ev_fork) {
+            int erc = arena_event(s->device, &s->ev_fork);
+            if (!erc) erc = arena_event(s->device, &s->ev_join);
+            if (erc) return erc;
+        }
+        hipStream_t cside = g_side_stream[s->device];
+        if (cside == s->stream) cside = nullptr;
+        zk_launch_bytecode_from_code(s->stream, cside, s->ev_fork, s->ev_join, s->bcc, s->bcc_kgen, status, s->d_tally);
+        break;
+    }
     case SESSION_REKEY: zk_launch_state_rekey(s->stream, s->rekey, status, s->d_tally); break;
     case SESSION_EVM: {
         // the state-sorted lane mapping is derived from the step column on every pass
@@ -4089,6 +4107,152 @@ extern "C" int zk_sig_assign(const zk_sig_inputs* in, const zk_sig_wire* out, ui
     if (!rc) rc = zk_collect(s, result);
     if (!rc && !dev && status_out) rc = zk_read_status(s, status_out);
     if (!rc) rc = zk_sig_assign_read(s, dev ? nullptr : out, n_keccak_out, n_sig_rows_out);
+    zk_close(s);
+    return rc;
+}
+
+// ---- Bytecode table + Bytecode-circuit witness + keccak rows from raw contract code (bytecode_code.hpp, k_bytecode_code.hip)
+extern "C" int zk_bytecode_from_code_open(const zk_code_set* in, const zk_code_wire* out_dev, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_bytecode_from_code_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(in && out && in->randomness && in->offsets && (in->code || in->n_bytes == 0), "zk_bytecode_from_code_open: bad arguments");
+    ARG_TRY(in->k <= 28, "zk_bytecode_from_code_open: k must be at most 28");
+    ARG_TRY(in->n_bytes < (1ull << 31) && in->n_codes < (1ull << 31) && in->n_bytes + in->n_codes < (1ull << 31),
+            "zk_bytecode_from_code_open: n_bytes + n_codes must be below 2^31");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    ARG_TRY(dev || !out_dev, "zk_bytecode_from_code_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    ARG_TRY(in->k > 0 || !(out_dev && out_dev->rows), "zk_bytecode_from_code_open: rows asked for with k == 0");
+    const u64 n_codes = in->n_codes, n_bytes = in->n_bytes, n_rows = n_bytes + n_codes;
+    zk_session* s = new zk_session();
+    s->kind = SESSION_BCC;
+    s->n = n_rows;
+    BccArgs& a = s->bcc;
+    KeccakGenArgs& g = s->bcc_kgen;
+    memset(&a, 0, sizeof(a));
+    memset(&g, 0, sizeof(g));
+    int rc = 0;
+    const void* p = nullptr;
+    void* d = nullptr;
+    u64 rh[4];
+    Fr r;
+    std::vector<u64> h_off((size_t)n_codes + 1, 0);
+    std::vector<BcaChunk> chunks;
+    std::vector<u32> code_chunk0((size_t)n_codes + 1, 0), row_off((size_t)n_codes + 1, 0);
+    // the offsets are validated on the host (a device caller's are read back once); the chunk table over them is index plumbing
+    if (dev) {
+        if (fetch_small(s->stream, h_off.data(), in->offsets, (n_codes + 1) * 8)) { rc = -2; g_err = "offsets download failed"; goto fail; }
+        if (fetch_small(s->stream, rh, in->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
+    } else {
+        memcpy(h_off.data(), in->offsets, (n_codes + 1) * 8);
+        memcpy(rh, in->randomness, 32);
+    }
+    if (h_off[0] != 0) { rc = -1; g_err = "zk_bytecode_from_code_open: offsets must start at 0"; goto fail; }
+    for (u64 j = 0; j < n_codes; j++)
+        if (h_off[j] > h_off[j + 1]) { rc = -1; g_err = "zk_bytecode_from_code_open: offsets must be non-decreasing"; goto fail; }
+    if (h_off[n_codes] != n_bytes) { rc = -1; g_err = "zk_bytecode_from_code_open: offsets must end at n_bytes"; goto fail; }
+    for (u64 j = 0; j < n_codes; j++) {
+        code_chunk0[j] = (u32)chunks.size();
+        row_off[j] = (u32)(h_off[j] + j);
+        for (u64 b = h_off[j]; b < h_off[j + 1]; b += BCA_CHUNK) {
+            BcaChunk c;
+            c.code = (u32)j; c.start = (u32)b;
+            c.count = (u32)((h_off[j + 1] - b < BCA_CHUNK) ? h_off[j + 1] - b : BCA_CHUNK);
+            c.first = 0;
+            chunks.push_back(c);
+        }
+    }
+    code_chunk0[n_codes] = (u32)chunks.size();
+    row_off[n_codes] = (u32)n_rows;
+    if (dev || !n_bytes) {
+        if ((rc = stage(s, n_bytes ? in->code : nullptr, (size_t)n_bytes, dev, &p))) goto fail;
+        a.code = (const uint8_t*)p;
+    } else {  // staged with its last aligned word whole (the sponge reads whole aligned words)
+        if ((rc = dev_alloc(s, &d, (size_t)((n_bytes + 15) & ~7ull)))) goto fail;
+        if (hipMemcpyAsync(d, in->code, (size_t)n_bytes, hipMemcpyHostToDevice, s->stream) != hipSuccess) { rc = -2; g_err = "zk_bytecode_from_code_open: code upload failed"; goto fail; }
+        a.code = (const uint8_t*)d;
+    }
+    if ((rc = stage(s, in->offsets, (size_t)(n_codes + 1) * 8, dev, &p))) goto fail;
+    a.offsets = (const u64*)p;
+    if ((rc = stage(s, row_off.data(), row_off.size() * 4, false, &p))) goto fail;
+    a.row_off = (const u32*)p;
+    if ((rc = stage(s, chunks.empty() ? nullptr : chunks.data(), chunks.size() * sizeof(BcaChunk), false, &p))) goto fail;
+    a.p.chunks = (const BcaChunk*)p;
+    if ((rc = stage(s, code_chunk0.data(), code_chunk0.size() * 4, false, &p))) goto fail;
+    a.p.code_chunk0 = (const u32*)p;
+    a.n_bytes = n_bytes; a.n_codes = n_codes; a.n_rows = n_rows; a.n_out = in->k ? 1ull << in->k : 0;
+    a.p.n_codes = n_codes; a.p.n_chunks = chunks.size();
+    for (int q = 0; q < 4; q++) { r.v[2 * q] = (u32)rh[q]; r.v[2 * q + 1] = (u32)(rh[q] >> 32); }
+    {
+        u64* d_rpow = nullptr;
+        if ((rc = dev_alloc(s, (void**)&d_rpow, BCA_RPOW_ROWS * 32))) goto fail;
+        zk_launch_bca_rpow(s->stream, r, d_rpow);
+        a.p.rpow = d_rpow;
+    }
+    // the host vectors above go out of scope with this call
+    if (hipStreamSynchronize(s->stream) != hipSuccess) { rc = -2; g_err = "zk_bytecode_from_code_open: upload failed"; goto fail; }
+    if ((rc = dev_alloc(s, &d, chunks.size() * 32))) goto fail;
+    a.p.chunk_acc = (u64*)d;
+    if ((rc = dev_alloc(s, &d, chunks.size() * 4))) goto fail;
+    a.p.chunk_m = (u32*)d;
+    if ((rc = dev_alloc(s, &d, chunks.size() * (size_t)BCA_MAP_STRIDE))) goto fail;
+    a.p.chunk_map = (uint8_t*)d;
+    if ((rc = dev_alloc(s, &d, chunks.size() * 4))) goto fail;
+    a.p.chunk_state = (u32*)d;
+    if ((rc = dev_alloc(s, &d, chunks.size() * 32))) goto fail;
+    a.p.chunk_in = (u64*)d;
+    if ((rc = dev_alloc(s, &d, (size_t)n_bytes * 32))) goto fail;
+    a.part = (u64*)d;
+    // the keccak pass over the same bytes (KeccakCircuit.add mode), as zk_keccak_open sets it up
+    g.data = a.code;
+    g.offsets = a.offsets;
+    g.n = n_codes;
+    g.mode = KT_MODE_CIRCUIT;
+    if (!getenv("ZK_KECCAK_NO_GROUPS")) {
+        u32* d_list = nullptr;
+        if ((rc = dev_alloc(s, (void**)&d_list, ((size_t)n_codes + 1) * sizeof(u32)))) goto fail;
+        g.long_list = d_list + 1;
+        g.long_count = d_list;
+    }
+    if ((rc = keccak_rpow_open(s, rh, &g.rpow))) goto fail;
+#define BCC_OUT_BUF(field, bytes)                                                     \
+    if (out_dev && out_dev->field) a.field = out_dev->field;                          \
+    else { if ((rc = dev_alloc(s, &d, (size_t)(bytes)))) goto fail; a.field = (u64*)d; }
+    BCC_OUT_BUF(table, n_rows * BCC_TABLE_NCELLS * 32)
+    BCC_OUT_BUF(rows, a.n_out * BCA_OUT_NCELLS * 32)
+#undef BCC_OUT_BUF
+    if (out_dev && out_dev->keccak) g.rows = out_dev->keccak;
+    else { if ((rc = dev_alloc(s, &d, (size_t)n_codes * KT_NCELLS * 32))) goto fail; g.rows = (u64*)d; }
+    a.keccak = g.rows;
+    if ((rc = session_common_init(s))) goto fail;
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_bytecode_from_code_read(zk_session* s, const zk_code_wire* host) {
+    ARG_TRY(s && s->kind == SESSION_BCC, "zk_bytecode_from_code_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    const BccArgs& a = s->bcc;
+    ARG_TRY(!(host && host->rows) || a.n_out, "zk_bytecode_from_code_read: rows asked for with k == 0");
+    if (host) {
+        if (host->table && a.n_rows) HIP_TRY(hipMemcpyAsync(host->table, a.table, (size_t)a.n_rows * BCC_TABLE_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        if (host->rows) HIP_TRY(hipMemcpyAsync(host->rows, a.rows, (size_t)a.n_out * BCA_OUT_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        if (host->keccak && a.n_codes) HIP_TRY(hipMemcpyAsync(host->keccak, a.keccak, (size_t)a.n_codes * KT_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+extern "C" int zk_bytecode_from_code(const zk_code_set* in, const zk_code_wire* out, uint32_t opts, zk_result* result) {
+    ARG_TRY(result && out && in, "zk_bytecode_from_code: null argument");
+    ARG_TRY(in->k > 0 || !out->rows, "zk_bytecode_from_code: rows asked for with k == 0");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    int rc = zk_bytecode_from_code_open(in, dev ? out : nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc) rc = zk_bytecode_from_code_read(s, dev ? nullptr : out);
     zk_close(s);
     return rc;
 }

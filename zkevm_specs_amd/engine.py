@@ -927,6 +927,69 @@ def open_tx_assign(tx, randomness, outs=None, device=None):
                  opts, cls=TxAssignSession)
 
 
+# ---- Bytecode table + circuit rows + keccak rows from raw contract code (zk_bytecode_from_code*) ----------------------------------
+CODE_OUTPUTS = ("table", "rows", "keccak")
+
+
+def bytecode_from_code_shapes(n_bytes, n_codes, k):
+    """name -> shape of the uint64 outputs of zk_bytecode_from_code* (rows: None when k == 0)"""
+    return {"table": (n_bytes + n_codes, 6, 4), "rows": (12, 1 << int(k), 4) if int(k) else None, "keccak": (n_codes, 5, 4)}
+
+
+def _bytecode_from_code_args(code, offsets, k, randomness, outs=None):
+    """zk_bytecode_from_code_open / zk_bytecode_from_code over code uint8[n_bytes] (the contracts back to back) and offsets
+    uint64[n_codes + 1] -> (ZkCodeSet, ZkCodeWire of the device outputs or None, opts, kept arrays).  `outs` (device tensors only,
+    each optional): table / rows / keccak buffers the session writes in place."""
+    _expect(code, "code", 1, (None,))
+    _expect(offsets, "offsets", 8, (None,))
+    n_bytes, n_codes = int(code.shape[0]), int(offsets.shape[0]) - 1
+    if n_codes < 0:
+        raise ValueError("offsets: expected n_codes + 1 entries")
+    shapes = bytecode_from_code_shapes(n_bytes, n_codes, k)
+    outs = dict(outs or {})
+    for name, v in outs.items():
+        if v is not None:
+            if shapes[name] is None:
+                raise ValueError("rows_dev needs k > 0")
+            _expect(v, name, 8, shapes[name])
+    out_list = [outs.get(name) for name in CODE_OUTPUTS]
+    a, opts = _prep([code, offsets] + out_list, outputs=range(2, 5))
+    if any(v is not None for v in out_list) and not opts:
+        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
+    rc = _randomness_cells(randomness, a[0])
+    if opts and not _is_device(rc):
+        raise ValueError("mix of host and device buffers")
+    keep = a + [rc]
+    t = _lib.ZkCodeSet(ptr(a[0], n_bytes), n_bytes, ptr(a[1]), n_codes, int(k), 0, ptr(rc))
+    w = _lib.ZkCodeWire(*[ptr(x) for x in a[2:]]) if opts else None
+    return t, w, opts, keep
+
+
+class BytecodeFromCodeSession(Session):
+    """zk_bytecode_from_code_open: launch() / collect() like the other assignments (status per table row, always 0);
+    read() -> (table uint64[n_bytes + n_codes, 6, 4], rows uint64[12, 2^k, 4] or None when k == 0, keccak uint64[n_codes, 5, 4])
+    of the last pass, as host arrays"""
+
+    def read(self):
+        shapes = bytecode_from_code_shapes(*self._keep[-1])
+        out = [None if shapes[name] is None else np.zeros(shapes[name], dtype=np.uint64) for name in CODE_OUTPUTS]
+        w = _lib.ZkCodeWire(*[ptr(x, x.size if x is not None else 0) for x in out])
+        check(self._lib.zk_bytecode_from_code_read(self._h, ctypes.byref(w)), "zk_bytecode_from_code_read", self._lib)
+        return tuple(out)
+
+
+def open_bytecode_from_code(code, offsets, k, randomness, table_dev=None, rows_dev=None, keccak_dev=None, device=None):
+    """code uint8[n_bytes] + offsets uint64[n_codes + 1] (raw contract code), k (0: no circuit rows), randomness (int or uint64[4])
+    -> BytecodeFromCodeSession.  numpy inputs are staged to HBM; torch CUDA tensors are used in place, and table_dev / rows_dev /
+    keccak_dev (CUDA tensors of the shapes read() returns) then receive the outputs in place: rows_dev and keccak_dev are what
+    open_bytecode takes, table_dev is zk_evm_tables.bytecode."""
+    lib = _lib.init(device)
+    t, w, opts, keep = _bytecode_from_code_args(code, offsets, k, randomness, {"table": table_dev, "rows": rows_dev, "keccak": keccak_dev})
+    sizes = (int(t.n_bytes), int(t.n_codes), int(k))
+    return _open(lib, lib.zk_bytecode_from_code_open, sizes[0] + sizes[1], (keep, t, w, sizes), ctypes.byref(t),
+                 ctypes.byref(w) if w is not None else None, opts, cls=BytecodeFromCodeSession)
+
+
 # ---- Sig circuit witness assignment (zk_sig_assign*) ------------------------------------------------------------------------------
 SIG_ASSIGN_INPUTS = ("fields", "addr", "expect_valid")
 SIG_ASSIGN_OUTPUTS = ("bytes", "cells", "meta", "keccak", "sig_table", "aux")

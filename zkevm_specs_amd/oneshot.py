@@ -112,6 +112,18 @@ def bytecode_assign(in_rows, offsets, lengths, k, randomness, device=None):
     return Result(r), rows
 
 
+def bytecode_from_code(code, offsets, k, randomness, device=None):
+    """zk_bytecode_from_code over raw contract code (engine._bytecode_from_code_args) -> (Result, table uint64[n_bytes + n_codes, 6, 4],
+    rows uint64[12, 2^k, 4] (None when k == 0), keccak uint64[n_codes, 5, 4])"""
+    lib = _lib.init(device)
+    t, _, opts, keep = engine._bytecode_from_code_args(_host(code, np.uint8), _host(offsets, np.uint64), k, randomness)
+    shapes = engine.bytecode_from_code_shapes(int(t.n_bytes), int(t.n_codes), k)
+    out = [None if shapes[name] is None else np.zeros(shapes[name], dtype=np.uint64) for name in engine.CODE_OUTPUTS]
+    w, r = _lib.ZkCodeWire(*[ptr(x, x.size if x is not None else 0) for x in out]), ZkResult()
+    check(lib.zk_bytecode_from_code(ctypes.byref(t), ctypes.byref(w), opts, ctypes.byref(r)), "zk_bytecode_from_code", lib)
+    return (Result(r), *out)
+
+
 def ecdsa_verify(sig_bytes, v=None, layout=0, v_stride=1, device=None):
     """zk_ecdsa_verify -> (Result, status uint32[n])"""
     lib = _lib.init(device)
