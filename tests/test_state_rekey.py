@@ -1,7 +1,13 @@
 """RW table -> State-circuit operations (the sort half; include/zkevm_hip.h zk_state_ops_from_rw*):
 the C-ABI entry against the checker oracle/rw_state_oracle.py — ops, op flags, order and per-row status bit for bit.
 CPU suite: through libzkevm_cpu.so (the same per-row functions and compact-key plan, std::stable_sort).  GPU suite: the HIP
-path (radix passes on the device) on the same cases, 200 fuzzed tables, and the full 2^18-step block."""
+path (radix passes on the device) on the same cases, 200 fuzzed tables, and the full 2^18-step block.
+Directed tables (tests/rekey_cases.py; the list with what each reaches is in DESIGN.md §3 "RW table → State operations"): the tile edges of
+the fast sweep (8,192 keys; look-backs of one, two and three rounds) and of the generic path (4,096 keys), digit distributions over five /
+ten tiles (one key everywhere, sorted, descending with ties, a tile per top digit, digits 0x00 / 0xff, one odd row), the plan's boundaries
+(key widths 4 ... 65 bits, a 32-bit run, a run across two output words, two class widths, nothing kept), the rank rule's thresholds, all
+eleven classes interleaved row by row up to 263,169 rows, two passes of one session, and the assign / compact consumers at 20,000 and 73,729
+rows.  Each case asserts the plan it aims at with the plain-Python plan model first; cases of at most 20,000 rows also run in the CPU suite."""
 import os
 import random
 
@@ -124,10 +130,12 @@ def test_checker_matches_trace_generator():
 
 def fused_equals_two_steps(rows, flags, device):
     """zk_state_assign_from_rw (ops read straight from the RW rows) == zk_state_ops_from_rw followed by zk_state_assign"""
+    fused_equals_two_steps_arrays(rows_to_rowmajor(rows, 14), np.array(flags, dtype=np.uint32), device)
+
+
+def fused_equals_two_steps_arrays(rw, fl, device):
     from zkevm_specs_amd import engine
 
-    rw = rows_to_rowmajor(rows, 14)
-    fl = np.array(flags, dtype=np.uint32)
     _, _, ops, op_flags = oneshot.state_ops_from_rw(rw, fl, device=device)
     r2, st2, rows2, rf2, mpt2 = oneshot.state_assign(ops, op_flags, device=device)
     with engine.open_state_assign_from_rw(rw, fl, device=device) as a:
@@ -245,10 +253,12 @@ def test_gpu_full_block_2p18():
 def compact_equals_full(rows, flags, device, tamper=0):
     """ZK_OPT_STATE_COMPACT: the 15-cell witness of the assignment is columns 0..7 and 50..56 of the 57-cell one, and the State circuit
     gives every row the status it gives the 57-cell row — also after damage to cells both forms carry"""
+    return compact_equals_full_arrays(rows_to_rowmajor(rows, 14), np.array(flags, dtype=np.uint32), device, tamper)
+
+
+def compact_equals_full_arrays(rw, fl, device, tamper=0):
     from zkevm_specs_amd import engine
 
-    rw = rows_to_rowmajor(rows, 14)
-    fl = np.array(flags, dtype=np.uint32)
     with engine.open_state_assign_from_rw(rw, fl, device=device) as a:
         assert a.run().ok
         full, rf, mpt = a.read()
@@ -257,7 +267,7 @@ def compact_equals_full(rows, flags, device, tamper=0):
         comp, rf_c, mpt_c = a.read()
     assert comp.shape == (15, full.shape[1], 4) and np.array_equal(comp, np.concatenate([full[:8], full[50:]])) and np.array_equal(rf, rf_c)
     assert np.array_equal(mpt, mpt_c)
-    rng = random.Random(len(rows) + tamper)
+    rng = random.Random(int(rw.shape[0]) + tamper)
     decomposed = set()  # rows whose address / storage-key cells were damaged: the cells the limb / byte columns decompose
     for _ in range(tamper):
         c, i = rng.randrange(15), rng.randrange(full.shape[1])
@@ -320,3 +330,93 @@ def test_gpu_compact_state_rows():
     assert f_full == 0 and f_comp == 0
     _, f_full, f_comp = compact_equals_full(rows, flags, None, tamper=300)
     assert f_full >= 100 and f_comp >= 100
+
+
+# ---- Directed tables (tests/rekey_cases.py): the tiles of both sort paths, digit distributions, the plan's boundaries, the rank rule,
+# the class scan.  Every case first asserts, with the plain-Python plan model, the (key_bits, path, ranked fields) it aims at.
+from tests import rekey_cases as rc  # noqa: E402
+
+
+@pytest.mark.parametrize("name", rc.CPU_CASES)
+def test_cpu_backend_directed_tables(name, monkeypatch):
+    rc.run_case(name, "cpu", monkeypatch)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", rc.ALL_CASES)
+def test_gpu_directed_tables(name, monkeypatch):
+    rc.run_case(name, None, monkeypatch)
+
+
+@pytest.mark.parametrize("name", ["plan-two-class-widths", "rank-ninth-candidate-raw", "rank-half-equal-257", "plan-mask-80000001"])
+def test_plan_model_orders_like_the_checker(name):
+    """the model's compact keys, taken in (key, table index) order, are the checker's op order: the model the cases are aimed with
+    states the same order as the sort it describes"""
+    _, rw, fl, rows = rc.build_case(name)
+    plan = rc.plan_model(rows)
+    keys = rc.model_keys(rows, plan)
+    assert all(k is None or k < 1 << plan["key_bits"] for k in keys)
+    order = sorted((i for i, k in enumerate(keys) if k is not None), key=lambda i: keys[i])
+    e_ops, _, _ = rc.expected(rows, fl)
+    assert [int(v) - 1 for v in e_ops[7, 1:, 0]] == order
+
+
+def test_directed_tables_reach_every_listed_structure():
+    """the table of cases by itself: sizes, paths and tile counts the documents list"""
+    d = {k: rc.describe(c) for k, c in rc.CASES.items()}
+    fast = sorted(v["n"] for k, v in d.items() if k.startswith("fast-tiles-"))
+    assert fast == [8191, 8192, 8193, 16384, 16385, 73728, 73729, 139269]
+    assert {v["passes"] % 2 for k, v in d.items() if k.startswith("fast-tiles-")} == {0, 1}
+    assert d["fast-tiles-73728"]["tiles"] == 9 and d["fast-tiles-73729"]["tiles"] == 10 and d["fast-tiles-139269"]["tiles"] == 18
+    gen = {k: v for k, v in d.items() if k.startswith("generic-tiles-")}
+    assert sorted(v["n"] for v in gen.values()) == [4095, 4096, 4097, 36865] and all(v["path"] == "generic" and v["key_bits"] > 64 for v in gen.values())
+    assert d["both-paths-36865-fast"]["path"] == "fast" and d["both-paths-36865-generic"]["path"] == "generic"
+    assert sum(1 for k in d if k.startswith("digits-fast-")) == sum(1 for k in d if k.startswith("digits-generic-")) == 7
+    assert all(v["tiles"] == (5 if v["path"] == "fast" else 10) for k, v in d.items() if k.startswith("digits-"))
+    assert {v["key_bits"] for k, v in d.items() if k.startswith("plan-key-bits-")} == {4, 8, 9, 32, 33, 64, 65}
+    assert d["scan-eleven-classes-263169"]["n"] == 256 * 1024 + 1025 and d["scan-eleven-classes-263169"]["path"] == "fast"
+    assert set(rc.CPU_CASES) == {k for k, v in d.items() if v["n"] <= 20000 and not rc.CASES[k]["env"]}
+
+
+def session_twice(device):
+    """two passes of one zk_state_ops_from_rw session over a five-tile fast table: the tickets, descriptors and histograms of the sweep
+    are zeroed per launch, so both passes give the checker's ops"""
+    from zkevm_specs_amd import engine
+
+    _, rw, fl, rows = rc.build_case(rc.SESSION_TABLE)
+    exp = rc.expected(rows, fl)
+    with engine.open_state_ops_from_rw(rw, fl, device=device) as s:
+        for _ in range(2):
+            res = s.run()
+            status = s.read_status()
+            ops, op_flags = s.read()
+            rc.assert_ops_equal((ops, op_flags, status, res.fail_count), exp)
+
+
+def test_cpu_backend_session_twice():
+    session_twice("cpu")
+
+
+@pytest.mark.gpu
+def test_gpu_session_twice():
+    session_twice(None)
+
+
+def test_cpu_backend_consumers_20000():
+    rw, fl = rc.consumer_table(20000)
+    fused_equals_two_steps_arrays(rw, fl, "cpu")
+    compact_equals_full_arrays(rw, fl, "cpu")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [20000, 73729])
+def test_gpu_fused_assign_directed(n):
+    fused_equals_two_steps_arrays(*rc.consumer_table(n), None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [20000, 73729])
+def test_gpu_compact_state_rows_directed(n):
+    rw, fl = rc.consumer_table(n)
+    compact_equals_full_arrays(rw, fl, None)
+    compact_equals_full_arrays(rw, fl, None, tamper=n // 25)

@@ -195,7 +195,7 @@ __global__ __launch_bounds__(1024) void rwk_pack64_kernel(RekeyArgs a, u32* stat
     }
     __syncthreads();
     for (u32 t = threadIdx.x; t < a.n_passes * 256; t += 1024)
-        if (s_gh[t]) atomicAdd(&a.sweep[t], s_gh[t]);
+        if (s_gh[t]) atomicAdd(&a.sweep[RWK_SWEEP_GHIST + t], s_gh[t]);
 }
 // One radix pass in one kernel: tiles take tickets in order, rank their keys (stable, as below), publish their digit counts and
 // look back over the earlier tiles' descriptors for their prefix (descriptor word: count | 1 << 30 = this tile only, | 2 << 30 =
@@ -208,8 +208,8 @@ __global__ __launch_bounds__(RWK_SW_BLOCK) void rwk_sweep_kernel(RekeyArgs a, co
     __shared__ u32 s_scan[256], s_texcl[256], s_gbase[256];
     __shared__ u32 s_tile;
     const u32 wv = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    u32* ticket = a.sweep + 8 * 256;
-    u32* err = a.sweep + 8 * 256 + 8;
+    u32* ticket = a.sweep + RWK_SWEEP_TICKET;
+    u32* err = a.sweep + RWK_SWEEP_ERR;
     u32* desc = a.sweep + RWK_SWEEP_HEAD + (u64)pass * a.ntiles_fast * 256;
     if (threadIdx.x == 0) s_tile = atomicAdd(&ticket[pass], 1u);
 #pragma unroll
@@ -217,7 +217,7 @@ __global__ __launch_bounds__(RWK_SW_BLOCK) void rwk_sweep_kernel(RekeyArgs a, co
     __syncthreads();
     {   // digit bases: exclusive scan of the pass's global histogram (every thread takes part in the barriers)
         const u32 d = threadIdx.x & 255u;
-        const u32 g = a.sweep[pass * 256 + d];
+        const u32 g = a.sweep[RWK_SWEEP_GHIST + pass * 256 + d];
         if (threadIdx.x < 256) s_scan[d] = g;
         __syncthreads();
         for (u32 s = 1; s < 256; s <<= 1) {

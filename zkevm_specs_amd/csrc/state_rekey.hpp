@@ -173,9 +173,15 @@ struct RekeyArgs {
     u32 fast;
     u32 ntiles_fast;
     u64* key64_a; u64* key64_b;  // [n] each
-    u32* sweep;           // zeroed per launch: ghist [8][256], ticket [8], error flag [8], then desc [n_passes][ntiles_fast][256]
+    u32* sweep;           // zeroed per launch: error flag [8], ticket [8], ghist [8][256], then desc [n_passes][ntiles_fast][256]
 };
-#define RWK_SWEEP_HEAD (8 * 256 + 16)
+// The error flag (a look-back gave up) is the buffer's first word: the session's two tallies sit RWK_SWEEP_FRONT words in front of it, so
+// that zk_collect reads the tallies and the flag of a pass that ran the sweep in one copy.
+#define RWK_SWEEP_ERR 0
+#define RWK_SWEEP_TICKET 8
+#define RWK_SWEEP_GHIST 16
+#define RWK_SWEEP_HEAD (16 + 8 * 256)
+#define RWK_SWEEP_FRONT 16
 // one sweep tile = one 1024-thread block over RWK_SW_ITEMS keys per thread
 #define RWK_SW_BLOCK 1024
 #ifndef RWK_SW_ITEMS

@@ -1,6 +1,7 @@
 // libzkevm_hip.so — HIP kernels (gfx950) + C ABI (include/zkevm_hip.h).
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
@@ -635,6 +636,8 @@ struct zk_session {
     bool fused_verify = false;    // SESSION_ASSIGN whose rows are evaluated where they are computed (zk_state_verify_from_rw_open):
                                   // d_tally[0] = the State circuit's tally, d_tally[1] = rejected RW rows + failed assignments
     u32* rekey_status = nullptr;  // ... whose per-RW-row codes go here (the session's statuses are per op)
+    bool sweep_ran = false;       // a pass since the last collect ran rwk_sweep_kernel: the collect reads the sweep's error word
+    ZkTally* rekey_tally = nullptr;  // fast sort: the session's two tallies live RWK_SWEEP_FRONT words in front of rekey.sweep (one read-back)
     u64 cpa_n_table = 0, cpa_n_rw = 0;
     u32* d_hist = nullptr;   // EVM: (group, state) bins (histogram -> cursors)
     u32* d_cursor = nullptr; // EVM: per-bin scatter cursors (cleared by every histogram pass)
@@ -894,7 +897,9 @@ static int build_index(zk_session* s, ZkTable& t, bool mpt_fingerprints = false,
 }
 
 static int session_common_init(zk_session* s) {
-    int rc = dev_alloc(s, (void**)&s->d_tally, 2 * sizeof(ZkTally));
+    int rc = 0;
+    if (s->rekey_tally) s->d_tally = s->rekey_tally;  // (rekey_setup: in front of the sweep's error word)
+    else rc = dev_alloc(s, (void**)&s->d_tally, 2 * sizeof(ZkTally));
     if (rc) return rc;
     hipLaunchKernelGGL(tally_reset_kernel, dim3(1), dim3(2), 0, s->stream, s->d_tally, (u32*)nullptr);
     s->tally_last = s->d_tally;
@@ -1671,7 +1676,11 @@ static int rekey_setup(zk_session* s, const uint64_t* rw, const uint32_t* rw_fla
     if (a.fast) {
         if ((rc = dev_alloc(s, (void**)&a.key64_a, (size_t)n * 8))) return rc;
         if ((rc = dev_alloc(s, (void**)&a.key64_b, (size_t)n * 8))) return rc;
-        if ((rc = dev_alloc(s, (void**)&a.sweep, ((size_t)RWK_SWEEP_HEAD + (size_t)a.n_passes * a.ntiles_fast * 256) * 4))) return rc;
+        static_assert(2 * sizeof(ZkTally) <= RWK_SWEEP_FRONT * 4, "the two tallies fit in front of the sweep buffer");
+        u32* block = nullptr;
+        if ((rc = dev_alloc(s, (void**)&block, ((size_t)RWK_SWEEP_FRONT + RWK_SWEEP_HEAD + (size_t)a.n_passes * a.ntiles_fast * 256) * 4))) return rc;
+        s->rekey_tally = (ZkTally*)block;
+        a.sweep = block + RWK_SWEEP_FRONT;
     } else {
         if ((rc = dev_alloc(s, (void**)&a.keys, (size_t)a.key_words * n * 4))) return rc;
         if ((rc = dev_alloc(s, (void**)&a.hist, (size_t)a.ntiles * 256 * 4))) return rc;
@@ -2757,12 +2766,16 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
         if (s->fused_verify) {
             if (!s->fused_order_ready) {  // (a session's RW table does not change between passes)
                 zk_launch_state_rekey(s->stream, s->rekey, s->rekey_status, s->d_tally + 1);
+                s->sweep_ran = s->rekey.fast != 0;
                 zk_launch_state_assign(s->stream, s->assign, nullptr, nullptr);  // (the roots alone: root_rank is set)
             }
             zk_launch_state_rows_fused(s->stream, s->state, s->assign, status, s->d_tally, s->d_tally + 1);
             break;
         }
-        if (s->assign_from_rw) zk_launch_state_rekey(s->stream, s->rekey, s->rekey_status, s->d_tally);  // rejected RW rows count in the same tally
+        if (s->assign_from_rw) {  // rejected RW rows count in the same tally
+            zk_launch_state_rekey(s->stream, s->rekey, s->rekey_status, s->d_tally);
+            s->sweep_ran = s->rekey.fast != 0;
+        }
         zk_launch_state_assign(s->stream, s->assign, status, s->d_tally);
         break;
     case SESSION_ECDSA: zk_launch_ecdsa(s->stream, s->ecdsa, status, s->d_tally); break;
@@ -2816,7 +2829,10 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
         zk_launch_bytecode_from_code(s->stream, cside, s->ev_fork, s->ev_join, s->bcc, s->bcc_kgen, status, s->d_tally);
         break;
     }
-    case SESSION_REKEY: zk_launch_state_rekey(s->stream, s->rekey, status, s->d_tally); break;
+    case SESSION_REKEY:
+        zk_launch_state_rekey(s->stream, s->rekey, status, s->d_tally);
+        s->sweep_ran = s->rekey.fast != 0;
+        break;
     case SESSION_EVM: {
         // the state-sorted lane mapping is derived from the step column on every pass
         if (s->evm.perm) {
@@ -2983,9 +2999,30 @@ extern "C" int zk_collect(zk_session* s, zk_result* r) {
         if (check_deferred) HIP_TRY(hipMemcpyAsync(&n_def, s->evm.defer_count, 4, hipMemcpyDeviceToHost, s->stream));  // rides on the tally's synchronisation
         if (read_ranges) HIP_TRY(hipMemcpyAsync(gs, s->d_group_start, sizeof gs, hipMemcpyDeviceToHost, s->stream));
         ZkTally t_asg = {0ull, ~0ull};
-        if (s->fused_verify) HIP_TRY(hipMemcpyAsync(&t_asg, s->d_tally + 1, sizeof t_asg, hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipMemcpyAsync(&t, s->tally_last, sizeof t, hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream));
+        // A pass that ran the fast sort (rwk_sweep_kernel): its error word comes with the tallies, which sit right in front of it — one
+        // copy instead of the tallies' one or two.  The word is set when a tile's look-back gave up waiting for a predecessor: every later
+        // tile then scattered from a truncated prefix and the order is not the sort's.
+        u32 sweep_err = 0;
+        if (s->sweep_ran && s->rekey_tally && s->d_tally == s->rekey_tally) {
+            struct SweepHead { ZkTally tally[2]; u32 pad[RWK_SWEEP_FRONT - 8]; u32 err; } head;
+            static_assert(offsetof(SweepHead, err) == (RWK_SWEEP_FRONT + RWK_SWEEP_ERR) * 4, "tallies, padding, error word");
+            HIP_TRY(hipMemcpyAsync(&head, s->d_tally, offsetof(SweepHead, err) + 4, hipMemcpyDeviceToHost, s->stream));
+            HIP_TRY(hipStreamSynchronize(s->stream));
+            t = head.tally[s->tally_last - s->d_tally];
+            if (s->fused_verify) t_asg = head.tally[1];
+            sweep_err = head.err;
+        } else {
+            if (s->fused_verify) HIP_TRY(hipMemcpyAsync(&t_asg, s->d_tally + 1, sizeof t_asg, hipMemcpyDeviceToHost, s->stream));
+            HIP_TRY(hipMemcpyAsync(&t, s->tally_last, sizeof t, hipMemcpyDeviceToHost, s->stream));
+            HIP_TRY(hipStreamSynchronize(s->stream));
+        }
+        s->sweep_ran = false;
+        if (sweep_err) {  // no order, no verdict
+            g_err = "zk_collect: the RW -> State sort did not complete (a tile of rwk_sweep_kernel gave up its look-back: the sorted order, "
+                    "and everything derived from it in this pass, is invalid)";
+            s->launches = 0;
+            return -1;
+        }
         if (t_asg.fail_count) {  // no witness: what assign_state_circuit raises in the reference is an error here, not a verdict
             char msg[240];
             snprintf(msg, sizeof msg, "zk_state_verify_from_rw: the State witness assignment failed for %llu RW rows / ops (first: %llu, code 0x%08x; "
