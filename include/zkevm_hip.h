@@ -185,6 +185,19 @@ typedef struct zk_evm_tables {
                                  * always).  Costs two cross-queue barriers (~8 us) and saves the sum of the two launches: a gain
                                  * when the device is shared with other sessions' passes (the Super circuit), a loss alone */
 int zk_evm_open(const zk_evm_tables* t, uint32_t opts, zk_session** out);
+/* One-shot: open + one pass + collect + close.  Two things differ from a session opened with zk_evm_open, results never:
+ *  - The packed RW key records of the last ZK_P2_RW_TAIL per-mille of the rows (environment, read once; default 50, 0 = none:
+ *    the launch geometry of a session) are built by the open's second launch beside the step sort, not by its first.  The head
+ *    ends on a 64-row boundary:
+ *    n_head = (n_rw - n_rw * tail / 1000) rounded up to a multiple of 64, rows [n_head, n_rw) are the tail, row 0 is always head.
+ *    The dense RW index needs consecutive rw_counters over the whole table; whether the tail has them is only known after that
+ *    launch, which is also the one that would have built the open-addressing index.  A table that is consecutive up to n_head and
+ *    not behind it is therefore verified TWICE: the first result is discarded and the call repeated as with ZK_OPT_GENERIC_INDEX
+ *    (a caller's status buffer is rewritten; zk_timing_sums counts the call once, zk_last_host_phases adds the discarded run to the
+ *    open).  A witness whose rw_counters are not consecutive is off the fast path and may pay double here; it pays once when the
+ *    gap lies in the head or when the caller passes ZK_OPT_GENERIC_INDEX itself.
+ *  - Without a status buffer (status_out == NULL, and always in the batch form) no per-pair status is stored anywhere:
+ *    zk_result's fail_count / first_fail_row / first_fail_code carry the verdict. */
 int zk_evm_verify(const zk_evm_tables* t, uint32_t opts,
                   uint32_t* status_out /* nullable, n_steps-1 entries */, zk_result* result);
 /* Batch form: n independent witnesses (e.g. the blocks of a queue), each verified exactly as zk_evm_verify does — its own open

@@ -15,11 +15,14 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 cmd="python $root/bench.py --full --no-cpu-baseline --no-cold-leg --no-fresh-leg $*"
 if [ -n "${PROFILE_CMD:-}" ]; then cmd="$PROFILE_CMD"; fi  # e.g. PROFILE_CMD="python tools/bench_row_kernels.py" (run from the repo root)
-rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- $cmd > "$out/trace.log" 2>&1
-rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -- $cmd > "$out/pmc_fetch.log" 2>&1
-rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out/pmc_write" -- $cmd > "$out/pmc_write.log" 2>&1
-rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VMEM_RD SQ_WAIT_ANY SQ_ACTIVE_INST_ANY \
-    --output-format csv -d "$out/pmc_sq" -- $cmd > "$out/pmc_sq.log" 2>&1
+# every pass under its own time limit, and no pass after one that failed, timed out or died: a card that has faulted gets nothing more
+lim="timeout -k 10 ${PROFILE_PASS_SECONDS:-420}"
+stop() { echo "profile_bench: the $1 pass ended with status $2; stopping (see $out/$1.log)"; tail -5 "$out/$1.log"; exit 1; }
+$lim rocprofv3 --kernel-trace --stats --output-format csv -d "$out/trace" -- $cmd > "$out/trace.log" 2>&1 || stop trace $?
+$lim rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$out/pmc_fetch" -- $cmd > "$out/pmc_fetch.log" 2>&1 || stop pmc_fetch $?
+$lim rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$out/pmc_write" -- $cmd > "$out/pmc_write.log" 2>&1 || stop pmc_write $?
+$lim rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VMEM_RD SQ_WAIT_ANY SQ_ACTIVE_INST_ANY \
+    --output-format csv -d "$out/pmc_sq" -- $cmd > "$out/pmc_sq.log" 2>&1 || stop pmc_sq $?
 python - "$out" "$tag" "$*" <<'PY'
 import csv, glob, sys, collections, json
 out, tag, args = sys.argv[1], sys.argv[2], sys.argv[3]

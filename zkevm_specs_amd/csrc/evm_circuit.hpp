@@ -48,7 +48,7 @@ enum { CDT_Bytecode = 1, CDT_Memory, CDT_TxCalldata, CDT_TxLog, CDT_RlcAcc };  /
 // anything back (no host synchronisation at open); the evaluation kernels patch their copy of EvmArgs from this block at
 // entry (evm_args_resolve).  Zero-initialised, so every field is phrased such that 0 is the "nothing built" state.
 struct EvmDyn {
-    u32 rw_sparse;      // set by rw_prepare_kernel when the RW rows are NOT consecutive rw_counters from rw_base
+    u32 rw_sparse;      // non-zero when the RW rows are NOT consecutive rw_counters from rw_base: bit 0 set by the open's phase 1, bit 1 by the rows a one-shot open packs in phase 2
     u32 codes_n;        // directory entries (0: no directory, generic bytecode index only)
     u64 rw_base;
     u32 codes_mask;

@@ -322,7 +322,17 @@ __global__ __launch_bounds__(1024) void evm_state_scatter_kernel(const uint16_t*
 //   evm_open_fill_kernel    every slot table / "min" array of the session to 0xFF.., every counter / status array to 0
 //   evm_open_phase1_kernel  block ranges: small-table index inserts + EndBlock aggregates + tally reset | RW table:
 //                           density verdict + packed key records (one read of the key cells) | bytecode directory events
-//   evm_open_phase2_kernel  block ranges: directory entries | generic RW index (does nothing when the rows are dense)
+//   evm_open_phase2_kernel  block ranges: sort scatter | directory entries | generic RW index (does nothing when phase 1 found
+//                           its rows dense) | one-shot opens only: the key records of the last ZK_P2_RW_TAIL per-mille of the RW rows
+// The one-shot entries (zk_evm_verify, zk_evm_verify_batch) open with two differences, resident sessions with neither:
+//   - the RW key pack is split: phase 1 packs rows [0, n_head), phase 2's last blocks pack [n_head, n_rw) beside the scatter, whose
+//     serial chain (histogram load, 512-bin scan, LDS ranks, one returning atomic per bin, perm stores) leaves HBM idle.  Every
+//     dependency stays a kernel boundary: nothing in phase 2 reads what the tail blocks write.  The density verdict has one bit per
+//     launch (EvmDyn::rw_sparse); phase 2's generic blocks test phase 1's bit alone.  A dense head in front of a sparse tail
+//     (rw_sparse == 2) has no generic index: the pass's RW lookups miss cleanly, the host discards that result at collect and
+//     repeats the call with ZK_OPT_GENERIC_INDEX (evm_oneshot_run).
+//   - without a caller's status buffer the session has no status array: the evaluation launches get status == nullptr (every store
+//     is guarded, evm_kernel.hpp) and the fill kernel has n_pairs words less to clear.  The tally carries the verdict.
 // A launch costs the host ~10 us on this stack and the device ~3 us of gap: round 2's open was 20 launches, 15 hipMallocs and
 // two host synchronisations (0.49 ms for 2^18 steps); the independent builds now share launches and overlap on the device
 // (the RW pass streams HBM, the others are latency-bound).
@@ -341,7 +351,9 @@ __global__ __launch_bounds__(256) void evm_open_fill_kernel(uint4* ff, u64 n_ff,
 // 448 bytes apart — and the quad ORs its partial key words together (rw_pack_row's record, bit for bit).
 //   lane 0: rw_counter[0..128)   tag[0..128)   address[0..128)        lane 2: rw[0..128)   id[0..128)   field_tag[0..128)
 //   lane 1: rw_counter[128..256) tag[128..256) address[128..256)      lane 3: rw[128..)    id[128..)    field_tag[128..)
-__device__ __forceinline__ void rw_prepare_quad(const ZkTable& t, u64* keys, EvmDyn* dyn, u32 vthread) {
+// `sparse_bit`: the bit of the verdict word this launch owns — 1 for phase 1, 2 for the rows a one-shot open packs in phase 2
+// (EvmOpenTables::tail_row0), where the generic-index blocks of the same launch test bit 0 alone.
+__device__ __forceinline__ void rw_prepare_quad(const ZkTable& t, u64* keys, EvmDyn* dyn, u32 vthread, u32 sparse_bit = 1u) {
     const u32 r = vthread >> 2, q = vthread & 3u;
     const bool in = r < t.n;
     uint4 c0 = make_uint4(0, 0, 0, 0), c1 = c0, c2 = c0;
@@ -386,7 +398,7 @@ __device__ __forceinline__ void rw_prepare_quad(const ZkTable& t, u64* keys, Evm
     const u32 qshift = threadIdx.x & 60u;
     const bool fits = ((__ballot(fit) >> qshift) & 0xfull) == 0xfull;
     const unsigned long long nd = __ballot(in && !dense_ok);
-    if (nd != 0ull && (threadIdx.x & 63u) == 0) atomicOr(&dyn->rw_sparse, 1u);
+    if (nd != 0ull && (threadIdx.x & 63u) == 0) atomicOr(&dyn->rw_sparse, sparse_bit);
     if (r == 0 && q == 0 && in) dyn->rw_base = base;
 #pragma unroll
     for (int m = 1; m <= 2; m <<= 1) {
@@ -420,6 +432,7 @@ struct EvmOpenTables {
     EvmSortArgs sort;    // sort.perm != nullptr: the first pass's counting sort rides on the two launches (histogram in phase 1, scatter in phase 2)
     u32 hist_block0;
     u32 lat_period;      // phase 1: every lat_period-th block of the launch's first part is one of the latency-bound ranges' (0 / 1: they all come first)
+    u32 tail_row0, tail_blocks;  // one-shot opens: RW rows [tail_row0, rw.n) are packed by the last tail_blocks blocks of phase 2, not by phase 1 (0, 0: none)
 #ifdef ZK_DIAG_P1
     u32 diag_skip;       // tuning builds only (tools/p1_ranges.py): ranges of phase 1 that return at once — results are INVALID
 #endif
@@ -515,10 +528,19 @@ __global__ __launch_bounds__(1024) void evm_open_phase2_kernel(EvmOpenTables o, 
         dirb_finalize_entry(o.dir, b * blockDim.x + threadIdx.x);
         return;
     }
-    if (!force_generic && o.dyn->rw_sparse == 0u) return;
+    const u32 generic_blocks = gridDim.x - scatter_blocks - dir_blocks - o.tail_blocks;
+    if (b >= dir_blocks + generic_blocks) {
+        // One-shot opens: the last part of the RW key pack streams here, behind the scatter's latency chain, instead of in phase 1.
+        // 256 rows per block from a 64-row boundary: quads and wavefronts line up as in phase 1.  These blocks own bit 1 of the verdict.
+        rw_prepare_quad(o.rw, o.rw_keys, o.dyn, o.tail_row0 * 4u + (b - dir_blocks - generic_blocks) * blockDim.x + threadIdx.x, 2u);
+        return;
+    }
+    // Bit 0 is phase 1's verdict, final before this launch; bit 1 may be set by the tail blocks while this one runs and is not looked at
+    // here.  (A dense head with a sparse tail therefore has no generic index: the host sees rw_sparse == 2 and repeats the verification.)
+    if (!force_generic && (o.dyn->rw_sparse & 1u) == 0u) return;
     if (force_generic && b == dir_blocks && threadIdx.x == 0) o.dyn->rw_sparse = 1u;  // generic-index sessions never use the dense path
     u32* slots = const_cast<u32*>(o.rw.slots);
-    const u32 stride = (gridDim.x - scatter_blocks - dir_blocks) * blockDim.x;
+    const u32 stride = generic_blocks * blockDim.x;
     for (u32 r = (b - dir_blocks) * blockDim.x + threadIdx.x; r < o.rw.n; r += stride) {
         // a row that equals a row already on its probe path (equal rows hash alike, slots are never freed: of m equal rows every
         // one but the first to land sees one) is a duplicate: EvmDyn::agg_rw_dups, for EndBlock's len(rw_table)
@@ -1010,7 +1032,14 @@ static inline u32 index_cap(u64 n) {
 //   rw_generic_index_kernel  (does nothing when the rows are dense)
 //   dirb_* x 5               bytecode directory
 // and the evaluation kernels pick the verdicts up from EvmDyn (evm_args_resolve).
-extern "C" int zk_evm_open(const zk_evm_tables* t, uint32_t opts, zk_session** out) {
+// `internal`: how the one-shot entries mark their sessions (never a public ZK_OPT_* bit; zk_evm_open passes 0) —
+//   EVM_OPEN_ONESHOT    the RW key pack's tail rides in phase 2 (ZK_P2_RW_TAIL per-mille of the rows; 0 = the resident geometry)
+//   EVM_OPEN_NO_STATUS  the caller passed no status buffer: the session has none either (zk_launch hands nullptr to the kernels)
+enum { EVM_OPEN_ONESHOT = 1u, EVM_OPEN_NO_STATUS = 2u };
+#ifndef ZK_P2_RW_TAIL_DEFAULT
+#define ZK_P2_RW_TAIL_DEFAULT 50  // per-mille of n_rw packed in phase 2 by a one-shot open (the sweep that chose it)
+#endif
+static int evm_open_session(const zk_evm_tables* t, uint32_t opts, u32 internal, zk_session** out) {
     ARG_TRY(t_device >= 0, "zk_evm_open: call zk_init first");
     HIP_TRY(hipSetDevice(t_device));
     ARG_TRY(t && out && t->steps && t->n_steps >= 2 && t->n_steps < (1ull << 32), "zk_evm_open: bad arguments");
@@ -1071,7 +1100,9 @@ extern "C" int zk_evm_open(const zk_evm_tables* t, uint32_t opts, zk_session** o
         u32* const dir_first = cur; cur += cap_big;
         u32* const small_slots = cur;
         // ---- one zero region: EvmDyn, the two histograms, the per-pair status, the directory's last / runs / bad -------------
-        const size_t dyn_bytes = 256, hist_bytes = EVM_N_BINS * sizeof(u32), status_bytes = (((size_t)s->n * sizeof(u32)) + 15) & ~(size_t)15;
+        // (a one-shot call without a status buffer has no status array: nothing would read it)
+        const bool no_status = (internal & EVM_OPEN_NO_STATUS) != 0;
+        const size_t dyn_bytes = 256, hist_bytes = EVM_N_BINS * sizeof(u32), status_bytes = no_status ? 0 : (((size_t)s->n * sizeof(u32)) + 15) & ~(size_t)15;
         const size_t zero_bytes = dyn_bytes + 2 * hist_bytes + status_bytes + 3 * (size_t)cap_big * 4;
         char* zero = nullptr;
         if ((rc = dev_alloc(s, (void**)&zero, zero_bytes))) goto fail;
@@ -1088,7 +1119,7 @@ extern "C" int zk_evm_open(const zk_evm_tables* t, uint32_t opts, zk_session** o
         static_assert((EVM_N_BINS * sizeof(u32)) % 16 == 0, "zero region pieces are 16-byte multiples");
         s->d_hist = (u32*)(zero + dyn_bytes);
         s->d_hist2 = (u32*)(zero + dyn_bytes + hist_bytes);
-        s->d_status = (u32*)(zero + dyn_bytes + 2 * hist_bytes);
+        s->d_status = no_status ? nullptr : (u32*)(zero + dyn_bytes + 2 * hist_bytes);
         u32* const dir_last = (u32*)(zero + dyn_bytes + 2 * hist_bytes + status_bytes);
         E.dyn = dyn;
         E.defer_count = &dyn->n_deferred;
@@ -1131,7 +1162,21 @@ extern "C" int zk_evm_open(const zk_evm_tables* t, uint32_t opts, zk_session** o
             E.rw_keys = d_keys;
             o.rw_keys = d_keys;
         }
-        const u32 rw_row_blocks = o.rw_keys ? (u32)((t->n_rw + 63) / 64) : 0u;  // four lanes per row
+        // One-shot opens: the last ZK_P2_RW_TAIL per-mille of the RW rows are packed by phase 2 (evm_open_phase2_kernel's last block range).
+        // The head ends on a 64-row boundary (whole phase-1 blocks) and keeps at least row 0, which writes EvmDyn::rw_base; the tail is
+        // whole 256-row blocks from there, the last one partial.  Every row is in exactly one of the two ranges: the key table is not
+        // cleared between sessions.  Setting 0 (and every resident session): n_head == n_rw, no tail blocks, the grids of round 6.
+        u64 n_head = t->n_rw;
+        if ((internal & EVM_OPEN_ONESHOT) && o.rw_keys && t->n_rw < (1ull << 30)) {
+            static const u32 tail_pm = [] { const char* e = getenv("ZK_P2_RW_TAIL"); const int v = e ? atoi(e) : ZK_P2_RW_TAIL_DEFAULT; return (u32)(v < 0 ? 0 : v > 999 ? 999 : v); }();
+            const u64 h = (t->n_rw - t->n_rw * tail_pm / 1000 + 63) & ~63ull;
+            if (h < t->n_rw) n_head = h;
+        }
+        const u32 rw_row_blocks = o.rw_keys ? (u32)((n_head + 63) / 64) : 0u;  // four lanes per row
+        if (n_head < t->n_rw) {
+            o.tail_row0 = (u32)n_head;
+            o.tail_blocks = (u32)((t->n_rw - n_head + EVM_OPEN_P2_BLOCK / 4 - 1) / (EVM_OPEN_P2_BLOCK / 4));
+        }
         o.dir_block0 = blk;
         u32 dir_row_blocks = 0;
         if (want_dir) {  // bytecode directory (code_dir_build.hpp)
@@ -1198,6 +1243,11 @@ extern "C" int zk_evm_open(const zk_evm_tables* t, uint32_t opts, zk_session** o
         {   // latency-bound blocks dealt into the first 1 / ZK_P1_LAT_SPREAD of the RW range (evm_open_phase1_kernel)
             static const u32 spread = [] { const char* e = getenv("ZK_P1_LAT_SPREAD"); const int v = e ? atoi(e) : 2; return (u32)(v < 0 ? 0 : v); }();
             o.lat_period = (o.rw_block0 && spread) ? o.rec_block0 / (spread * o.rw_block0) : 0u;
+            // With a tail the RW range is shorter and the quotient may turn even.  Blocks are dealt round-robin over the 8 XCDs: at
+            // period 4 every latency-bound block of the launch lands on two of them, at period 2 on four (measured at 2^18 steps,
+            // tail 100: phase 1 63.6 us at period 4, 49.7 us at period 5).  An odd period visits all eight.  Without a tail the
+            // quotient stays as it is: the resident geometry is not touched.
+            if (o.tail_blocks && o.lat_period > 1u) o.lat_period |= 1u;
         }
 #ifdef ZK_DIAG_P1
         if (const char* e = getenv("ZK_DIAG_P1_SKIP")) o.diag_skip = (u32)atoi(e);
@@ -1205,13 +1255,13 @@ extern "C" int zk_evm_open(const zk_evm_tables* t, uint32_t opts, zk_session** o
         {
             const u32 dir_blocks = want_dir ? DIRB_MAX_ENTRIES / EVM_OPEN_P2_BLOCK : 0u;
             const u32 rw_blocks = t->n_rw ? EVM_OPEN_RW_GENERIC_BLOCKS : 0u;
-            bool phase2 = scatter_blocks + dir_blocks + rw_blocks != 0;
+            bool phase2 = scatter_blocks + dir_blocks + rw_blocks + o.tail_blocks != 0;
 #ifdef ZK_DIAG_P1
             if (o.diag_skip) phase2 = false;  // its inputs are missing
 #endif
             hipExtLaunchKernelGGL(evm_open_phase1_kernel, dim3(grid1 ? grid1 : 1u), dim3(256), 0, s->stream, nullptr, phase2 ? nullptr : s->ev_open1, 0, o);
             if (phase2)
-                hipExtLaunchKernelGGL(evm_open_phase2_kernel, dim3(scatter_blocks + dir_blocks + rw_blocks), dim3(EVM_OPEN_P2_BLOCK), 0, s->stream, nullptr,
+                hipExtLaunchKernelGGL(evm_open_phase2_kernel, dim3(scatter_blocks + dir_blocks + rw_blocks + o.tail_blocks), dim3(EVM_OPEN_P2_BLOCK), 0, s->stream, nullptr,
                                       s->ev_open1, 0, o, scatter_blocks, dir_blocks, generic ? 1u : 0u);
         }
         if (hipGetLastError() != hipSuccess) { rc = -2; g_err = "zk_evm_open: a build kernel failed to launch"; goto fail; }
@@ -1229,15 +1279,25 @@ fail:
     zk_close(s);
     return rc;
 }
+extern "C" int zk_evm_open(const zk_evm_tables* t, uint32_t opts, zk_session** out) { return evm_open_session(t, opts, 0u, out); }
+
+// What a collected one-shot session says about its split key pack: phase 1 found its rows dense (so phase 2 built no generic index)
+// and the tail blocks did not — the pass looked its RW rows up in an empty index and its result is not the witness's.
+static bool evm_sparse_tail_only(const zk_session* s) {
+    return s->kind == SESSION_EVM && s->h_result && ((const EvmResultBlock*)s->h_result)->dyn.rw_sparse == 2u;
+}
 
 static void session_timing(zk_session* s, double pass_ms, double* open_ms, double* span_ms);
 static int evm_enqueue_tail(zk_session* s);
 static bool evm_publish_enqueue(zk_session* s);
-extern "C" int zk_evm_verify(const zk_evm_tables* t, uint32_t opts, uint32_t* status_out, zk_result* result) {
-    ARG_TRY(result, "zk_evm_verify: result is null");
+// One open + pass + collect + close of a one-shot witness.  *redo: the result is to be discarded and the call repeated with
+// ZK_OPT_GENERIC_INDEX (evm_sparse_tail_only); the timing sums and `result` then wait for that second run.
+static int evm_oneshot_run(const zk_evm_tables* t, uint32_t opts, uint32_t* status_out, zk_result* result, bool* redo, double host_us[4]) {
     zk_session* s = nullptr;
+    *redo = false;
     const auto h0 = std::chrono::steady_clock::now();
-    int rc = zk_evm_open(t, opts | ZK_OPT_SINGLE_PASS, &s);  // one pass: the step records would not pay for themselves
+    // one pass: the step records would not pay for themselves
+    int rc = evm_open_session(t, opts | ZK_OPT_SINGLE_PASS, EVM_OPEN_ONESHOT | (status_out ? 0u : EVM_OPEN_NO_STATUS), &s);
     if (rc) return rc;
     const auto h1 = std::chrono::steady_clock::now();
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
@@ -1245,19 +1305,36 @@ extern "C" int zk_evm_verify(const zk_evm_tables* t, uint32_t opts, uint32_t* st
     const auto h2 = std::chrono::steady_clock::now();
     if (!rc) rc = zk_collect(s, result);
     const auto h3 = std::chrono::steady_clock::now();
-    if (!rc) {
+    if (!rc) *redo = evm_sparse_tail_only(s);
+    if (!rc && !*redo) {
         t_timing[1] = result->kernel_ms;
         session_timing(s, result->kernel_ms, &t_timing[0], &t_timing[2]);
         for (int k = 0; k < 3; k++) t_timing_sum[k] += t_timing[k];
         t_timing_count++;
     }
-    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
+    if (!rc && !*redo && status_out && !dev) rc = zk_read_status(s, status_out);
     zk_close(s);
     const auto h4 = std::chrono::steady_clock::now();
-    t_host_phase[0] = std::chrono::duration<double, std::micro>(h1 - h0).count();
-    t_host_phase[1] = std::chrono::duration<double, std::micro>(h2 - h1).count();
-    t_host_phase[2] = std::chrono::duration<double, std::micro>(h3 - h2).count();
-    t_host_phase[3] = std::chrono::duration<double, std::micro>(h4 - h3).count();
+    host_us[0] = std::chrono::duration<double, std::micro>(h1 - h0).count();
+    host_us[1] = std::chrono::duration<double, std::micro>(h2 - h1).count();
+    host_us[2] = std::chrono::duration<double, std::micro>(h3 - h2).count();
+    host_us[3] = std::chrono::duration<double, std::micro>(h4 - h3).count();
+    return rc;
+}
+extern "C" int zk_evm_verify(const zk_evm_tables* t, uint32_t opts, uint32_t* status_out, zk_result* result) {
+    ARG_TRY(result, "zk_evm_verify: result is null");
+    bool redo = false;
+    double us[4] = {0, 0, 0, 0};
+    int rc = evm_oneshot_run(t, opts, status_out, result, &redo, us);
+    if (!rc && redo) {
+        // an RW table that is dense up to the split and not behind it: once more with the generic index (a caller's status buffer is
+        // rewritten by this run; the discarded run counts as host time of the open)
+        const double first = us[0] + us[1] + us[2] + us[3];
+        rc = evm_oneshot_run(t, opts | ZK_OPT_GENERIC_INDEX, status_out, result, &redo, us);
+        us[0] += first;
+    }
+    if (rc && us[0] == 0) return rc;  // (the open failed: the last call's phases stay)
+    for (int k = 0; k < 4; k++) t_host_phase[k] = us[k];
     return rc;
 }
 
@@ -1287,12 +1364,22 @@ extern "C" int zk_evm_verify_batch(const zk_evm_tables* const* t, uint64_t n, ui
         const int slot = (int)(i & 1u);
         if (pend[slot]) {  // witness i - 2
             rc = zk_collect(pend[slot], &results[i - 2]);
+            const bool redo = !rc && evm_sparse_tail_only(pend[slot]);
             zk_close(pend[slot]);
             pend[slot] = nullptr;
+            if (redo) {  // dense up to the split, not behind it: this witness once more with the generic index, on its slot's stream, before the slot is reused
+                t_stream = g_batch_stream[t_device][slot];
+                rc = evm_open_session(t[i - 2], opts | ZK_OPT_SINGLE_PASS | ZK_OPT_GENERIC_INDEX, EVM_OPEN_ONESHOT | EVM_OPEN_NO_STATUS, &pend[slot]);
+                t_stream = caller;
+                if (!rc) rc = zk_launch(pend[slot], nullptr);
+                if (!rc) rc = zk_collect(pend[slot], &results[i - 2]);
+                if (pend[slot]) zk_close(pend[slot]);
+                pend[slot] = nullptr;
+            }
         }
         if (!rc && i < n) {
             t_stream = g_batch_stream[t_device][slot];
-            rc = zk_evm_open(t[i], opts | ZK_OPT_SINGLE_PASS, &pend[slot]);
+            rc = evm_open_session(t[i], opts | ZK_OPT_SINGLE_PASS, EVM_OPEN_ONESHOT | EVM_OPEN_NO_STATUS, &pend[slot]);
             t_stream = caller;
             if (!rc) rc = zk_launch(pend[slot], nullptr);
         }
