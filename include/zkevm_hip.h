@@ -853,6 +853,64 @@ int zk_bytecode_from_code_open(const zk_code_set* in, const zk_code_wire* out_de
 int zk_bytecode_from_code_read(zk_session* s, const zk_code_wire* host);
 int zk_bytecode_from_code(const zk_code_set* in, const zk_code_wire* out, uint32_t opts, zk_result* result);
 
+/* ---- EVM circuit tx, block and withdrawal tables from raw block data: replaces Transaction.table_assignments(),
+ *      Block.table_assignments() and Withdrawal.table_assignments() (src/zkevm_specs/evm_circuit/typing.py:209-281, 116-137, 306-314)
+ *      over a block's objects, followed by flatten_tx_table / flatten_block_table / flatten_withdrawal_table and the upload of the
+ *      result (one 160-byte row + a flag per byte of calldata; the calldata itself is 1 byte).
+ *      Inputs (zk_block_data), 256-bit words as 4 x u64 little-endian:
+ *        tx_fields uint64[n_txs][9][4]: id, nonce, gas, gas_price, caller_address, callee_address (0 when None), value, invalid_tx,
+ *          tx_sign_hash (the reference's mock 1234, typing.py:265, is data here); to_is_none uint32[n_txs] (non-zero: IsCreate = 1);
+ *        access_list uint32[n_txs][2]: access tuples a, storage keys over all of them k -> AccessListGasCost = 2400 a + 1900 k;
+ *        calldata: the txs' data back to back, at any byte alignment, with byte offsets uint64[n_txs + 1] (offsets[0] = 0,
+ *          non-decreasing; offsets[n_txs] bytes are read), as zk_tx_inputs;
+ *        block uint64[8][4], nullable (NULL: no block table; n_history must be 0 then): coinbase, gas_limit, number, timestamp,
+ *          prev_randao, base_fee, chainid, withdrawal_root; history_hashes uint64[n_history][4], oldest first (the reference's list,
+ *          [-1] the latest); withdrawals uint64[n_withdrawals][4][4]: id, validator_id, address, amount.
+ *      Outputs (zk_block_tables), cell for cell and flag for flag what the flatten_* functions return for the same objects — the rows
+ *      in the set's order (ascending over the cells as integers), is_word in bit 0 of the flag:
+ *        tx uint64[12 n_txs + offsets[n_txs]][5][4] (tx_id, tag, index, value lo, hi) + tx_flags uint32[..]: per tx in id order the rows of
+ *          tags 1..12 (Nonce, Gas, GasPrice, CallerAddress, CalleeAddress, IsCreate, Value, CallDataLength, CallDataGasCost, TxInvalid,
+ *          AccessListGasCost, TxSignHash), then a CallData row (tag 13) per byte in index order.  GasPrice, CallerAddress, CalleeAddress
+ *          and Value are Words (flag 1, lo / hi split at 128 bits); every other value is FQ(v): the 256-bit input reduced mod the BN254
+ *          scalar modulus p, hi = 0, flag 0.  CallDataGasCost = 4 per zero byte + 16 per non-zero byte;
+ *        block uint64[8 + n_history][4][4] (tag, number, value lo, hi) + block_flags uint32[..]: tags 1..7, then the HistoryHash rows
+ *          (tag 8) in ascending order of their number cell FQ(number - n_history + j) for history_hashes[j], then WithdrawalRoot (tag 9).
+ *          Coinbase, PrevRandao, BaseFee and HistoryHash are Words, the rest values reduced mod p;
+ *        withdrawals uint64[n_withdrawals][4][4]: the four cells reduced mod p, in id order (zk_evm_tables.withdrawals).
+ *      zk_evm_tables_from_block_sizes: the three row counts.  zk_evm_tables_from_block_open: with ZK_OPT_DEVICE_PTRS every input is a
+ *      device pointer and the non-null pointers of `out_dev` receive the outputs in place (null: the session owns that buffer);
+ *      without the flag out_dev must be NULL.  What is checked at open — the tx and withdrawal ids, the offsets, the block number — is
+ *      read back once when device-resident and fixed for the session (the session keeps its own copy); the other fields and the
+ *      calldata bytes are read by every pass.  zk_launch / zk_collect / zk_close as for the other assignments: there is no failing
+ *      case (the tally is always clean; rows_evaluated = the tx table's rows, status uint32[that] all 0).
+ *      zk_evm_tables_from_block_read copies the last pass's outputs to the non-null HOST pointers of `host`.
+ *      Domain, rejected at sizes / open with an error code and its text in zk_last_error, never guessed:
+ *        ZK_ERR_BTB_ID       a tx or withdrawal id is no canonical cell (>= p), or the ids are not strictly ascending (with distinct
+ *                            ascending ids the reference's sets have no duplicate rows and their order is closed-form);
+ *        ZK_ERR_BTB_OFFSETS  offsets[0] != 0, or offsets that decrease;
+ *        ZK_ERR_BTB_HISTORY  n_history > min(256, number) (the reference's assert, typing.py:104);
+ *        ZK_ERR_BTB_ROWS     2^31 rows or more in one table. */
+#define ZK_ERR_BTB_ID (-60)
+#define ZK_ERR_BTB_OFFSETS (-61)
+#define ZK_ERR_BTB_HISTORY (-62)
+#define ZK_ERR_BTB_ROWS (-63)
+typedef struct zk_block_data {
+    const uint64_t* tx_fields;   const uint32_t* to_is_none;  const uint32_t* access_list;  uint64_t n_txs;
+    const uint8_t* calldata;     const uint64_t* calldata_offsets;   /* uint64[n_txs + 1] */
+    const uint64_t* block;                                            /* uint64[8][4], nullable */
+    const uint64_t* history_hashes;  uint64_t n_history;             /* oldest first */
+    const uint64_t* withdrawals;     uint64_t n_withdrawals;
+} zk_block_data;
+typedef struct zk_block_tables {               /* each pointer nullable */
+    uint64_t* tx;           uint32_t* tx_flags;     /* uint64[12 n_txs + calldata bytes][5][4], uint32[..] */
+    uint64_t* block;        uint32_t* block_flags;  /* uint64[8 + n_history][4][4], uint32[..] (no rows when zk_block_data.block is NULL) */
+    uint64_t* withdrawals;                          /* uint64[n_withdrawals][4][4] */
+} zk_block_tables;
+int zk_evm_tables_from_block_sizes(const zk_block_data* in, uint32_t opts, uint64_t* n_tx_rows, uint64_t* n_block_rows, uint64_t* n_withdrawal_rows);
+int zk_evm_tables_from_block_open(const zk_block_data* in, const zk_block_tables* out_dev, uint32_t opts, zk_session** out);
+int zk_evm_tables_from_block_read(zk_session* s, const zk_block_tables* host);
+int zk_evm_tables_from_block(const zk_block_data* in, const zk_block_tables* out, uint32_t opts, zk_result* result);
+
 #ifdef __cplusplus
 }
 #endif

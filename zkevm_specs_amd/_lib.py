@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = [
     "zk_pi_assign_sizes", "zk_pi_assign_open", "zk_pi_assign_read", "zk_pi_assign",
     "zk_sig_assign_open", "zk_sig_assign_read", "zk_sig_assign",
     "zk_bytecode_from_code_open", "zk_bytecode_from_code_read", "zk_bytecode_from_code",
+    "zk_evm_tables_from_block_sizes", "zk_evm_tables_from_block_open", "zk_evm_tables_from_block_read", "zk_evm_tables_from_block",
 ]
 
 OPT_DEVICE_PTRS = 1
@@ -126,6 +127,16 @@ class ZkCodeWire(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("table", "rows", "keccak")]
 
 
+class ZkBlockData(ctypes.Structure):
+    _fields_ = [("tx_fields", ctypes.c_void_p), ("to_is_none", ctypes.c_void_p), ("access_list", ctypes.c_void_p), ("n_txs", ctypes.c_uint64),
+                ("calldata", ctypes.c_void_p), ("calldata_offsets", ctypes.c_void_p), ("block", ctypes.c_void_p),
+                ("history_hashes", ctypes.c_void_p), ("n_history", ctypes.c_uint64), ("withdrawals", ctypes.c_void_p), ("n_withdrawals", ctypes.c_uint64)]
+
+
+class ZkBlockTables(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("tx", "tx_flags", "block", "block_flags", "withdrawals")]
+
+
 class ZkEcdsaBatch(ctypes.Structure):
     _fields_ = [("bytes", ctypes.c_void_p), ("layout", ctypes.c_uint32), ("v", ctypes.c_void_p), ("v_stride", ctypes.c_uint32),
                 ("n", ctypes.c_uint64), ("out_dev", ctypes.c_void_p), ("out_stride", ctypes.c_uint32)]
@@ -159,6 +170,7 @@ class ZkPiWire(ctypes.Structure):
 # ZK_ERR_PI_* (include/zkevm_hip.h): why zk_pi_assign* rejected its inputs
 ERR_PI_TXS, ERR_PI_WITHDRAWALS, ERR_PI_CALLDATA, ERR_PI_FIELD, ERR_PI_ROWS = -50, -51, -52, -53, -54
 ERR_EXP_CELL, ERR_EXP_ORDER, ERR_EXP_ROWS = -40, -41, -42  # ZK_ERR_EXP_* (include/zkevm_hip.h): why zk_exp_assign* rejected its events
+ERR_BTB_ID, ERR_BTB_OFFSETS, ERR_BTB_HISTORY, ERR_BTB_ROWS = -60, -61, -62, -63  # ZK_ERR_BTB_*: why zk_evm_tables_from_block* rejected its inputs
 
 
 class ZkBlock(ctypes.Structure):
@@ -313,6 +325,10 @@ def _bind(lib):
     lib.zk_bytecode_from_code_open.argtypes = [ctypes.POINTER(ZkCodeSet), ctypes.POINTER(ZkCodeWire), u32, ctypes.POINTER(vp)]
     lib.zk_bytecode_from_code_read.argtypes = [vp, ctypes.POINTER(ZkCodeWire)]
     lib.zk_bytecode_from_code.argtypes = [ctypes.POINTER(ZkCodeSet), ctypes.POINTER(ZkCodeWire), u32, ctypes.POINTER(ZkResult)]
+    lib.zk_evm_tables_from_block_sizes.argtypes = [ctypes.POINTER(ZkBlockData), u32, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_evm_tables_from_block_open.argtypes = [ctypes.POINTER(ZkBlockData), ctypes.POINTER(ZkBlockTables), u32, ctypes.POINTER(vp)]
+    lib.zk_evm_tables_from_block_read.argtypes = [vp, ctypes.POINTER(ZkBlockTables)]
+    lib.zk_evm_tables_from_block.argtypes = [ctypes.POINTER(ZkBlockData), ctypes.POINTER(ZkBlockTables), u32, ctypes.POINTER(ZkResult)]
     lib.zk_launch.argtypes = [vp, vp]
     lib.zk_collect.argtypes = [vp, ctypes.POINTER(ZkResult)]
     lib.zk_read_status.argtypes = [vp, vp]

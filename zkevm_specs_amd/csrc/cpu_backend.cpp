@@ -32,6 +32,7 @@
 #include "state_assign.hpp"
 #include "bytecode_assign.hpp"
 #include "bytecode_code.hpp"
+#include "block_tables.hpp"
 #include "state_rekey.hpp"
 #include "ecc_circuit.hpp"
 #include "withdrawal_circuit.hpp"
@@ -101,7 +102,7 @@ struct zk_session {
     std::vector<u64> w64[4];              // assignment sessions: work / output buffers
     std::vector<u32> out32;
     void (*pass)(zk_session*) = nullptr;  // assignment sessions: one pass computes the outputs and fills `status`
-    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code
+    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code, 11 tables from block
     u64 n_ops = 0;                        // RW -> State ops: 1 + kept rows
     std::vector<u32> rekey_plan;          // RW -> State ops: the RwkHostPlan's plan (as words) ...
     std::vector<u32> rekey_jobs;          // ... and its rank jobs (cls, field, base, count)
@@ -125,6 +126,9 @@ struct zk_session {
     KeccakGenArgs bcc_kgen;
     std::vector<u64> bcc64[8];      // offsets, rpow, chunk_acc, chunk_in, part, table, rows, keccak rpow
     std::vector<u32> bcc32[4];      // row_off, code_chunk0, chunk_m, chunk_state
+    BtbArgs btb;                    // EVM tx / block / withdrawal tables from raw block data
+    std::vector<u64> btb64[10];     // tx_fields, offsets, ids, block, hashes, withdrawals, withdrawal ids, tx, block table, withdrawal table
+    std::vector<u32> btb32[6];      // to_is_none, access_list, gas_part, gas_pre, tx_flags, block_flags
     CpaArgs cpa;
     CpaPlan cpa_plan;
     EcdsaArgs ecdsa;
@@ -1181,6 +1185,111 @@ extern "C" int zk_bytecode_from_code(const zk_code_set* in, const zk_code_wire* 
     rc = zk_launch(s, nullptr);
     if (!rc) rc = zk_collect(s, result);
     if (!rc) rc = zk_bytecode_from_code_read(s, out);
+    zk_close(s);
+    return rc;
+}
+
+// ---- EVM circuit tx / block / withdrawal tables from raw block data (block_tables.hpp): the device functions in host loops
+static void tables_from_block_pass(zk_session* s) {
+    BtbArgs& a = s->btb;
+    for (u64 b = 0; b < a.n_gas_blocks; b++) a.gas_part[b] = btb_gas_block(a, b);
+    btb_gas_prefix(a);
+    for (u64 row = 0; row < a.n_tx_rows; row++) {
+        const u64 i = btb_tx_of_row(a, row, 0);
+        const u64 o0 = a.offs[i], o1 = a.offs[i + 1];
+        for (u32 q = 0; q < BTB_TX_PIECES; q++) btb_tx_piece(a, i, o0, o1, row, q, a.tx[(row * BTB_TX_PIECES + q) * 2], a.tx[(row * BTB_TX_PIECES + q) * 2 + 1]);
+        a.tx_flags[row] = btb_tx_flag(i, o0, row);
+    }
+    for (u64 r = 0; r < a.n_block_rows; r++) btb_block_row(a, r);
+    for (u64 r = 0; r < a.n_wd; r++) btb_wd_row(a, r);
+}
+#define BTB_ARGS_OK(t) ((t) && (t)->calldata_offsets && ((t)->n_txs == 0 || ((t)->tx_fields && (t)->to_is_none && (t)->access_list)) && \
+                        ((t)->n_history == 0 || (t)->history_hashes) && ((t)->n_withdrawals == 0 || (t)->withdrawals))
+static int btb_prepare(const zk_block_data* t, BtbPlan& z) {
+    char msg[256];
+    int rc = btb_plan_counts(t->n_txs, t->n_history, t->n_withdrawals, t->block != nullptr, msg, sizeof msg);  // (before any array is read)
+    if (!rc) rc = btb_plan(t->tx_fields, t->calldata_offsets, t->n_txs, t->block, t->n_history, t->withdrawals, t->n_withdrawals, 0, z, msg, sizeof msg);
+    if (rc) { g_err = msg; return rc; }
+    if (z.n_bytes && !t->calldata) { g_err = "zk_evm_tables_from_block: calldata is null"; return -1; }
+    return 0;
+}
+extern "C" int zk_evm_tables_from_block_sizes(const zk_block_data* t, uint32_t opts, uint64_t* n_tx_rows, uint64_t* n_block_rows, uint64_t* n_withdrawal_rows) {
+    NO_DEVICE_PTRS(opts, "zk_evm_tables_from_block_sizes");
+    ARG_TRY(BTB_ARGS_OK(t), "zk_evm_tables_from_block_sizes: bad arguments");
+    BtbPlan z;
+    const int rc = btb_prepare(t, z);
+    if (rc) return rc;
+    if (n_tx_rows) *n_tx_rows = z.n_tx_rows;
+    if (n_block_rows) *n_block_rows = z.n_block_rows;
+    if (n_withdrawal_rows) *n_withdrawal_rows = t->n_withdrawals;
+    return 0;
+}
+extern "C" int zk_evm_tables_from_block_open(const zk_block_data* t, const zk_block_tables* out_dev, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_evm_tables_from_block_open");
+    ARG_TRY(BTB_ARGS_OK(t) && out, "zk_evm_tables_from_block_open: bad arguments");
+    ARG_TRY(!out_dev, "zk_evm_tables_from_block_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    BtbPlan z;
+    int rc = btb_prepare(t, z);
+    if (rc) return rc;
+    const u64 n = t->n_txs, nw = t->n_withdrawals, nh = t->n_history;
+    zk_session* s = new_session(z.n_tx_rows, false);
+    BtbArgs& a = s->btb;
+    memset(&a, 0, sizeof(a));
+    s->btb64[0].assign(t->tx_fields, t->tx_fields + n * BTB_NTX_FIELDS * 4);
+    s->btb64[1].assign(t->calldata_offsets, t->calldata_offsets + n + 1);
+    s->btb64[2].assign(n * 4 + 4, 0);
+    for (u64 i = 0; i < n; i++) memcpy(s->btb64[2].data() + 4 * i, t->tx_fields + i * BTB_NTX_FIELDS * 4, 32);
+    if (t->block) s->btb64[3].assign(t->block, t->block + BTB_NBLOCK_FIELDS * 4);
+    s->btb64[4].assign(t->history_hashes, t->history_hashes + nh * 4);
+    s->btb64[5].assign(t->withdrawals, t->withdrawals + nw * BTB_WD_NCELLS * 4);
+    s->btb64[6].assign(nw * 4 + 4, 0);
+    for (u64 i = 0; i < nw; i++) memcpy(s->btb64[6].data() + 4 * i, t->withdrawals + i * BTB_WD_NCELLS * 4, 32);
+    s->btb64[7].assign(z.n_tx_rows * BTB_TX_NCELLS * 4 + 4, 0);
+    s->btb64[8].assign(z.n_block_rows * BTB_BLOCK_NCELLS * 4 + 4, 0);
+    s->btb64[9].assign(nw * BTB_WD_NCELLS * 4 + 4, 0);
+    s->btb32[0].assign(t->to_is_none, t->to_is_none + n);
+    s->btb32[1].assign(t->access_list, t->access_list + 2 * n);
+    s->a8.assign(z.n_bytes + 16, 0);
+    if (z.n_bytes) memcpy(s->a8.data(), t->calldata, z.n_bytes);
+    a.txf = s->btb64[0].data(); a.offs = s->btb64[1].data(); a.ids = s->btb64[2].data(); a.block = s->btb64[3].data();
+    a.hashes = s->btb64[4].data(); a.wd = s->btb64[5].data(); a.wd_ids = s->btb64[6].data();
+    a.to_none = s->btb32[0].data(); a.access = s->btb32[1].data(); a.calldata = s->a8.data();
+    a.n_txs = n; a.n_bytes = z.n_bytes; a.n_tx_rows = z.n_tx_rows; a.n_hist = nh; a.n_block_rows = z.n_block_rows; a.n_wd = nw;
+    if (t->block) memcpy(a.number, t->block + 4 * 2, 32);
+    a.mis = (u32)((uintptr_t)a.calldata & 15u);
+    a.hist_rot = z.hist_rot;
+    a.n_gas_blocks = z.n_bytes ? (a.mis + z.n_bytes + BTB_GAS_BLOCK - 1) / BTB_GAS_BLOCK : 0;
+    s->btb32[2].assign(a.n_gas_blocks + 1, 0);
+    s->btb32[3].assign(a.n_gas_blocks + 1, 0);
+    s->btb32[4].assign(z.n_tx_rows + 1, 0);
+    s->btb32[5].assign(z.n_block_rows + 1, 0);
+    a.gas_part = s->btb32[2].data(); a.gas_pre = s->btb32[3].data();
+    a.tx = s->btb64[7].data(); a.tx_flags = s->btb32[4].data(); a.blk = s->btb64[8].data(); a.blk_flags = s->btb32[5].data(); a.wdt = s->btb64[9].data();
+    s->pass = tables_from_block_pass;
+    s->assign_kind = 11;
+    *out = s;
+    return 0;
+}
+extern "C" int zk_evm_tables_from_block_read(zk_session* s, const zk_block_tables* host) {
+    ARG_TRY(s && s->assign_kind == 11, "zk_evm_tables_from_block_read: bad arguments");
+    const BtbArgs& a = s->btb;
+    if (host) {
+        if (host->tx) memcpy(host->tx, a.tx, a.n_tx_rows * BTB_TX_NCELLS * 32);
+        if (host->tx_flags) memcpy(host->tx_flags, a.tx_flags, a.n_tx_rows * 4);
+        if (host->block) memcpy(host->block, a.blk, a.n_block_rows * BTB_BLOCK_NCELLS * 32);
+        if (host->block_flags) memcpy(host->block_flags, a.blk_flags, a.n_block_rows * 4);
+        if (host->withdrawals) memcpy(host->withdrawals, a.wdt, a.n_wd * BTB_WD_NCELLS * 32);
+    }
+    return 0;
+}
+extern "C" int zk_evm_tables_from_block(const zk_block_data* t, const zk_block_tables* out_wire, uint32_t opts, zk_result* result) {
+    ARG_TRY(result && out_wire && t, "zk_evm_tables_from_block: null argument");
+    zk_session* s = nullptr;
+    int rc = zk_evm_tables_from_block_open(t, nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc) rc = zk_evm_tables_from_block_read(s, out_wire);
     zk_close(s);
     return rc;
 }

@@ -14,6 +14,7 @@
 #include "secp256k1.hpp"
 #include "bytecode_assign.hpp"
 #include "bytecode_code.hpp"
+#include "block_tables.hpp"
 #include "copy_assign.hpp"
 #include "pi_circuit.hpp"
 #include "state_rekey.hpp"
@@ -79,6 +80,8 @@ void zk_launch_bca_prefix(hipStream_t st, const BcaArgs& a);  // its prefix pass
 // Bytecode table + circuit rows + keccak rows from raw code (k_bytecode_code.hip); side / ev_fork / ev_join as zk_launch_pi_assign
 void zk_launch_bytecode_from_code(hipStream_t st, hipStream_t side, hipEvent_t ev_fork, hipEvent_t ev_join, const BccArgs& a,
                                   const KeccakGenArgs& g, u32* status, ZkTally* tally);
+// EVM circuit tx / block / withdrawal tables from raw block data (k_block_tables.hip): the calldata's non-zero counts, then every row
+void zk_launch_block_tables(hipStream_t st, const BtbArgs& a, u32* status);
 void zk_launch_pi_rows(hipStream_t st, const PiArgs& a, u64 lo, u64 hi, u32* status, ZkTally* tally);
 void zk_launch_pi_copy(hipStream_t st, const PiCopyArgs& a, u32* status, ZkTally* tally);
 void zk_launch_cpa_rpow(hipStream_t st, const Fr& r, u64* out);

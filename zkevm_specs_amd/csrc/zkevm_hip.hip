@@ -605,7 +605,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_BTB = 23, SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -648,6 +648,7 @@ struct zk_session {
     KeccakGenArgs pia_kgen;
     BccArgs bcc;                    // SESSION_BCC (zk_bytecode_from_code*): the chunk tables sit in bcc.p, the keccak pass's arguments in bcc_kgen
     KeccakGenArgs bcc_kgen;
+    BtbArgs btb;                    // SESSION_BTB (zk_evm_tables_from_block*)
     u64 pia_host[4] = {0, 0, 0, 0};  // small host words the open uploads (their source must outlive the asynchronous copy)
     RekeyArgs rekey;
     RwkPlan rekey_plan_host;      // the compact-key plan as uploaded (host copy owned by the session: the upload needs no synchronisation of its own)
@@ -2916,6 +2917,7 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
         zk_launch_bytecode_from_code(s->stream, cside, s->ev_fork, s->ev_join, s->bcc, s->bcc_kgen, status, s->d_tally);
         break;
     }
+    case SESSION_BTB: zk_launch_block_tables(s->stream, s->btb, status); break;
     case SESSION_REKEY:
         zk_launch_state_rekey(s->stream, s->rekey, status, s->d_tally);
         s->sweep_ran = s->rekey.fast != 0;
@@ -4377,6 +4379,158 @@ extern "C" int zk_bytecode_from_code(const zk_code_set* in, const zk_code_wire* 
     rc = zk_launch(s, nullptr);
     if (!rc) rc = zk_collect(s, result);
     if (!rc) rc = zk_bytecode_from_code_read(s, dev ? nullptr : out);
+    zk_close(s);
+    return rc;
+}
+
+// ---- EVM circuit tx / block / withdrawal tables from raw block data (block_tables.hpp, k_block_tables.hip)
+#define BTB_ARGS_OK(t) ((t) && (t)->calldata_offsets && ((t)->n_txs == 0 || ((t)->tx_fields && (t)->to_is_none && (t)->access_list)) && \
+                        ((t)->n_history == 0 || (t)->history_hashes) && ((t)->n_withdrawals == 0 || (t)->withdrawals))
+// What the open checks, on the host: a device caller's tx fields, offsets, block and withdrawals are read back once (one wait)
+struct BtbHost {
+    std::vector<u64> txf, offs, block, wd;
+    BtbPlan z;
+};
+static int btb_prepare(const zk_block_data* t, bool dev, hipStream_t st, BtbHost& h) {
+    char msg[256];
+    int rc = btb_plan_counts(t->n_txs, t->n_history, t->n_withdrawals, t->block != nullptr, msg, sizeof msg);  // (before anything is read or allocated)
+    if (rc) { g_err = msg; return rc; }
+    const u64 n = t->n_txs, nw = t->n_withdrawals;
+    h.txf.assign((size_t)n * BTB_NTX_FIELDS * 4 + 4, 0);
+    h.offs.assign((size_t)n + 1, 0);
+    h.block.assign(BTB_NBLOCK_FIELDS * 4, 0);
+    h.wd.assign((size_t)nw * BTB_WD_NCELLS * 4 + 4, 0);
+    if (dev) {
+        if (n) HIP_TRY(hipMemcpyAsync(h.txf.data(), t->tx_fields, (size_t)n * BTB_NTX_FIELDS * 32, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(h.offs.data(), t->calldata_offsets, ((size_t)n + 1) * 8, hipMemcpyDeviceToHost, st));
+        if (t->block) HIP_TRY(hipMemcpyAsync(h.block.data(), t->block, BTB_NBLOCK_FIELDS * 32, hipMemcpyDeviceToHost, st));
+        if (nw) HIP_TRY(hipMemcpyAsync(h.wd.data(), t->withdrawals, (size_t)nw * BTB_WD_NCELLS * 32, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    } else {
+        if (n) memcpy(h.txf.data(), t->tx_fields, (size_t)n * BTB_NTX_FIELDS * 32);
+        memcpy(h.offs.data(), t->calldata_offsets, ((size_t)n + 1) * 8);
+        if (t->block) memcpy(h.block.data(), t->block, BTB_NBLOCK_FIELDS * 32);
+        if (nw) memcpy(h.wd.data(), t->withdrawals, (size_t)nw * BTB_WD_NCELLS * 32);
+    }
+    const u32 mis = dev ? (u32)((uintptr_t)t->calldata & 15u) : 0u;  // (host calldata is staged into an aligned buffer)
+    rc = btb_plan(h.txf.data(), h.offs.data(), n, t->block ? h.block.data() : nullptr, t->n_history, h.wd.data(), nw, mis, h.z, msg, sizeof msg);
+    if (rc) { g_err = msg; return rc; }
+    if (h.z.n_bytes && !t->calldata) { g_err = "zk_evm_tables_from_block: calldata is null"; return -1; }
+    return 0;
+}
+extern "C" int zk_evm_tables_from_block_sizes(const zk_block_data* t, uint32_t opts, uint64_t* n_tx_rows, uint64_t* n_block_rows, uint64_t* n_withdrawal_rows) {
+    ARG_TRY(t_device >= 0, "zk_evm_tables_from_block_sizes: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(BTB_ARGS_OK(t), "zk_evm_tables_from_block_sizes: bad arguments");
+    BtbHost h;
+    const int rc = btb_prepare(t, opts & ZK_OPT_DEVICE_PTRS, t_stream ? t_stream : g_own_stream[t_device], h);
+    if (rc) return rc;
+    if (n_tx_rows) *n_tx_rows = h.z.n_tx_rows;
+    if (n_block_rows) *n_block_rows = h.z.n_block_rows;
+    if (n_withdrawal_rows) *n_withdrawal_rows = t->n_withdrawals;
+    return 0;
+}
+extern "C" int zk_evm_tables_from_block_open(const zk_block_data* t, const zk_block_tables* out_dev, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_evm_tables_from_block_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(BTB_ARGS_OK(t) && out, "zk_evm_tables_from_block_open: bad arguments");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    ARG_TRY(dev || !out_dev, "zk_evm_tables_from_block_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    zk_session* s = new zk_session();
+    s->kind = SESSION_BTB;
+    BtbArgs& a = s->btb;
+    memset(&a, 0, sizeof(a));
+    BtbHost h;
+    std::vector<u64> ids, wd_ids;
+    std::vector<u32> wave_tx;
+    const void* p = nullptr;
+    void* d = nullptr;
+    const u64 n = t->n_txs, nw = t->n_withdrawals, nh = t->n_history;
+    int rc = btb_prepare(t, dev, s->stream, h);
+    if (rc) goto fail;
+    {
+        const BtbPlan& z = h.z;
+        s->n = z.n_tx_rows;
+        ids.assign((size_t)n * 4 + 4, 0);
+        wd_ids.assign((size_t)nw * 4 + 4, 0);
+        for (u64 i = 0; i < n; i++) memcpy(ids.data() + 4 * i, h.txf.data() + i * BTB_NTX_FIELDS * 4, 32);
+        for (u64 i = 0; i < nw; i++) memcpy(wd_ids.data() + 4 * i, h.wd.data() + i * BTB_WD_NCELLS * 4, 32);
+        if ((rc = stage(s, t->tx_fields, (size_t)n * BTB_NTX_FIELDS * 32, dev, &p))) goto fail;
+        a.txf = (const u64*)p;
+        if ((rc = stage(s, t->to_is_none, (size_t)n * 4, dev, &p))) goto fail;
+        a.to_none = (const u32*)p;
+        if ((rc = stage(s, t->access_list, (size_t)n * 8, dev, &p))) goto fail;
+        a.access = (const u32*)p;
+        if ((rc = stage(s, z.n_bytes ? t->calldata : nullptr, (size_t)z.n_bytes, dev, &p))) goto fail;
+        a.calldata = (const uint8_t*)p;
+        if ((rc = stage(s, t->block, t->block ? BTB_NBLOCK_FIELDS * 32 : 0, dev, &p))) goto fail;
+        a.block = (const u64*)p;
+        if ((rc = stage(s, t->history_hashes, (size_t)nh * 32, dev, &p))) goto fail;
+        a.hashes = (const u64*)p;
+        if ((rc = stage(s, t->withdrawals, (size_t)nw * BTB_WD_NCELLS * 32, dev, &p))) goto fail;
+        a.wd = (const u64*)p;
+        // the session's own copies of what was checked (fixed for the session: a caller that rewrites its offsets cannot move a store)
+        if ((rc = stage(s, h.offs.data(), ((size_t)n + 1) * 8, false, &p))) goto fail;
+        a.offs = (const u64*)p;
+        if ((rc = stage(s, ids.data(), (size_t)n * 32, false, &p))) goto fail;
+        a.ids = (const u64*)p;
+        if ((rc = stage(s, wd_ids.data(), (size_t)nw * 32, false, &p))) goto fail;
+        a.wd_ids = (const u64*)p;
+        wave_tx.assign((size_t)((z.n_tx_rows * BTB_TX_PIECES + 63) / 64) + 1, 0);
+        btb_wave_index(h.offs.data(), n, z.n_tx_rows, wave_tx.data());
+        if ((rc = stage(s, wave_tx.data(), wave_tx.size() * 4, false, &p))) goto fail;
+        a.wave_tx = (const u32*)p;
+        a.n_txs = n; a.n_bytes = z.n_bytes; a.n_tx_rows = z.n_tx_rows; a.n_hist = nh; a.n_block_rows = z.n_block_rows; a.n_wd = nw;
+        if (t->block) memcpy(a.number, h.block.data() + 4 * 2, 32);
+        a.mis = z.n_bytes ? (u32)((uintptr_t)a.calldata & 15u) : 0u;
+        a.hist_rot = z.hist_rot;
+        a.n_gas_blocks = z.n_bytes ? (a.mis + z.n_bytes + BTB_GAS_BLOCK - 1) / BTB_GAS_BLOCK : 0;
+        // the host vectors above go out of scope with this call
+        if (hipStreamSynchronize(s->stream) != hipSuccess) { rc = -2; g_err = "zk_evm_tables_from_block_open: upload failed"; goto fail; }
+        if ((rc = dev_alloc(s, &d, ((size_t)a.n_gas_blocks + 1) * 4))) goto fail;
+        a.gas_part = (u32*)d;
+        if ((rc = dev_alloc(s, &d, ((size_t)a.n_gas_blocks + 1) * 4))) goto fail;
+        a.gas_pre = (u32*)d;
+#define BTB_OUT_BUF(member, field, type, bytes)                                             \
+    if (out_dev && out_dev->member) a.field = out_dev->member;                              \
+    else { if ((rc = dev_alloc(s, &d, (size_t)(bytes)))) goto fail; a.field = (type*)d; }
+        BTB_OUT_BUF(tx, tx, u64, z.n_tx_rows * BTB_TX_NCELLS * 32)
+        BTB_OUT_BUF(tx_flags, tx_flags, u32, z.n_tx_rows * 4)
+        BTB_OUT_BUF(block, blk, u64, z.n_block_rows * BTB_BLOCK_NCELLS * 32)
+        BTB_OUT_BUF(block_flags, blk_flags, u32, z.n_block_rows * 4)
+        BTB_OUT_BUF(withdrawals, wdt, u64, nw * BTB_WD_NCELLS * 32)
+#undef BTB_OUT_BUF
+    }
+    if ((rc = session_common_init(s))) goto fail;
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_evm_tables_from_block_read(zk_session* s, const zk_block_tables* host) {
+    ARG_TRY(s && s->kind == SESSION_BTB, "zk_evm_tables_from_block_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    const BtbArgs& a = s->btb;
+    if (host) {
+        if (host->tx && a.n_tx_rows) HIP_TRY(hipMemcpyAsync(host->tx, a.tx, (size_t)a.n_tx_rows * BTB_TX_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        if (host->tx_flags && a.n_tx_rows) HIP_TRY(hipMemcpyAsync(host->tx_flags, a.tx_flags, (size_t)a.n_tx_rows * 4, hipMemcpyDeviceToHost, s->stream));
+        if (host->block && a.n_block_rows) HIP_TRY(hipMemcpyAsync(host->block, a.blk, (size_t)a.n_block_rows * BTB_BLOCK_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        if (host->block_flags && a.n_block_rows) HIP_TRY(hipMemcpyAsync(host->block_flags, a.blk_flags, (size_t)a.n_block_rows * 4, hipMemcpyDeviceToHost, s->stream));
+        if (host->withdrawals && a.n_wd) HIP_TRY(hipMemcpyAsync(host->withdrawals, a.wdt, (size_t)a.n_wd * BTB_WD_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+extern "C" int zk_evm_tables_from_block(const zk_block_data* t, const zk_block_tables* out_wire, uint32_t opts, zk_result* result) {
+    ARG_TRY(result && out_wire && t, "zk_evm_tables_from_block: null argument");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    int rc = zk_evm_tables_from_block_open(t, dev ? out_wire : nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc) rc = zk_evm_tables_from_block_read(s, dev ? nullptr : out_wire);
     zk_close(s);
     return rc;
 }

@@ -990,6 +990,92 @@ def open_bytecode_from_code(code, offsets, k, randomness, table_dev=None, rows_d
                  ctypes.byref(w) if w is not None else None, opts, cls=BytecodeFromCodeSession)
 
 
+# ---- EVM circuit tx / block / withdrawal tables from raw block data (zk_evm_tables_from_block*) -------------------------------------
+BLOCK_TABLES_INPUTS = ("tx_fields", "to_is_none", "access_list", "calldata", "offsets", "block", "history_hashes", "withdrawals")
+BLOCK_TABLES_OUTPUTS = ("tx", "tx_flags", "block", "block_flags", "withdrawals")
+CALLDATA_GAS_BLOCK = 256  # bytes of calldata per partial count of the calldata-gas kernel (csrc/block_tables.hpp BTB_GAS_BLOCK)
+
+
+def evm_tables_from_block_shapes(n_txs, calldata_bytes, n_history, n_withdrawals, has_block=True):
+    """name -> (shape, dtype) of the outputs of zk_evm_tables_from_block* (include/zkevm_hip.h)"""
+    t, b, m = 12 * int(n_txs) + int(calldata_bytes), (8 + int(n_history)) if has_block else 0, int(n_withdrawals)
+    return {"tx": ((t, 5, 4), np.uint64), "tx_flags": ((t,), np.uint32), "block": ((b, 4, 4), np.uint64), "block_flags": ((b,), np.uint32),
+            "withdrawals": ((m, 4, 4), np.uint64)}
+
+
+def _evm_tables_from_block_args(raw, outs=None):
+    """zk_evm_tables_from_block* over `raw` = dict(tx_fields uint64[n, 9, 4], to_is_none uint32[n], access_list uint32[n, 2], calldata
+    uint8[b], offsets uint64[n + 1], block uint64[8, 4] or None, history_hashes uint64[h, 4], withdrawals uint64[m, 4, 4]) -> (ZkBlockData,
+    ZkBlockTables of the device outputs or None, opts, kept arrays, shapes).  `outs` (device tensors only, each optional): buffers of
+    BLOCK_TABLES_OUTPUTS the session writes in place; they are sized from raw["calldata"], whose extent must be the offsets' last entry
+    (the opening functions check that against the library's own count)."""
+    n, h, m = _rows(raw["tx_fields"]), _rows(raw.get("history_hashes")), _rows(raw.get("withdrawals"))
+    _expect(raw["tx_fields"], "tx_fields", 8, (None, 9, 4))
+    _expect(raw["to_is_none"], "to_is_none", 4, (n,))
+    _expect(raw["access_list"], "access_list", 4, (n, 2))
+    _expect(raw["calldata"], "calldata", 1, (None,))
+    _expect(raw["offsets"], "offsets", 8, (n + 1,))
+    _expect(raw.get("block"), "block", 8, (8, 4))
+    _expect(raw.get("history_hashes"), "history_hashes", 8, (None, 4))
+    _expect(raw.get("withdrawals"), "withdrawals", 8, (None, 4, 4))
+    shapes = evm_tables_from_block_shapes(n, raw["calldata"].shape[0], h, m, raw.get("block") is not None)
+    outs = dict(outs or {})
+    for k, v in outs.items():
+        if v is not None:
+            _expect(v, k, np.dtype(shapes[k][1]).itemsize, shapes[k][0])
+    out_list = [outs.get(k) for k in BLOCK_TABLES_OUTPUTS]
+    a, opts = _prep([raw.get(k) for k in BLOCK_TABLES_INPUTS] + out_list, outputs=range(8, 8 + len(out_list)))
+    if any(v is not None for v in out_list) and not opts:
+        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
+    t = _lib.ZkBlockData(ptr(a[0], n), ptr(a[1], n), ptr(a[2], n), n, ptr(a[3], int(a[3].shape[0])), ptr(a[4]), ptr(a[5]), ptr(a[6], h), h,
+                         ptr(a[7], m), m)
+    w = _lib.ZkBlockTables(*[ptr(x, int(x.shape[0]) if x is not None else 0) for x in a[8:]]) if opts else None
+    return t, w, opts, a, shapes
+
+
+def evm_tables_from_block_sizes(raw, device=None, _prepared=None):
+    """(tx-table rows, block-table rows, withdrawal rows) of the raw block data `raw`; raises EngineError (rc = _lib.ERR_BTB_*) for inputs
+    outside the domain"""
+    lib = _lib.init(device)
+    t, _, opts, keep, _ = _prepared or _evm_tables_from_block_args(raw)
+    a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    check(lib.zk_evm_tables_from_block_sizes(ctypes.byref(t), opts, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
+          "zk_evm_tables_from_block_sizes", lib)
+    return int(a.value), int(b.value), int(c.value)
+
+
+def _check_block_table_sizes(sizes, shapes):
+    if sizes != (shapes["tx"][0][0], shapes["block"][0][0], shapes["withdrawals"][0][0]):
+        raise ValueError(f"calldata: its extent must be the offsets' last entry (the library counts {sizes[0]} tx-table rows, the buffers "
+                         f"are sized for {shapes['tx'][0][0]})")
+
+
+class TablesFromBlockSession(Session):
+    """zk_evm_tables_from_block_open: launch() / collect() like the other assignments (status per tx-table row, always 0);
+    read() -> dict of the last pass's tx / tx_flags / block / block_flags / withdrawals as host arrays"""
+
+    def read(self, names=BLOCK_TABLES_OUTPUTS):
+        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in self.shapes.items() if k in names}
+        w = _lib.ZkBlockTables(*[ptr(out[k], out[k].shape[0]) if k in out else None for k in BLOCK_TABLES_OUTPUTS])
+        check(self._lib.zk_evm_tables_from_block_read(self._h, ctypes.byref(w)), "zk_evm_tables_from_block_read", self._lib)
+        return out
+
+
+def open_evm_tables_from_block(raw, outs=None, device=None):
+    """The EVM circuit's tx, block and withdrawal tables from raw block data `raw` (see _evm_tables_from_block_args) ->
+    TablesFromBlockSession.  numpy inputs are staged to HBM; torch CUDA tensors are used in place, and the CUDA tensors of `outs` (tx /
+    tx_flags / block / block_flags / withdrawals, shapes of evm_tables_from_block_shapes) then receive the tables in place: what
+    open_evm's wire and open_copy's tx / tx_flags take."""
+    lib = _lib.init(device)
+    prepared = _evm_tables_from_block_args(raw, outs)
+    t, w, opts, keep, shapes = prepared
+    _check_block_table_sizes(evm_tables_from_block_sizes(raw, device, prepared), shapes)
+    s = _open(lib, lib.zk_evm_tables_from_block_open, shapes["tx"][0][0], (keep, t, w), ctypes.byref(t),
+              ctypes.byref(w) if w is not None else None, opts, cls=TablesFromBlockSession)
+    s.shapes = shapes
+    return s
+
+
 # ---- Sig circuit witness assignment (zk_sig_assign*) ------------------------------------------------------------------------------
 SIG_ASSIGN_INPUTS = ("fields", "addr", "expect_valid")
 SIG_ASSIGN_OUTPUTS = ("bytes", "cells", "meta", "keccak", "sig_table", "aux")

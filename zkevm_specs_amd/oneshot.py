@@ -124,6 +124,21 @@ def bytecode_from_code(code, offsets, k, randomness, device=None):
     return (Result(r), *out)
 
 
+def evm_tables_from_block(raw, device=None):
+    """zk_evm_tables_from_block over raw block data of host arrays (engine._evm_tables_from_block_args) -> (Result, dict of tx uint64[12 n +
+    b, 5, 4], tx_flags, block uint64[8 + h, 4, 4] (no rows without a block), block_flags, withdrawals uint64[m, 4, 4])"""
+    lib = _lib.init(device)
+    dtypes = {"calldata": np.uint8, "to_is_none": np.uint32, "access_list": np.uint32}
+    raw = {k: _host(raw.get(k), dtypes.get(k, np.uint64)) for k in engine.BLOCK_TABLES_INPUTS}
+    prepared = engine._evm_tables_from_block_args(raw)
+    t, _, opts, keep, shapes = prepared
+    engine._check_block_table_sizes(engine.evm_tables_from_block_sizes(raw, device, prepared), shapes)
+    out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items()}
+    w, r = _lib.ZkBlockTables(*[ptr(out[k], out[k].shape[0]) for k in engine.BLOCK_TABLES_OUTPUTS]), ZkResult()
+    check(lib.zk_evm_tables_from_block(ctypes.byref(t), ctypes.byref(w), opts, ctypes.byref(r)), "zk_evm_tables_from_block", lib)
+    return Result(r), out
+
+
 def ecdsa_verify(sig_bytes, v=None, layout=0, v_stride=1, device=None):
     """zk_ecdsa_verify -> (Result, status uint32[n])"""
     lib = _lib.init(device)
