@@ -911,6 +911,58 @@ int zk_evm_tables_from_block_open(const zk_block_data* in, const zk_block_tables
 int zk_evm_tables_from_block_read(zk_session* s, const zk_block_tables* host);
 int zk_evm_tables_from_block(const zk_block_data* in, const zk_block_tables* out, uint32_t opts, zk_result* result);
 
+/* ---- EVM circuit witness from compact trace records: replaces flatten_rw_table / flatten_steps over RWTableRow / StepState objects
+ *      (src/zkevm_specs/evm_circuit/table.py:447-457, step.py:6-75) and the upload of their result: 14 cells x 32 B + a flag per RW row,
+ *      13 x 32 B per step.  A producer of traces holds these values in their natural widths; the records below carry them so.
+ *      Inputs (zk_trace), integers little-endian, a "pool word" 256 bits as 4 x u64:
+ *        RW ops: head uint32[n_rw], id / addr / val / prev uint64[n_rw]; rw_counter uint64[n_rw], nullable (NULL: the counter of op i is
+ *          rw_base + i); pool uint64[n_pool][4].  head: bit 0 is_write, bits 1-4 tag, bits 8-15 field_tag, bit 16 value.is_word, bit 17
+ *          value_prev.is_word, bit 20 the address is a pool word, bit 21 storage_key is present, bit 22 value is a pool word, bit 23
+ *          value_prev is a pool word, bit 24 aux0 is present; every other bit must be zero.  An op consumes its pool words in the order
+ *          address, key, value, prev, aux, and the ops consume the pool in their order: the offsets are computed, not passed.
+ *        steps uint64[n_steps][13]: w0 = execution_state (bits 0-7) | is_root << 8 | is_create << 9 (other bits zero); w1..w8 rw_counter,
+ *          call_id, program_counter, stack_pointer, gas_left, memory_word_size, reversible_write_counter, log_id; w9..w12 the code hash.
+ *      Outputs (zk_trace_witness): rw uint64[n_rw][14][4], rw_flags uint32[n_rw], steps uint64[n_steps][13][4] - the arrays zk_evm_tables
+ *      takes, cell for cell and flag for flag what flatten_rw_table / flatten_steps return for the same rows:
+ *        rw_counter, is_write, tag, id, field_tag and every step integer are FQ(u64); address FQ(addr), a pool word reduced mod the BN254
+ *        scalar modulus p; storage_key and aux0 Word(w) split at 128 bits, absent Word(0); value / value_prev: narrow (v, 0) with either
+ *        flag, wide with the is_word bit (w mod 2^128, w >> 128), wide without it (w mod p, 0); the flag word is head bits 16-17; the
+ *        step cells in flatten_steps' order, the code hash as a Word.
+ *      zk_evm_witness_from_trace_sizes: the checks below, and the row counts.  zk_evm_witness_from_trace_open: with ZK_OPT_DEVICE_PTRS
+ *      every input is a device pointer and the non-null pointers of `out_dev` receive the outputs in place (null: the session owns that
+ *      buffer); without the flag out_dev must be NULL.  The checks run on the device at open and one verdict block of 32 bytes is read
+ *      back, not the arrays.  The session keeps its own copy of the heads, of the counters and of the per-row pool offsets: a caller that
+ *      rewrites a head between passes cannot move a store.  id, addr, val, prev, the pool and the steps are read by every pass (on the
+ *      CPU backend from the caller's arrays, which are that backend's resident memory and must outlive the session).
+ *      zk_launch / zk_collect / zk_close as for the other assignments: there is no failing case (the tally is always clean;
+ *      rows_evaluated = n_rw, status uint32[n_rw] all 0).  zk_evm_witness_from_trace_read copies the last pass's outputs to the non-null
+ *      HOST pointers of `host`.
+ *      Domain, rejected at sizes / open with an error code and its text in zk_last_error, never guessed:
+ *        ZK_ERR_TRC_HEAD   a reserved bit of a head or of a step's w0 is set;
+ *        ZK_ERR_TRC_ORDER  the rw_counters are not strictly ascending, or rw_base + n_rw passes 2^64 (strictly ascending counters make
+ *                          the set's order the input order and leave no duplicates);
+ *        ZK_ERR_TRC_POOL   n_pool differs from the words the heads consume;
+ *        ZK_ERR_TRC_ROWS   2^31 rows or more. */
+#define ZK_ERR_TRC_HEAD (-70)
+#define ZK_ERR_TRC_ORDER (-71)
+#define ZK_ERR_TRC_POOL (-72)
+#define ZK_ERR_TRC_ROWS (-73)
+typedef struct zk_trace {
+    const uint32_t* head;  const uint64_t* id;  const uint64_t* addr;  const uint64_t* val;  const uint64_t* prev;  /* [n_rw] each */
+    const uint64_t* rw_counter;  uint64_t rw_base;   /* uint64[n_rw], nullable: rw_base + i */
+    uint64_t n_rw;
+    const uint64_t* pool;  uint64_t n_pool;          /* uint64[n_pool][4] */
+    const uint64_t* steps; uint64_t n_steps;         /* uint64[n_steps][13] */
+} zk_trace;
+typedef struct zk_trace_witness {                    /* each pointer nullable */
+    uint64_t* rw;  uint32_t* rw_flags;               /* uint64[n_rw][14][4], uint32[n_rw] */
+    uint64_t* steps;                                 /* uint64[n_steps][13][4] */
+} zk_trace_witness;
+int zk_evm_witness_from_trace_sizes(const zk_trace* in, uint32_t opts, uint64_t* n_rw_rows, uint64_t* n_step_rows);
+int zk_evm_witness_from_trace_open(const zk_trace* in, const zk_trace_witness* out_dev, uint32_t opts, zk_session** out);
+int zk_evm_witness_from_trace_read(zk_session* s, const zk_trace_witness* host);
+int zk_evm_witness_from_trace(const zk_trace* in, const zk_trace_witness* out, uint32_t opts, zk_result* result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,7 @@ EXPORTED_SYMBOLS = [
     "zk_sig_assign_open", "zk_sig_assign_read", "zk_sig_assign",
     "zk_bytecode_from_code_open", "zk_bytecode_from_code_read", "zk_bytecode_from_code",
     "zk_evm_tables_from_block_sizes", "zk_evm_tables_from_block_open", "zk_evm_tables_from_block_read", "zk_evm_tables_from_block",
+    "zk_evm_witness_from_trace_sizes", "zk_evm_witness_from_trace_open", "zk_evm_witness_from_trace_read", "zk_evm_witness_from_trace",
 ]
 
 OPT_DEVICE_PTRS = 1
@@ -137,6 +138,16 @@ class ZkBlockTables(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("tx", "tx_flags", "block", "block_flags", "withdrawals")]
 
 
+class ZkTrace(ctypes.Structure):
+    _fields_ = [("head", ctypes.c_void_p), ("id", ctypes.c_void_p), ("addr", ctypes.c_void_p), ("val", ctypes.c_void_p), ("prev", ctypes.c_void_p),
+                ("rw_counter", ctypes.c_void_p), ("rw_base", ctypes.c_uint64), ("n_rw", ctypes.c_uint64), ("pool", ctypes.c_void_p),
+                ("n_pool", ctypes.c_uint64), ("steps", ctypes.c_void_p), ("n_steps", ctypes.c_uint64)]
+
+
+class ZkTraceWitness(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("rw", "rw_flags", "steps")]
+
+
 class ZkEcdsaBatch(ctypes.Structure):
     _fields_ = [("bytes", ctypes.c_void_p), ("layout", ctypes.c_uint32), ("v", ctypes.c_void_p), ("v_stride", ctypes.c_uint32),
                 ("n", ctypes.c_uint64), ("out_dev", ctypes.c_void_p), ("out_stride", ctypes.c_uint32)]
@@ -171,6 +182,7 @@ class ZkPiWire(ctypes.Structure):
 ERR_PI_TXS, ERR_PI_WITHDRAWALS, ERR_PI_CALLDATA, ERR_PI_FIELD, ERR_PI_ROWS = -50, -51, -52, -53, -54
 ERR_EXP_CELL, ERR_EXP_ORDER, ERR_EXP_ROWS = -40, -41, -42  # ZK_ERR_EXP_* (include/zkevm_hip.h): why zk_exp_assign* rejected its events
 ERR_BTB_ID, ERR_BTB_OFFSETS, ERR_BTB_HISTORY, ERR_BTB_ROWS = -60, -61, -62, -63  # ZK_ERR_BTB_*: why zk_evm_tables_from_block* rejected its inputs
+ERR_TRC_HEAD, ERR_TRC_ORDER, ERR_TRC_POOL, ERR_TRC_ROWS = -70, -71, -72, -73  # ZK_ERR_TRC_*: why zk_evm_witness_from_trace* rejected its records
 
 
 class ZkBlock(ctypes.Structure):
@@ -329,6 +341,10 @@ def _bind(lib):
     lib.zk_evm_tables_from_block_open.argtypes = [ctypes.POINTER(ZkBlockData), ctypes.POINTER(ZkBlockTables), u32, ctypes.POINTER(vp)]
     lib.zk_evm_tables_from_block_read.argtypes = [vp, ctypes.POINTER(ZkBlockTables)]
     lib.zk_evm_tables_from_block.argtypes = [ctypes.POINTER(ZkBlockData), ctypes.POINTER(ZkBlockTables), u32, ctypes.POINTER(ZkResult)]
+    lib.zk_evm_witness_from_trace_sizes.argtypes = [ctypes.POINTER(ZkTrace), u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_evm_witness_from_trace_open.argtypes = [ctypes.POINTER(ZkTrace), ctypes.POINTER(ZkTraceWitness), u32, ctypes.POINTER(vp)]
+    lib.zk_evm_witness_from_trace_read.argtypes = [vp, ctypes.POINTER(ZkTraceWitness)]
+    lib.zk_evm_witness_from_trace.argtypes = [ctypes.POINTER(ZkTrace), ctypes.POINTER(ZkTraceWitness), u32, ctypes.POINTER(ZkResult)]
     lib.zk_launch.argtypes = [vp, vp]
     lib.zk_collect.argtypes = [vp, ctypes.POINTER(ZkResult)]
     lib.zk_read_status.argtypes = [vp, vp]

@@ -33,6 +33,7 @@
 #include "bytecode_assign.hpp"
 #include "bytecode_code.hpp"
 #include "block_tables.hpp"
+#include "trace_witness.hpp"
 #include "state_rekey.hpp"
 #include "ecc_circuit.hpp"
 #include "withdrawal_circuit.hpp"
@@ -102,7 +103,7 @@ struct zk_session {
     std::vector<u64> w64[4];              // assignment sessions: work / output buffers
     std::vector<u32> out32;
     void (*pass)(zk_session*) = nullptr;  // assignment sessions: one pass computes the outputs and fills `status`
-    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code, 11 tables from block
+    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code, 11 tables from block, 12 witness from trace
     u64 n_ops = 0;                        // RW -> State ops: 1 + kept rows
     std::vector<u32> rekey_plan;          // RW -> State ops: the RwkHostPlan's plan (as words) ...
     std::vector<u32> rekey_jobs;          // ... and its rank jobs (cls, field, base, count)
@@ -129,6 +130,9 @@ struct zk_session {
     BtbArgs btb;                    // EVM tx / block / withdrawal tables from raw block data
     std::vector<u64> btb64[10];     // tx_fields, offsets, ids, block, hashes, withdrawals, withdrawal ids, tx, block table, withdrawal table
     std::vector<u32> btb32[6];      // to_is_none, access_list, gas_part, gas_pre, tx_flags, block_flags
+    TrwArgs trw;                    // EVM witness from compact trace records
+    std::vector<u64> trw64[4];      // counters, offsets, rw, steps
+    std::vector<u32> trw32[2];      // heads, rw_flags
     CpaArgs cpa;
     CpaPlan cpa_plan;
     EcdsaArgs ecdsa;
@@ -1290,6 +1294,91 @@ extern "C" int zk_evm_tables_from_block(const zk_block_data* t, const zk_block_t
     rc = zk_launch(s, nullptr);
     if (!rc) rc = zk_collect(s, result);
     if (!rc) rc = zk_evm_tables_from_block_read(s, out_wire);
+    zk_close(s);
+    return rc;
+}
+
+// ---- EVM circuit witness from compact trace records (trace_witness.hpp): the device functions in host loops.  The session keeps its
+//      own heads, counters and pool offsets; id / addr / val / prev / pool / steps stay the caller's arrays and every pass reads them.
+static void witness_from_trace_pass(zk_session* s) {
+    TrwArgs& a = s->trw;
+    for (u64 row = 0; row < a.n_rw; row++) {
+        const u32 h = a.head[row];
+        const u64 off = a.off[row];
+        for (u32 q = 0; q < TRW_RW_PIECES; q++) trw_rw_piece(a, row, h, off, q, a.rw[(row * TRW_RW_PIECES + q) * 2], a.rw[(row * TRW_RW_PIECES + q) * 2 + 1]);
+        a.rw_flags[row] = trw_rw_flag(h);
+    }
+    for (u64 row = 0; row < a.n_steps; row++)
+        for (u32 q = 0; q < TRW_STEP_PIECES; q++) trw_step_piece(a, row, q, a.steps[(row * TRW_STEP_PIECES + q) * 2], a.steps[(row * TRW_STEP_PIECES + q) * 2 + 1]);
+}
+#define TRW_ARGS_OK(t) ((t) && ((t)->n_rw == 0 || ((t)->head && (t)->id && (t)->addr && (t)->val && (t)->prev)) && ((t)->n_pool == 0 || (t)->pool) && \
+                        ((t)->n_steps == 0 || (t)->steps))
+// the open's checks; head / ctr / off (nullable) receive the session's copies
+static int trw_prepare(const zk_trace* t, u32* head, u64* ctr, u64* off) {
+    char msg[256];
+    int rc = trw_plan_counts(t->n_rw, t->n_steps, t->rw_base, t->rw_counter != nullptr, msg, sizeof msg);  // (before any array is read)
+    if (rc) { g_err = msg; return rc; }
+    u64 v[TRW_V_WORDS];
+    trw_check_host(t->head, t->rw_counter, t->n_rw, t->steps, t->n_steps, head, ctr, off, v);
+    rc = trw_verdict_error(v, t->n_pool, msg, sizeof msg);
+    if (rc) g_err = msg;
+    return rc;
+}
+extern "C" int zk_evm_witness_from_trace_sizes(const zk_trace* t, uint32_t opts, uint64_t* n_rw_rows, uint64_t* n_step_rows) {
+    NO_DEVICE_PTRS(opts, "zk_evm_witness_from_trace_sizes");
+    ARG_TRY(TRW_ARGS_OK(t), "zk_evm_witness_from_trace_sizes: bad arguments");
+    const int rc = trw_prepare(t, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if (n_rw_rows) *n_rw_rows = t->n_rw;
+    if (n_step_rows) *n_step_rows = t->n_steps;
+    return 0;
+}
+extern "C" int zk_evm_witness_from_trace_open(const zk_trace* t, const zk_trace_witness* out_dev, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_evm_witness_from_trace_open");
+    ARG_TRY(TRW_ARGS_OK(t) && out, "zk_evm_witness_from_trace_open: bad arguments");
+    ARG_TRY(!out_dev, "zk_evm_witness_from_trace_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    char msg[256];
+    if (int rc = trw_plan_counts(t->n_rw, t->n_steps, t->rw_base, t->rw_counter != nullptr, msg, sizeof msg)) { g_err = msg; return rc; }  // (before anything is allocated)
+    std::vector<u32> head(t->n_rw + 1, 0);
+    std::vector<u64> ctr(t->rw_counter ? t->n_rw + 1 : 0, 0), off(t->n_rw + 1, 0);
+    const int rc = trw_prepare(t, head.data(), t->rw_counter ? ctr.data() : nullptr, off.data());
+    if (rc) return rc;
+    zk_session* s = new_session(t->n_rw, false);
+    TrwArgs& a = s->trw;
+    memset(&a, 0, sizeof(a));
+    s->trw32[0].swap(head);
+    s->trw64[0].swap(ctr);
+    s->trw64[1].swap(off);
+    s->trw64[2].assign(t->n_rw * TRW_RW_NCELLS * 4 + 4, 0);
+    s->trw64[3].assign(t->n_steps * TRW_STEP_NCELLS * 4 + 4, 0);
+    s->trw32[1].assign(t->n_rw + 1, 0);
+    a.id = t->id; a.addr = t->addr; a.val = t->val; a.prev = t->prev; a.pool = t->pool; a.steps_in = t->steps;
+    a.n_rw = t->n_rw; a.n_pool = t->n_pool; a.n_steps = t->n_steps; a.rw_base = t->rw_base;
+    a.head = s->trw32[0].data(); a.ctr = t->rw_counter ? s->trw64[0].data() : nullptr; a.off = s->trw64[1].data();
+    a.rw = s->trw64[2].data(); a.rw_flags = s->trw32[1].data(); a.steps = s->trw64[3].data();
+    s->pass = witness_from_trace_pass;
+    s->assign_kind = 12;
+    *out = s;
+    return 0;
+}
+extern "C" int zk_evm_witness_from_trace_read(zk_session* s, const zk_trace_witness* host) {
+    ARG_TRY(s && s->assign_kind == 12, "zk_evm_witness_from_trace_read: bad arguments");
+    const TrwArgs& a = s->trw;
+    if (host) {
+        if (host->rw) memcpy(host->rw, a.rw, a.n_rw * TRW_RW_NCELLS * 32);
+        if (host->rw_flags) memcpy(host->rw_flags, a.rw_flags, a.n_rw * 4);
+        if (host->steps) memcpy(host->steps, a.steps, a.n_steps * TRW_STEP_NCELLS * 32);
+    }
+    return 0;
+}
+extern "C" int zk_evm_witness_from_trace(const zk_trace* t, const zk_trace_witness* out_wire, uint32_t opts, zk_result* result) {
+    ARG_TRY(result && out_wire && t, "zk_evm_witness_from_trace: null argument");
+    zk_session* s = nullptr;
+    int rc = zk_evm_witness_from_trace_open(t, nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc) rc = zk_evm_witness_from_trace_read(s, out_wire);
     zk_close(s);
     return rc;
 }

@@ -15,6 +15,7 @@
 #include "bytecode_assign.hpp"
 #include "bytecode_code.hpp"
 #include "block_tables.hpp"
+#include "trace_witness.hpp"
 #include "copy_assign.hpp"
 #include "pi_circuit.hpp"
 #include "state_rekey.hpp"
@@ -82,6 +83,10 @@ void zk_launch_bytecode_from_code(hipStream_t st, hipStream_t side, hipEvent_t e
                                   const KeccakGenArgs& g, u32* status, ZkTally* tally);
 // EVM circuit tx / block / withdrawal tables from raw block data (k_block_tables.hip): the calldata's non-zero counts, then every row
 void zk_launch_block_tables(hipStream_t st, const BtbArgs& a, u32* status);
+// EVM circuit witness from compact trace records (k_trace_witness.hip): the open's checks + pool offsets into a.verdict / a.head / a.ctr /
+// a.off, and a pass's row writer
+void zk_launch_trace_witness_check(hipStream_t st, const TrwArgs& a);
+void zk_launch_trace_witness(hipStream_t st, const TrwArgs& a, u32* status);
 void zk_launch_pi_rows(hipStream_t st, const PiArgs& a, u64 lo, u64 hi, u32* status, ZkTally* tally);
 void zk_launch_pi_copy(hipStream_t st, const PiCopyArgs& a, u32* status, ZkTally* tally);
 void zk_launch_cpa_rpow(hipStream_t st, const Fr& r, u64* out);

@@ -605,7 +605,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_BTB = 23, SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_TRW = 24, SESSION_BTB = 23, SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -649,6 +649,7 @@ struct zk_session {
     BccArgs bcc;                    // SESSION_BCC (zk_bytecode_from_code*): the chunk tables sit in bcc.p, the keccak pass's arguments in bcc_kgen
     KeccakGenArgs bcc_kgen;
     BtbArgs btb;                    // SESSION_BTB (zk_evm_tables_from_block*)
+    TrwArgs trw;                    // SESSION_TRW (zk_evm_witness_from_trace*)
     u64 pia_host[4] = {0, 0, 0, 0};  // small host words the open uploads (their source must outlive the asynchronous copy)
     RekeyArgs rekey;
     RwkPlan rekey_plan_host;      // the compact-key plan as uploaded (host copy owned by the session: the upload needs no synchronisation of its own)
@@ -2918,6 +2919,7 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
         break;
     }
     case SESSION_BTB: zk_launch_block_tables(s->stream, s->btb, status); break;
+    case SESSION_TRW: zk_launch_trace_witness(s->stream, s->trw, status); break;
     case SESSION_REKEY:
         zk_launch_state_rekey(s->stream, s->rekey, status, s->d_tally);
         s->sweep_ran = s->rekey.fast != 0;
@@ -4531,6 +4533,130 @@ extern "C" int zk_evm_tables_from_block(const zk_block_data* t, const zk_block_t
     rc = zk_launch(s, nullptr);
     if (!rc) rc = zk_collect(s, result);
     if (!rc) rc = zk_evm_tables_from_block_read(s, dev ? nullptr : out_wire);
+    zk_close(s);
+    return rc;
+}
+
+// ---- EVM circuit witness from compact trace records (trace_witness.hpp, k_trace_witness.hip)
+#define TRW_ARGS_OK(t) ((t) && ((t)->n_rw == 0 || ((t)->head && (t)->id && (t)->addr && (t)->val && (t)->prev)) && ((t)->n_pool == 0 || (t)->pool) && \
+                        ((t)->n_steps == 0 || (t)->steps))
+// Open a session over the records: the inputs staged (host callers) or used in place, the checks and the pool offsets run on the device,
+// the 32-byte verdict block read back (one wait).  check_only: no output buffers (zk_evm_witness_from_trace_sizes closes the session).
+static int trw_open(const zk_trace* t, const zk_trace_witness* out_dev, uint32_t opts, bool check_only, zk_session** out) {
+    char msg[256];
+    if (int rc = trw_plan_counts(t->n_rw, t->n_steps, t->rw_base, t->rw_counter != nullptr, msg, sizeof msg)) { g_err = msg; return rc; }  // (before anything is read or allocated)
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = new zk_session();
+    s->kind = SESSION_TRW;
+    s->n = t->n_rw;
+    TrwArgs& a = s->trw;
+    memset(&a, 0, sizeof(a));
+    const void* p = nullptr;
+    void* d = nullptr;
+    const u64 n = t->n_rw, ns = t->n_steps;
+    u64 v[TRW_V_WORDS];
+    int rc = 0;
+    if ((rc = stage(s, t->head, (size_t)n * 4, dev, &p))) goto fail;
+    a.head_in = (const u32*)p;
+    if (t->rw_counter && n) {
+        if ((rc = stage(s, t->rw_counter, (size_t)n * 8, dev, &p))) goto fail;
+        a.ctr_in = (const u64*)p;
+    }
+    if ((rc = stage(s, t->id, (size_t)n * 8, dev, &p))) goto fail;
+    a.id = (const u64*)p;
+    if ((rc = stage(s, t->addr, (size_t)n * 8, dev, &p))) goto fail;
+    a.addr = (const u64*)p;
+    if ((rc = stage(s, t->val, (size_t)n * 8, dev, &p))) goto fail;
+    a.val = (const u64*)p;
+    if ((rc = stage(s, t->prev, (size_t)n * 8, dev, &p))) goto fail;
+    a.prev = (const u64*)p;
+    if ((rc = stage(s, t->pool, (size_t)t->n_pool * 32, dev, &p))) goto fail;
+    a.pool = (const u64*)p;
+    if ((rc = stage(s, t->steps, (size_t)ns * TRW_STEP_WORDS * 8, dev, &p))) goto fail;
+    a.steps_in = (const u64*)p;
+    a.n_rw = n; a.n_pool = t->n_pool; a.n_steps = ns; a.rw_base = t->rw_base;
+    // the session's own copies of what is checked (fixed for the session: a caller that rewrites a head cannot move a store)
+    if ((rc = dev_alloc(s, &d, (size_t)n * 4 + 4))) goto fail;
+    a.head = (u32*)d;
+    if (a.ctr_in) {
+        if ((rc = dev_alloc(s, &d, (size_t)n * 8))) goto fail;
+        a.ctr = (u64*)d;
+    }
+    if ((rc = dev_alloc(s, &d, (size_t)n * 8 + 8))) goto fail;
+    a.off = (u64*)d;
+    if ((rc = dev_alloc(s, &d, TRW_V_WORDS * 8))) goto fail;
+    a.verdict = (u64*)d;
+    zk_launch_trace_witness_check(s->stream, a);
+    if (hipGetLastError() != hipSuccess) { rc = -2; g_err = "zk_evm_witness_from_trace: the open's check launch failed"; goto fail; }
+    if ((rc = d2h_now(s->stream, v, a.verdict, sizeof v))) goto fail;  // (also: the staged host arrays are uploaded)
+    if ((rc = trw_verdict_error(v, t->n_pool, msg, sizeof msg))) { g_err = msg; goto fail; }
+    if (!check_only) {
+#define TRW_OUT_BUF(member, type, bytes)                                                    \
+    if (out_dev && out_dev->member) a.member = out_dev->member;                             \
+    else { if ((rc = dev_alloc(s, &d, (size_t)(bytes)))) goto fail; a.member = (type*)d; }
+        TRW_OUT_BUF(rw, u64, n * TRW_RW_NCELLS * 32)
+        TRW_OUT_BUF(rw_flags, u32, n * 4)
+        TRW_OUT_BUF(steps, u64, ns * TRW_STEP_NCELLS * 32)
+#undef TRW_OUT_BUF
+        if ((rc = session_common_init(s))) goto fail;
+    }
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_evm_witness_from_trace_sizes(const zk_trace* t, uint32_t opts, uint64_t* n_rw_rows, uint64_t* n_step_rows) {
+    ARG_TRY(t_device >= 0, "zk_evm_witness_from_trace_sizes: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(TRW_ARGS_OK(t), "zk_evm_witness_from_trace_sizes: bad arguments");
+    if (opts & ZK_OPT_DEVICE_PTRS) {
+        zk_session* s = nullptr;
+        const int rc = trw_open(t, nullptr, opts, true, &s);
+        if (rc) return rc;
+        zk_close(s);
+    } else {  // host arrays: the same checks in a host loop
+        char msg[256];
+        int rc = trw_plan_counts(t->n_rw, t->n_steps, t->rw_base, t->rw_counter != nullptr, msg, sizeof msg);
+        if (!rc) {
+            u64 v[TRW_V_WORDS];
+            trw_check_host(t->head, t->rw_counter, t->n_rw, t->steps, t->n_steps, nullptr, nullptr, nullptr, v);
+            rc = trw_verdict_error(v, t->n_pool, msg, sizeof msg);
+        }
+        if (rc) { g_err = msg; return rc; }
+    }
+    if (n_rw_rows) *n_rw_rows = t->n_rw;
+    if (n_step_rows) *n_step_rows = t->n_steps;
+    return 0;
+}
+extern "C" int zk_evm_witness_from_trace_open(const zk_trace* t, const zk_trace_witness* out_dev, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_evm_witness_from_trace_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(TRW_ARGS_OK(t) && out, "zk_evm_witness_from_trace_open: bad arguments");
+    ARG_TRY((opts & ZK_OPT_DEVICE_PTRS) || !out_dev, "zk_evm_witness_from_trace_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    return trw_open(t, out_dev, opts, false, out);
+}
+extern "C" int zk_evm_witness_from_trace_read(zk_session* s, const zk_trace_witness* host) {
+    ARG_TRY(s && s->kind == SESSION_TRW, "zk_evm_witness_from_trace_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    const TrwArgs& a = s->trw;
+    if (host) {
+        if (host->rw && a.n_rw) HIP_TRY(hipMemcpyAsync(host->rw, a.rw, (size_t)a.n_rw * TRW_RW_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        if (host->rw_flags && a.n_rw) HIP_TRY(hipMemcpyAsync(host->rw_flags, a.rw_flags, (size_t)a.n_rw * 4, hipMemcpyDeviceToHost, s->stream));
+        if (host->steps && a.n_steps) HIP_TRY(hipMemcpyAsync(host->steps, a.steps, (size_t)a.n_steps * TRW_STEP_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return 0;
+}
+extern "C" int zk_evm_witness_from_trace(const zk_trace* t, const zk_trace_witness* out_wire, uint32_t opts, zk_result* result) {
+    ARG_TRY(result && out_wire && t, "zk_evm_witness_from_trace: null argument");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    int rc = zk_evm_witness_from_trace_open(t, dev ? out_wire : nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc) rc = zk_evm_witness_from_trace_read(s, dev ? nullptr : out_wire);
     zk_close(s);
     return rc;
 }

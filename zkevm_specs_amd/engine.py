@@ -1076,6 +1076,77 @@ def open_evm_tables_from_block(raw, outs=None, device=None):
     return s
 
 
+# ---- EVM circuit witness from compact trace records (zk_evm_witness_from_trace*) ---------------------------------------------------
+TRACE_INPUTS = ("head", "id", "addr", "val", "prev", "rw_counter", "pool", "steps")
+TRACE_OUTPUTS = ("rw", "rw_flags", "steps")
+
+
+def evm_witness_from_trace_shapes(n_rw, n_steps):
+    """name -> (shape, dtype) of the outputs of zk_evm_witness_from_trace* (include/zkevm_hip.h)"""
+    return {"rw": ((int(n_rw), 14, 4), np.uint64), "rw_flags": ((int(n_rw),), np.uint32), "steps": ((int(n_steps), 13, 4), np.uint64)}
+
+
+def _evm_witness_from_trace_args(trace, outs=None):
+    """zk_evm_witness_from_trace* over `trace` = dict(head uint32[n], id / addr / val / prev uint64[n], rw_counter uint64[n] or None (then
+    rw_base, default 1: the counter of op i is rw_base + i), pool uint64[m, 4], steps uint64[k, 13]) -> (ZkTrace, ZkTraceWitness of the
+    device outputs or None, opts, kept arrays, shapes).  trace.py makes such records.  `outs` (device tensors only, each optional):
+    buffers of TRACE_OUTPUTS the session writes in place."""
+    n, m, k = _rows(trace.get("head")), _rows(trace.get("pool")), _rows(trace.get("steps"))
+    _expect(trace.get("head"), "head", 4, (None,))
+    for name in ("id", "addr", "val", "prev", "rw_counter"):
+        _expect(trace.get(name), name, 8, (n,))
+        if n and name != "rw_counter" and trace.get(name) is None:
+            raise ValueError(f"{name}: missing")
+    _expect(trace.get("pool"), "pool", 8, (None, 4))
+    _expect(trace.get("steps"), "steps", 8, (None, 13))
+    shapes = evm_witness_from_trace_shapes(n, k)
+    outs = dict(outs or {})
+    for key, v in outs.items():
+        if v is not None:
+            _expect(v, key, np.dtype(shapes[key][1]).itemsize, shapes[key][0])
+    out_list = [outs.get(key) for key in TRACE_OUTPUTS]
+    a, opts = _prep([trace.get(key) for key in TRACE_INPUTS] + out_list, outputs=range(8, 8 + len(out_list)))
+    if any(v is not None for v in out_list) and not opts:
+        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
+    t = _lib.ZkTrace(ptr(a[0], n), ptr(a[1], n), ptr(a[2], n), ptr(a[3], n), ptr(a[4], n), ptr(a[5], n), int(trace.get("rw_base", 1)), n,
+                     ptr(a[6], m), m, ptr(a[7], k), k)
+    w = _lib.ZkTraceWitness(*[ptr(x, int(x.shape[0]) if x is not None else 0) for x in a[8:]]) if opts else None
+    return t, w, opts, a, shapes
+
+
+def evm_witness_from_trace_sizes(trace, device=None, _prepared=None):
+    """(RW rows, step rows) of the trace records `trace`; raises EngineError (rc = _lib.ERR_TRC_*) for records outside the domain"""
+    lib = _lib.init(device)
+    t, _, opts, keep, _ = _prepared or _evm_witness_from_trace_args(trace)
+    a, b = ctypes.c_uint64(), ctypes.c_uint64()
+    check(lib.zk_evm_witness_from_trace_sizes(ctypes.byref(t), opts, ctypes.byref(a), ctypes.byref(b)), "zk_evm_witness_from_trace_sizes", lib)
+    return int(a.value), int(b.value)
+
+
+class WitnessFromTraceSession(Session):
+    """zk_evm_witness_from_trace_open: launch() / collect() like the other assignments (status per RW row, always 0); read() -> dict of
+    the last pass's rw / rw_flags / steps as host arrays"""
+
+    def read(self, names=TRACE_OUTPUTS):
+        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in self.shapes.items() if k in names}
+        w = _lib.ZkTraceWitness(*[ptr(out[k], out[k].shape[0]) if k in out else None for k in TRACE_OUTPUTS])
+        check(self._lib.zk_evm_witness_from_trace_read(self._h, ctypes.byref(w)), "zk_evm_witness_from_trace_read", self._lib)
+        return out
+
+
+def open_evm_witness_from_trace(trace, outs=None, device=None):
+    """The EVM circuit's RW table, its flags and its step table from compact trace records `trace` (see _evm_witness_from_trace_args) ->
+    WitnessFromTraceSession.  numpy inputs are staged to HBM (the CPU backend reads id / addr / val / prev / pool / steps in place, every
+    pass); torch CUDA tensors are used in place, and the CUDA tensors of `outs` (rw / rw_flags / steps, shapes of
+    evm_witness_from_trace_shapes) then receive the rows in place: what open_evm's wire and the from-RW State sessions take."""
+    lib = _lib.init(device)
+    t, w, opts, keep, shapes = _evm_witness_from_trace_args(trace, outs)
+    s = _open(lib, lib.zk_evm_witness_from_trace_open, shapes["rw"][0][0], (keep, t, w), ctypes.byref(t),
+              ctypes.byref(w) if w is not None else None, opts, cls=WitnessFromTraceSession)
+    s.shapes = shapes
+    return s
+
+
 # ---- Sig circuit witness assignment (zk_sig_assign*) ------------------------------------------------------------------------------
 SIG_ASSIGN_INPUTS = ("fields", "addr", "expect_valid")
 SIG_ASSIGN_OUTPUTS = ("bytes", "cells", "meta", "keccak", "sig_table", "aux")

@@ -139,6 +139,19 @@ def evm_tables_from_block(raw, device=None):
     return Result(r), out
 
 
+def evm_witness_from_trace(trace, device=None):
+    """zk_evm_witness_from_trace over trace records of host arrays (engine._evm_witness_from_trace_args, trace.py) -> (Result, dict of rw
+    uint64[n, 14, 4], rw_flags uint32[n], steps uint64[k, 13, 4])"""
+    lib = _lib.init(device)
+    rec = {k: _host(trace.get(k), np.uint32 if k == "head" else np.uint64) for k in engine.TRACE_INPUTS}
+    rec["rw_base"] = trace.get("rw_base", 1)
+    t, _, opts, keep, shapes = engine._evm_witness_from_trace_args(rec)
+    out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items()}
+    w, r = _lib.ZkTraceWitness(*[ptr(out[k], out[k].shape[0]) for k in engine.TRACE_OUTPUTS]), ZkResult()
+    check(lib.zk_evm_witness_from_trace(ctypes.byref(t), ctypes.byref(w), opts, ctypes.byref(r)), "zk_evm_witness_from_trace", lib)
+    return Result(r), out
+
+
 def ecdsa_verify(sig_bytes, v=None, layout=0, v_stride=1, device=None):
     """zk_ecdsa_verify -> (Result, status uint32[n])"""
     lib = _lib.init(device)
