@@ -963,6 +963,75 @@ int zk_evm_witness_from_trace_open(const zk_trace* in, const zk_trace_witness* o
 int zk_evm_witness_from_trace_read(zk_session* s, const zk_trace_witness* host);
 int zk_evm_witness_from_trace(const zk_trace* in, const zk_trace_witness* out, uint32_t opts, zk_result* result);
 
+/* ---- ECC precompile calls: from the INPUT words of ecAdd / ecMul / ecPairing calls to what both circuits derive from them.  Where
+ *      zk_ecc_ops takes every op's result from the caller (points[..][4..5], pair_out) and zk_ecc_assign copies it into rows, this
+ *      entry computes the result on the device: the ECC circuit's ops and rows (circuit2rows, src/zkevm_specs/ecc_circuit.py:386-421),
+ *      and the EVM circuit's ecc table and aux rows of kinds 6 / 7 / 8, which the reference's tests build with py_ecc
+ *      (tests/evm/precompiles/test_ecAdd.py:80-101, test_ecMul.py, test_ecPairing.py:180-222).
+ *      Inputs (zk_ecc_calls), 256-bit words as 4 x u64 little-endian, NOT reduced, each the integer of one 32-byte word of the
+ *      precompile's input; order and layout of the pairing arrays are zk_ecc_ops', so those can be reused:
+ *        add_in uint64[n_add][4][4]: p.x, p.y, q.x, q.y;   mul_in uint64[n_mul][3][4]: p.x, p.y, s;
+ *        pair_pts uint64[pair_off[n_pairing]][6][4] in EIP-197 order (p.x, p.y, x.c1, x.c0, y.c1, y.c0), pair_off uint32[n_pairing + 1]
+ *        (pair_off[0] = 0, non-decreasing; an op may have no pair); randomness: one cell (keccak_randomness).
+ *        A pairing call whose byte length is no multiple of 192 cannot be expressed in pairs and stays the caller's to handle (its
+ *        aux row is (rlc, pairs, 0, 0)).  The reference disagrees with itself there: its EVM test takes the RLC over ALL the bytes
+ *        (test_ecPairing.py:180-200) while assign_pairing takes it over whole pairs (ecc_circuit.py:204-227).
+ *      Semantics, n = n_add + n_mul + n_pairing calls in circuit2rows order (adds, muls, pairings):
+ *        is_valid is what EccCircuitRow.assign_add / assign_mul / assign_pairing compute (ecc_circuit.py:49-232): every coordinate below
+ *        the base modulus p, (0, 0) the point at infinity, the point on the curve (G2: on the twist), and for pairings both subgroup
+ *        checks ([r]P, [r]Q at infinity).  A valid call's result is the precompile's (EIP-196 / EIP-197): p + q; [s]P with s the full
+ *        256-bit integer, infinity as (0, 0); 1 or 0 for the pairing product, 1 for the empty input.  An invalid call's result is zero
+ *        with is_valid 0, what ecadd.py:29-35 and ecpairing.py:34-61 require of a failed call.  input_rlc is assign_pairing's
+ *        (ecc_circuit.py:204-227: the words p.x, p.y, x.c0, x.c1, y.c0, y.c1 of every pair as 32 little-endian bytes, reversed); 0 for
+ *        add / mul.  (The reference's EVM test orders the G2 words as the input does, x.c1 first, test_ecPairing.py:181-190: the same
+ *        bytes in another order.  Table and aux row come from one value here, so the lookup of ecpairing.py:51-61 holds either way.)
+ *        Quirk, pinned: ECCVerifyChip takes ecMul's scalar as FP(s) (util/ec.py:120-166, ecc_circuit.py:125-129), i.e. s mod p, while the
+ *        group's order is r and the row carries Word(s).  For s >= p the ECC circuit (zk_ecc_verify / zk_ecc_open) therefore REJECTS the
+ *        row of the correct EVM result this entry returns: already at the scalar's own copy constraint (ECC_COPY_QX: the chip holds s mod
+ *        p, the row s), and its product [s mod p]P would differ from [s]P as well.  The entry returns the EVM result.  Likewise a
+ *        coordinate >= p fails its copy constraint there, and an invalid pairing call has no satisfying row (verify_pairing insists on
+ *        the subgroup checks): such calls are well-defined EVM-side (is_valid 0, zero result) and rejected by the ECC circuit.
+ *      Outputs (zk_ecc_call_wire), every member nullable:
+ *        points uint64[n_add + n_mul][6][4], pair_out uint64[n_pairing][4]: with the caller's pair_pts / pair_off a complete zk_ecc_ops;
+ *        rows uint64[n][13][4]: circuit2rows' rows, what zk_ecc_open takes (out_x / out_y: the residue mod p, as zk_ecc_assign writes it);
+ *        ecc_table uint64[n capacity][13][4]: every call's row with out_x / out_y as FQ cells (the residue reduced mod the scalar
+ *          modulus) — the first occurrence of every distinct row, in input order (the EVM tables are sets: sig_table's rule); the row
+ *          count comes out of zk_ecc_from_calls_read / zk_ecc_from_calls (zk_evm_tables.ecc / n_ecc);
+ *        aux uint64[n][12][4] + aux_kind uint32[n], row i for call i in zk_evm_tables.aux's layout: kind 6 px, py, qx, qy as lo / hi then
+ *          outx, outy; kind 7 px, py, s as lo / hi then outx, outy; kind 8 input_rlc, input_pairs, is_valid_input, output; unused cells 0.
+ *      Session protocol as zk_sig_assign_*: with ZK_OPT_DEVICE_PTRS the inputs are device pointers and the non-null members of out_dev
+ *      are written in place (null, or a null out_dev: the session owns that buffer); without it out_dev must be NULL.  zk_launch
+ *      (status_dev: uint32[n], always 0 — an invalid call has defined outputs, there is no failing case) / zk_collect / zk_read_status /
+ *      zk_close.  The open reads back pair_off and the randomness cell only (pair_off is fixed for the session: it keeps its own copy);
+ *      points are never read back, and the call words are read by every pass (on the CPU backend from the caller's arrays, which are
+ *      that backend's resident memory and must outlive the session).  A pass is the add / mul
+ *      launch (one lane per call), pairing stage 1 (one lane per pair: zk_ecc_open's record), pairing stage 2 (one lane per call) and
+ *      the table's two launches; every output is final in stream order.  zk_ecc_from_calls_read copies the last pass's outputs to the
+ *      non-null HOST pointers of `host` (nullable) and the table's row count out (nullable).
+ *      Domain, rejected at open with an error code and its text in zk_last_error, never guessed:
+ *        ZK_ERR_ECL_OFFSETS     pair_off[0] != 0, or offsets that decrease;
+ *        ZK_ERR_ECL_ROWS        2^31 calls or pairs, or more;
+ *        ZK_ERR_ECL_RANDOMNESS  the randomness cell is not canonical. */
+#define ZK_ERR_ECL_OFFSETS (-80)
+#define ZK_ERR_ECL_ROWS (-81)
+#define ZK_ERR_ECL_RANDOMNESS (-82)
+typedef struct zk_ecc_calls {
+    const uint64_t* add_in;     uint64_t n_add;      /* uint64[n_add][4][4] */
+    const uint64_t* mul_in;     uint64_t n_mul;      /* uint64[n_mul][3][4] */
+    const uint64_t* pair_pts;   const uint32_t* pair_off;   uint64_t n_pairing;
+    const uint64_t* randomness;                      /* one cell: keccak_randomness */
+} zk_ecc_calls;
+typedef struct zk_ecc_call_wire {                    /* each pointer nullable */
+    uint64_t* points;    uint64_t* pair_out;         /* uint64[n_add + n_mul][6][4], uint64[n_pairing][4] */
+    uint64_t* rows;                                  /* uint64[n][13][4] */
+    uint64_t* ecc_table;                             /* uint64[n capacity][13][4] */
+    uint64_t* aux;       uint32_t* aux_kind;         /* uint64[n][12][4], uint32[n] */
+} zk_ecc_call_wire;
+int zk_ecc_from_calls_open(const zk_ecc_calls* in, const zk_ecc_call_wire* out_dev, uint32_t opts, zk_session** out);
+int zk_ecc_from_calls_read(zk_session* s, const zk_ecc_call_wire* host, uint64_t* n_table_rows_out);
+int zk_ecc_from_calls(const zk_ecc_calls* in, const zk_ecc_call_wire* out, uint32_t opts, uint32_t* status_out,
+                      uint64_t* n_table_rows_out, zk_result* result);
+
 #ifdef __cplusplus
 }
 #endif

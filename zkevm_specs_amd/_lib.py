@@ -31,6 +31,7 @@ EXPORTED_SYMBOLS = [
     "zk_bytecode_from_code_open", "zk_bytecode_from_code_read", "zk_bytecode_from_code",
     "zk_evm_tables_from_block_sizes", "zk_evm_tables_from_block_open", "zk_evm_tables_from_block_read", "zk_evm_tables_from_block",
     "zk_evm_witness_from_trace_sizes", "zk_evm_witness_from_trace_open", "zk_evm_witness_from_trace_read", "zk_evm_witness_from_trace",
+    "zk_ecc_from_calls_open", "zk_ecc_from_calls_read", "zk_ecc_from_calls",
 ]
 
 OPT_DEVICE_PTRS = 1
@@ -148,6 +149,15 @@ class ZkTraceWitness(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("rw", "rw_flags", "steps")]
 
 
+class ZkEccCalls(ctypes.Structure):
+    _fields_ = [("add_in", ctypes.c_void_p), ("n_add", ctypes.c_uint64), ("mul_in", ctypes.c_void_p), ("n_mul", ctypes.c_uint64),
+                ("pair_pts", ctypes.c_void_p), ("pair_off", ctypes.c_void_p), ("n_pairing", ctypes.c_uint64), ("randomness", ctypes.c_void_p)]
+
+
+class ZkEccCallWire(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("points", "pair_out", "rows", "ecc_table", "aux", "aux_kind")]
+
+
 class ZkEcdsaBatch(ctypes.Structure):
     _fields_ = [("bytes", ctypes.c_void_p), ("layout", ctypes.c_uint32), ("v", ctypes.c_void_p), ("v_stride", ctypes.c_uint32),
                 ("n", ctypes.c_uint64), ("out_dev", ctypes.c_void_p), ("out_stride", ctypes.c_uint32)]
@@ -183,6 +193,7 @@ ERR_PI_TXS, ERR_PI_WITHDRAWALS, ERR_PI_CALLDATA, ERR_PI_FIELD, ERR_PI_ROWS = -50
 ERR_EXP_CELL, ERR_EXP_ORDER, ERR_EXP_ROWS = -40, -41, -42  # ZK_ERR_EXP_* (include/zkevm_hip.h): why zk_exp_assign* rejected its events
 ERR_BTB_ID, ERR_BTB_OFFSETS, ERR_BTB_HISTORY, ERR_BTB_ROWS = -60, -61, -62, -63  # ZK_ERR_BTB_*: why zk_evm_tables_from_block* rejected its inputs
 ERR_TRC_HEAD, ERR_TRC_ORDER, ERR_TRC_POOL, ERR_TRC_ROWS = -70, -71, -72, -73  # ZK_ERR_TRC_*: why zk_evm_witness_from_trace* rejected its records
+ERR_ECL_OFFSETS, ERR_ECL_ROWS, ERR_ECL_RANDOMNESS = -80, -81, -82  # ZK_ERR_ECL_*: why zk_ecc_from_calls* rejected its calls
 
 
 class ZkBlock(ctypes.Structure):
@@ -345,6 +356,10 @@ def _bind(lib):
     lib.zk_evm_witness_from_trace_open.argtypes = [ctypes.POINTER(ZkTrace), ctypes.POINTER(ZkTraceWitness), u32, ctypes.POINTER(vp)]
     lib.zk_evm_witness_from_trace_read.argtypes = [vp, ctypes.POINTER(ZkTraceWitness)]
     lib.zk_evm_witness_from_trace.argtypes = [ctypes.POINTER(ZkTrace), ctypes.POINTER(ZkTraceWitness), u32, ctypes.POINTER(ZkResult)]
+    lib.zk_ecc_from_calls_open.argtypes = [ctypes.POINTER(ZkEccCalls), ctypes.POINTER(ZkEccCallWire), u32, ctypes.POINTER(vp)]
+    lib.zk_ecc_from_calls_read.argtypes = [vp, ctypes.POINTER(ZkEccCallWire), ctypes.POINTER(u64)]
+    lib.zk_ecc_from_calls.argtypes = [ctypes.POINTER(ZkEccCalls), ctypes.POINTER(ZkEccCallWire), u32, vp, ctypes.POINTER(u64),
+                                      ctypes.POINTER(ZkResult)]
     lib.zk_launch.argtypes = [vp, vp]
     lib.zk_collect.argtypes = [vp, ctypes.POINTER(ZkResult)]
     lib.zk_read_status.argtypes = [vp, vp]

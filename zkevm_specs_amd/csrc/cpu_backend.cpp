@@ -36,6 +36,7 @@
 #include "trace_witness.hpp"
 #include "state_rekey.hpp"
 #include "ecc_circuit.hpp"
+#include "ecc_calls.hpp"
 #include "withdrawal_circuit.hpp"
 #include "tx_assign.hpp"
 #include "sig_assign.hpp"
@@ -103,7 +104,7 @@ struct zk_session {
     std::vector<u64> w64[4];              // assignment sessions: work / output buffers
     std::vector<u32> out32;
     void (*pass)(zk_session*) = nullptr;  // assignment sessions: one pass computes the outputs and fills `status`
-    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code, 11 tables from block, 12 witness from trace
+    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code, 11 tables from block, 12 witness from trace, 13 ECC precompile calls
     u64 n_ops = 0;                        // RW -> State ops: 1 + kept rows
     std::vector<u32> rekey_plan;          // RW -> State ops: the RwkHostPlan's plan (as words) ...
     std::vector<u32> rekey_jobs;          // ... and its rank jobs (cls, field, base, count)
@@ -148,6 +149,11 @@ struct zk_session {
     PiaSizes pia_sizes;
     KeccakGenArgs pia_kgen;
     EccArgs ecc_assign;             // ECC assignment session (the verify session's args live in its `row` closure)
+    EccCallArgs ecl;                // ECC precompile calls
+    std::vector<u64> ecl64[10];     // [3..8]: points, pair_out, rows, table candidates, table, aux
+    std::vector<u32> ecl32[4];      // pair_off, aux_kind, tdup, pair_flags
+    std::vector<bn::Fq12> ecl_f;    // the pairs' Miller values
+    u64 n_ecl_table = 0;
     std::vector<u64> pia64[20];     // PI assignment: inputs, work buffers and outputs of 64-bit words
     std::vector<u32> pia32[6];
     std::vector<uint8_t> pia8[4];
@@ -2068,6 +2074,97 @@ extern "C" int zk_sig_assign(const zk_sig_inputs* in, const zk_sig_wire* out, ui
     if (!rc) rc = zk_collect(s, result);
     if (!rc && status_out) rc = zk_read_status(s, status_out);
     if (!rc) rc = zk_sig_assign_read(s, out, n_keccak_out, n_sig_rows_out);
+    zk_close(s);
+    return rc;
+}
+
+// ---- ECC precompile calls (ecc_calls.hpp): the device functions in host loops
+static void ecc_calls_pass(zk_session* s) {
+    const EccCallArgs& a = s->ecl;
+    const long long np = (long long)(a.n_add + a.n_mul), n = np + (long long)a.n_pairing;
+    const long long n_pp = a.n_pairing ? (long long)a.pair_off[a.n_pairing] : 0;
+#pragma omp parallel for schedule(dynamic, 16)
+    for (long long i = 0; i < np; i++) ecc_call_point(a, (u64)i);
+    EccPairArgs pr{};
+    pr.a.pair_pts = a.pair_pts;
+    pr.pair_flags = a.pair_flags;
+    pr.pair_f = a.pair_f;
+#pragma omp parallel for schedule(dynamic, 1)
+    for (long long t = 0; t < n_pp; t++) ecc_pair_stage1(pr, (u32)t);
+#pragma omp parallel for schedule(dynamic, 1)
+    for (long long k = 0; k < (long long)a.n_pairing; k++) ecc_call_pairing(a, (u64)k);
+    // the ecc table: first occurrences in input order (equal rows are adjacent once sorted by (row, index))
+    const u64* tc = a.tcand;
+    std::vector<u64> idx((size_t)n);
+    for (long long k = 0; k < n; k++) idx[k] = (u64)k;
+    std::sort(idx.begin(), idx.end(), [tc](u64 x, u64 y) {
+        const int c = memcmp(tc + x * ECL_ROW_WORDS, tc + y * ECL_ROW_WORDS, ECL_ROW_WORDS * 8);
+        return c ? c < 0 : x < y;
+    });
+    for (long long k = 0; k < n; k++) a.tdup[idx[k]] = k && ecl_row_eq(tc + idx[k - 1] * ECL_ROW_WORDS, tc + idx[k] * ECL_ROW_WORDS);
+    u64 m = 0;
+    for (long long k = 0; k < n; k++)
+        if (!a.tdup[k]) memcpy(a.ecc_table + m++ * ECL_ROW_WORDS, tc + (u64)k * ECL_ROW_WORDS, ECL_ROW_WORDS * 8);
+    s->n_ecl_table = m;
+    std::fill(s->status.begin(), s->status.end(), 0u);
+}
+extern "C" int zk_ecc_from_calls_open(const zk_ecc_calls* in, const zk_ecc_call_wire* out_dev, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_ecc_from_calls_open");
+    ARG_TRY(in && out && !out_dev, "zk_ecc_from_calls_open: bad arguments (out_dev needs ZK_OPT_DEVICE_PTRS)");
+    EccCallArgs a;
+    memset(&a, 0, sizeof(a));
+    const char* err = nullptr;
+    if (int rc = ecc_calls_check(in, a, &err)) { g_err = std::string("zk_ecc_from_calls_open: ") + err; return rc; }
+    const u64 np = a.n_add + a.n_mul, n = np + a.n_pairing, n_pp = a.n_pairing ? in->pair_off[a.n_pairing] : 0;
+    zk_session* s = new_session(n, false);
+    // (the call words are read in place by every pass: the caller's arrays are this backend's resident memory; pair_off is copied)
+    s->ecl32[0].assign(a.n_pairing + 1, 0u);
+    if (a.n_pairing) memcpy(s->ecl32[0].data(), in->pair_off, (a.n_pairing + 1) * 4);
+    s->ecl64[3].assign(np * 24 + 4, 0);
+    s->ecl64[4].assign(a.n_pairing * 4 + 4, 0);
+    s->ecl64[5].assign(n * ECL_ROW_WORDS, 0);
+    s->ecl64[6].assign(n * ECL_ROW_WORDS, 0);
+    s->ecl64[7].assign(n * ECL_ROW_WORDS, 0);
+    s->ecl64[8].assign(n * ECL_AUX_CELLS * 4, 0);
+    s->ecl32[1].assign(n, 0u);
+    s->ecl32[2].assign(n, 0u);
+    s->ecl32[3].assign(n_pp + 1, 0u);
+    s->ecl_f.resize(n_pp + 1);
+    a.add_in = in->add_in; a.mul_in = in->mul_in; a.pair_pts = in->pair_pts; a.pair_off = s->ecl32[0].data();
+    a.points = s->ecl64[3].data(); a.pair_out = s->ecl64[4].data(); a.rows = s->ecl64[5].data(); a.tcand = s->ecl64[6].data();
+    a.ecc_table = s->ecl64[7].data(); a.aux = s->ecl64[8].data(); a.aux_kind = s->ecl32[1].data(); a.tdup = s->ecl32[2].data();
+    a.pair_flags = s->ecl32[3].data(); a.pair_f = s->ecl_f.data();
+    s->ecl = a;
+    s->pass = ecc_calls_pass;
+    s->assign_kind = 13;
+    *out = s;
+    return 0;
+}
+extern "C" int zk_ecc_from_calls_read(zk_session* s, const zk_ecc_call_wire* host, uint64_t* n_table_rows_out) {
+    ARG_TRY(s && s->assign_kind == 13, "zk_ecc_from_calls_read: bad arguments");
+    const EccCallArgs& a = s->ecl;
+    const u64 np = a.n_add + a.n_mul, n = np + a.n_pairing;
+    if (host) {
+        if (host->points) memcpy(host->points, a.points, (size_t)np * 192);
+        if (host->pair_out) memcpy(host->pair_out, a.pair_out, (size_t)a.n_pairing * 32);
+        if (host->rows) memcpy(host->rows, a.rows, (size_t)n * ECL_ROW_WORDS * 8);
+        if (host->ecc_table) memcpy(host->ecc_table, a.ecc_table, (size_t)s->n_ecl_table * ECL_ROW_WORDS * 8);
+        if (host->aux) memcpy(host->aux, a.aux, (size_t)n * ECL_AUX_CELLS * 32);
+        if (host->aux_kind) memcpy(host->aux_kind, a.aux_kind, (size_t)n * 4);
+    }
+    if (n_table_rows_out) *n_table_rows_out = s->n_ecl_table;
+    return 0;
+}
+extern "C" int zk_ecc_from_calls(const zk_ecc_calls* in, const zk_ecc_call_wire* out, uint32_t opts, uint32_t* status_out,
+                                 uint64_t* n_table_rows_out, zk_result* result) {
+    ARG_TRY(result && out, "zk_ecc_from_calls: null output");
+    zk_session* s = nullptr;
+    int rc = zk_ecc_from_calls_open(in, nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && status_out) rc = zk_read_status(s, status_out);
+    if (!rc) rc = zk_ecc_from_calls_read(s, out, n_table_rows_out);
     zk_close(s);
     return rc;
 }

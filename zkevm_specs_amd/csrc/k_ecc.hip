@@ -75,6 +75,9 @@ void zk_launch_ecc_range(hipStream_t st, const EccPairArgs& s, u64 lo, u64 hi, u
     if (t_hi > t_lo) hipLaunchKernelGGL(ecc_pair_stage1_kernel, dim3((t_hi - t_lo + 63) / 64), dim3(64), 0, st, s, t_lo, t_hi);
     if (hi > lo_pr) hipLaunchKernelGGL(ecc_pair_stage2_kernel, dim3((u32)((hi - lo_pr + 63) / 64)), dim3(64), 0, st, s, lo_pr, hi, status, tally);
 }
+void zk_launch_ecc_pair_stage1(hipStream_t st, const EccPairArgs& s, u32 t_lo, u32 t_hi) {
+    if (t_hi > t_lo) hipLaunchKernelGGL(ecc_pair_stage1_kernel, dim3((t_hi - t_lo + 63) / 64), dim3(64), 0, st, s, t_lo, t_hi);
+}
 void zk_launch_fq12_op(hipStream_t st, int op, const u64* x, const u64* y, u64* out, u64 n12) {
     hipLaunchKernelGGL(ecc_fq12_op_kernel, dim3((u32)((n12 + 63) / 64)), dim3(64), 0, st, op, x, y, out, n12);
 }

@@ -20,6 +20,7 @@
 #include "pi_circuit.hpp"
 #include "state_rekey.hpp"
 #include "ecc_circuit.hpp"
+#include "ecc_calls.hpp"
 #include "withdrawal_circuit.hpp"
 #include "tx_assign.hpp"
 #include "sig_assign.hpp"
@@ -98,6 +99,10 @@ void zk_launch_ecc(hipStream_t st, const EccArgs& a, bool assign, u32* status, Z
 // rows [lo, hi) of an ECC session: add / mul rows, then the pairs [t_lo, t_hi) of the pairing ops in range (stage 1) and those ops'
 // rows (stage 2), three launches in stream order (twin tally; status is never null)
 void zk_launch_ecc_range(hipStream_t st, const EccPairArgs& s, u64 lo, u64 hi, u32 t_lo, u32 t_hi, u32* status, ZkTally* tally);
+// stage 1 alone, over the pairs [t_lo, t_hi) (the launch zk_launch_ecc_range makes; ECC precompile calls run it ahead of their own stage 2)
+void zk_launch_ecc_pair_stage1(hipStream_t st, const EccPairArgs& s, u32 t_lo, u32 t_hi);
+// ECC precompile calls (k_ecc_calls.hip): add / mul calls, pairing stage 1 over n_pairs pairs, pairing calls, the ecc table; status all 0
+void zk_launch_ecc_calls(hipStream_t st, const EccCallArgs& a, u32 n_pairs, u32* status);
 void zk_launch_fq12_op(hipStream_t st, int op, const u64* x, const u64* y, u64* out, u64 n12);  // zk_fr_op 19..25
 // Withdrawal circuit (k_withdrawal.hip): verify held rows [lo, hi) (status / twin tally); assign rows [0, a.n_out) (+ keccak rows)
 void zk_launch_withdrawal_rows(hipStream_t st, const WithdrawalArgs& a, u64 lo, u64 hi, u32* status, ZkTally* tally);

@@ -605,7 +605,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_TRW = 24, SESSION_BTB = 23, SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_ECL = 25, SESSION_TRW = 24, SESSION_BTB = 23, SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -650,6 +650,8 @@ struct zk_session {
     KeccakGenArgs bcc_kgen;
     BtbArgs btb;                    // SESSION_BTB (zk_evm_tables_from_block*)
     TrwArgs trw;                    // SESSION_TRW (zk_evm_witness_from_trace*)
+    EccCallArgs ecl;                // SESSION_ECL (zk_ecc_from_calls*)
+    u32 ecl_n_pairs = 0;            // ... pair_off[n_pairing], validated at open: stage 1's lanes
     u64 pia_host[4] = {0, 0, 0, 0};  // small host words the open uploads (their source must outlive the asynchronous copy)
     RekeyArgs rekey;
     RwkPlan rekey_plan_host;      // the compact-key plan as uploaded (host copy owned by the session: the upload needs no synchronisation of its own)
@@ -2920,6 +2922,7 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     }
     case SESSION_BTB: zk_launch_block_tables(s->stream, s->btb, status); break;
     case SESSION_TRW: zk_launch_trace_witness(s->stream, s->trw, status); break;
+    case SESSION_ECL: zk_launch_ecc_calls(s->stream, s->ecl, s->ecl_n_pairs, status); break;
     case SESSION_REKEY:
         zk_launch_state_rekey(s->stream, s->rekey, status, s->d_tally);
         s->sweep_ran = s->rekey.fast != 0;
@@ -4235,6 +4238,118 @@ extern "C" int zk_sig_assign(const zk_sig_inputs* in, const zk_sig_wire* out, ui
     if (!rc) rc = zk_collect(s, result);
     if (!rc && !dev && status_out) rc = zk_read_status(s, status_out);
     if (!rc) rc = zk_sig_assign_read(s, dev ? nullptr : out, n_keccak_out, n_sig_rows_out);
+    zk_close(s);
+    return rc;
+}
+
+// ---- ECC precompile calls (ecc_calls.hpp, k_ecc_calls.hip)
+extern "C" int zk_ecc_from_calls_open(const zk_ecc_calls* in, const zk_ecc_call_wire* out_dev, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_ecc_from_calls_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(in && out, "zk_ecc_from_calls_open: bad arguments");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    ARG_TRY(dev || !out_dev, "zk_ecc_from_calls_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    zk_session* s = new zk_session();
+    s->kind = SESSION_ECL;
+    EccCallArgs& a = s->ecl;
+    memset(&a, 0, sizeof(a));
+    int rc = 0;
+    const void* p = nullptr;
+    {   // pair_off and the randomness cell are what the host looks at: ecc_calls_check reads them through `h`, every other pointer
+        // it only compares with null (an op count that is out of range is refused before pair_off is fetched)
+        zk_ecc_calls h = *in;
+        u64 rh[4] = {0, 0, 0, 0};
+        std::vector<u32> off;
+        const bool counts_ok = in->n_pairing < (1ull << 31);
+        if (dev && in->randomness) {
+            if (fetch_small(s->stream, rh, in->randomness, 32)) { rc = -2; g_err = "zk_ecc_from_calls_open: randomness download failed"; goto fail; }
+            h.randomness = rh;
+        }
+        if (dev && counts_ok && in->n_pairing && in->pair_off) {
+            off.assign(in->n_pairing + 1, 0u);
+            if (d2h_now(s->stream, off.data(), in->pair_off, (in->n_pairing + 1) * 4)) { rc = -2; g_err = "zk_ecc_from_calls_open: pair_off download failed"; goto fail; }
+            h.pair_off = off.data();
+        }
+        const char* err = nullptr;
+        if ((rc = ecc_calls_check(&h, a, &err))) { g_err = std::string("zk_ecc_from_calls_open: ") + err; goto fail; }
+        s->ecl_n_pairs = in->n_pairing ? h.pair_off[in->n_pairing] : 0u;
+        // the validated offsets stay with the session, on the host and in a device buffer of its own: a caller that rewrites its
+        // pair_off between passes cannot move a lane's reads or stores
+        if (in->n_pairing) s->ecc_pair_off.assign(h.pair_off, h.pair_off + in->n_pairing + 1);
+    }
+    {
+        const u64 np = a.n_add + a.n_mul, n = np + a.n_pairing, n_pp = s->ecl_n_pairs;
+        s->n = n;
+        if ((rc = stage(s, in->add_in, (size_t)a.n_add * 128, dev, &p))) goto fail;
+        a.add_in = (const u64*)p;
+        if ((rc = stage(s, in->mul_in, (size_t)a.n_mul * 96, dev, &p))) goto fail;
+        a.mul_in = (const u64*)p;
+        if ((rc = stage(s, in->pair_pts, (size_t)n_pp * 192, dev, &p))) goto fail;
+        a.pair_pts = (const u64*)p;
+        if ((rc = stage(s, a.n_pairing ? s->ecc_pair_off.data() : nullptr, a.n_pairing ? (size_t)(a.n_pairing + 1) * 4 : 0, false, &p))) goto fail;
+        a.pair_off = (const u32*)p;
+        void* d = nullptr;
+        if ((rc = dev_alloc(s, &d, (size_t)n * ECL_ROW_WORDS * 8))) goto fail;
+        a.tcand = (u64*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)n * 4))) goto fail;
+        a.tdup = (u32*)d;
+        if ((rc = dev_alloc(s, &d, 64))) goto fail;
+        a.n_table = (u32*)d;
+        if (hipMemsetAsync(d, 0, 64, s->stream) != hipSuccess) { rc = -2; g_err = "zk_ecc_from_calls_open: counter reset failed"; goto fail; }  // (a read before any pass: no rows)
+        if ((rc = dev_alloc(s, &d, (size_t)(n_pp ? n_pp : 1) * sizeof(u32)))) goto fail;
+        a.pair_flags = (u32*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)(n_pp ? n_pp : 1) * sizeof(bn::Fq12)))) goto fail;
+        a.pair_f = (bn::Fq12*)d;
+        const zk_ecc_call_wire* o = out_dev;
+#define ECL_OUT(field, type, bytes)                                                       \
+        if (o && o->field) a.field = (type)o->field;                                      \
+        else { if ((rc = dev_alloc(s, &d, (size_t)(bytes) + 32))) goto fail; a.field = (type)d; }
+        ECL_OUT(points, u64*, np * 192)
+        ECL_OUT(pair_out, u64*, a.n_pairing * 32)
+        ECL_OUT(rows, u64*, n * ECL_ROW_WORDS * 8)
+        ECL_OUT(ecc_table, u64*, n * ECL_ROW_WORDS * 8)
+        ECL_OUT(aux, u64*, n * ECL_AUX_CELLS * 32)
+        ECL_OUT(aux_kind, u32*, n * 4)
+#undef ECL_OUT
+    }
+    if ((rc = session_common_init(s))) goto fail;
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_ecc_from_calls_read(zk_session* s, const zk_ecc_call_wire* host, uint64_t* n_table_rows_out) {
+    ARG_TRY(s && s->kind == SESSION_ECL, "zk_ecc_from_calls_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    const EccCallArgs& a = s->ecl;
+    const u64 np = a.n_add + a.n_mul, n = np + a.n_pairing;
+    u32 cnt = 0;
+    HIP_TRY(hipMemcpyAsync(&cnt, a.n_table, 4, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (host) {
+        if (host->points && np) HIP_TRY(hipMemcpyAsync(host->points, a.points, (size_t)np * 192, hipMemcpyDeviceToHost, s->stream));
+        if (host->pair_out && a.n_pairing) HIP_TRY(hipMemcpyAsync(host->pair_out, a.pair_out, (size_t)a.n_pairing * 32, hipMemcpyDeviceToHost, s->stream));
+        if (host->rows) HIP_TRY(hipMemcpyAsync(host->rows, a.rows, (size_t)n * ECL_ROW_WORDS * 8, hipMemcpyDeviceToHost, s->stream));
+        if (host->ecc_table && cnt) HIP_TRY(hipMemcpyAsync(host->ecc_table, a.ecc_table, (size_t)cnt * ECL_ROW_WORDS * 8, hipMemcpyDeviceToHost, s->stream));
+        if (host->aux) HIP_TRY(hipMemcpyAsync(host->aux, a.aux, (size_t)n * ECL_AUX_CELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        if (host->aux_kind) HIP_TRY(hipMemcpyAsync(host->aux_kind, a.aux_kind, (size_t)n * 4, hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    if (n_table_rows_out) *n_table_rows_out = cnt;
+    return 0;
+}
+extern "C" int zk_ecc_from_calls(const zk_ecc_calls* in, const zk_ecc_call_wire* out, uint32_t opts, uint32_t* status_out,
+                                 uint64_t* n_table_rows_out, zk_result* result) {
+    ARG_TRY(result && out, "zk_ecc_from_calls: null output");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    int rc = zk_ecc_from_calls_open(in, dev ? out : nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, dev ? status_out : nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && !dev && status_out) rc = zk_read_status(s, status_out);
+    if (!rc) rc = zk_ecc_from_calls_read(s, dev ? nullptr : out, n_table_rows_out);
     zk_close(s);
     return rc;
 }

@@ -1214,6 +1214,77 @@ def open_sig_assign(sig, randomness, outs=None, device=None):
                  cls=SigAssignSession)
 
 
+# ---- ECC precompile calls (zk_ecc_from_calls*) -------------------------------------------------------------------------------------
+ECC_CALLS_INPUTS = ("add_in", "mul_in", "pair_pts", "pair_off")
+ECC_CALLS_OUTPUTS = ("points", "pair_out", "rows", "ecc_table", "aux", "aux_kind")
+
+
+def ecc_calls_shapes(n_add, n_mul, n_pairing):
+    """name -> (shape, dtype) of the outputs of zk_ecc_from_calls* (ecc_table: its capacity, one row per call)"""
+    n = n_add + n_mul + n_pairing
+    return {"points": ((n_add + n_mul, 6, 4), np.uint64), "pair_out": ((n_pairing, 4), np.uint64), "rows": ((n, 13, 4), np.uint64),
+            "ecc_table": ((n, 13, 4), np.uint64), "aux": ((n, 12, 4), np.uint64), "aux_kind": ((n,), np.uint32)}
+
+
+def _ecc_calls_args(calls, randomness, outs=None):
+    """zk_ecc_from_calls_open / zk_ecc_from_calls over `calls` = dict(add_in uint64[n_add, 4, 4]: p.x, p.y, q.x, q.y; mul_in
+    uint64[n_mul, 3, 4]: p.x, p.y, s; pair_pts uint64[m, 6, 4] in EIP-197 order + pair_off uint32[n_pairing + 1]) — the arrays of
+    ecc_circuit.ecc_calls_wire — -> (ZkEccCalls, ZkEccCallWire of the device outputs or None, opts, kept arrays, output shapes).
+    `outs` (device tensors only, each optional): buffers of ECC_CALLS_OUTPUTS the session writes in place."""
+    add_in, mul_in, pair_pts, pair_off = (calls[k] for k in ECC_CALLS_INPUTS)
+    n_add, n_mul, n_pairing = int(add_in.shape[0]), int(mul_in.shape[0]), int(pair_off.shape[0]) - 1
+    _expect(add_in, "add_in", 8, (None, 4, 4))
+    _expect(mul_in, "mul_in", 8, (None, 3, 4))
+    _expect(pair_pts, "pair_pts", 8, (None, 6, 4))
+    _expect(pair_off, "pair_off", 4, (n_pairing + 1,))
+    shapes = ecc_calls_shapes(n_add, n_mul, n_pairing)
+    outs = dict(outs or {})
+    for k, v in outs.items():
+        if v is not None:
+            _expect(v, k, np.dtype(shapes[k][1]).itemsize, shapes[k][0])
+    out_list = [outs.get(k) for k in ECC_CALLS_OUTPUTS]
+    a, opts = _prep([add_in, mul_in, pair_pts, pair_off] + out_list, outputs=range(4, 4 + len(out_list)))
+    if any(v is not None for v in out_list) and not opts:
+        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
+    rc = _randomness_cells(randomness, a[0])
+    keep = a + [rc]
+    t = _lib.ZkEccCalls(ptr(a[0], n_add), n_add, ptr(a[1], n_mul), n_mul, ptr(a[2], _rows(a[2])), ptr(a[3], n_pairing), n_pairing, ptr(rc))
+    w = _lib.ZkEccCallWire(*[ptr(x) for x in a[4:]]) if opts else None
+    return t, w, opts, keep, shapes
+
+
+class EccCallsSession(Session):
+    """zk_ecc_from_calls_open: launch() / collect() like the circuits (every status 0); read() -> the wire dict of the last pass
+    (host arrays, ecc_table cut to its rows); n_table_rows() the table's row count alone"""
+
+    def _count(self, w=None):
+        nt = ctypes.c_uint64()
+        check(self._lib.zk_ecc_from_calls_read(self._h, ctypes.byref(w) if w is not None else None, ctypes.byref(nt)),
+              "zk_ecc_from_calls_read", self._lib)
+        return int(nt.value)
+
+    def read(self):
+        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in self.shapes.items()}
+        nt = self._count(_lib.ZkEccCallWire(*[ptr(out[k]) for k in ECC_CALLS_OUTPUTS]))
+        out["ecc_table"] = out["ecc_table"][:nt]
+        return out
+
+    def n_table_rows(self):
+        return self._count()
+
+
+def open_ecc_from_calls(calls, randomness, outs=None, device=None):
+    """ECC precompile calls session (see _ecc_calls_args): from the calls' input words to the ECC circuit's ops and rows and the EVM
+    circuit's ecc table and aux rows.  With device tensors the outputs stay in HBM: in `outs`' buffers where given (ready for
+    open_ecc / open_evm), else in the session's own."""
+    lib = _lib.init(device)
+    t, w, opts, keep, shapes = _ecc_calls_args(calls, randomness, outs)
+    s = _open(lib, lib.zk_ecc_from_calls_open, int(t.n_add + t.n_mul + t.n_pairing), (keep, t, w), ctypes.byref(t),
+              ctypes.byref(w) if w is not None else None, opts, cls=EccCallsSession)
+    s.shapes = shapes
+    return s
+
+
 # ---- Exp circuit witness assignment (zk_exp_assign*) ------------------------------------------------------------------------------
 def _exp_events_struct(events, max_exp_steps):
     """the ZkExpEvents block over a prepared event array (None or empty: a null pointer, dummy rows only)"""

@@ -271,6 +271,20 @@ def sig_assign(sig, randomness, device=None):
     return Result(r), status[:n], out
 
 
+def ecc_from_calls(calls, randomness, device=None):
+    """zk_ecc_from_calls over the input words of ecAdd / ecMul / ecPairing calls (engine._ecc_calls_args) -> (Result, status uint32[n],
+    wire dict: points, pair_out, rows, ecc_table (cut to its rows), aux, aux_kind)"""
+    lib = _lib.init(device)
+    t, _, opts, keep, shapes = engine._ecc_calls_args({k: _host(calls[k]) for k in engine.ECC_CALLS_INPUTS}, randomness)
+    n = int(t.n_add + t.n_mul + t.n_pairing)
+    out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items()}
+    w = _lib.ZkEccCallWire(*[ptr(out[k]) for k in engine.ECC_CALLS_OUTPUTS])
+    status, r, nt = np.zeros(max(n, 1), dtype=np.uint32), ZkResult(), ctypes.c_uint64()
+    check(lib.zk_ecc_from_calls(ctypes.byref(t), ctypes.byref(w), opts, ptr(status), ctypes.byref(nt), ctypes.byref(r)), "zk_ecc_from_calls", lib)
+    out["ecc_table"] = out["ecc_table"][: nt.value]
+    return Result(r), status[:n], out
+
+
 def pi_assign(pd, keccak_rand=255, byte_pow_base=255, device=None):
     """zk_pi_assign over raw public data (engine._pi_assign_args) -> (Result, wire dict of engine.PI_ASSIGN_OUTPUTS)"""
     lib = _lib.init(device)
