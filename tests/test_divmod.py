@@ -1,10 +1,13 @@
 """Long division used by the MOD / ADDMOD / MULMOD / SHR witness values (csrc/fr.hpp: Knuth D with a reciprocal-based
 trial quotient) against Python integers: 256 / 256 and 512 / 256, random and the cases the trial-quotient step is
-delicate on (top limb of the partial remainder equal to the divisor's, all-ones limbs, single-limb divisors)."""
+delicate on (top limb of the partial remainder equal to the divisor's, all-ones limbs, single-limb divisors), structured limbs and
+add-back triples; a census by the path model of tests/evm_arith_cases.py says which paths of the routine the cases take."""
 import ctypes
 import random
 
 import numpy as np
+
+from tests import evm_arith_cases as ac
 
 
 def _pack(x, words):
@@ -40,6 +43,8 @@ def _cases(bits, rng):
         for k in (32, 64, 96, bits - db):
             if 0 <= k and db + k <= bits:
                 out += [((d << k) - 1, d), ((d << k) + 1 & M, d), (((d << k) - 1) ^ (1 << (k // 2)), d)]
+    # limbs at the edges of the 32-bit range, 1..8 of them in the divisor (every word shift), and the add-back triples on every digit
+    out += ac.structured_pairs(rng, bits, 3000) + ac.addback_pairs(bits) + ac.fix2_pairs(rng, bits)
     return out
 
 
@@ -50,6 +55,12 @@ def test_u256_and_u512_long_division(hostsim):
         got = _run(hostsim, wide, pairs)
         for (n, d), (q, r) in zip(pairs, got):
             assert (q, r) == (n // d, n % d), (wide, hex(n), hex(d), hex(q), hex(r))
+        # what the cases reach, by the model (it classifies only): every path at least ac.MIN_PER_PATH times, the add-back on the
+        # lowest and the highest quotient digit it can fall on
+        counts, digits = ac.census_of_pairs(pairs, bits // 32)
+        for name in ac.BRANCHES + tuple(f"ws{k}" for k in range(8)) + ("bs0", "bsnz"):
+            assert counts.get(name, 0) >= ac.MIN_PER_PATH, (bits, name, counts.get(name, 0))
+        assert (min(digits), max(digits)) == ac.ADDBACK_DIGIT_RANGE_RAW[bits // 32], (bits, sorted(digits))
 
 
 def test_fr_inv_and_div_match_python(hostsim):
