@@ -1045,7 +1045,7 @@ static void bytecode_assign_pass(zk_session* s) {
 extern "C" int zk_bytecode_assign_open(const uint64_t* in_rows, uint64_t n_rows, const uint64_t* offsets, const uint64_t* lengths, uint64_t n_codes,
                                        uint32_t k, const uint64_t* randomness, uint64_t* rows_dev, uint32_t opts, zk_session** out) {
     NO_DEVICE_PTRS(opts, "zk_bytecode_assign_open");
-    ARG_TRY(out && offsets && lengths && randomness && k >= 1 && k <= 30 && n_rows < (1ull << 31) && n_codes < (1ull << 31) && (in_rows || n_rows == 0) &&
+    ARG_TRY(out && offsets && (lengths || n_codes == 0) && randomness && k >= 1 && k <= 30 && n_rows < (1ull << 31) && n_codes < (1ull << 31) && (in_rows || n_rows == 0) &&
             !rows_dev, "zk_bytecode_assign_open: bad arguments");
     ARG_TRY(offsets[0] == 0 && offsets[n_codes] == n_rows, "zk_bytecode_assign_open: offsets must span the rows");
     for (u64 j = 0; j < n_codes; j++) ARG_TRY(offsets[j] <= offsets[j + 1], "zk_bytecode_assign_open: offsets must be non-decreasing");
