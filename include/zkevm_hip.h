@@ -963,6 +963,35 @@ int zk_evm_witness_from_trace_open(const zk_trace* in, const zk_trace_witness* o
 int zk_evm_witness_from_trace_read(zk_session* s, const zk_trace_witness* host);
 int zk_evm_witness_from_trace(const zk_trace* in, const zk_trace_witness* out, uint32_t opts, zk_result* result);
 
+/* ---- State circuit from the same compact trace records: the State verdict (zk_state_verify_from_trace*) and the State op list
+ *      (zk_state_ops_from_trace*) of the RW ops of a zk_trace, without the 448-byte wire rows in between.
+ *      DEFINED BY COMPOSITION: for records zk_evm_witness_from_trace accepts, every output - n_ops, the statuses (per op in sorted order
+ *      with op 0 the StartOp; per RW row for the ops form), the zk_result, the op list uint64[12][n_ops][4] and its flags - is bit for bit
+ *      what the matching _from_rw entry returns over the rw / rw_flags zk_evm_witness_from_trace writes for the same records, and so is a
+ *      return of -1 when there is no witness (see zk_state_verify_from_rw_open), with the same text under this entry's name.  The wire's
+ *      reductions are part of that: a pool address is FQ(w) (the "wider than 160 bits" check sees the reduced value), a wide value without
+ *      its is_word bit (w mod p, 0), with it (w mod 2^128, w >> 128), an absent storage_key or aux0 Word(0); a head whose tag nibble is
+ *      not one of Target's values gives the re-keying's (ZK_KIND_VALUE_ERROR << 24) | 1.
+ *      Of zk_trace the RW half is read: head, id, addr, val, rw_counter / rw_base, n_rw (> 0), pool, n_pool.  prev is never read and may
+ *      be NULL (the State circuit has no value_prev; its pool words still count in the offsets); steps / n_steps are ignored.
+ *      The records' domain is checked at open exactly as zk_evm_witness_from_trace_open checks it: ZK_ERR_TRC_HEAD / _ORDER / _POOL /
+ *      _ROWS with the same text under this entry's name, on the device, one verdict block read back; the counts that need no array are
+ *      checked before any array is read.
+ *      ZK_OPT_DEVICE_PTRS, zk_launch, zk_collect, zk_read_status, zk_close, zk_session_set_stream: as for the _from_rw entries
+ *      (ops_dev / op_flags_dev: capacity n_rw + 1 ops).  Resident passes of the verdict session keep what the first collected pass built:
+ *      the ops in State order as one 48-byte record each, the first-access links, the MPT rows and the root ranks; later passes stream
+ *      those records and evaluate.  The session keeps its own copy of the heads, counters and pool offsets.  id, addr, val and the pool
+ *      stay the caller's: with ZK_OPT_DEVICE_PTRS they must stay valid and unchanged for the session's life (the first pass reads id /
+ *      addr / val, every pass reads the pool words of wide cells); host arrays are copied at open. */
+int zk_state_verify_from_trace_open(const zk_trace* in, uint32_t opts, uint64_t* n_ops_out, zk_session** out);
+int zk_state_verify_from_trace(const zk_trace* in, uint32_t opts, uint32_t* status_out /* n_ops <= n_rw + 1 */, uint64_t* n_ops_out,
+                               zk_result* result);
+int zk_state_ops_from_trace_open(const zk_trace* in, uint64_t* ops_dev, uint32_t* op_flags_dev, uint32_t opts, uint64_t* n_ops_out,
+                                 zk_session** out);
+int zk_state_ops_from_trace_read(zk_session* s, uint64_t* ops_host, uint32_t* op_flags_host, uint64_t* n_ops_out);
+int zk_state_ops_from_trace(const zk_trace* in, uint64_t* ops_out, uint32_t* op_flags_out, uint64_t* n_ops_out, uint32_t opts,
+                            uint32_t* status_out /* n_rw */, zk_result* result);
+
 /* ---- ECC precompile calls: from the INPUT words of ecAdd / ecMul / ecPairing calls to what both circuits derive from them.  Where
  *      zk_ecc_ops takes every op's result from the caller (points[..][4..5], pair_out) and zk_ecc_assign copies it into rows, this
  *      entry computes the result on the device: the ECC circuit's ops and rows (circuit2rows, src/zkevm_specs/ecc_circuit.py:386-421),

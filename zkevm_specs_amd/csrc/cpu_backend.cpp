@@ -1389,6 +1389,99 @@ extern "C" int zk_evm_witness_from_trace(const zk_trace* t, const zk_trace_witne
     return rc;
 }
 
+// ---- State circuit from compact trace records (state_trace.hpp).  The device reads the records where its from-RW kernels read wire rows;
+//      here the record's cells (strc_cell, one at a time: the definition) are laid out as the rows the host passes of the _from_rw entries
+//      take, which copy what they keep at open.  Errors carry those entries' texts under this entry's name.
+#include "state_trace.hpp"
+static void strc_retitle(const char* name) {
+    const std::string cur = g_err;
+    const size_t c = cur.find(':');
+    g_err = std::string(name) + (c == std::string::npos ? ": " + cur : cur.substr(c));
+}
+#define STRC_ARGS_OK(t) ((t) && (t)->n_rw > 0 && (t)->head && (t)->id && (t)->addr && (t)->val && ((t)->n_pool == 0 || (t)->pool))
+static int strc_rows(const zk_trace* t, const char* name, std::vector<u64>& rw, std::vector<u32>& fl) {
+    char msg[256];
+    int rc = trw_plan_counts(t->n_rw, 0, t->rw_base, t->rw_counter != nullptr, msg, sizeof msg);  // (before any array is read)
+    if (!rc) {
+        std::vector<u32> head(t->n_rw);
+        std::vector<u64> off(t->n_rw);
+        u64 v[TRW_V_WORDS];
+        trw_check_host(t->head, t->rw_counter, t->n_rw, nullptr, 0, head.data(), nullptr, off.data(), v);
+        rc = trw_verdict_error(v, t->n_pool, msg, sizeof msg);
+        if (!rc) {
+            StrcArgs c;
+            memset(&c, 0, sizeof(c));
+            c.head = head.data(); c.ctr = t->rw_counter; c.id = t->id; c.addr = t->addr; c.val = t->val; c.off = off.data(); c.pool = t->pool;
+            c.n = t->n_rw; c.rw_base = t->rw_base;
+            rw.assign(t->n_rw * RWK_RW_NCELLS * 4, 0);
+            fl.assign(t->n_rw, 0);
+            for (u64 row = 0; row < t->n_rw; row++) {
+                for (u32 k = 0; k < RWK_RW_NCELLS; k++) {
+                    if (k == 10 || k == 11) continue;  // value_prev: not read by the State circuit
+                    const Fr x = strc_cell(c, row, head[row], off[row], k);
+                    for (int w = 0; w < 4; w++) rw[(row * RWK_RW_NCELLS + k) * 4 + w] = (u64)x.v[2 * w] | ((u64)x.v[2 * w + 1] << 32);
+                }
+                fl[row] = trw_rw_flag(head[row]);
+            }
+            return 0;
+        }
+    }
+    g_err = msg;
+    strc_retitle(name);
+    return rc;
+}
+extern "C" int zk_state_ops_from_trace_open(const zk_trace* t, uint64_t* ops_dev, uint32_t* op_flags_dev, uint32_t opts, uint64_t* n_ops_out,
+                                            zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_state_ops_from_trace_open");
+    ARG_TRY(out && STRC_ARGS_OK(t) && !ops_dev && !op_flags_dev, "zk_state_ops_from_trace_open: bad arguments");
+    std::vector<u64> rw;
+    std::vector<u32> fl;
+    int rc = strc_rows(t, "zk_state_ops_from_trace", rw, fl);
+    if (rc) return rc;
+    rc = zk_state_ops_from_rw_open(rw.data(), fl.data(), t->n_rw, nullptr, nullptr, opts, n_ops_out, out);
+    if (rc) strc_retitle("zk_state_ops_from_trace_open");
+    return rc;
+}
+extern "C" int zk_state_ops_from_trace_read(zk_session* s, uint64_t* ops_host, uint32_t* op_flags_host, uint64_t* n_ops_out) {
+    ARG_TRY(s && s->assign_kind == 4, "zk_state_ops_from_trace_read: bad arguments");
+    return zk_state_ops_from_rw_read(s, ops_host, op_flags_host, n_ops_out);
+}
+extern "C" int zk_state_ops_from_trace(const zk_trace* t, uint64_t* ops_out, uint32_t* op_flags_out, uint64_t* n_ops_out, uint32_t opts,
+                                       uint32_t* status_out, zk_result* result) {
+    ARG_TRY(result && n_ops_out, "zk_state_ops_from_trace: null output");
+    zk_session* s = nullptr;
+    int rc = zk_state_ops_from_trace_open(t, nullptr, nullptr, opts, n_ops_out, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc) rc = zk_state_ops_from_trace_read(s, ops_out, op_flags_out, n_ops_out);
+    if (!rc && status_out) rc = zk_read_status(s, status_out);
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_state_verify_from_trace_open(const zk_trace* t, uint32_t opts, uint64_t* n_ops_out, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_state_verify_from_trace_open");
+    ARG_TRY(out && STRC_ARGS_OK(t), "zk_state_verify_from_trace_open: bad arguments");
+    std::vector<u64> rw;
+    std::vector<u32> fl;
+    int rc = strc_rows(t, "zk_state_verify_from_trace", rw, fl);
+    if (rc) return rc;
+    rc = zk_state_verify_from_rw_open(rw.data(), fl.data(), t->n_rw, opts, n_ops_out, out);
+    if (rc) strc_retitle("zk_state_verify_from_trace");
+    return rc;
+}
+extern "C" int zk_state_verify_from_trace(const zk_trace* t, uint32_t opts, uint32_t* status_out, uint64_t* n_ops_out, zk_result* result) {
+    ARG_TRY(result, "zk_state_verify_from_trace: result is null");
+    zk_session* s = nullptr;
+    int rc = zk_state_verify_from_trace_open(t, opts, n_ops_out, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && status_out) rc = zk_read_status(s, status_out);
+    zk_close(s);
+    return rc;
+}
+
 static void copy_assign_pass(zk_session* s) {
     CpaArgs& a = s->cpa;
     for (u64 c = 0; c < a.n_chunks; c++) cpa_chunk(a, c);

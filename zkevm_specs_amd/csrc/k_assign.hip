@@ -377,6 +377,71 @@ void zk_launch_state_assign(hipStream_t st, const AssignArgs& a, u32* status, Zk
     hipLaunchKernelGGL(assign_rank_kernel<false>, dim3(a.nb), dim3(ASG_BLOCK), 0, st, a);
     hipLaunchKernelGGL(assign_rows_kernel<false>, dim3(a.nb), dim3(ASG_BLOCK), 0, st, a, status, tally);
 }
+// ---- the third source: the sorted packed op stream of a State session over trace records (state_trace.hpp).  The insert, mark and rank
+// passes read the ops; the scan and the root pass (assign_rows_kernel<.., false>) see first / rank only and are shared.  Kernels of
+// their own, not a third value of RW: the two instantiations above are what they were.
+__global__ __launch_bounds__(ASG_BLOCK) void assign_insert_trace_kernel(AssignArgs a, StrcArgs src) {
+    const u64 i = (u64)blockIdx.x * ASG_BLOCK + threadIdx.x;
+    if (i < a.n && strc_stream_has_key(src, i)) asg_insert_by(a, (u32)i, [&src](u32 j) { return strc_mpt_key(src, j); });
+}
+__global__ __launch_bounds__(ASG_BLOCK) void assign_mark_trace_kernel(AssignArgs a, StrcArgs src) {
+    __shared__ u32 s_cnt[ASG_BLOCK / 64];
+    __shared__ u32 s_min[ASG_BLOCK / 64];
+    const u64 i = (u64)blockIdx.x * ASG_BLOCK + threadIdx.x;
+    const u32 lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const bool keyed = i < a.n && strc_stream_has_key(src, i);
+    u32 f = ASG_NONE;
+    if (keyed) f = asg_find_first_by(a, (u32)i, [&src](u32 j) { return strc_mpt_key(src, j); });
+    if (i < a.n) a.first[i] = f;
+    const unsigned long long bf = __ballot(keyed && f == (u32)i), bk = __ballot(keyed);
+    if (lane == 0) {
+        s_cnt[w] = (u32)__popcll(bf);
+        s_min[w] = bk ? (u32)i + (u32)__ffsll((long long)bk) - 1u : ASG_NONE;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u32 c = 0, m = ASG_NONE;
+        for (int k = 0; k < ASG_BLOCK / 64; k++) { c += s_cnt[k]; m = s_min[k] < m ? s_min[k] : m; }
+        a.blk_cnt[blockIdx.x] = c;
+        a.blk_next[blockIdx.x] = m;
+    }
+}
+__global__ __launch_bounds__(ASG_BLOCK) void assign_rank_trace_kernel(AssignArgs a, StrcArgs src) {
+    __shared__ u32 s_cnt[ASG_BLOCK / 64];
+    const u64 i = (u64)blockIdx.x * ASG_BLOCK + threadIdx.x;
+    const u32 lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const bool is_first = i < a.n && a.first[i] == (u32)i;
+    const unsigned long long bf = __ballot(is_first);
+    if (lane == 0) s_cnt[w] = (u32)__popcll(bf);
+    __syncthreads();
+    if (is_first) {
+        u32 r = a.blk_cnt[blockIdx.x] + (u32)__popcll(bf & ((1ull << lane) - 1ull));
+        for (u32 k = 0; k < w; k++) r += s_cnt[k];
+        a.rank[i] = r;
+        const StrcRow row = strc_stream_row(src, i);
+        Fr q[ASG_MPT_NCELLS];
+        asg_mpt_cells_of([&row](u32 s) { return strc_row_slot(row, s, false); }, strc_row_flags(row, false), r, q);  // (a keyed op is not the StartOp)
+        u64* out = a.mpt + (u64)r * (ASG_MPT_NCELLS * 4);
+#pragma unroll
+        for (int c = 0; c < ASG_MPT_NCELLS; c++) asg_store(out + 4 * c, q[c]);
+        ZkTable t;  // the State circuit's MPT index, as assign_rank_kernel enters it (the session always has one)
+        t.n = (u32)a.n;
+        const u64 h = state_mpt_hash_cells(q);
+        const u32 v = state_mpt_slot_value(t, r, h);
+        u32 s = (u32)h & a.mpt_mask;
+        while (atomicCAS(&a.mpt_slots[s], ZK_EMPTY_SLOT, v) != ZK_EMPTY_SLOT) s = (s + 1) & a.mpt_mask;
+    }
+}
+// the roots alone (a.root_rank, a.mpt_slots set), over the stream src.stream
+void zk_launch_state_assign_trace(hipStream_t st, const AssignArgs& a, const StrcArgs& src) {
+    const u32 cap = a.mask + 1u + a.mpt_mask + 1u;
+    hipLaunchKernelGGL(slots_fill_kernel_asg, dim3((cap + 255) / 256), dim3(256), 0, st, a.slots, cap);
+    hipLaunchKernelGGL(assign_insert_trace_kernel, dim3(a.nb), dim3(ASG_BLOCK), 0, st, a, src);
+    hipLaunchKernelGGL(assign_mark_trace_kernel, dim3(a.nb), dim3(ASG_BLOCK), 0, st, a, src);
+    hipLaunchKernelGGL(assign_scan_kernel, dim3(1), dim3(1024), 0, st, a);
+    hipLaunchKernelGGL(assign_rank_trace_kernel, dim3(a.nb), dim3(ASG_BLOCK), 0, st, a, src);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(assign_rows_kernel<false, false>), dim3(a.nb), dim3(ASG_BLOCK), 0, st, a, (u32*)nullptr, (ZkTally*)nullptr);
+}
 void zk_launch_bca_rpow(hipStream_t st, const Fr& r, u64* out) { hipLaunchKernelGGL(bca_rpow_kernel, dim3(1), dim3(128), 0, st, r, out); }
 void zk_launch_bytecode_assign(hipStream_t st, const BcaArgs& a, u32* status, ZkTally* tally) {
     const u32 gc = (u32)((a.n_codes + 63) / 64), gk = (u32)((a.n_chunks + 63) / 64);

@@ -441,29 +441,29 @@ void zk_launch_rekey_scan(hipStream_t st, const RekeyArgs& a) {
     if (grid > 256u) grid = 256u;
     hipLaunchKernelGGL(rwk_scan_kernel, dim3(grid), dim3(RWK_SCAN_BLOCK), 0, st, a);
 }
-void zk_launch_state_rekey(hipStream_t st, const RekeyArgs& a, u32* status, ZkTally* tally) {
-    const u32 grid = (u32)((a.n + RWK_BLOCK - 1) / RWK_BLOCK);
-    if (a.n_jobs) {
-        hipMemsetAsync(a.job_cursor, 0, sizeof(u32) * a.n_jobs, st);
-        hipLaunchKernelGGL(rwk_collect_kernel, dim3(grid), dim3(RWK_BLOCK), 0, st, a);
-        for (u32 j = 0; j < a.n_jobs; j++)
-            hipLaunchKernelGGL(rwk_rank_kernel, dim3((a.jobs[j].count + RWK_BLOCK - 1) / RWK_BLOCK), dim3(RWK_BLOCK), 0, st, a, j);
-    }
-    if (a.fast) {
-        {   // > 64 KiB of dynamic LDS has to be asked for, once per device
-            static std::mutex m;
-            static bool asked[64] = {false};
-            int dev = 0;
-            (void)hipGetDevice(&dev);
-            std::lock_guard<std::mutex> lock(m);
-            if (dev >= 0 && dev < 64 && !asked[dev]) {
-                (void)hipFuncSetAttribute((const void*)rwk_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RWK_SW_TILE * 12);
-                asked[dev] = true;
-            }
+// The launch in pieces: the rank kernels of the plan's jobs (after a collect pass filled job_rows / job_vals), and the radix passes over
+// packed keys (-> the sorted order).  The passes see keys and indices only, so a front end over another row source (k_state_trace.hip)
+// runs its own collect / pack kernels around them.
+void zk_launch_rekey_rank_jobs(hipStream_t st, const RekeyArgs& a) {
+    for (u32 j = 0; j < a.n_jobs; j++)
+        hipLaunchKernelGGL(rwk_rank_kernel, dim3((a.jobs[j].count + RWK_BLOCK - 1) / RWK_BLOCK), dim3(RWK_BLOCK), 0, st, a, j);
+}
+void zk_rekey_sweep_begin(hipStream_t st, const RekeyArgs& a) {  // fast sort: before the pack kernel that fills the global histograms
+    {   // > 64 KiB of dynamic LDS has to be asked for, once per device
+        static std::mutex m;
+        static bool asked[64] = {false};
+        int dev = 0;
+        (void)hipGetDevice(&dev);
+        std::lock_guard<std::mutex> lock(m);
+        if (dev >= 0 && dev < 64 && !asked[dev]) {
+            (void)hipFuncSetAttribute((const void*)rwk_sweep_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, RWK_SW_TILE * 12);
+            asked[dev] = true;
         }
-        hipMemsetAsync(a.sweep, 0, ((size_t)RWK_SWEEP_HEAD + (size_t)a.n_passes * a.ntiles_fast * 256) * 4, st);
-        u32 g64 = (u32)((a.n + 1023) / 1024);
-        hipLaunchKernelGGL(rwk_pack64_kernel, dim3(g64 > 256u ? 256u : g64), dim3(1024), 0, st, a, status, tally);
+    }
+    hipMemsetAsync(a.sweep, 0, ((size_t)RWK_SWEEP_HEAD + (size_t)a.n_passes * a.ntiles_fast * 256) * 4, st);
+}
+const u32* zk_launch_rekey_passes(hipStream_t st, const RekeyArgs& a) {
+    if (a.fast) {
         const u64* kin = a.key64_a;
         const u32* iin = nullptr;
         u64* kbufs[2] = {a.key64_b, a.key64_a};
@@ -474,10 +474,8 @@ void zk_launch_state_rekey(hipStream_t st, const RekeyArgs& a, u32* status, ZkTa
             kin = kbufs[p & 1u];
             iin = ibufs[p & 1u];
         }
-        if (a.ops) hipLaunchKernelGGL(rwk_emit_kernel, dim3((u32)((a.n_ops + RWK_BLOCK - 1) / RWK_BLOCK)), dim3(RWK_BLOCK), 0, st, a, iin);
-        return;
+        return iin;
     }
-    hipLaunchKernelGGL(rwk_pack_kernel, dim3(grid), dim3(RWK_BLOCK), 0, st, a, status, tally);
     const u32* in = nullptr;
     u32* bufs[2] = {a.idx_a, a.idx_b};
     for (u32 p = 0; p < a.n_passes; p++) {
@@ -487,5 +485,22 @@ void zk_launch_state_rekey(hipStream_t st, const RekeyArgs& a, u32* status, ZkTa
         hipLaunchKernelGGL(rwk_scatter_kernel, dim3(a.ntiles), dim3(RWK_BLOCK), 0, st, a, in, out, word, shift);
         in = out;
     }
-    if (a.ops) hipLaunchKernelGGL(rwk_emit_kernel, dim3((u32)((a.n_ops + RWK_BLOCK - 1) / RWK_BLOCK)), dim3(RWK_BLOCK), 0, st, a, in);
+    return in;
+}
+void zk_launch_state_rekey(hipStream_t st, const RekeyArgs& a, u32* status, ZkTally* tally) {
+    const u32 grid = (u32)((a.n + RWK_BLOCK - 1) / RWK_BLOCK);
+    if (a.n_jobs) {
+        hipMemsetAsync(a.job_cursor, 0, sizeof(u32) * a.n_jobs, st);
+        hipLaunchKernelGGL(rwk_collect_kernel, dim3(grid), dim3(RWK_BLOCK), 0, st, a);
+        zk_launch_rekey_rank_jobs(st, a);
+    }
+    if (a.fast) {
+        zk_rekey_sweep_begin(st, a);
+        u32 g64 = (u32)((a.n + 1023) / 1024);
+        hipLaunchKernelGGL(rwk_pack64_kernel, dim3(g64 > 256u ? 256u : g64), dim3(1024), 0, st, a, status, tally);
+    } else {
+        hipLaunchKernelGGL(rwk_pack_kernel, dim3(grid), dim3(RWK_BLOCK), 0, st, a, status, tally);
+    }
+    const u32* order = zk_launch_rekey_passes(st, a);
+    if (a.ops) hipLaunchKernelGGL(rwk_emit_kernel, dim3((u32)((a.n_ops + RWK_BLOCK - 1) / RWK_BLOCK)), dim3(RWK_BLOCK), 0, st, a, order);
 }

@@ -54,11 +54,11 @@ __global__ __launch_bounds__(1024) void trw_offset_scan_kernel(TrwArgs a) {
     }
     if (t == 0) a.verdict[TRW_V_POOL] = carry;
 }
-void zk_launch_trace_witness_check(hipStream_t st, const TrwArgs& a) {
+void zk_launch_trace_witness_check(hipStream_t st, const TrwArgs& a, bool with_offsets) {
     hipLaunchKernelGGL(trw_verdict_reset_kernel, dim3(1), dim3(64), 0, st, a.verdict);
     const u32 nb_rw = (u32)((a.n_rw + 255) / 256), nb_steps = (u32)((a.n_steps + 255) / 256);
     if (nb_rw + nb_steps) hipLaunchKernelGGL(trw_check_kernel, dim3(nb_rw + nb_steps), dim3(256), 0, st, a, nb_rw);
-    if (a.n_rw) hipLaunchKernelGGL(trw_offset_scan_kernel, dim3(1), dim3(1024), 0, st, a);
+    if (a.n_rw && with_offsets) hipLaunchKernelGGL(trw_offset_scan_kernel, dim3(1), dim3(1024), 0, st, a);
 }
 
 // One launch, three ranges of workgroups:

@@ -16,6 +16,7 @@
 #include "bytecode_code.hpp"
 #include "block_tables.hpp"
 #include "trace_witness.hpp"
+#include "state_trace.hpp"
 #include "copy_assign.hpp"
 #include "pi_circuit.hpp"
 #include "state_rekey.hpp"
@@ -76,6 +77,20 @@ void zk_launch_state_assign(hipStream_t st, const AssignArgs& a, u32* status, Zk
 void zk_launch_state_rows_fused(hipStream_t st, const StateArgs& sa, const AssignArgs& g, u32* status, ZkTally* tally, ZkTally* asg_tally);
 void zk_launch_rekey_scan(hipStream_t st, const RekeyArgs& a);  // open-time class masks of the RW -> State re-keying
 void zk_launch_state_rekey(hipStream_t st, const RekeyArgs& a, u32* status, ZkTally* tally);
+// its pieces, for a front end over another row source: the rank kernels of a.jobs, the fast sort's per-launch reset, the radix passes over
+// packed keys (-> the sorted order of the kept rows, then the left-out ones)
+void zk_launch_rekey_rank_jobs(hipStream_t st, const RekeyArgs& a);
+void zk_rekey_sweep_begin(hipStream_t st, const RekeyArgs& a);
+const u32* zk_launch_rekey_passes(hipStream_t st, const RekeyArgs& a);
+// State circuit from compact trace records (state_trace.hpp, k_state_trace.hip): the open's checks with the pool offsets by a chunked scan
+// (sums: ceil(n_rw / 1024) words of scratch) and its class scan; the re-keying and the sort, then
+// the op list (a.ops) or the sorted packed op stream (src.stream); the MPT passes over that stream (k_assign.hip: the roots alone); the
+// State circuit on rows computed from it
+void zk_launch_state_trace_check(hipStream_t st, const TrwArgs& a, u64* sums);
+void zk_launch_state_trace_scan(hipStream_t st, const RekeyArgs& a, const StrcArgs& src);
+void zk_launch_state_trace_rekey(hipStream_t st, const RekeyArgs& a, const StrcArgs& src, u32* status, ZkTally* tally);
+void zk_launch_state_assign_trace(hipStream_t st, const AssignArgs& a, const StrcArgs& src);
+void zk_launch_state_rows_trace(hipStream_t st, const StateArgs& sa, const AssignArgs& g, const StrcArgs& src, u32* status, ZkTally* tally, ZkTally* asg_tally);
 void zk_launch_bca_rpow(hipStream_t st, const Fr& r, u64* out);
 void zk_launch_bytecode_assign(hipStream_t st, const BcaArgs& a, u32* status, ZkTally* tally);
 void zk_launch_bca_prefix(hipStream_t st, const BcaArgs& a);  // its prefix pass alone (value_rlc and counter entering every chunk)
@@ -86,7 +101,8 @@ void zk_launch_bytecode_from_code(hipStream_t st, hipStream_t side, hipEvent_t e
 void zk_launch_block_tables(hipStream_t st, const BtbArgs& a, u32* status);
 // EVM circuit witness from compact trace records (k_trace_witness.hip): the open's checks + pool offsets into a.verdict / a.head / a.ctr /
 // a.off, and a pass's row writer
-void zk_launch_trace_witness_check(hipStream_t st, const TrwArgs& a);
+// (with_offsets = false: the checks alone — a.off and the verdict's pool word are then the caller's to fill, zk_launch_state_trace_check)
+void zk_launch_trace_witness_check(hipStream_t st, const TrwArgs& a, bool with_offsets = true);
 void zk_launch_trace_witness(hipStream_t st, const TrwArgs& a, u32* status);
 void zk_launch_pi_rows(hipStream_t st, const PiArgs& a, u64 lo, u64 hi, u32* status, ZkTally* tally);
 void zk_launch_pi_copy(hipStream_t st, const PiCopyArgs& a, u32* status, ZkTally* tally);

@@ -134,9 +134,10 @@ ZK_HD bool asg_key_eq(const AsgKey& x, const AsgKey& y) { return fr_eq(x.addr, y
 ZK_HD u64 asg_key_hash(const AsgKey& k) { return zk_hash_cell(zk_hash_cell(zk_hash_cell(0x6d7074u, k.addr), k.ft), k.key); }
 
 // Claim / join the slot of op i's key; afterwards the slot holds the smallest op index with that key.
-template <bool RW = false>
-ZK_HD void asg_insert(const AssignArgs& a, u32 i) {
-    const AsgKey k = asg_key_of<RW>(a, i);
+// (`key_of(j)`: the AsgKey of op j — asg_key_of<RW> for the two sources here, state_trace.hpp's for the packed op stream)
+template <class KEYOF>
+ZK_HD void asg_insert_by(const AssignArgs& a, u32 i, KEYOF key_of) {
+    const AsgKey k = key_of(i);
     u32 s = (u32)asg_key_hash(k) & a.mask;
     for (;;) {
 #if defined(ZK_HOSTSIM)
@@ -150,7 +151,7 @@ ZK_HD void asg_insert(const AssignArgs& a, u32 i) {
         }
 #endif
         // `cur` is some op with the slot's key (the occupant only ever changes to an op with the same key)
-        if (asg_key_eq(asg_key_of<RW>(a, cur), k)) {
+        if (asg_key_eq(key_of(cur), k)) {
 #if defined(ZK_HOSTSIM)
             if (i < a.slots[s]) a.slots[s] = i;
 #else
@@ -162,15 +163,23 @@ ZK_HD void asg_insert(const AssignArgs& a, u32 i) {
     }
 }
 template <bool RW = false>
-ZK_HD u32 asg_find_first(const AssignArgs& a, u32 i) {
-    const AsgKey k = asg_key_of<RW>(a, i);
+ZK_HD void asg_insert(const AssignArgs& a, u32 i) {
+    asg_insert_by(a, i, [&a](u32 j) { return asg_key_of<RW>(a, j); });
+}
+template <class KEYOF>
+ZK_HD u32 asg_find_first_by(const AssignArgs& a, u32 i, KEYOF key_of) {
+    const AsgKey k = key_of(i);
     u32 s = (u32)asg_key_hash(k) & a.mask;
     for (;;) {
         const u32 cur = a.slots[s];
         if (cur == ZK_EMPTY_SLOT) return ASG_NONE;  // unreachable after asg_insert
-        if (cur == i || asg_key_eq(asg_key_of<RW>(a, cur), k)) return cur;
+        if (cur == i || asg_key_eq(key_of(cur), k)) return cur;
         s = (s + 1) & a.mask;
     }
+}
+template <bool RW = false>
+ZK_HD u32 asg_find_first(const AssignArgs& a, u32 i) {
+    return asg_find_first_by(a, i, [&a](u32 j) { return asg_key_of<RW>(a, j); });
 }
 
 ZK_HD void asg_store(u64* out, const Fr& x) {
@@ -212,14 +221,14 @@ ZK_HD u32 asg_mock_status(u32 flags, const Fr& ft, const Fr& vlo, const Fr& vhi,
 
 // MPTTableRow of first-occurrence op i with rank r (:921-929): address, proof_type, storage_key lo/hi,
 // root lo/hi, root_prev lo/hi, value lo/hi, value_prev lo/hi.
-template <bool RW = false>
-ZK_HD void asg_mpt_cells(const AssignArgs& a, u64 i, u32 r, Fr q[ASG_MPT_NCELLS]) {
-    const u32 flags = asg_flags<RW>(a, i);
-    const Fr ft = asg_slot<RW>(a, ASG_FT, i);
-    const Fr key = asg_slot<RW>(a, ASG_KEY, i);
-    const Fr vlo = asg_slot<RW>(a, ASG_VLO, i), vhi = asg_slot<RW>(a, ASG_VHI, i);
-    const Fr ilo = asg_slot<RW>(a, ASG_ILO, i), ihi = asg_slot<RW>(a, ASG_IHI, i);
-    q[0] = asg_reduce(asg_slot<RW>(a, ASG_ADDR, i));
+// (`slot(s)`: slot s of the op, `flags` its type bits)
+template <class SLOT>
+ZK_HD void asg_mpt_cells_of(SLOT slot, u32 flags, u32 r, Fr q[ASG_MPT_NCELLS]) {
+    const Fr ft = slot(ASG_FT);
+    const Fr key = slot(ASG_KEY);
+    const Fr vlo = slot(ASG_VLO), vhi = slot(ASG_VHI);
+    const Fr ilo = slot(ASG_ILO), ihi = slot(ASG_IHI);
+    q[0] = asg_reduce(slot(ASG_ADDR));
     // isinstance(field_tag, AccountFieldTag) -> from_account_field_tag (table.py:341-350: Nonce..NonExisting -> 1..4), else StorageMod
     q[1] = fr_from_u64((flags & 4u) ? fr_lo64(ft) : 6ull);
     q[2] = u256_lo(key);
@@ -231,6 +240,10 @@ ZK_HD void asg_mpt_cells(const AssignArgs& a, u64 i, u32 r, Fr q[ASG_MPT_NCELLS]
     q[7] = fr_zero();
     asg_word_of(vlo, vhi, q[8], q[9]);
     asg_word_of(ilo, ihi, q[10], q[11]);
+}
+template <bool RW = false>
+ZK_HD void asg_mpt_cells(const AssignArgs& a, u64 i, u32 r, Fr q[ASG_MPT_NCELLS]) {
+    asg_mpt_cells_of([&a, i](u32 s) { return asg_slot<RW>(a, s, i); }, asg_flags<RW>(a, i), r, q);
 }
 template <bool RW = false>
 ZK_HD void asg_write_mpt(const AssignArgs& a, u64 i, u32 r) {

@@ -121,6 +121,63 @@ ZK_HD RwkOp rwk_op(const u64* row, u32 rw_flags, const RwkKey& k) {
     }
     return o;
 }
+// The same two mappings over a cell provider `cell(k)` (cell k of the wire row as an Fr) instead of a row pointer: for sources that hold
+// the row's cells in another form (state_trace.hpp: compact trace records).  Only the cells the mapping uses are asked for.
+template <class CELL>
+ZK_HD RwkKey rwk_key_of(CELL cell) {
+    RwkKey k;
+    k.status = 0;
+    const Fr target = cell(2);
+    const u32 tag = fr_fits32(target) ? rwk_tag_of_target(target.v[0]) : 0u;
+    k.cls = tag;
+    k.f[RWK_F_RWC] = cell(0);
+    k.f[RWK_F_ID] = cell(3);
+    const Fr c4 = cell(4);
+    k.f[RWK_F_ADDR] = c4;
+    k.f[RWK_F_FT] = cell(5);
+    const Fr klo = cell(6), khi = cell(7);
+    Fr key = klo;
+    key.v[4] |= khi.v[0]; key.v[5] |= khi.v[1]; key.v[6] |= khi.v[2]; key.v[7] |= khi.v[3];
+    k.f[RWK_F_KEY] = key;
+    if (tag == 0u) {
+        k.cls = RWK_CLASS_DROPPED;
+        k.status = ZK_CODE(ZK_VALUE_ERROR, RWK_SITE_TARGET);
+        return k;
+    }
+    if (!fr_fits128(khi)) {
+        k.cls = RWK_CLASS_DROPPED;
+        k.status = ZK_CODE(ZK_OVERFLOW_ERROR, RWK_SITE_KEY);
+        return k;
+    }
+    if (tag == 5u) {
+        k.f[RWK_F_ADDR] = fr_zero();
+        k.f[RWK_F_FT] = c4;
+        if (!fr_le_u64(c4, RWK_MAX_FIELD_TAG)) k.cls = RWK_CLASS_DROPPED;
+    } else if (tag == 6u) {
+        k.f[RWK_F_ID] = fr_zero();
+    } else if (tag == 10u) {
+        k.f[RWK_F_ADDR] = rwk_shr(c4, 48);
+        k.f[RWK_F_FT] = fr_from_u64((u64)(c4.v[1] & 0xffffu));
+        k.f[RWK_F_KEY] = fr_from_u64((u64)c4.v[0]);
+    }
+    return k;
+}
+template <class CELL>
+ZK_HD RwkOp rwk_op_of(CELL cell, u32 rw_flags, const RwkKey& k) {
+    RwkOp o;
+    o.rw = cell(1);
+    o.vlo = cell(8);
+    o.vhi = cell(9);
+    o.ilo = fr_zero();
+    o.ihi = fr_zero();
+    o.flags = rw_flags & 1u;
+    if (k.cls == 4u || k.cls == 6u) {
+        o.ilo = cell(12);
+        o.ihi = cell(13);
+        o.flags |= 2u | (k.cls == 6u ? 4u : 0u);
+    }
+    return o;
+}
 
 // ---- the compact, order-preserving key ------------------------------------------------------------------------------------
 // Within one class (state tag) a key bit that is the same in every row of the class cannot decide a comparison, and rows of

@@ -664,6 +664,8 @@ struct zk_session {
     u32* rekey_status = nullptr;  // ... whose per-RW-row codes go here (the session's statuses are per op)
     bool sweep_ran = false;       // a pass since the last collect ran rwk_sweep_kernel: the collect reads the sweep's error word
     ZkTally* rekey_tally = nullptr;  // fast sort: the session's two tallies live RWK_SWEEP_FRONT words in front of rekey.sweep (one read-back)
+    bool from_trace = false;      // a rekey / fused_verify session over compact trace records (zk_state_*_from_trace*): rekey.rw is null,
+    StrcArgs strc;                // ... the rows come from these records (state_trace.hpp)
     u64 cpa_n_table = 0, cpa_n_rw = 0;
     u32* d_hist = nullptr;   // EVM: (group, state) bins (histogram -> cursors)
     u32* d_cursor = nullptr; // EVM: per-bin scatter cursors (cleared by every histogram pass)
@@ -1722,16 +1724,15 @@ extern "C" int zk_state_assign(const uint64_t* ops, const uint32_t* op_flags, ui
 #include "state_rekey_plan.hpp"
 // Stage the RW table, run the class scan, build the plan and allocate the sort's buffers (s->rekey); with want_ops the op list's
 // buffers too (ops_dev / op_flags_dev: the caller's, or session-owned when null).  s->n is left to the caller.
+static int rekey_plan_setup(zk_session* s, const std::vector<u32>& h_masks, bool want_ops, uint64_t* ops_dev, uint32_t* op_flags_dev);
 static int rekey_setup(zk_session* s, const uint64_t* rw, const uint32_t* rw_flags, uint64_t n, bool dev, bool want_ops,
                        uint64_t* ops_dev, uint32_t* op_flags_dev) {
     RekeyArgs& a = s->rekey;
     memset(&a, 0, sizeof(a));
     int rc = 0;
     const void* p = nullptr;
-    RwkHostPlan hp;
     std::vector<u32> h_masks(2 * RWK_MASK_WORDS_H + RWK_NCLASSES);
     const size_t mask_bytes = h_masks.size() * 4;
-    RwkPlan* d_plan = nullptr;
     if ((rc = stage(s, rw, (size_t)n * RWK_RW_NCELLS * 32, dev, &p))) return rc;
     a.rw = (const u64*)p;
     if (rw_flags) {
@@ -1744,6 +1745,15 @@ static int rekey_setup(zk_session* s, const uint64_t* rw, const uint32_t* rw_fla
     zk_launch_rekey_scan(s->stream, a);
     HIP_TRY(hipMemcpyAsync(h_masks.data(), a.masks, mask_bytes, hipMemcpyDeviceToHost, s->stream));
     HIP_TRY(hipStreamSynchronize(s->stream));
+    return rekey_plan_setup(s, h_masks, want_ops, ops_dev, op_flags_dev);
+}
+// The part behind the class scan, whatever the rows' source: the plan from the masks, the sort's buffers, the op list's
+static int rekey_plan_setup(zk_session* s, const std::vector<u32>& h_masks, bool want_ops, uint64_t* ops_dev, uint32_t* op_flags_dev) {
+    RekeyArgs& a = s->rekey;
+    const u64 n = a.n;
+    int rc = 0;
+    RwkHostPlan hp;
+    RwkPlan* d_plan = nullptr;
     {
         const char* e = getenv("ZK_REKEY_NO_RANKS");  // (read per open: the tests switch it inside one process)
         rwk_build_plan(h_masks.data(), !(e && e[0] == '1'), hp);
@@ -2855,6 +2865,15 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     case SESSION_KECCAK: zk_launch_keccak_table(s->stream, s->keccak_gen, status, s->d_tally); break;
     case SESSION_ASSIGN:
         if (s->fused_verify) {
+            if (s->from_trace) {  // the same passes over compact trace records: the sort leaves the sorted packed op stream, the rest reads it
+                if (!s->fused_order_ready) {
+                    zk_launch_state_trace_rekey(s->stream, s->rekey, s->strc, s->rekey_status, s->d_tally + 1);
+                    s->sweep_ran = s->rekey.fast != 0;
+                    zk_launch_state_assign_trace(s->stream, s->assign, s->strc);
+                }
+                zk_launch_state_rows_trace(s->stream, s->state, s->assign, s->strc, status, s->d_tally, s->d_tally + 1);
+                break;
+            }
             if (!s->fused_order_ready) {  // (a session's RW table does not change between passes)
                 zk_launch_state_rekey(s->stream, s->rekey, s->rekey_status, s->d_tally + 1);
                 s->sweep_ran = s->rekey.fast != 0;
@@ -2924,7 +2943,8 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     case SESSION_TRW: zk_launch_trace_witness(s->stream, s->trw, status); break;
     case SESSION_ECL: zk_launch_ecc_calls(s->stream, s->ecl, s->ecl_n_pairs, status); break;
     case SESSION_REKEY:
-        zk_launch_state_rekey(s->stream, s->rekey, status, s->d_tally);
+        if (s->from_trace) zk_launch_state_trace_rekey(s->stream, s->rekey, s->strc, status, s->d_tally);
+        else zk_launch_state_rekey(s->stream, s->rekey, status, s->d_tally);
         s->sweep_ran = s->rekey.fast != 0;
         break;
     case SESSION_EVM: {
@@ -3119,8 +3139,8 @@ extern "C" int zk_collect(zk_session* s, zk_result* r) {
         }
         if (t_asg.fail_count) {  // no witness: what assign_state_circuit raises in the reference is an error here, not a verdict
             char msg[240];
-            snprintf(msg, sizeof msg, "zk_state_verify_from_rw: the State witness assignment failed for %llu RW rows / ops (first: %llu, code 0x%08x; "
-                     "zk_state_assign_from_rw reports each)", (unsigned long long)t_asg.fail_count, (unsigned long long)(t_asg.first_fail >> 32),
+            snprintf(msg, sizeof msg, "%s: the State witness assignment failed for %llu RW rows / ops (first: %llu, code 0x%08x; "
+                     "zk_state_assign_from_rw reports each)", s->from_trace ? "zk_state_verify_from_trace" : "zk_state_verify_from_rw", (unsigned long long)t_asg.fail_count, (unsigned long long)(t_asg.first_fail >> 32),
                      (unsigned)(t_asg.first_fail & 0xffffffffull));
             g_err = msg;
             s->launches = 0;
@@ -4772,6 +4792,182 @@ extern "C" int zk_evm_witness_from_trace(const zk_trace* t, const zk_trace_witne
     rc = zk_launch(s, nullptr);
     if (!rc) rc = zk_collect(s, result);
     if (!rc) rc = zk_evm_witness_from_trace_read(s, dev ? nullptr : out_wire);
+    zk_close(s);
+    return rc;
+}
+
+// ---- State circuit from compact trace records (state_trace.hpp, k_state_trace.hip): the records of zk_evm_witness_from_trace without the
+// wire rows in between.  Results by composition: those of the _from_rw twin over the rw / rw_flags the expansion writes.
+#define STRC_ARGS_OK(t) ((t) && (t)->n_rw > 0 && (t)->head && (t)->id && (t)->addr && (t)->val && ((t)->n_pool == 0 || (t)->pool))
+// `name:` in front of the text behind the first colon of the current error (the texts are the from-RW / trace-witness entries')
+static void strc_retitle(const char* name) {
+    const std::string cur = g_err;
+    const size_t c = cur.find(':');
+    g_err = std::string(name) + (c == std::string::npos ? ": " + cur : cur.substr(c));
+}
+// The records staged (host callers) or used in place, the trace session's checks run on the device (the verdict block read back once),
+// the class scan over the records, the plan and the sort's buffers.  s->strc / s->rekey are ready afterwards; s->n is left to the caller.
+static int strc_setup(zk_session* s, const zk_trace* t, bool dev, bool want_ops, uint64_t* ops_dev, uint32_t* op_flags_dev, const char* name) {
+    char msg[256];
+    TrwArgs& w = s->trw;
+    memset(&w, 0, sizeof(w));
+    RekeyArgs& a = s->rekey;
+    memset(&a, 0, sizeof(a));
+    StrcArgs& c = s->strc;
+    memset(&c, 0, sizeof(c));
+    s->from_trace = true;
+    const u64 n = t->n_rw;
+    const void* p = nullptr;
+    void* d = nullptr;
+    u64 v[TRW_V_WORDS];
+    int rc = 0;
+    std::vector<u32> h_masks(2 * RWK_MASK_WORDS_H + RWK_NCLASSES);
+    const size_t mask_bytes = h_masks.size() * 4;
+    if ((rc = stage(s, t->head, (size_t)n * 4, dev, &p))) return rc;
+    w.head_in = (const u32*)p;
+    if (t->rw_counter) {
+        if ((rc = stage(s, t->rw_counter, (size_t)n * 8, dev, &p))) return rc;
+        w.ctr_in = (const u64*)p;
+    }
+    if ((rc = stage(s, t->id, (size_t)n * 8, dev, &p))) return rc;
+    w.id = (const u64*)p;
+    if ((rc = stage(s, t->addr, (size_t)n * 8, dev, &p))) return rc;
+    w.addr = (const u64*)p;
+    if ((rc = stage(s, t->val, (size_t)n * 8, dev, &p))) return rc;
+    w.val = (const u64*)p;
+    if ((rc = stage(s, t->pool, (size_t)t->n_pool * 32, dev, &p))) return rc;
+    w.pool = (const u64*)p;
+    w.n_rw = n; w.n_pool = t->n_pool; w.n_steps = 0; w.rw_base = t->rw_base;  // (prev and the steps are not read)
+    if ((rc = dev_alloc(s, &d, (size_t)n * 4 + 4))) return rc;
+    w.head = (u32*)d;
+    if (w.ctr_in) {
+        if ((rc = dev_alloc(s, &d, (size_t)n * 8))) return rc;
+        w.ctr = (u64*)d;
+    }
+    if ((rc = dev_alloc(s, &d, (size_t)n * 8 + 8))) return rc;
+    w.off = (u64*)d;
+    if ((rc = dev_alloc(s, &d, TRW_V_WORDS * 8))) return rc;
+    w.verdict = (u64*)d;
+    if ((rc = dev_alloc(s, &d, (size_t)((n + 1023) / 1024) * 8))) return rc;  // the offset scan's chunk sums
+    zk_launch_state_trace_check(s->stream, w, (u64*)d);
+    if (hipGetLastError() != hipSuccess) { g_err = std::string(name) + ": the open's check launch failed"; return -2; }
+    if ((rc = d2h_now(s->stream, v, w.verdict, sizeof v))) return rc;
+    if ((rc = trw_verdict_error(v, t->n_pool, msg, sizeof msg))) { g_err = msg; strc_retitle(name); return rc; }
+    c.head = w.head; c.ctr = w.ctr; c.id = w.id; c.addr = w.addr; c.val = w.val; c.off = w.off; c.pool = w.pool;
+    c.n = n; c.rw_base = t->rw_base;
+    a.n = n;
+    if ((rc = dev_alloc(s, (void**)&a.masks, mask_bytes))) return rc;
+    HIP_TRY(hipMemsetAsync(a.masks, 0, mask_bytes, s->stream));
+    zk_launch_state_trace_scan(s->stream, a, c);
+    HIP_TRY(hipMemcpyAsync(h_masks.data(), a.masks, mask_bytes, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return rekey_plan_setup(s, h_masks, want_ops, ops_dev, op_flags_dev);
+}
+static int strc_counts(const zk_trace* t, const char* name) {  // the counts that need no array, before anything is read or allocated
+    char msg[256];
+    if (int rc = trw_plan_counts(t->n_rw, 0, t->rw_base, t->rw_counter != nullptr, msg, sizeof msg)) { g_err = msg; strc_retitle(name); return rc; }
+    return 0;
+}
+extern "C" int zk_state_ops_from_trace_open(const zk_trace* t, uint64_t* ops_dev, uint32_t* op_flags_dev, uint32_t opts, uint64_t* n_ops_out,
+                                            zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_state_ops_from_trace_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(out && STRC_ARGS_OK(t), "zk_state_ops_from_trace_open: bad arguments");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    ARG_TRY(dev || (!ops_dev && !op_flags_dev), "zk_state_ops_from_trace_open: output buffers need ZK_OPT_DEVICE_PTRS");
+    if (int rc = strc_counts(t, "zk_state_ops_from_trace")) return rc;
+    zk_session* s = new zk_session();
+    s->kind = SESSION_REKEY;
+    s->n = t->n_rw;
+    int rc = strc_setup(s, t, dev, true, ops_dev, op_flags_dev, "zk_state_ops_from_trace");
+    if (!rc) rc = session_common_init(s);
+    if (rc) { zk_close(s); return rc; }
+    if (n_ops_out) *n_ops_out = s->rekey.n_ops;
+    *out = s;
+    return 0;
+}
+extern "C" int zk_state_ops_from_trace_read(zk_session* s, uint64_t* ops_host, uint32_t* op_flags_host, uint64_t* n_ops_out) {
+    ARG_TRY(s && s->kind == SESSION_REKEY && s->from_trace, "zk_state_ops_from_trace_read: bad arguments");
+    return zk_state_ops_from_rw_read(s, ops_host, op_flags_host, n_ops_out);
+}
+extern "C" int zk_state_ops_from_trace(const zk_trace* t, uint64_t* ops_out, uint32_t* op_flags_out, uint64_t* n_ops_out, uint32_t opts,
+                                       uint32_t* status_out, zk_result* result) {
+    ARG_TRY(result && n_ops_out, "zk_state_ops_from_trace: null output");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    int rc = zk_state_ops_from_trace_open(t, dev ? ops_out : nullptr, dev ? op_flags_out : nullptr, opts, n_ops_out, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && !dev) rc = zk_state_ops_from_trace_read(s, ops_out, op_flags_out, n_ops_out);
+    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
+    zk_close(s);
+    return rc;
+}
+// Records -> State circuit verdict: the first pass re-keys and sorts the records, writes the sorted packed op stream (48 bytes per op),
+// runs the MPT passes over it and evaluates; once a collect has seen a pass with a witness, later passes stream the ops and evaluate.
+extern "C" int zk_state_verify_from_trace_open(const zk_trace* t, uint32_t opts, uint64_t* n_ops_out, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_state_verify_from_trace_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(out && STRC_ARGS_OK(t), "zk_state_verify_from_trace_open: bad arguments");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    if (int rc = strc_counts(t, "zk_state_verify_from_trace")) return rc;
+    ARG_TRY(t->n_rw < (1ull << 31) - 1, "zk_state_verify_from_trace_open: bad arguments");
+    zk_session* s = new zk_session();
+    s->kind = SESSION_ASSIGN;
+    int rc = strc_setup(s, t, dev, false, nullptr, nullptr, "zk_state_verify_from_trace");
+    if (rc) { zk_close(s); return rc; }
+    const u64 n = s->rekey.n_ops, n_rw = t->n_rw;
+    s->n = n;
+    s->assign_from_rw = true;
+    s->fused_verify = true;
+    AssignArgs& a = s->assign;
+    StateArgs& v = s->state;
+    u32 cap = 16, mcap = 16;
+    a.n = n;
+    a.nb = (u32)((n + ASG_BLOCK - 1) / ASG_BLOCK);
+    if ((rc = dev_alloc(s, (void**)&s->strc.stream, (size_t)n * STRC_STREAM_WORDS * 8))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&a.mpt, (size_t)n * ASG_MPT_NCELLS * 32))) goto fail;
+    while (cap < 2 * n + 2) cap <<= 1;
+    mcap = cap;  // (as many MPT rows as ops at most)
+    a.mask = cap - 1;
+    a.mpt_mask = mcap - 1;
+    if ((rc = dev_alloc(s, (void**)&a.slots, ((size_t)cap + mcap) * 4))) goto fail;  // key slots, then the MPT index: one fill
+    a.mpt_slots = a.slots + cap;
+    if ((rc = dev_alloc(s, (void**)&a.first, (size_t)n * 4))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&a.rank, (size_t)n * 4))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&a.root_rank, (size_t)n * 4))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&a.blk_cnt, (size_t)(a.nb + 1) * 4))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&a.blk_next, (size_t)(a.nb + 1) * 4))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&s->rekey_status, (size_t)n_rw * 4))) goto fail;
+    v.rows.cells = nullptr;
+    v.rows.flags = nullptr;
+    v.rows.n = n;
+    v.eval_lo = 0;
+    v.eval_hi = n;
+    v.mpt.cells = a.mpt;
+    v.mpt.flags = nullptr;
+    v.mpt.n = (u32)n;  // a capacity: see StateFusedArgs
+    v.mpt.ncells = MPT_NCELLS;
+    v.mpt.slots = a.mpt_slots;
+    v.mpt.mask = a.mpt_mask;
+    if ((rc = session_common_init(s))) goto fail;
+    if (n_ops_out) *n_ops_out = n;
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_state_verify_from_trace(const zk_trace* t, uint32_t opts, uint32_t* status_out, uint64_t* n_ops_out, zk_result* result) {
+    ARG_TRY(result, "zk_state_verify_from_trace: result is null");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    int rc = zk_state_verify_from_trace_open(t, opts, n_ops_out, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
     zk_close(s);
     return rc;
 }

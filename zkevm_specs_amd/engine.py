@@ -1086,16 +1086,16 @@ def evm_witness_from_trace_shapes(n_rw, n_steps):
     return {"rw": ((int(n_rw), 14, 4), np.uint64), "rw_flags": ((int(n_rw),), np.uint32), "steps": ((int(n_steps), 13, 4), np.uint64)}
 
 
-def _evm_witness_from_trace_args(trace, outs=None):
+def _evm_witness_from_trace_args(trace, outs=None, optional=()):
     """zk_evm_witness_from_trace* over `trace` = dict(head uint32[n], id / addr / val / prev uint64[n], rw_counter uint64[n] or None (then
     rw_base, default 1: the counter of op i is rw_base + i), pool uint64[m, 4], steps uint64[k, 13]) -> (ZkTrace, ZkTraceWitness of the
     device outputs or None, opts, kept arrays, shapes).  trace.py makes such records.  `outs` (device tensors only, each optional):
-    buffers of TRACE_OUTPUTS the session writes in place."""
+    buffers of TRACE_OUTPUTS the session writes in place.  `optional`: per-op arrays the entry does not read and that may be missing."""
     n, m, k = _rows(trace.get("head")), _rows(trace.get("pool")), _rows(trace.get("steps"))
     _expect(trace.get("head"), "head", 4, (None,))
     for name in ("id", "addr", "val", "prev", "rw_counter"):
         _expect(trace.get(name), name, 8, (n,))
-        if n and name != "rw_counter" and trace.get(name) is None:
+        if n and name != "rw_counter" and name not in optional and trace.get(name) is None:
             raise ValueError(f"{name}: missing")
     _expect(trace.get("pool"), "pool", 8, (None, 4))
     _expect(trace.get("steps"), "steps", 8, (None, 13))
@@ -1144,6 +1144,51 @@ def open_evm_witness_from_trace(trace, outs=None, device=None):
     s = _open(lib, lib.zk_evm_witness_from_trace_open, shapes["rw"][0][0], (keep, t, w), ctypes.byref(t),
               ctypes.byref(w) if w is not None else None, opts, cls=WitnessFromTraceSession)
     s.shapes = shapes
+    return s
+
+
+# ---- State circuit from compact trace records (zk_state_verify_from_trace* / zk_state_ops_from_trace*) ---------------------------------
+def _state_from_trace_args(trace, outs=()):
+    """The RW half of `trace` (see _evm_witness_from_trace_args; prev and steps are not read and may be missing) -> (ZkTrace, opts, kept
+    arrays, n_rw); outs: flat output buffers as for _rw_args, prepared with the inputs"""
+    rec = {k: trace.get(k) for k in TRACE_INPUTS if k != "steps"}
+    rec["rw_base"] = trace.get("rw_base", 1)
+    n = _rows(rec.get("head"))
+    for buf, name, size, per_row in outs:
+        _expect(buf, name, size, (None,))
+        if buf is not None and int(buf.shape[0]) < per_row * (n + 1):
+            raise ValueError(f"{name} holds fewer than {per_row * (n + 1)} entries")
+    t, _, opts, keep, _ = _evm_witness_from_trace_args(rec, optional=("prev",))
+    bufs = [o[0] for o in outs]
+    if any(b is not None for b in bufs):
+        if not opts or not all(_is_device(b) for b in bufs if b is not None):
+            raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
+        if not all(_is_contiguous(b) for b in bufs if b is not None):
+            raise ValueError("output buffer must be contiguous")
+    return t, opts, (keep, t, bufs), n
+
+
+def open_state_verify_from_trace(trace, device=None):
+    """The State circuit's verdict over the RW ops of compact trace records (zk_state_verify_from_trace_open) -> Session over the n_ops =
+    1 + kept ops State rows, exactly open_state_verify_from_rw over the rw / rw_flags open_evm_witness_from_trace writes for the same
+    records, without those rows.  CUDA tensors are used in place: id / addr / val / pool must stay unchanged while the session lives."""
+    lib = _lib.init(device)
+    t, opts, keep, _ = _state_from_trace_args(trace)
+    h, n_ops = ctypes.c_void_p(), ctypes.c_uint64()
+    check(lib.zk_state_verify_from_trace_open(ctypes.byref(t), opts, ctypes.byref(n_ops), ctypes.byref(h)), "zk_state_verify_from_trace_open", lib)
+    return Session(h, int(n_ops.value), keep, lib=lib)
+
+
+def open_state_ops_from_trace(trace, ops_dev=None, op_flags_dev=None, device=None):
+    """The State op list of the RW ops of compact trace records (zk_state_ops_from_trace_open) -> RekeySession, exactly
+    open_state_ops_from_rw over the expanded rows; ops_dev / op_flags_dev as there (capacity n_rw + 1 ops)."""
+    lib = _lib.init(device)
+    t, opts, keep, n = _state_from_trace_args(trace, ((ops_dev, "ops_dev", 8, 48), (op_flags_dev, "op_flags_dev", 4, 1)))
+    h, n_ops = ctypes.c_void_p(), ctypes.c_uint64()
+    check(lib.zk_state_ops_from_trace_open(ctypes.byref(t), ptr(ops_dev), ptr(op_flags_dev), opts, ctypes.byref(n_ops), ctypes.byref(h)),
+          "zk_state_ops_from_trace_open", lib)
+    s = RekeySession(h, n, keep, lib=lib)
+    s.n_ops = int(n_ops.value)
     return s
 
 

@@ -152,6 +152,35 @@ def evm_witness_from_trace(trace, device=None):
     return Result(r), out
 
 
+def _state_trace_records(trace):
+    rec = {k: _host(trace.get(k), np.uint32 if k == "head" else np.uint64) for k in engine.TRACE_INPUTS if k != "steps"}
+    rec["rw_base"] = trace.get("rw_base", 1)
+    return rec
+
+
+def state_verify_from_trace(trace, device=None):
+    """zk_state_verify_from_trace over trace records of host arrays -> (Result of the State circuit, status uint32[n_ops] per State row):
+    what state_verify_from_rw returns over evm_witness_from_trace's rw / rw_flags"""
+    lib = _lib.init(device)
+    t, opts, keep, n = engine._state_from_trace_args(_state_trace_records(trace))
+    status, r, n_ops = np.zeros(n + 1, dtype=np.uint32), ZkResult(), ctypes.c_uint64()
+    check(lib.zk_state_verify_from_trace(ctypes.byref(t), opts, ptr(status), ctypes.byref(n_ops), ctypes.byref(r)), "zk_state_verify_from_trace", lib)
+    return Result(r), status[: int(n_ops.value)]
+
+
+def state_ops_from_trace(trace, device=None):
+    """zk_state_ops_from_trace -> (Result, status uint32[n] per RW op, ops uint64[12, n_ops, 4], op_flags uint32[n_ops]): what
+    state_ops_from_rw returns over evm_witness_from_trace's rw / rw_flags"""
+    lib = _lib.init(device)
+    t, opts, keep, n = engine._state_from_trace_args(_state_trace_records(trace))
+    ops, flags = np.zeros(12 * (n + 1) * 4, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint32)
+    status, r, n_ops = np.zeros(n, dtype=np.uint32), ZkResult(), ctypes.c_uint64()
+    check(lib.zk_state_ops_from_trace(ctypes.byref(t), ptr(ops), ptr(flags), ctypes.byref(n_ops), opts, ptr(status), ctypes.byref(r)),
+          "zk_state_ops_from_trace", lib)
+    m = int(n_ops.value)
+    return Result(r), status, ops[: 48 * m].reshape(12, m, 4), flags[:m]
+
+
 def ecdsa_verify(sig_bytes, v=None, layout=0, v_stride=1, device=None):
     """zk_ecdsa_verify -> (Result, status uint32[n])"""
     lib = _lib.init(device)
