@@ -991,6 +991,21 @@ int zk_state_ops_from_trace_open(const zk_trace* in, uint64_t* ops_dev, uint32_t
 int zk_state_ops_from_trace_read(zk_session* s, uint64_t* ops_host, uint32_t* op_flags_host, uint64_t* n_ops_out);
 int zk_state_ops_from_trace(const zk_trace* in, uint64_t* ops_out, uint32_t* op_flags_out, uint64_t* n_ops_out, uint32_t opts,
                             uint32_t* status_out /* n_rw */, zk_result* result);
+/* The State WITNESS of the same records (zk_state_assign_from_trace*): the third member of the family, the twin of
+ * zk_state_assign_from_rw_open.  By the same composition rule every output - n_ops, the rows uint64[57][n_ops][4] (uint64[15][n_ops][4]
+ * with ZK_OPT_STATE_COMPACT), row_flags uint32[n_ops], the MPT rows uint64[n_mpt][12][4] in first-occurrence order and n_mpt, the status
+ * per OP and the zk_result - is bit for bit what zk_state_assign_from_rw_open returns over the rw / rw_flags zk_evm_witness_from_trace
+ * writes for the same records; rejected RW rows count in the same tally, first_fail_row then being the RW row.  Inputs read, domain
+ * errors (under this entry's name) and resident data as for the two entries above.  With ZK_OPT_DEVICE_PTRS rows_dev / row_flags_dev /
+ * mpt_dev (each nullable: the session then owns the buffer) have capacity n_rw + 1 rows, are packed for n_ops and receive the outputs in
+ * place.  zk_launch / zk_collect / zk_read_status / zk_state_assign_read / zk_session_set_stream / zk_close as on a
+ * zk_state_assign_from_rw_open session.  Every zk_launch runs the whole chain (re-keying, sort, op stream, MPT passes, row writer), as
+ * the from-RW twin does: nothing is carried from one pass to the next, so a second pass gives the same outputs whatever the first saw.
+ * The one-shot writes HOST buffers of capacity n_rw + 1 rows (mpt_out: n_rw + 1 rows), or with ZK_OPT_DEVICE_PTRS the device buffers. */
+int zk_state_assign_from_trace_open(const zk_trace* in, uint64_t* rows_dev, uint32_t* row_flags_dev, uint64_t* mpt_dev,
+                                    uint32_t opts, uint64_t* n_ops_out, zk_session** out);
+int zk_state_assign_from_trace(const zk_trace* in, uint64_t* rows_out, uint32_t* row_flags_out, uint64_t* mpt_out,
+                               uint64_t* n_mpt_out, uint64_t* n_ops_out, uint32_t opts, uint32_t* status_out, zk_result* result);
 
 /* ---- ECC precompile calls: from the INPUT words of ecAdd / ecMul / ecPairing calls to what both circuits derive from them.  Where
  *      zk_ecc_ops takes every op's result from the caller (points[..][4..5], pair_out) and zk_ecc_assign copies it into rows, this

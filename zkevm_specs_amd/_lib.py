@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "zk_evm_witness_from_trace_sizes", "zk_evm_witness_from_trace_open", "zk_evm_witness_from_trace_read", "zk_evm_witness_from_trace",
     "zk_ecc_from_calls_open", "zk_ecc_from_calls_read", "zk_ecc_from_calls",
     "zk_state_verify_from_trace_open", "zk_state_verify_from_trace", "zk_state_ops_from_trace_open", "zk_state_ops_from_trace_read", "zk_state_ops_from_trace",
+    "zk_state_assign_from_trace_open", "zk_state_assign_from_trace",
 ]
 
 OPT_DEVICE_PTRS = 1
@@ -362,6 +363,8 @@ def _bind(lib):
     lib.zk_state_ops_from_trace_open.argtypes = [ctypes.POINTER(ZkTrace), vp, vp, u32, ctypes.POINTER(u64), ctypes.POINTER(vp)]
     lib.zk_state_ops_from_trace_read.argtypes = [vp, vp, vp, ctypes.POINTER(u64)]
     lib.zk_state_ops_from_trace.argtypes = [ctypes.POINTER(ZkTrace), vp, vp, ctypes.POINTER(u64), u32, vp, ctypes.POINTER(ZkResult)]
+    lib.zk_state_assign_from_trace_open.argtypes = [ctypes.POINTER(ZkTrace), vp, vp, vp, u32, ctypes.POINTER(u64), ctypes.POINTER(vp)]
+    lib.zk_state_assign_from_trace.argtypes = [ctypes.POINTER(ZkTrace), vp, vp, vp, ctypes.POINTER(u64), ctypes.POINTER(u64), u32, vp, ctypes.POINTER(ZkResult)]
     lib.zk_ecc_from_calls_open.argtypes = [ctypes.POINTER(ZkEccCalls), ctypes.POINTER(ZkEccCallWire), u32, ctypes.POINTER(vp)]
     lib.zk_ecc_from_calls_read.argtypes = [vp, ctypes.POINTER(ZkEccCallWire), ctypes.POINTER(u64)]
     lib.zk_ecc_from_calls.argtypes = [ctypes.POINTER(ZkEccCalls), ctypes.POINTER(ZkEccCallWire), u32, vp, ctypes.POINTER(u64),

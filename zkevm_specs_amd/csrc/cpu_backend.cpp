@@ -1481,6 +1481,32 @@ extern "C" int zk_state_verify_from_trace(const zk_trace* t, uint32_t opts, uint
     zk_close(s);
     return rc;
 }
+// Records -> State witness: the record's cells laid out as wire rows, then the from-RW twin's host passes (which copy what they keep).
+extern "C" int zk_state_assign_from_trace_open(const zk_trace* t, uint64_t* rows_dev, uint32_t* row_flags_dev, uint64_t* mpt_dev,
+                                               uint32_t opts, uint64_t* n_ops_out, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_state_assign_from_trace_open");
+    ARG_TRY(out && STRC_ARGS_OK(t) && !rows_dev && !row_flags_dev && !mpt_dev, "zk_state_assign_from_trace_open: bad arguments");
+    std::vector<u64> rw;
+    std::vector<u32> fl;
+    int rc = strc_rows(t, "zk_state_assign_from_trace", rw, fl);
+    if (rc) return rc;
+    rc = zk_state_assign_from_rw_open(rw.data(), fl.data(), t->n_rw, nullptr, nullptr, nullptr, opts, n_ops_out, out);
+    if (rc) strc_retitle("zk_state_assign_from_trace_open");
+    return rc;
+}
+extern "C" int zk_state_assign_from_trace(const zk_trace* t, uint64_t* rows_out, uint32_t* row_flags_out, uint64_t* mpt_out,
+                                          uint64_t* n_mpt_out, uint64_t* n_ops_out, uint32_t opts, uint32_t* status_out, zk_result* result) {
+    ARG_TRY(result && n_mpt_out && n_ops_out, "zk_state_assign_from_trace: null output");
+    zk_session* s = nullptr;
+    int rc = zk_state_assign_from_trace_open(t, nullptr, nullptr, nullptr, opts, n_ops_out, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc) rc = zk_state_assign_read(s, rows_out, row_flags_out, mpt_out, *n_ops_out, n_mpt_out);
+    if (!rc && status_out) rc = zk_read_status(s, status_out);
+    zk_close(s);
+    return rc;
+}
 
 static void copy_assign_pass(zk_session* s) {
     CpaArgs& a = s->cpa;

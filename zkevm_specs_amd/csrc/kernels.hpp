@@ -90,6 +90,7 @@ void zk_launch_state_trace_check(hipStream_t st, const TrwArgs& a, u64* sums);
 void zk_launch_state_trace_scan(hipStream_t st, const RekeyArgs& a, const StrcArgs& src);
 void zk_launch_state_trace_rekey(hipStream_t st, const RekeyArgs& a, const StrcArgs& src, u32* status, ZkTally* tally);
 void zk_launch_state_assign_trace(hipStream_t st, const AssignArgs& a, const StrcArgs& src);
+void zk_launch_state_assign_rows_trace(hipStream_t st, const AssignArgs& a, const StrcArgs& src, u32* status, ZkTally* tally);
 void zk_launch_state_rows_trace(hipStream_t st, const StateArgs& sa, const AssignArgs& g, const StrcArgs& src, u32* status, ZkTally* tally, ZkTally* asg_tally);
 void zk_launch_bca_rpow(hipStream_t st, const Fr& r, u64* out);
 void zk_launch_bytecode_assign(hipStream_t st, const BcaArgs& a, u32* status, ZkTally* tally);

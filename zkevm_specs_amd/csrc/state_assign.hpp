@@ -11,7 +11,8 @@
 //                   slot holding the SMALLEST op index with that key (atomicMin)
 //   asg_find_first  op -> that smallest index
 //   asg_write_mpt   MPTTableRow of a first-occurrence op (rank r: root_prev = 3 + 5 r, root = root_prev + 5)
-//   asg_write_row   op2row: reductions mod p, 16-bit address limbs, storage-key bytes, root, type bits
+//   asg_write_row   op2row: reductions mod p, 16-bit address limbs, storage-key bytes, root, type bits (asg_row_cells_of: the cells over
+//                   a slot provider and a store functor, for every source of ops and every store shape)
 //   asg_status      exception class of the reference for this op (see include/zkevm_hip.h)
 // The ranks (exclusive prefix count of first occurrences) and the "next MPT-keyed op" suffix-min are
 // computed with wave ballots + one small single-block scan over per-block partials (zkevm_hip.hip).
@@ -255,47 +256,61 @@ ZK_HD void asg_write_mpt(const AssignArgs& a, u64 i, u32 r) {
 }
 
 // op2row (:827-852) with the back-filled root; returns the op's status code.
-template <bool RW = false>
-ZK_HD u32 asg_write_row(const AssignArgs& a, u64 i, u64 root, bool is_first) {
-    const u64 n = a.n;
-    u64* rows = a.rows;
-#define ASG_OUT(c) (rows + ((u64)(((c) >= 50 && a.compact) ? (c) - 42 : (c)) * n + i) * 4)
-    const u32 flags = asg_flags<RW>(a, i);
-    const Fr addr = asg_slot<RW>(a, ASG_ADDR, i);
-    const Fr key = asg_slot<RW>(a, ASG_KEY, i);
-    const Fr ft = asg_slot<RW>(a, ASG_FT, i);
-    const Fr vlo = asg_slot<RW>(a, ASG_VLO, i), vhi = asg_slot<RW>(a, ASG_VHI, i);
-    const Fr ilo = asg_slot<RW>(a, ASG_ILO, i), ihi = asg_slot<RW>(a, ASG_IHI, i);
-    // RW source: every slot is read before the first store (the stores may alias the loads for the compiler: each later slot would
-    // re-read the row's target cell); op-list source: the four slots are loaded where they are stored (8 fewer live registers each)
-    const Fr rwc = RW ? asg_slot<RW>(a, ASG_RWC, i) : fr_zero(), rw = RW ? asg_slot<RW>(a, ASG_RW, i) : fr_zero();
-    const Fr tag = RW ? asg_slot<RW>(a, ASG_TAG, i) : fr_zero(), id = RW ? asg_slot<RW>(a, ASG_ID, i) : fr_zero();
-    const Fr lex = RW ? asg_slot<RW>(a, ASG_LEX, i) : fr_zero();
-    asg_store(ASG_OUT(0), asg_reduce(RW ? rwc : asg_slot<RW>(a, ASG_RWC, i)));
-    asg_store_u64(ASG_OUT(1), fr_is_zero(RW ? rw : asg_slot<RW>(a, ASG_RW, i)) ? 0 : 1);  // `op.rw == RW.Read` :829
-    asg_store(ASG_OUT(2), asg_reduce(RW ? tag : asg_slot<RW>(a, ASG_TAG, i)));
-    asg_store(ASG_OUT(3), asg_reduce(RW ? id : asg_slot<RW>(a, ASG_ID, i)));
-    asg_store(ASG_OUT(4), asg_reduce(addr));
-    asg_store(ASG_OUT(5), asg_reduce(ft));
-    asg_store(ASG_OUT(6), u256_lo(key));
-    asg_store(ASG_OUT(7), u256_hi(key));
-    if (!a.compact) {
+// (`slot(s)`: slot s of the op, `flags` its type bits; `store(c, x)`: cell c of the 57 is x — the caller places it, whole or by halves,
+// and maps 50..56 to 8..14 for the compact form; EARLY: every slot is read before the first store)
+template <bool EARLY, class SLOT, class STORE>
+ZK_HD u32 asg_row_cells_of(bool compact, u64 root, bool is_first, SLOT slot, u32 flags, STORE store) {
+    const Fr addr = slot(ASG_ADDR);
+    const Fr key = slot(ASG_KEY);
+    const Fr ft = slot(ASG_FT);
+    const Fr vlo = slot(ASG_VLO), vhi = slot(ASG_VHI);
+    const Fr ilo = slot(ASG_ILO), ihi = slot(ASG_IHI);
+    // EARLY (the RW rows, the trace records): every slot is read before the first store (the stores may alias the loads for the compiler:
+    // each later slot would re-read the row's target cell); op-list source: the four slots are loaded where they are stored (8 fewer
+    // live registers each)
+    const Fr rwc = EARLY ? slot(ASG_RWC) : fr_zero(), rw = EARLY ? slot(ASG_RW) : fr_zero();
+    const Fr tag = EARLY ? slot(ASG_TAG) : fr_zero(), id = EARLY ? slot(ASG_ID) : fr_zero();
+    const Fr lex = EARLY ? slot(ASG_LEX) : fr_zero();
+    store(0, asg_reduce(EARLY ? rwc : slot(ASG_RWC)));
+    store(1, fr_from_u64(fr_is_zero(EARLY ? rw : slot(ASG_RW)) ? 0 : 1));  // `op.rw == RW.Read` :829
+    store(2, asg_reduce(EARLY ? tag : slot(ASG_TAG)));
+    store(3, asg_reduce(EARLY ? id : slot(ASG_ID)));
+    store(4, asg_reduce(addr));
+    store(5, asg_reduce(ft));
+    store(6, u256_lo(key));
+    store(7, u256_hi(key));
+    if (!compact) {
 #pragma unroll
-        for (int k = 0; k < 10; k++) asg_store_u64(ASG_OUT(8 + k), (addr.v[k >> 1] >> (16 * (k & 1))) & 0xffffu);
+        for (int k = 0; k < 10; k++) store(8 + k, fr_from_u64((addr.v[k >> 1] >> (16 * (k & 1))) & 0xffffu));
 #pragma unroll
-        for (int k = 0; k < 32; k++) asg_store_u64(ASG_OUT(18 + k), fr_byte(key, k));
+        for (int k = 0; k < 32; k++) store(18 + k, fr_from_u64(fr_byte(key, k)));
     }
-    asg_store(ASG_OUT(50), vlo);
-    asg_store(ASG_OUT(51), vhi);
-    asg_store(ASG_OUT(52), ilo);
-    asg_store(ASG_OUT(53), ihi);
-    asg_store_u64(ASG_OUT(54), root);
-    asg_store_u64(ASG_OUT(55), 0);
-    asg_store(ASG_OUT(56), RW ? lex : asg_slot<RW>(a, ASG_LEX, i));
-#undef ASG_OUT
-    a.row_flags[i] = flags & 3u;
+    store(50, vlo);
+    store(51, vhi);
+    store(52, ilo);
+    store(53, ihi);
+    store(54, fr_from_u64(root));
+    store(55, fr_zero());
+    store(56, EARLY ? lex : slot(ASG_LEX));
     u32 code = is_first ? asg_mock_status(flags, ft, vlo, vhi, ilo, ihi) : 0u;
     // op.address.to_bytes(20, "little") :834 -> OverflowError
     if (!code && (addr.v[5] | addr.v[6] | addr.v[7])) code = ZK_CODE(ZK_OVERFLOW_ERROR, ASG_SITE_ADDRESS);
     return code;
+}
+// column of cell c in the rows array ([57][n][4], or [15][n][4] compact: cells 0..7 and 50..56)
+ZK_HD u32 asg_row_col(u32 c, bool compact) { return (c >= 50 && compact) ? c - 42 : c; }
+// the whole row of op i written by one caller, a cell at a time
+template <bool EARLY, class SLOT>
+ZK_HD u32 asg_write_row_of(const AssignArgs& a, u64 i, u64 root, bool is_first, SLOT slot, u32 flags) {
+    const u64 n = a.n;
+    u64* rows = a.rows;
+    const bool compact = a.compact;
+    const u32 code = asg_row_cells_of<EARLY>(compact, root, is_first, slot, flags,
+                                             [rows, n, i, compact](u32 c, const Fr& x) { asg_store(rows + ((u64)asg_row_col(c, compact) * n + i) * 4, x); });
+    a.row_flags[i] = flags & 3u;
+    return code;
+}
+template <bool RW = false>
+ZK_HD u32 asg_write_row(const AssignArgs& a, u64 i, u64 root, bool is_first) {
+    return asg_write_row_of<RW>(a, i, root, is_first, [&a, i](u32 s) { return asg_slot<RW>(a, s, i); }, asg_flags<RW>(a, i));
 }

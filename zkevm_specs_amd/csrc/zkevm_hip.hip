@@ -664,7 +664,7 @@ struct zk_session {
     u32* rekey_status = nullptr;  // ... whose per-RW-row codes go here (the session's statuses are per op)
     bool sweep_ran = false;       // a pass since the last collect ran rwk_sweep_kernel: the collect reads the sweep's error word
     ZkTally* rekey_tally = nullptr;  // fast sort: the session's two tallies live RWK_SWEEP_FRONT words in front of rekey.sweep (one read-back)
-    bool from_trace = false;      // a rekey / fused_verify session over compact trace records (zk_state_*_from_trace*): rekey.rw is null,
+    bool from_trace = false;      // a rekey / assign / fused_verify session over compact trace records (zk_state_*_from_trace*): rekey.rw is null,
     StrcArgs strc;                // ... the rows come from these records (state_trace.hpp)
     u64 cpa_n_table = 0, cpa_n_rw = 0;
     u32* d_hist = nullptr;   // EVM: (group, state) bins (histogram -> cursors)
@@ -2882,6 +2882,12 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
             zk_launch_state_rows_fused(s->stream, s->state, s->assign, status, s->d_tally, s->d_tally + 1);
             break;
         }
+        if (s->from_trace) {  // zk_state_assign_from_trace: the sort leaves the packed op stream, the MPT passes and the row writer read it
+            zk_launch_state_trace_rekey(s->stream, s->rekey, s->strc, s->rekey_status, s->d_tally);
+            s->sweep_ran = s->rekey.fast != 0;
+            zk_launch_state_assign_rows_trace(s->stream, s->assign, s->strc, status, s->d_tally);
+            break;
+        }
         if (s->assign_from_rw) {  // rejected RW rows count in the same tally
             zk_launch_state_rekey(s->stream, s->rekey, s->rekey_status, s->d_tally);
             s->sweep_ran = s->rekey.fast != 0;
@@ -4967,6 +4973,72 @@ extern "C" int zk_state_verify_from_trace(const zk_trace* t, uint32_t opts, uint
     if (rc) return rc;
     rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
     if (!rc) rc = zk_collect(s, result);
+    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
+    zk_close(s);
+    return rc;
+}
+// Records -> State witness: every pass re-keys and sorts the records, writes the sorted packed op stream, runs the MPT passes over it and
+// writes the rows from it (assign_rows_trace_kernel); nothing is kept between passes, as in the from-RW
+// twin.
+extern "C" int zk_state_assign_from_trace_open(const zk_trace* t, uint64_t* rows_dev, uint32_t* row_flags_dev, uint64_t* mpt_dev,
+                                               uint32_t opts, uint64_t* n_ops_out, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_state_assign_from_trace_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(out && STRC_ARGS_OK(t), "zk_state_assign_from_trace_open: bad arguments");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    ARG_TRY(dev || (!rows_dev && !row_flags_dev && !mpt_dev), "zk_state_assign_from_trace_open: output buffers need ZK_OPT_DEVICE_PTRS");
+    if (int rc = strc_counts(t, "zk_state_assign_from_trace")) return rc;
+    ARG_TRY(t->n_rw < (1ull << 31) - 1, "zk_state_assign_from_trace_open: bad arguments");
+    zk_session* s = new zk_session();
+    s->kind = SESSION_ASSIGN;
+    int rc = strc_setup(s, t, dev, false, nullptr, nullptr, "zk_state_assign_from_trace");
+    if (rc) { zk_close(s); return rc; }
+    const u64 n = s->rekey.n_ops, n_rw = t->n_rw;
+    s->n = n;
+    s->assign_from_rw = true;
+    AssignArgs& a = s->assign;
+    u32 cap = 16, mcap = 16;
+    a.n = n;
+    a.nb = (u32)((n + ASG_BLOCK - 1) / ASG_BLOCK);
+    a.rows = rows_dev;
+    a.row_flags = row_flags_dev;
+    a.mpt = mpt_dev;
+    a.compact = (opts & ZK_OPT_STATE_COMPACT) ? 1u : 0u;
+    if ((rc = dev_alloc(s, (void**)&s->strc.stream, (size_t)n * STRC_STREAM_WORDS * 8))) goto fail;
+    if (!a.rows && (rc = dev_alloc(s, (void**)&a.rows, (size_t)n * (a.compact ? 15 : ASG_ROW_NCELLS) * 32))) goto fail;
+    if (!a.row_flags && (rc = dev_alloc(s, (void**)&a.row_flags, (size_t)n * 4))) goto fail;
+    if (!a.mpt && (rc = dev_alloc(s, (void**)&a.mpt, (size_t)n * ASG_MPT_NCELLS * 32))) goto fail;
+    while (cap < 2 * n + 2) cap <<= 1;
+    mcap = cap;  // (the rank pass over the stream enters every MPT row into the State circuit's MPT index: as many rows as ops at most)
+    a.mask = cap - 1;
+    a.mpt_mask = mcap - 1;
+    if ((rc = dev_alloc(s, (void**)&a.slots, ((size_t)cap + mcap) * 4))) goto fail;
+    a.mpt_slots = a.slots + cap;
+    if ((rc = dev_alloc(s, (void**)&a.first, (size_t)n * 4))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&a.rank, (size_t)n * 4))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&a.blk_cnt, (size_t)(a.nb + 1) * 4))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&a.blk_next, (size_t)(a.nb + 1) * 4))) goto fail;
+    if ((rc = dev_alloc(s, (void**)&s->rekey_status, (size_t)n_rw * 4))) goto fail;
+    if ((rc = session_common_init(s))) goto fail;
+    if (n_ops_out) *n_ops_out = n;
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_state_assign_from_trace(const zk_trace* t, uint64_t* rows_out, uint32_t* row_flags_out, uint64_t* mpt_out,
+                                          uint64_t* n_mpt_out, uint64_t* n_ops_out, uint32_t opts, uint32_t* status_out, zk_result* result) {
+    ARG_TRY(result && n_mpt_out && n_ops_out, "zk_state_assign_from_trace: null output");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    int rc = zk_state_assign_from_trace_open(t, dev ? rows_out : nullptr, dev ? row_flags_out : nullptr, dev ? mpt_out : nullptr, opts,
+                                             n_ops_out, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc) rc = dev ? zk_state_assign_read(s, nullptr, nullptr, nullptr, 0, n_mpt_out)
+                      : zk_state_assign_read(s, rows_out, row_flags_out, mpt_out, *n_ops_out, n_mpt_out);
     if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
     zk_close(s);
     return rc;

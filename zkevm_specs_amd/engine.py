@@ -1147,7 +1147,7 @@ def open_evm_witness_from_trace(trace, outs=None, device=None):
     return s
 
 
-# ---- State circuit from compact trace records (zk_state_verify_from_trace* / zk_state_ops_from_trace*) ---------------------------------
+# ---- State circuit from compact trace records (zk_state_verify_from_trace* / zk_state_ops_from_trace* / zk_state_assign_from_trace*) ---------------------------------
 def _state_from_trace_args(trace, outs=()):
     """The RW half of `trace` (see _evm_witness_from_trace_args; prev and steps are not read and may be missing) -> (ZkTrace, opts, kept
     arrays, n_rw); outs: flat output buffers as for _rw_args, prepared with the inputs"""
@@ -1189,6 +1189,24 @@ def open_state_ops_from_trace(trace, ops_dev=None, op_flags_dev=None, device=Non
           "zk_state_ops_from_trace_open", lib)
     s = RekeySession(h, n, keep, lib=lib)
     s.n_ops = int(n_ops.value)
+    return s
+
+
+def open_state_assign_from_trace(trace, rows_dev=None, row_flags_dev=None, mpt_dev=None, device=None, compact=False):
+    """The State witness of the RW ops of compact trace records (zk_state_assign_from_trace_open) -> AssignSession over the n_ops = 1 +
+    kept ops State rows (session.n), exactly open_state_assign_from_rw over the rw / rw_flags open_evm_witness_from_trace writes for the
+    same records, without those rows; rows_dev / row_flags_dev / mpt_dev as there (flat CUDA buffers of capacity n_rw + 1 rows, packed
+    for n_ops).  CUDA tensors are used in place: id / addr / val / pool must stay unchanged while the session lives."""
+    lib = _lib.init(device)
+    outs = ((rows_dev, "rows_dev", 8, (15 if compact else 57) * 4), (row_flags_dev, "row_flags_dev", 4, 1), (mpt_dev, "mpt_dev", 8, 48))
+    t, opts, keep, _ = _state_from_trace_args(trace, outs)
+    if compact:
+        opts |= _lib.OPT_STATE_COMPACT
+    h, n_ops = ctypes.c_void_p(), ctypes.c_uint64()
+    check(lib.zk_state_assign_from_trace_open(ctypes.byref(t), ptr(rows_dev), ptr(row_flags_dev), ptr(mpt_dev), opts, ctypes.byref(n_ops),
+                                              ctypes.byref(h)), "zk_state_assign_from_trace_open", lib)
+    s = AssignSession(h, int(n_ops.value), keep, lib=lib)
+    s.compact = bool(compact)
     return s
 
 

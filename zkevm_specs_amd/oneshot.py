@@ -181,6 +181,24 @@ def state_ops_from_trace(trace, device=None):
     return Result(r), status, ops[: 48 * m].reshape(12, m, 4), flags[:m]
 
 
+def state_assign_from_trace(trace, device=None, compact=False):
+    """zk_state_assign_from_trace over trace records of host arrays -> (Result, status uint32[n_ops] per op, rows uint64[57, n_ops, 4] (15
+    with compact), row_flags uint32[n_ops], mpt uint64[n_mpt, 12, 4]): what a zk_state_assign_from_rw_open session returns over
+    evm_witness_from_trace's rw / rw_flags"""
+    lib = _lib.init(device)
+    t, opts, keep, n = engine._state_from_trace_args(_state_trace_records(trace))
+    if compact:
+        opts |= _lib.OPT_STATE_COMPACT
+    nc = 15 if compact else 57
+    rows, rflags = np.zeros(nc * (n + 1) * 4, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint32)
+    mpt, n_mpt, n_ops = np.zeros((n + 1, 12, 4), dtype=np.uint64), ctypes.c_uint64(), ctypes.c_uint64()
+    status, r = np.zeros(n + 1, dtype=np.uint32), ZkResult()
+    check(lib.zk_state_assign_from_trace(ctypes.byref(t), ptr(rows), ptr(rflags), ptr(mpt), ctypes.byref(n_mpt), ctypes.byref(n_ops), opts,
+                                         ptr(status), ctypes.byref(r)), "zk_state_assign_from_trace", lib)
+    m = int(n_ops.value)
+    return Result(r), status[:m], rows[: nc * m * 4].reshape(nc, m, 4), rflags[:m], mpt[: int(n_mpt.value)]
+
+
 def ecdsa_verify(sig_bytes, v=None, layout=0, v_stride=1, device=None):
     """zk_ecdsa_verify -> (Result, status uint32[n])"""
     lib = _lib.init(device)

@@ -159,13 +159,18 @@ class SuperCircuit:
     """Sessions of the four circuits over one witness set; launch() enqueues one pass of each, collect() returns
     ({circuit: Result}, total fail_count, first failing (circuit, row, code))."""
 
-    def __init__(self, parts, device=None, to_device=None, shard=None, state_compact=False, state_fused=False, exp_from_events=False):
+    def __init__(self, parts, device=None, to_device=None, shard=None, state_compact=False, state_fused=False, exp_from_events=False,
+                 state_trace=None):
         """shard = (rank, world): ONE global block, every circuit's rows cut into `world` contiguous ranges with that
         circuit's halo (distributed.HALO), all tables whole on every rank (BASELINE configs[4]).  The
         witness assignment (State / Bytecode / Copy rows from ops / unrolled codes / copy events) runs over the whole
         block on every rank — it is open-time work, tables and op lists being replicated anyway — and the rank keeps its
         slice.  self.rows then holds the rank's evaluated rows, self.global_rows the block's, self.row_lo each circuit's
-        first global row."""
+        first global row.
+        state_trace: compact trace records of the block's RW ops (a dict as engine.open_state_verify_from_trace takes).  When given and
+        parts["state_ops"] is None, the State part is built from the records instead of from evm["rw"]: the 57-cell and the compact rows by
+        engine.open_state_assign_from_trace, the fused verdict by engine.open_state_verify_from_trace.  That the records expand to
+        evm["rw"] / evm["rw_flags"] (engine.open_evm_witness_from_trace) is the caller's contract: it is not checked here."""
         from . import distributed
 
         to_dev_fn = to_device if to_device is not None else (lambda x: x)
@@ -205,7 +210,10 @@ class SuperCircuit:
         self.state_fused = bool(state_fused) and self.state_from_rw and world == 1 and not self.state_compact
         st_fused = None
         if self.state_fused:
-            st_fused = engine.open_state_verify_from_rw(evm_w["rw"], evm_w["rw_flags"], device=device)
+            if state_trace is not None:
+                st_fused = engine.open_state_verify_from_trace(self._state_trace(state_trace, dev), device=device)
+            else:
+                st_fused = engine.open_state_verify_from_rw(evm_w["rw"], evm_w["rw_flags"], device=device)
             self._keep.append(st_fused)
             res0 = st_fused.run()  # re-keying + sort + MPT roots + first evaluation; raises if the assignment itself fails
             self.assign_ms = res0.kernel_ms
@@ -222,12 +230,20 @@ class SuperCircuit:
                 rows_b = torch.empty(nc * 4 * (n_rw + 1), dtype=torch.int64, device=evm_w["rw"].device)
                 flags_b = torch.empty(n_rw + 1, dtype=torch.int32, device=evm_w["rw"].device)
                 mpt_b = torch.empty(48 * (n_rw + 1), dtype=torch.int64, device=evm_w["rw"].device)
-                with engine.open_state_assign_from_rw(evm_w["rw"], evm_w["rw_flags"], rows_b, flags_b, mpt_b, device=device, compact=self.state_compact) as a:
+                if state_trace is not None:
+                    a = engine.open_state_assign_from_trace(self._state_trace(state_trace, dev), rows_b, flags_b, mpt_b, device=device, compact=self.state_compact)
+                else:
+                    a = engine.open_state_assign_from_rw(evm_w["rw"], evm_w["rw_flags"], rows_b, flags_b, mpt_b, device=device, compact=self.state_compact)
+                with a:
                     res = a.run()
                     n, m = a.n, a.n_mpt()
                 rows, flags, mpt = rows_b[: nc * 4 * n].view(nc, n, 4), flags_b[:n], mpt_b[: 48 * m].view(m, 12, 4)
             else:
-                with engine.open_state_assign_from_rw(evm_w["rw"], evm_w["rw_flags"], device=device, compact=self.state_compact) as a:
+                if state_trace is not None:
+                    a = engine.open_state_assign_from_trace(self._state_trace(state_trace, dev), device=device, compact=self.state_compact)
+                else:
+                    a = engine.open_state_assign_from_rw(evm_w["rw"], evm_w["rw_flags"], device=device, compact=self.state_compact)
+                with a:
                     res = a.run()
                     rows, flags, mpt = a.read()
         else:
@@ -373,6 +389,11 @@ class SuperCircuit:
             self._launch_order = [k for k in order if k in self.sessions] + [k for k in self.sessions if k not in order]
             for k, s in self.sessions.items():
                 s.set_stream(self._streams[k])
+
+    @staticmethod
+    def _state_trace(trace, dev):
+        """the RW half of the records, its arrays where the block's tables are"""
+        return {k: (v if k == "rw_base" else dev(v)) for k, v in trace.items() if k != "steps"}
 
     def launch(self):
         for k in (self._launch_order or self.sessions):
