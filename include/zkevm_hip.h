@@ -1076,6 +1076,81 @@ int zk_ecc_from_calls_read(zk_session* s, const zk_ecc_call_wire* host, uint64_t
 int zk_ecc_from_calls(const zk_ecc_calls* in, const zk_ecc_call_wire* out, uint32_t opts, uint32_t* status_out,
                       uint64_t* n_table_rows_out, zk_result* result);
 
+/* ---- Copy-circuit witness from raw code, calldata and trace records: zk_copy_assign without its `data` array.  zk_copy_assign takes
+ *      every source byte of every copy event as value | is_code << 8, collected by a host loop per byte (and, for Bytecode copies, a host
+ *      is_code scan of the contract).  Those bytes are already on the device in the same block: a Bytecode source is a slice of the code
+ *      set zk_bytecode_from_code takes, a TxCalldata source a slice of the calldata zk_evm_tables_from_block / zk_tx_assign take, a
+ *      Memory source the values of the Memory read ops of the zk_trace records — the ops CopyCircuit.copy appends to the RW table
+ *      (typing.py:1122-1131).  This entry gathers `data` there and runs the Copy assignment over it.  What it removes is a host pass and a
+ *      second copy of data the device holds; it is not a bandwidth saving (the upload it drops is 2 bytes per source byte).
+ *      DEFINED BY COMPOSITION: for inputs it accepts, every output of zk_copy_assign - rows, row_flags, table, rw, rw_flags, the counts - is
+ *      bit for bit what zk_copy_assign returns for the same events with the `data` / `data_offsets` defined below.  The new outputs are
+ *      the gathered data uint16[n_data], data_offsets uint64[n_events + 1] and a status per EVENT.
+ *      Inputs (zk_copy_sources):
+ *        events, flags, n_events, randomness: exactly zk_copy_events', with the same domain checks; RlcAcc, like TxLog, is no source;
+ *        src_ref uint32[n_events]: for a Bytecode source the index of the code in the code set, for a TxCalldata source the index of the
+ *          tx in calldata_offsets; ignored otherwise.  dst_ref uint32[n_events]: for a Bytecode destination the index of the written
+ *          code; NULL when no event has one.  The refs are read at open, for every event of their kind (whatever its length);
+ *        code, n_code_bytes, code_offsets, n_codes: as zk_code_set; calldata, calldata_offsets, n_txs: as zk_block_data, at any byte
+ *          alignment; trace: a zk_trace of which head, id, addr, val, rw_counter / rw_base and n_rw (which may be 0) are read - pool,
+ *          prev and steps never are and may be NULL.
+ *        The events' id cells (code hash, call id, tx id) are NOT matched against the sources: the refs say where the bytes are, and the
+ *        Copy circuit's own bytecode / tx / RW lookups remain the check of the ids.
+ *      Gathered data: per event n_real = min(length, max(src_addr_end - src_addr, 0)) bytes; data_offsets is the running sum (host
+ *      arithmetic over the event cells).  Byte i < n_real of an event:
+ *        Bytecode source: byte src_addr + i of code src_ref;  TxCalldata source: byte src_addr + i of the calldata of tx src_ref;
+ *        Memory source: val of the trace op whose rw_counter is event.rw_counter + i * stride, stride 2 when the destination is Memory or
+ *          TxLog (a write op follows each read), else 1 (padded reads are a suffix and consume no counter).  With rw_counter NULL the op's
+ *          index is counter - rw_base, else it is found by binary search.  The op must be a Memory read: head bit 0 clear, tag nibble
+ *          Target.Memory (9), no address pool bit, id == the event's src_id lo with src_id hi zero, addr == src_addr + i;
+ *        is_code: 0 when neither side is Bytecode, else init_is_code (as zk_bytecode_from_code: PUSH1..PUSH32 open 1..32 data bytes, 0x5f
+ *          none, the counter restarts per code) of the Bytecode side's code - the source's when both sides are - at position
+ *          src_addr + i, or dst_addr + i when that code is the destination.  Every pass scans the code set for it (64-byte chunks, a
+ *          wavefront each; no code is walked serially by one lane).
+ *      Status per event (zk_launch: status_dev uint32[n_events]; the zk_result's tally runs over events, rows_evaluated = n_events):
+ *      0, or (ZK_KIND_VALUE_ERROR << 24) | site, never a guess:
+ *        1  a ref that is read is out of range;     2  src_addr_end lies beyond the source code / calldata (only when n_real > 0);
+ *        3  dst_addr + n_real lies beyond the destination code;
+ *        4  no trace op has the counter a read needs;     5  the op at that counter is not the Memory read described above;
+ *        6  the op's value is no byte (256 or more, or the head marks it as a pool word).
+ *      Sites 1-3 are per event, 4-6 per byte: an event's status is its lowest per-event site, else the site of its failing byte with the
+ *      lowest i.  A failing byte is gathered as 0 (is_code 0) and the event's other bytes normally; every byte of an event with site
+ *      1-3 is 0.  The rows are zk_copy_assign's over the data as gathered, failing inputs included.
+ *      zk_copy_assign_from_sources_sizes: the checks below and the counts.  _open: with ZK_OPT_DEVICE_PTRS every input is a device pointer
+ *      and rows_dev / row_flags_dev / table_dev / rw_dev / rw_flags_dev / data_dev uint16[n_data] receive the outputs in place (each
+ *      nullable: the session then owns that buffer); without the flag they must be NULL.  The events' integer cells, the refs, the
+ *      offsets and the trace's heads and counters are read at open and kept by the session (nothing a caller rewrites later can move a
+ *      load or a store); code, calldata, id / addr / val and the events' id cells stay the caller's and are read by every pass.  Every
+ *      zk_launch runs the whole chain (is_code scan, gather, Copy assignment): nothing is carried from one pass to the next.  zk_launch /
+ *      zk_collect / zk_read_status / zk_session_set_stream / zk_close as on a zk_copy_assign_open session; _read copies what
+ *      zk_copy_assign_read copies, plus data_host and data_offsets_host (always a HOST array).  The one-shot's status_out is a device
+ *      pointer with ZK_OPT_DEVICE_PTRS, like its other outputs.
+ *      Domain, rejected at sizes / open with an error code and its text in zk_last_error:
+ *        ZK_ERR_CPS_OFFSETS  code or calldata offsets that do not start at 0 or that decrease, code_offsets[n_codes] != n_code_bytes;
+ *        ZK_ERR_CPS_ROWS     2^31 or more source bytes (or code bytes, codes, txs);
+ *        ZK_ERR_TRC_HEAD / _ORDER / _ROWS as zk_evm_witness_from_trace_open reports them, on the device with one verdict block read
+ *        back (_POOL is not checked: the pool is not read); the event-field errors of zk_copy_assign, with their texts - all under this
+ *        entry's name. */
+#define ZK_ERR_CPS_OFFSETS (-90)
+#define ZK_ERR_CPS_ROWS (-91)
+typedef struct zk_copy_sources {
+    const uint64_t* events;     const uint32_t* flags;       uint64_t n_events;
+    const uint32_t* src_ref;    const uint32_t* dst_ref;     /* uint32[n_events]; dst_ref nullable */
+    const uint64_t* randomness;
+    const uint8_t* code;        uint64_t n_code_bytes;       const uint64_t* code_offsets;  uint64_t n_codes;
+    const uint8_t* calldata;    const uint64_t* calldata_offsets;   uint64_t n_txs;   /* offsets uint64[n_txs + 1] */
+    zk_trace trace;
+} zk_copy_sources;
+int zk_copy_assign_from_sources_sizes(const zk_copy_sources* in, uint32_t opts, uint64_t* n_rows, uint64_t* n_table, uint64_t* n_rw,
+                                      uint64_t* n_data);
+int zk_copy_assign_from_sources_open(const zk_copy_sources* in, uint64_t* rows_dev, uint32_t* row_flags_dev, uint64_t* table_dev,
+                                     uint64_t* rw_dev, uint32_t* rw_flags_dev, uint16_t* data_dev, uint32_t opts, zk_session** out);
+int zk_copy_assign_from_sources_read(zk_session* s, uint64_t* rows_host, uint32_t* row_flags_host, uint64_t* table_host,
+                                     uint64_t* rw_host, uint32_t* rw_flags_host, uint16_t* data_host, uint64_t* data_offsets_host);
+int zk_copy_assign_from_sources(const zk_copy_sources* in, uint64_t* rows_out, uint32_t* row_flags_out, uint64_t* table_out,
+                                uint64_t* rw_out, uint32_t* rw_flags_out, uint16_t* data_out, uint64_t* data_offsets_out,
+                                uint32_t opts, uint32_t* status_out, zk_result* result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = [
     "zk_ecc_from_calls_open", "zk_ecc_from_calls_read", "zk_ecc_from_calls",
     "zk_state_verify_from_trace_open", "zk_state_verify_from_trace", "zk_state_ops_from_trace_open", "zk_state_ops_from_trace_read", "zk_state_ops_from_trace",
     "zk_state_assign_from_trace_open", "zk_state_assign_from_trace",
+    "zk_copy_assign_from_sources_sizes", "zk_copy_assign_from_sources_open", "zk_copy_assign_from_sources_read", "zk_copy_assign_from_sources",
 ]
 
 OPT_DEVICE_PTRS = 1
@@ -147,6 +148,15 @@ class ZkTrace(ctypes.Structure):
                 ("n_pool", ctypes.c_uint64), ("steps", ctypes.c_void_p), ("n_steps", ctypes.c_uint64)]
 
 
+class ZkCopySources(ctypes.Structure):
+    """zk_copy_sources (include/zkevm_hip.h): copy events with refs into a code set, calldata and trace records"""
+    _fields_ = [("events", ctypes.c_void_p), ("flags", ctypes.c_void_p), ("n_events", ctypes.c_uint64),
+                ("src_ref", ctypes.c_void_p), ("dst_ref", ctypes.c_void_p), ("randomness", ctypes.c_void_p),
+                ("code", ctypes.c_void_p), ("n_code_bytes", ctypes.c_uint64), ("code_offsets", ctypes.c_void_p), ("n_codes", ctypes.c_uint64),
+                ("calldata", ctypes.c_void_p), ("calldata_offsets", ctypes.c_void_p), ("n_txs", ctypes.c_uint64),
+                ("trace", ZkTrace)]
+
+
 class ZkTraceWitness(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("rw", "rw_flags", "steps")]
 
@@ -196,6 +206,7 @@ ERR_EXP_CELL, ERR_EXP_ORDER, ERR_EXP_ROWS = -40, -41, -42  # ZK_ERR_EXP_* (inclu
 ERR_BTB_ID, ERR_BTB_OFFSETS, ERR_BTB_HISTORY, ERR_BTB_ROWS = -60, -61, -62, -63  # ZK_ERR_BTB_*: why zk_evm_tables_from_block* rejected its inputs
 ERR_TRC_HEAD, ERR_TRC_ORDER, ERR_TRC_POOL, ERR_TRC_ROWS = -70, -71, -72, -73  # ZK_ERR_TRC_*: why zk_evm_witness_from_trace* rejected its records
 ERR_ECL_OFFSETS, ERR_ECL_ROWS, ERR_ECL_RANDOMNESS = -80, -81, -82  # ZK_ERR_ECL_*: why zk_ecc_from_calls* rejected its calls
+ERR_CPS_OFFSETS, ERR_CPS_ROWS = -90, -91  # ZK_ERR_CPS_*: why zk_copy_assign_from_sources* rejected its sources
 
 
 class ZkBlock(ctypes.Structure):
@@ -369,6 +380,10 @@ def _bind(lib):
     lib.zk_ecc_from_calls_read.argtypes = [vp, ctypes.POINTER(ZkEccCallWire), ctypes.POINTER(u64)]
     lib.zk_ecc_from_calls.argtypes = [ctypes.POINTER(ZkEccCalls), ctypes.POINTER(ZkEccCallWire), u32, vp, ctypes.POINTER(u64),
                                       ctypes.POINTER(ZkResult)]
+    lib.zk_copy_assign_from_sources_sizes.argtypes = [ctypes.POINTER(ZkCopySources), u32] + [ctypes.POINTER(u64)] * 4
+    lib.zk_copy_assign_from_sources_open.argtypes = [ctypes.POINTER(ZkCopySources), vp, vp, vp, vp, vp, vp, u32, ctypes.POINTER(vp)]
+    lib.zk_copy_assign_from_sources_read.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.zk_copy_assign_from_sources.argtypes = [ctypes.POINTER(ZkCopySources), vp, vp, vp, vp, vp, vp, vp, u32, vp, ctypes.POINTER(ZkResult)]
     lib.zk_launch.argtypes = [vp, vp]
     lib.zk_collect.argtypes = [vp, ctypes.POINTER(ZkResult)]
     lib.zk_read_status.argtypes = [vp, vp]

@@ -67,3 +67,47 @@ class CopyEvents:
         events, flags, data, offsets = self.wire()
         res, rows, rf, table, rw, rwf = oneshot.copy_assign(events, flags, data, offsets, self.r)  # zk_copy_assign
         return rows, rf, table, rw, rwf
+
+
+class CopySources:
+    """CopyEvents without the per-byte host loop (zk_copy_assign_from_sources): `copy()` keeps CopyEvents.copy's arguments with `src_data`
+    replaced by `src_ref` / `dst_ref` — the index of the source (destination) code in the code set, or of the source tx in the calldata —
+    records one event and returns the same next rw_counter.  The bytes themselves are gathered on the device from `sources` =
+    dict(code, code_offsets, calldata, calldata_offsets, trace) (engine._copy_sources_args): what the block's other from-raw entries take."""
+
+    def __init__(self, r, sources):
+        self.r = _n(r)
+        self.sources = sources
+        self.events, self.flags, self.src_ref, self.dst_ref = [], [], [], []
+
+    def copy(self, rw_counter, src_id, src_tag, dst_id, dst_tag, src_addr, src_addr_end, dst_addr, copy_length, src_ref=0, dst_ref=0, log_id=0):
+        def ident(x):
+            if hasattr(x, "lo"):
+                return _n(x.lo), _n(x.hi), 1
+            return _n(x), 0, 0
+
+        s_lo, s_hi, s_w = ident(src_id)
+        d_lo, d_hi, d_w = ident(dst_id)
+        src_tag, dst_tag, length = int(src_tag), int(dst_tag), int(copy_length)
+        n_real = min(length, max(int(src_addr_end) - int(src_addr), 0))
+        self.events.append([s_lo, s_hi, src_tag, d_lo, d_hi, dst_tag, int(src_addr), int(src_addr_end), int(dst_addr), length, int(log_id),
+                            int(rw_counter)])
+        self.flags.append(s_w | (d_w << 1))
+        self.src_ref.append(int(src_ref))
+        self.dst_ref.append(int(dst_ref))
+        return int(rw_counter) + (n_real if src_tag == 2 else 0) + (length if dst_tag in (2, 4) else 0)
+
+    def wire(self):
+        """-> (events uint64[n, 12, 4], flags uint32[n], src_ref uint32[n], dst_ref uint32[n])"""
+        import numpy as np
+
+        from .wire import rows_to_rowmajor
+
+        return (rows_to_rowmajor(self.events, 12), np.array(self.flags, dtype=np.uint32), np.array(self.src_ref, dtype=np.uint32),
+                np.array(self.dst_ref, dtype=np.uint32))
+
+    def assign(self):
+        """-> (rows, row_flags, copy_table, rw, rw_flags) as CopyEvents.assign; an event whose bytes cannot be gathered raises (its status)"""
+        res, status, rows, rf, table, rw, rwf, _, _ = oneshot.copy_assign_from_sources(*self.wire(), self.sources, self.r)
+        raise_for_code(res.first_fail_code, f"copy event {res.first_fail_row}")
+        return rows, rf, table, rw, rwf

@@ -46,6 +46,7 @@
 static thread_local std::string g_err;
 #define ARG_TRY(cond, msg) do { if (!(cond)) { g_err = msg; return -1; } } while (0)
 #include "copy_assign_plan.hpp"  // (uses ARG_TRY)
+#include "copy_sources_plan.hpp"
 
 extern "C" const char* zk_last_error(void) { return g_err.c_str(); }
 extern "C" int zk_init(int) { return 0; }
@@ -104,7 +105,7 @@ struct zk_session {
     std::vector<u64> w64[4];              // assignment sessions: work / output buffers
     std::vector<u32> out32;
     void (*pass)(zk_session*) = nullptr;  // assignment sessions: one pass computes the outputs and fills `status`
-    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code, 11 tables from block, 12 witness from trace, 13 ECC precompile calls
+    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code, 11 tables from block, 12 witness from trace, 13 ECC precompile calls, 14 copy from sources
     u64 n_ops = 0;                        // RW -> State ops: 1 + kept rows
     std::vector<u32> rekey_plan;          // RW -> State ops: the RwkHostPlan's plan (as words) ...
     std::vector<u32> rekey_jobs;          // ... and its rank jobs (cls, field, base, count)
@@ -136,6 +137,10 @@ struct zk_session {
     std::vector<u32> trw32[2];      // heads, rw_flags
     CpaArgs cpa;
     CpaPlan cpa_plan;
+    CpsArgs cps;                    // Copy assignment from raw sources: the gather in front of `cpa` (its plan: cps_plan.cpa)
+    CpsPlan cps_plan;
+    std::vector<u64> cps64[4];      // is_code mask, counters, code offsets, per-event failing byte
+    std::vector<u32> cps32[1];      // heads
     EcdsaArgs ecdsa;
     KeccakGenArgs kgen;
     TxAssignArgs txa;
@@ -1525,6 +1530,34 @@ extern "C" int zk_copy_assign_sizes(const zk_copy_events* t, uint32_t opts, uint
     if (n_rw) *n_rw = pl.n_rw;
     return 0;
 }
+// the session's buffers and the Copy assignment's arguments over a plan the session owns and its source data (s->a16)
+static void cpa_session_setup(zk_session* s, CpaPlan& pl, const u64* events, u64 n_events, const u64* randomness) {
+    s->a64[0].assign(events, events + n_events * CPA_EV_NCELLS * 4);
+    s->a64[1].assign(CPA_RPOW_ROWS * 4, 0);
+    cpa_fill_rpow(cell_of(randomness), s->a64[1].data());
+    s->w64[0].assign(pl.chunks.size() * 4 + 4, 0);  // chunk_acc
+    s->w64[1].assign(pl.chunks.size() * 4 + 4, 0);  // chunk_in
+    s->w64[2].assign(n_events * 4 + 4, 0);          // ev_rlc
+    s->w64[3].assign(pl.n_rlc * 4 + 4, 0);          // rlc
+    s->a64[2].assign(pl.n_rows * CPA_ROW_NCELLS * 4 + 4, 0);   // rows
+    s->a64[3].assign(pl.n_table * CPA_TABLE_NCELLS * 4 + 4, 0);  // table
+    s->keccak_rows.assign(pl.n_rw * CPA_RW_NCELLS * 4 + 4, 0);  // rw rows
+    s->out32.assign(pl.n_rows + 1, 0);              // row flags
+    s->a32[0].assign(pl.n_rw + 1, 0);               // rw flags
+    CpaArgs& a = s->cpa;
+    a.events = s->a64[0].data(); a.ev = pl.ev.data(); a.row0 = pl.row0.data(); a.n_events = n_events; a.n_rows = pl.n_rows; a.data = s->a16.data();
+    a.rpow = s->a64[1].data(); a.chunks = pl.chunks.data(); a.n_chunks = pl.chunks.size(); a.chunk_acc = s->w64[0].data(); a.chunk_in = s->w64[1].data();
+    a.ev_rlc = s->w64[2].data(); a.rlc = s->w64[3].data(); a.rows = s->a64[2].data(); a.row_flags = s->out32.data(); a.table = s->a64[3].data();
+    a.rw = s->keccak_rows.data(); a.rw_flags = s->a32[0].data();
+}
+static void cpa_read_copy(const zk_session* s, const CpaPlan& pl, uint64_t* rows_host, uint32_t* row_flags_host, uint64_t* table_host, uint64_t* rw_host,
+                          uint32_t* rw_flags_host) {
+    if (rows_host) memcpy(rows_host, s->a64[2].data(), (size_t)pl.n_rows * CPA_ROW_NCELLS * 32);
+    if (row_flags_host) memcpy(row_flags_host, s->out32.data(), (size_t)pl.n_rows * 4);
+    if (table_host && pl.n_table) memcpy(table_host, s->a64[3].data(), (size_t)pl.n_table * CPA_TABLE_NCELLS * 32);
+    if (rw_host && pl.n_rw) memcpy(rw_host, s->keccak_rows.data(), (size_t)pl.n_rw * CPA_RW_NCELLS * 32);
+    if (rw_flags_host && pl.n_rw) memcpy(rw_flags_host, s->a32[0].data(), (size_t)pl.n_rw * 4);
+}
 extern "C" int zk_copy_assign_open(const zk_copy_events* t, uint64_t* rows_dev, uint32_t* row_flags_dev, uint64_t* table_dev, uint64_t* rw_dev,
                                    uint32_t* rw_flags_dev, uint32_t opts, zk_session** out) {
     NO_DEVICE_PTRS(opts, "zk_copy_assign_open");
@@ -1536,24 +1569,8 @@ extern "C" int zk_copy_assign_open(const zk_copy_events* t, uint64_t* rows_dev, 
     if (rc) { delete s; return rc; }
     s->n = s->hi = pl.n_rows;
     s->status.assign(pl.n_rows ? pl.n_rows : 1, 0u);
-    s->a64[0].assign(t->events, t->events + t->n_events * CPA_EV_NCELLS * 4);
     s->a16.assign(t->data, t->data + pl.n_data);
-    s->a64[1].assign(CPA_RPOW_ROWS * 4, 0);
-    cpa_fill_rpow(cell_of(t->randomness), s->a64[1].data());
-    s->w64[0].assign(pl.chunks.size() * 4 + 4, 0);  // chunk_acc
-    s->w64[1].assign(pl.chunks.size() * 4 + 4, 0);  // chunk_in
-    s->w64[2].assign(t->n_events * 4 + 4, 0);       // ev_rlc
-    s->w64[3].assign(pl.n_rlc * 4 + 4, 0);          // rlc
-    s->a64[2].assign(pl.n_rows * CPA_ROW_NCELLS * 4 + 4, 0);   // rows
-    s->a64[3].assign(pl.n_table * CPA_TABLE_NCELLS * 4 + 4, 0);  // table
-    s->keccak_rows.assign(pl.n_rw * CPA_RW_NCELLS * 4 + 4, 0);  // rw rows
-    s->out32.assign(pl.n_rows + 1, 0);              // row flags
-    s->a32[0].assign(pl.n_rw + 1, 0);               // rw flags
-    CpaArgs& a = s->cpa;
-    a.events = s->a64[0].data(); a.ev = pl.ev.data(); a.row0 = pl.row0.data(); a.n_events = t->n_events; a.n_rows = pl.n_rows; a.data = s->a16.data();
-    a.rpow = s->a64[1].data(); a.chunks = pl.chunks.data(); a.n_chunks = pl.chunks.size(); a.chunk_acc = s->w64[0].data(); a.chunk_in = s->w64[1].data();
-    a.ev_rlc = s->w64[2].data(); a.rlc = s->w64[3].data(); a.rows = s->a64[2].data(); a.row_flags = s->out32.data(); a.table = s->a64[3].data();
-    a.rw = s->keccak_rows.data(); a.rw_flags = s->a32[0].data();
+    cpa_session_setup(s, pl, t->events, t->n_events, t->randomness);
     s->pass = copy_assign_pass;
     s->assign_kind = 3;
     *out = s;
@@ -1562,12 +1579,7 @@ extern "C" int zk_copy_assign_open(const zk_copy_events* t, uint64_t* rows_dev, 
 extern "C" int zk_copy_assign_read(zk_session* s, uint64_t* rows_host, uint32_t* row_flags_host, uint64_t* table_host, uint64_t* rw_host,
                                    uint32_t* rw_flags_host) {
     ARG_TRY(s && s->assign_kind == 3, "zk_copy_assign_read: bad arguments");
-    const CpaPlan& pl = s->cpa_plan;
-    if (rows_host) memcpy(rows_host, s->a64[2].data(), (size_t)pl.n_rows * CPA_ROW_NCELLS * 32);
-    if (row_flags_host) memcpy(row_flags_host, s->out32.data(), (size_t)pl.n_rows * 4);
-    if (table_host && pl.n_table) memcpy(table_host, s->a64[3].data(), (size_t)pl.n_table * CPA_TABLE_NCELLS * 32);
-    if (rw_host && pl.n_rw) memcpy(rw_host, s->keccak_rows.data(), (size_t)pl.n_rw * CPA_RW_NCELLS * 32);
-    if (rw_flags_host && pl.n_rw) memcpy(rw_flags_host, s->a32[0].data(), (size_t)pl.n_rw * 4);
+    cpa_read_copy(s, s->cpa_plan, rows_host, row_flags_host, table_host, rw_host, rw_flags_host);
     return 0;
 }
 extern "C" int zk_copy_assign(const zk_copy_events* t, uint64_t* rows_out, uint32_t* row_flags_out, uint64_t* table_out, uint64_t* rw_out,
@@ -1579,6 +1591,107 @@ extern "C" int zk_copy_assign(const zk_copy_events* t, uint64_t* rows_out, uint3
     rc = zk_launch(s, nullptr);
     if (!rc) rc = zk_collect(s, result);
     if (!rc) rc = zk_copy_assign_read(s, rows_out, row_flags_out, table_out, rw_out, rw_flags_out);
+    zk_close(s);
+    return rc;
+}
+
+// ---- Copy-circuit witness assignment from raw sources (copy_sources.hpp): the gather's per-byte function in host loops, the is_code bits by
+//      the reference's recurrence, then the pass above.  The session keeps its plan (the events' integers, the refs' resolution, the offsets)
+//      and its own heads and counters; code, calldata, id / addr / val stay the caller's arrays and every pass reads them.
+static void copy_sources_pass(zk_session* s) {
+    CpsArgs& g = s->cps;
+    const CpsPlan& pl = s->cps_plan;
+    if (pl.any_code) cps_code_mask_host(g.code, s->cps64[2].data(), pl.chunk0.data(), pl.chunk0.size() - 1, s->cps64[0].data());
+    for (u64 e = 0; e < g.n_events; e++) {
+        cps_gather_event(g, e);
+        s->status[e] = cps_status(g.sev[e], g.ev_fail[e]);
+    }
+    copy_assign_pass(s);
+}
+#define CPS_ARGS_OK(t) ((t) && (t)->n_events > 0 && (t)->n_events < (1ull << 31) && (t)->events && (t)->src_ref &&                                  \
+                        ((t)->n_codes == 0 || (t)->code_offsets) && ((t)->n_code_bytes == 0 || (t)->code) && ((t)->n_txs == 0 || (t)->calldata_offsets) && \
+                        ((t)->trace.n_rw == 0 || ((t)->trace.head && (t)->trace.id && (t)->trace.addr && (t)->trace.val)))
+// the domain checks and the plan; head / ctr (nullable) receive the session's copies of the trace's heads and counters
+static int cps_prepare(const zk_copy_sources* t, CpsPlan& pl, u32* head, u64* ctr) {
+    const char* const name = "zk_copy_assign_from_sources";
+    const zk_trace& tr = t->trace;
+    char msg[256];
+    int rc = trw_plan_counts(tr.n_rw, 0, tr.rw_base, tr.rw_counter != nullptr, msg, sizeof msg);  // (before any array is read)
+    if (rc) { g_err = msg; cps_retitle(name); return rc; }
+    if ((rc = cps_plan(t->events, t->flags, t->src_ref, t->dst_ref, t->n_events, t->code_offsets, t->n_codes, t->n_code_bytes, t->calldata_offsets,
+                       t->n_txs, pl)))
+        return rc;
+    ARG_TRY(!t->n_txs || t->calldata_offsets[t->n_txs] == 0 || t->calldata, "zk_copy_assign_from_sources: calldata is null");
+    u64 v[TRW_V_WORDS];
+    trw_check_host(tr.head, tr.rw_counter, tr.n_rw, nullptr, 0, head, ctr, nullptr, v);
+    if ((rc = trw_verdict_error(v, v[TRW_V_POOL], msg, sizeof msg))) { g_err = msg; cps_retitle(name); }  // (the pool is not read: its count is not checked)
+    return rc;
+}
+extern "C" int zk_copy_assign_from_sources_sizes(const zk_copy_sources* t, uint32_t opts, uint64_t* n_rows, uint64_t* n_table, uint64_t* n_rw,
+                                                 uint64_t* n_data) {
+    NO_DEVICE_PTRS(opts, "zk_copy_assign_from_sources_sizes");
+    ARG_TRY(CPS_ARGS_OK(t), "zk_copy_assign_from_sources_sizes: bad arguments");
+    CpsPlan pl;
+    const int rc = cps_prepare(t, pl, nullptr, nullptr);
+    if (rc) return rc;
+    if (n_rows) *n_rows = pl.cpa.n_rows;
+    if (n_table) *n_table = pl.cpa.n_table;
+    if (n_rw) *n_rw = pl.cpa.n_rw;
+    if (n_data) *n_data = pl.data0[t->n_events];
+    return 0;
+}
+extern "C" int zk_copy_assign_from_sources_open(const zk_copy_sources* t, uint64_t* rows_dev, uint32_t* row_flags_dev, uint64_t* table_dev,
+                                                uint64_t* rw_dev, uint32_t* rw_flags_dev, uint16_t* data_dev, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_copy_assign_from_sources_open");
+    ARG_TRY(CPS_ARGS_OK(t) && out && t->randomness, "zk_copy_assign_from_sources_open: bad arguments");
+    ARG_TRY(!rows_dev && !row_flags_dev && !table_dev && !rw_dev && !rw_flags_dev && !data_dev, "zk_copy_assign_from_sources_open: output buffers need ZK_OPT_DEVICE_PTRS");
+    const zk_trace& tr = t->trace;
+    zk_session* s = new_session(t->n_events, false);
+    CpsPlan& pl = s->cps_plan;
+    s->cps32[0].assign(tr.n_rw + 1, 0);                         // heads
+    s->cps64[1].assign(tr.rw_counter ? tr.n_rw + 1 : 0, 0);     // counters
+    const int rc = cps_prepare(t, pl, s->cps32[0].data(), tr.rw_counter ? s->cps64[1].data() : nullptr);
+    if (rc) { delete s; return rc; }
+    const u64 n_data = pl.data0[t->n_events];
+    s->status.assign(t->n_events, 0u);
+    s->a16.assign(n_data + 1, 0);
+    cpa_session_setup(s, pl.cpa, t->events, t->n_events, t->randomness);
+    s->cps64[0].assign(pl.n_chunks + 1, 0);                     // is_code mask
+    s->cps64[2].assign(t->code_offsets, t->code_offsets + (t->n_codes ? t->n_codes + 1 : 0));  // the session's copy of the code offsets
+    s->cps64[3].assign(t->n_events, CPS_NO_FAIL);               // per-event failing byte
+    CpsArgs& g = s->cps;
+    memset(&g, 0, sizeof(g));
+    g.events = s->cpa.events; g.ev = pl.cpa.ev.data(); g.sev = pl.sev.data(); g.data0 = pl.data0.data(); g.n_events = t->n_events; g.n_data = n_data;
+    g.code = t->code; g.code_mask = s->cps64[0].data(); g.calldata = t->calldata;
+    g.head = s->cps32[0].data(); g.ctr = tr.rw_counter ? s->cps64[1].data() : nullptr; g.id = tr.id; g.addr = tr.addr; g.val = tr.val;
+    g.n_rw = tr.n_rw; g.rw_base = tr.rw_base;
+    g.data = s->a16.data();
+    g.ev_fail = (unsigned long long*)s->cps64[3].data();
+    s->pass = copy_sources_pass;
+    s->assign_kind = 14;
+    *out = s;
+    return 0;
+}
+extern "C" int zk_copy_assign_from_sources_read(zk_session* s, uint64_t* rows_host, uint32_t* row_flags_host, uint64_t* table_host,
+                                                uint64_t* rw_host, uint32_t* rw_flags_host, uint16_t* data_host, uint64_t* data_offsets_host) {
+    ARG_TRY(s && s->assign_kind == 14, "zk_copy_assign_from_sources_read: bad arguments");
+    const CpsPlan& pl = s->cps_plan;
+    cpa_read_copy(s, pl.cpa, rows_host, row_flags_host, table_host, rw_host, rw_flags_host);
+    if (data_host && s->cps.n_data) memcpy(data_host, s->cps.data, (size_t)s->cps.n_data * 2);
+    if (data_offsets_host) memcpy(data_offsets_host, pl.data0.data(), pl.data0.size() * 8);
+    return 0;
+}
+extern "C" int zk_copy_assign_from_sources(const zk_copy_sources* t, uint64_t* rows_out, uint32_t* row_flags_out, uint64_t* table_out,
+                                           uint64_t* rw_out, uint32_t* rw_flags_out, uint16_t* data_out, uint64_t* data_offsets_out,
+                                           uint32_t opts, uint32_t* status_out, zk_result* result) {
+    ARG_TRY(result && rows_out && row_flags_out, "zk_copy_assign_from_sources: null output");
+    zk_session* s = nullptr;
+    int rc = zk_copy_assign_from_sources_open(t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && status_out) rc = zk_read_status(s, status_out);
+    if (!rc) rc = zk_copy_assign_from_sources_read(s, rows_out, row_flags_out, table_out, rw_out, rw_flags_out, data_out, data_offsets_out);
     zk_close(s);
     return rc;
 }

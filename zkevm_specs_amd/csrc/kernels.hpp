@@ -18,6 +18,7 @@
 #include "trace_witness.hpp"
 #include "state_trace.hpp"
 #include "copy_assign.hpp"
+#include "copy_sources.hpp"
 #include "pi_circuit.hpp"
 #include "state_rekey.hpp"
 #include "ecc_circuit.hpp"
@@ -109,6 +110,9 @@ void zk_launch_pi_rows(hipStream_t st, const PiArgs& a, u64 lo, u64 hi, u32* sta
 void zk_launch_pi_copy(hipStream_t st, const PiCopyArgs& a, u32* status, ZkTally* tally);
 void zk_launch_cpa_rpow(hipStream_t st, const Fr& r, u64* out);
 void zk_launch_copy_assign(hipStream_t st, const CpaArgs& a, u32* status, ZkTally* tally);
+// The Copy assignment's source data from code, calldata and trace records (k_copy_sources.hip): the is_code scan of the code set (c.n_segs
+// > 0), the gather into a.data, the status per event and its tally; zk_launch_copy_assign over a.data follows in stream order
+void zk_launch_copy_sources(hipStream_t st, const CpsArgs& a, const CpsCodeArgs& c, u32* status, ZkTally* tally);
 void zk_launch_ecdsa(hipStream_t st, const EcdsaArgs& a, u32* status, ZkTally* tally);
 void zk_launch_ecdsa_comb_build(hipStream_t st, u32* table);  // the device's 8-bit fixed-base table of G (522 KB), built once
 // ECC circuit (k_ecc.hip): assign = circuit2rows into a.rows_out, else verify a.rows (status / tally)

@@ -605,7 +605,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_ECL = 25, SESSION_TRW = 24, SESSION_BTB = 23, SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_CPS = 26, SESSION_ECL = 25, SESSION_TRW = 24, SESSION_BTB = 23, SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -667,6 +667,9 @@ struct zk_session {
     bool from_trace = false;      // a rekey / assign / fused_verify session over compact trace records (zk_state_*_from_trace*): rekey.rw is null,
     StrcArgs strc;                // ... the rows come from these records (state_trace.hpp)
     u64 cpa_n_table = 0, cpa_n_rw = 0;
+    CpsArgs cps;                    // SESSION_CPS (zk_copy_assign_from_sources*): the gather in front of the Copy assignment in `cpa`
+    CpsCodeArgs cps_code;           // ... its is_code scan (n_segs = 0: no event has a Bytecode side)
+    std::vector<u64> cps_data0;     // ... the gathered array's offsets (host copy: zk_copy_assign_from_sources_read hands them out)
     u32* d_hist = nullptr;   // EVM: (group, state) bins (histogram -> cursors)
     u32* d_cursor = nullptr; // EVM: per-bin scatter cursors (cleared by every histogram pass)
     u32* d_hist2 = nullptr;  // EVM: the other histogram buffer (the two alternate between passes)
@@ -2248,16 +2251,21 @@ fail:
     zk_close(s);
     return rc;
 }
-extern "C" int zk_copy_assign_read(zk_session* s, uint64_t* rows_host, uint32_t* row_flags_host, uint64_t* table_host,
-                                   uint64_t* rw_host, uint32_t* rw_flags_host) {
-    ARG_TRY(s && s->kind == SESSION_CPA, "zk_copy_assign_read: bad arguments");
-    HIP_TRY(hipSetDevice(s->device));
+// the copies of a read, enqueued on the session's stream (the caller synchronises)
+static int cpa_read_enqueue(zk_session* s, uint64_t* rows_host, uint32_t* row_flags_host, uint64_t* table_host, uint64_t* rw_host, uint32_t* rw_flags_host) {
     const CpaArgs& a = s->cpa;
     if (rows_host) HIP_TRY(hipMemcpyAsync(rows_host, a.rows, (size_t)a.n_rows * CPA_ROW_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
     if (row_flags_host) HIP_TRY(hipMemcpyAsync(row_flags_host, a.row_flags, (size_t)a.n_rows * 4, hipMemcpyDeviceToHost, s->stream));
     if (table_host && s->cpa_n_table) HIP_TRY(hipMemcpyAsync(table_host, a.table, (size_t)s->cpa_n_table * CPA_TABLE_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
     if (rw_host && s->cpa_n_rw) HIP_TRY(hipMemcpyAsync(rw_host, a.rw, (size_t)s->cpa_n_rw * CPA_RW_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
     if (rw_flags_host && s->cpa_n_rw) HIP_TRY(hipMemcpyAsync(rw_flags_host, a.rw_flags, (size_t)s->cpa_n_rw * 4, hipMemcpyDeviceToHost, s->stream));
+    return 0;
+}
+extern "C" int zk_copy_assign_read(zk_session* s, uint64_t* rows_host, uint32_t* row_flags_host, uint64_t* table_host,
+                                   uint64_t* rw_host, uint32_t* rw_flags_host) {
+    ARG_TRY(s && s->kind == SESSION_CPA, "zk_copy_assign_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    if (int rc = cpa_read_enqueue(s, rows_host, row_flags_host, table_host, rw_host, rw_flags_host)) return rc;
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
 }
@@ -2272,6 +2280,224 @@ extern "C" int zk_copy_assign(const zk_copy_events* t, uint64_t* rows_out, uint3
     rc = zk_launch(s, nullptr);
     if (!rc) rc = zk_collect(s, result);
     if (!rc && !dev) rc = zk_copy_assign_read(s, rows_out, row_flags_out, table_out, rw_out, rw_flags_out);
+    zk_close(s);
+    return rc;
+}
+
+// ---- Copy-circuit witness assignment from raw sources (copy_sources.hpp, k_copy_sources.hip): the `data` array gathered on the device from
+// the code set, the calldata and the trace records, then the chain above over it
+#include "copy_sources_plan.hpp"
+#define CPS_ARGS_OK(t) ((t) && (t)->n_events > 0 && (t)->n_events < (1ull << 31) && (t)->events && (t)->src_ref &&                                  \
+                        ((t)->n_codes == 0 || (t)->code_offsets) && ((t)->n_code_bytes == 0 || (t)->code) && ((t)->n_txs == 0 || (t)->calldata_offsets) && \
+                        ((t)->trace.n_rw == 0 || ((t)->trace.head && (t)->trace.id && (t)->trace.addr && (t)->trace.val)))
+// a host view of `count` elements of an input array: the caller's (host callers), or a copy fetched on the calling thread's stream
+template <typename T>
+static int cps_host_view(const T* src, size_t count, bool dev, std::vector<T>& keep, const T** out) {
+    *out = src;
+    if (!dev || !src || !count) return 0;
+    keep.resize(count);
+    const hipStream_t st = t_stream ? t_stream : g_own_stream[t_device];
+    HIP_TRY(hipMemcpyAsync(keep.data(), src, count * sizeof(T), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    *out = keep.data();
+    return 0;
+}
+// Open a session over the sources: the integer inputs viewed on the host and planned, the trace's heads and counters checked on the
+// device (one verdict block read back).  check_only: the domain checks and the counts alone (the _sizes entry closes the session).
+static int cps_open(const zk_copy_sources* t, uint64_t* rows_dev, uint32_t* row_flags_dev, uint64_t* table_dev, uint64_t* rw_dev, uint32_t* rw_flags_dev,
+                    uint16_t* data_dev, uint32_t opts, bool check_only, u64* counts, zk_session** out) {
+    const char* const name = "zk_copy_assign_from_sources";
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    const zk_trace& tr = t->trace;
+    char msg[256];
+    if (int rc = trw_plan_counts(tr.n_rw, 0, tr.rw_base, tr.rw_counter != nullptr, msg, sizeof msg)) { g_err = msg; cps_retitle(name); return rc; }  // (before anything is read)
+    std::vector<u64> k_cells, k_code_off, k_cd_off;
+    std::vector<u32> k_flags, k_src, k_dst;
+    const u64 *cells, *code_off, *cd_off;
+    const u32 *flags, *src_ref, *dst_ref;
+    int rc = 0;
+    if ((rc = cps_host_view(t->events, (size_t)t->n_events * CPA_EV_NCELLS * 4, dev, k_cells, &cells))) return rc;
+    if ((rc = cps_host_view(t->flags, (size_t)t->n_events, dev, k_flags, &flags))) return rc;
+    if ((rc = cps_host_view(t->src_ref, (size_t)t->n_events, dev, k_src, &src_ref))) return rc;
+    if ((rc = cps_host_view(t->dst_ref, (size_t)t->n_events, dev, k_dst, &dst_ref))) return rc;
+    if ((rc = cps_host_view(t->code_offsets, t->n_codes ? (size_t)t->n_codes + 1 : 0, dev, k_code_off, &code_off))) return rc;
+    if ((rc = cps_host_view(t->calldata_offsets, t->n_txs ? (size_t)t->n_txs + 1 : 0, dev, k_cd_off, &cd_off))) return rc;
+    CpsPlan pl;
+    if ((rc = cps_plan(cells, flags, src_ref, dst_ref, t->n_events, code_off, t->n_codes, t->n_code_bytes, cd_off, t->n_txs, pl))) return rc;
+    const u64 n_cd_bytes = t->n_txs ? cd_off[t->n_txs] : 0;
+    ARG_TRY(n_cd_bytes == 0 || t->calldata, "zk_copy_assign_from_sources: calldata is null");
+    const u64 n = tr.n_rw, n_data = pl.data0[t->n_events];
+    zk_session* s = new zk_session();
+    s->kind = SESSION_CPS;
+    s->n = t->n_events;
+    s->cpa_n_table = pl.cpa.n_table;
+    s->cpa_n_rw = pl.cpa.n_rw;
+    CpaArgs& a = s->cpa;
+    CpsArgs& g = s->cps;
+    CpsCodeArgs& c = s->cps_code;
+    TrwArgs& w = s->trw;
+    memset(&a, 0, sizeof(a));
+    memset(&g, 0, sizeof(g));
+    memset(&c, 0, sizeof(c));
+    memset(&w, 0, sizeof(w));
+    const void* p = nullptr;
+    void* d = nullptr;
+    u64 v[TRW_V_WORDS], rh[4];
+    Fr r;
+    // the trace's heads and counters: checked as zk_evm_witness_from_trace_open checks them, the session keeps its own copies
+    if ((rc = stage(s, tr.head, (size_t)n * 4, dev, &p))) goto fail;
+    w.head_in = (const u32*)p;
+    if (tr.rw_counter && n) {
+        if ((rc = stage(s, tr.rw_counter, (size_t)n * 8, dev, &p))) goto fail;
+        w.ctr_in = (const u64*)p;
+    }
+    w.n_rw = n; w.rw_base = tr.rw_base;
+    if ((rc = dev_alloc(s, &d, (size_t)n * 4 + 4))) goto fail;
+    w.head = (u32*)d;
+    if (w.ctr_in) {
+        if ((rc = dev_alloc(s, &d, (size_t)n * 8))) goto fail;
+        w.ctr = (u64*)d;
+    }
+    if ((rc = dev_alloc(s, &d, TRW_V_WORDS * 8))) goto fail;
+    w.verdict = (u64*)d;
+    zk_launch_trace_witness_check(s->stream, w, false);  // (no pool offsets: the pool is not read, the verdict's pool word stays 0)
+    if (hipGetLastError() != hipSuccess) { rc = -2; g_err = "zk_copy_assign_from_sources: the open's check launch failed"; goto fail; }
+    if ((rc = d2h_now(s->stream, v, w.verdict, sizeof v))) goto fail;
+    if ((rc = trw_verdict_error(v, 0, msg, sizeof msg))) { g_err = msg; cps_retitle(name); goto fail; }
+    if (counts) { counts[0] = pl.cpa.n_rows; counts[1] = pl.cpa.n_table; counts[2] = pl.cpa.n_rw; counts[3] = n_data; }
+    if (check_only) {
+        zk_close(s);
+        return 0;
+    }
+    // the Copy assignment's arguments, as zk_copy_assign_open sets them, over the gathered array
+    if ((rc = stage(s, t->events, (size_t)t->n_events * CPA_EV_NCELLS * 32, dev, &p))) goto fail;
+    a.events = g.events = (const u64*)p;
+    if ((rc = stage(s, pl.cpa.ev.data(), pl.cpa.ev.size() * sizeof(CpaEvent), false, &p))) goto fail;
+    a.ev = g.ev = (const CpaEvent*)p;
+    if ((rc = stage(s, pl.cpa.row0.data(), pl.cpa.row0.size() * 8, false, &p))) goto fail;
+    a.row0 = (const u64*)p;
+    if ((rc = stage(s, pl.cpa.chunks.empty() ? nullptr : pl.cpa.chunks.data(), pl.cpa.chunks.size() * sizeof(CpaChunk), false, &p))) goto fail;
+    a.chunks = (const CpaChunk*)p;
+    a.n_events = g.n_events = t->n_events; a.n_rows = pl.cpa.n_rows; a.n_chunks = pl.cpa.chunks.size();
+    if (dev) {
+        if (fetch_small(s->stream, rh, t->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
+    } else {
+        memcpy(rh, t->randomness, 32);
+    }
+    for (int q = 0; q < 4; q++) { r.v[2 * q] = (u32)rh[q]; r.v[2 * q + 1] = (u32)(rh[q] >> 32); }
+    if ((rc = dev_alloc(s, &d, CPA_RPOW_ROWS * 32))) goto fail;
+    a.rpow = (const u64*)d;
+    zk_launch_cpa_rpow(s->stream, r, (u64*)d);
+    // the gather's: the plan's tables (the session's copies of everything a store or a load is indexed by) and the caller's bytes
+    if ((rc = stage(s, pl.sev.data(), pl.sev.size() * sizeof(CpsEv), false, &p))) goto fail;
+    g.sev = (const CpsEv*)p;
+    if ((rc = stage(s, pl.data0.data(), pl.data0.size() * 8, false, &p))) goto fail;
+    g.data0 = (const u64*)p;
+    g.n_data = n_data;
+    if ((rc = stage(s, t->code, (size_t)t->n_code_bytes, dev, &p))) goto fail;
+    g.code = c.code = (const uint8_t*)p;
+    if ((rc = stage(s, t->calldata, (size_t)n_cd_bytes, dev, &p))) goto fail;
+    g.calldata = (const uint8_t*)p;
+    if ((rc = stage(s, tr.id, (size_t)n * 8, dev, &p))) goto fail;
+    g.id = (const u64*)p;
+    if ((rc = stage(s, tr.addr, (size_t)n * 8, dev, &p))) goto fail;
+    g.addr = (const u64*)p;
+    if ((rc = stage(s, tr.val, (size_t)n * 8, dev, &p))) goto fail;
+    g.val = (const u64*)p;
+    g.head = w.head; g.ctr = w.ctr; g.n_rw = n; g.rw_base = tr.rw_base;
+    if (pl.any_code) {  // the is_code scan of the code set (every pass: the code bytes are the caller's)
+        if ((rc = stage(s, code_off, ((size_t)t->n_codes + 1) * 8, false, &p))) goto fail;
+        c.offsets = (const u64*)p;
+        if ((rc = stage(s, pl.chunk0.data(), pl.chunk0.size() * 4, false, &p))) goto fail;
+        c.chunk0 = (const u32*)p;
+        if ((rc = stage(s, pl.seg0.data(), pl.seg0.size() * 4, false, &p))) goto fail;
+        c.seg0 = (const u32*)p;
+        c.n_codes = (u32)t->n_codes; c.n_segs = (u32)pl.n_segs; c.n_chunks = pl.n_chunks;
+        if ((rc = dev_alloc(s, &d, (size_t)pl.n_chunks * CPS_MAP_STRIDE))) goto fail;
+        c.chunk_in = (uint8_t*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)pl.n_segs * CPS_MAP_STRIDE))) goto fail;
+        c.seg_map = (uint8_t*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)pl.n_segs))) goto fail;
+        c.seg_state = (uint8_t*)d;
+        if ((rc = dev_alloc(s, &d, (size_t)pl.n_chunks * 8))) goto fail;
+        c.mask = (u64*)d;
+        g.code_mask = c.mask;
+    }
+    // the plan vectors and the host views go out of scope with this call
+    if (hipStreamSynchronize(s->stream) != hipSuccess) { rc = -2; g_err = "zk_copy_assign_from_sources_open: upload failed"; goto fail; }
+    if ((rc = dev_alloc(s, &d, (size_t)t->n_events * 8))) goto fail;
+    g.ev_fail = (unsigned long long*)d;
+    g.data = data_dev;
+    if (!g.data && (rc = dev_alloc(s, (void**)&g.data, (size_t)n_data * 2))) goto fail;
+    a.data = g.data;
+    if ((rc = dev_alloc(s, &d, pl.cpa.chunks.size() * 32))) goto fail;
+    a.chunk_acc = (u64*)d;
+    if ((rc = dev_alloc(s, &d, pl.cpa.chunks.size() * 32))) goto fail;
+    a.chunk_in = (u64*)d;
+    if ((rc = dev_alloc(s, &d, (size_t)t->n_events * 32))) goto fail;
+    a.ev_rlc = (u64*)d;
+    a.rows = rows_dev; a.row_flags = row_flags_dev; a.table = table_dev; a.rw = rw_dev; a.rw_flags = rw_flags_dev;
+    if (!a.rows && (rc = dev_alloc(s, (void**)&a.rows, (size_t)pl.cpa.n_rows * CPA_ROW_NCELLS * 32))) goto fail;
+    if (!a.row_flags && (rc = dev_alloc(s, (void**)&a.row_flags, (size_t)pl.cpa.n_rows * 4))) goto fail;
+    if (!a.table && (rc = dev_alloc(s, (void**)&a.table, (size_t)pl.cpa.n_table * CPA_TABLE_NCELLS * 32))) goto fail;
+    if (!a.rw && (rc = dev_alloc(s, (void**)&a.rw, (size_t)pl.cpa.n_rw * CPA_RW_NCELLS * 32))) goto fail;
+    if (!a.rw_flags && (rc = dev_alloc(s, (void**)&a.rw_flags, (size_t)pl.cpa.n_rw * 4))) goto fail;
+    s->cps_data0.swap(pl.data0);
+    if ((rc = session_common_init(s))) goto fail;
+    *out = s;
+    return 0;
+fail:
+    zk_close(s);
+    return rc;
+}
+extern "C" int zk_copy_assign_from_sources_sizes(const zk_copy_sources* t, uint32_t opts, uint64_t* n_rows, uint64_t* n_table, uint64_t* n_rw,
+                                                 uint64_t* n_data) {
+    ARG_TRY(t_device >= 0, "zk_copy_assign_from_sources_sizes: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(CPS_ARGS_OK(t), "zk_copy_assign_from_sources_sizes: bad arguments");
+    u64 counts[4];
+    const int rc = cps_open(t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, opts, true, counts, nullptr);
+    if (rc) return rc;
+    if (n_rows) *n_rows = counts[0];
+    if (n_table) *n_table = counts[1];
+    if (n_rw) *n_rw = counts[2];
+    if (n_data) *n_data = counts[3];
+    return 0;
+}
+extern "C" int zk_copy_assign_from_sources_open(const zk_copy_sources* t, uint64_t* rows_dev, uint32_t* row_flags_dev, uint64_t* table_dev,
+                                                uint64_t* rw_dev, uint32_t* rw_flags_dev, uint16_t* data_dev, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_copy_assign_from_sources_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(CPS_ARGS_OK(t) && out && t->randomness, "zk_copy_assign_from_sources_open: bad arguments");
+    ARG_TRY((opts & ZK_OPT_DEVICE_PTRS) || (!rows_dev && !row_flags_dev && !table_dev && !rw_dev && !rw_flags_dev && !data_dev),
+            "zk_copy_assign_from_sources_open: output buffers need ZK_OPT_DEVICE_PTRS");
+    return cps_open(t, rows_dev, row_flags_dev, table_dev, rw_dev, rw_flags_dev, data_dev, opts, false, nullptr, out);
+}
+extern "C" int zk_copy_assign_from_sources_read(zk_session* s, uint64_t* rows_host, uint32_t* row_flags_host, uint64_t* table_host,
+                                                uint64_t* rw_host, uint32_t* rw_flags_host, uint16_t* data_host, uint64_t* data_offsets_host) {
+    ARG_TRY(s && s->kind == SESSION_CPS, "zk_copy_assign_from_sources_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    if (int rc = cpa_read_enqueue(s, rows_host, row_flags_host, table_host, rw_host, rw_flags_host)) return rc;
+    if (data_host && s->cps.n_data) HIP_TRY(hipMemcpyAsync(data_host, s->cps.data, (size_t)s->cps.n_data * 2, hipMemcpyDeviceToHost, s->stream));
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    if (data_offsets_host) memcpy(data_offsets_host, s->cps_data0.data(), s->cps_data0.size() * 8);
+    return 0;
+}
+extern "C" int zk_copy_assign_from_sources(const zk_copy_sources* t, uint64_t* rows_out, uint32_t* row_flags_out, uint64_t* table_out,
+                                           uint64_t* rw_out, uint32_t* rw_flags_out, uint16_t* data_out, uint64_t* data_offsets_out,
+                                           uint32_t opts, uint32_t* status_out, zk_result* result) {
+    ARG_TRY(result && rows_out && row_flags_out, "zk_copy_assign_from_sources: null output");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    int rc = zk_copy_assign_from_sources_open(t, dev ? rows_out : nullptr, dev ? row_flags_out : nullptr, dev ? table_out : nullptr,
+                                              dev ? rw_out : nullptr, dev ? rw_flags_out : nullptr, dev ? data_out : nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, dev ? status_out : nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && !dev && status_out) rc = zk_read_status(s, status_out);
+    // (data_offsets_out is host arithmetic over the events: a HOST array of n_events + 1 entries in either mode)
+    if (!rc) rc = dev ? zk_copy_assign_from_sources_read(s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, data_offsets_out)
+                      : zk_copy_assign_from_sources_read(s, rows_out, row_flags_out, table_out, rw_out, rw_flags_out, data_out, data_offsets_out);
     zk_close(s);
     return rc;
 }
@@ -2911,6 +3137,10 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     case SESSION_SGA: zk_launch_sig_assign(s->stream, s->sga, status, s->d_tally); break;
     case SESSION_PICOPY: zk_launch_pi_copy(s->stream, s->picopy, status, tally); break;
     case SESSION_CPA: zk_launch_copy_assign(s->stream, s->cpa, status, s->d_tally); break;
+    case SESSION_CPS:  // the status and the tally are the gather's, per event; the Copy assignment over the gathered data has no failing case
+        zk_launch_copy_sources(s->stream, s->cps, s->cps_code, status, s->d_tally);
+        zk_launch_copy_assign(s->stream, s->cpa, nullptr, s->d_tally);
+        break;
     case SESSION_EXA: zk_launch_exp_assign(s->stream, s->exa, status, s->d_tally); break;
     case SESSION_PIA: {
         // the digest (one message: a serial sponge) runs on the device's side stream beside the scans and the row writer; only the patch

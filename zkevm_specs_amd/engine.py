@@ -702,6 +702,102 @@ def open_copy_assign(events, flags, data, offsets, randomness, rows_dev=None, ro
     return s
 
 
+# ---- Copy-circuit witness assignment from raw sources (zk_copy_assign_from_sources*) ---------------------------------------------------
+COPY_SOURCE_KEYS = ("code", "code_offsets", "calldata", "calldata_offsets")
+_COPY_TRACE_KEYS = ("head", "id", "addr", "val", "rw_counter")
+
+
+def _copy_sources_args(events, flags, src_ref, dst_ref, sources, randomness, outs=(None,) * 6):
+    """zk_copy_assign_from_sources* -> (ZkCopySources, opts, kept arrays).  `sources` = dict(code uint8[], code_offsets uint64[n_codes + 1],
+    calldata uint8[], calldata_offsets uint64[n_txs + 1], trace = the RW half of a records dict (head, id, addr, val, rw_counter or None
+    with rw_base; see _evm_witness_from_trace_args) or None), each optional: a block without contract code, calldata or memory copies
+    leaves it out.  outs: a session's (rows_dev, row_flags_dev, table_dev, rw_dev, rw_flags_dev, data_dev), prepared with the inputs."""
+    randomness = _randomness_cells(randomness, events)
+    n = int(events.shape[0])
+    _expect(events, "copy events", 8, (None, 12, 4))
+    _expect(flags, "copy event flags", 4, (n,))
+    _expect(src_ref, "src_ref", 4, (n,))
+    _expect(dst_ref, "dst_ref", 4, (n,))
+    if src_ref is None:
+        raise ValueError("src_ref: missing")
+    _expect(sources.get("code"), "code", 1, (None,))
+    _expect(sources.get("calldata"), "calldata", 1, (None,))
+    _expect(sources.get("code_offsets"), "code_offsets", 8, (None,))
+    _expect(sources.get("calldata_offsets"), "calldata_offsets", 8, (None,))
+    trace = sources.get("trace") or {}
+    n_rw = _rows(trace.get("head"))
+    _expect(trace.get("head"), "head", 4, (None,))
+    for name in _COPY_TRACE_KEYS[1:]:
+        _expect(trace.get(name), name, 8, (n_rw,))
+        if n_rw and name != "rw_counter" and trace.get(name) is None:
+            raise ValueError(f"{name}: missing")
+    n_code_bytes, n_codes = _rows(sources.get("code")), max(_rows(sources.get("code_offsets")) - 1, 0)
+    n_txs = max(_rows(sources.get("calldata_offsets")) - 1, 0)
+    ins = [events, flags, src_ref, dst_ref, randomness, *(sources.get(k) for k in COPY_SOURCE_KEYS), *(trace.get(k) for k in _COPY_TRACE_KEYS)]
+    keep, opts = _prep(ins + list(outs), outputs=range(len(ins), len(ins) + len(outs)))
+    if any(o is not None for o in outs) and not opts:
+        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
+    k = keep
+    tr = _lib.ZkTrace(ptr(k[9], n_rw), ptr(k[10], n_rw), ptr(k[11], n_rw), ptr(k[12], n_rw), None, ptr(k[13], n_rw), int(trace.get("rw_base", 1)),
+                      n_rw, None, 0, None, 0)
+    t = _lib.ZkCopySources(ptr(k[0]), ptr(k[1]), n, ptr(k[2]), ptr(k[3]), ptr(k[4]), ptr(k[5], n_code_bytes), n_code_bytes,
+                           ptr(k[6], n_codes), n_codes, ptr(k[7], _rows(k[7])), ptr(k[8], n_txs), n_txs, tr)
+    return t, opts, keep
+
+
+def copy_assign_from_sources_sizes(events, flags, src_ref, dst_ref, sources, device=None, _prepared=None):
+    """(n_rows, n_table, n_rw, n_data) the events expand to over `sources`; raises EngineError (rc = _lib.ERR_CPS_* / ERR_TRC_*) outside
+    the domain"""
+    lib = _lib.init(device)
+    t, opts, keep = _prepared or _copy_sources_args(events, flags, src_ref, dst_ref, sources, None)
+    c = [ctypes.c_uint64() for _ in range(4)]
+    check(lib.zk_copy_assign_from_sources_sizes(ctypes.byref(t), opts, *(ctypes.byref(x) for x in c)), "zk_copy_assign_from_sources_sizes", lib)
+    return tuple(int(x.value) for x in c)
+
+
+def _check_copy_sources_outs(outs, sizes):
+    n_rows, n_table, n_rw, n_data = sizes
+    shapes = ((20, n_rows, 4), (n_rows,), (n_table, 14, 4), (n_rw, 14, 4), (n_rw,), (n_data,))
+    for o, name, size, shape in zip(outs, ("rows_dev", "row_flags_dev", "table_dev", "rw_dev", "rw_flags_dev", "data_dev"), (8, 4, 8, 8, 4, 2), shapes):
+        _expect(o, name, size, shape)
+
+
+class CopySourcesSession(Session):
+    """zk_copy_assign_from_sources_open: launch() / collect() / read_status() over the EVENTS (status per event); read() -> the Copy
+    assignment's outputs and the gathered data"""
+
+    def read(self):
+        """-> (rows uint64[20, n, 4], row_flags uint32[n], table uint64[m, 14, 4], rw uint64[k, 14, 4], rw_flags uint32[k], data uint16[d],
+        data_offsets uint64[n_events + 1]) on the host"""
+        n_rows, n_table, n_rw, n_data = self.sizes
+        rows, rf = np.empty((20, n_rows, 4), dtype=np.uint64), np.empty(n_rows, dtype=np.uint32)
+        table = np.empty((n_table, 14, 4), dtype=np.uint64)
+        rw, rwf = np.empty((n_rw, 14, 4), dtype=np.uint64), np.empty(n_rw, dtype=np.uint32)
+        data, offsets = np.empty(n_data, dtype=np.uint16), np.empty(self.n + 1, dtype=np.uint64)
+        check(self._lib.zk_copy_assign_from_sources_read(self._h, ptr(rows, n_rows), ptr(rf, n_rows), ptr(table, n_table), ptr(rw, n_rw), ptr(rwf, n_rw),
+                                                         ptr(data, n_data), ptr(offsets)), "zk_copy_assign_from_sources_read", self._lib)
+        return rows, rf, table, rw, rwf, data, offsets
+
+
+def open_copy_assign_from_sources(events, flags, src_ref, dst_ref, sources, randomness, rows_dev=None, row_flags_dev=None, table_dev=None,
+                                  rw_dev=None, rw_flags_dev=None, data_dev=None, device=None):
+    """open_copy_assign without its `data` array: events / flags as there, src_ref / dst_ref uint32[n] (dst_ref None when no event writes a
+    code) and `sources` (see _copy_sources_args) -> CopySourcesSession over the n events.  The source bytes are gathered on the device
+    from the code set, the calldata and the trace records, then the Copy assignment runs over them: its outputs are open_copy_assign's
+    for the gathered data.  numpy inputs are staged to HBM; torch CUDA tensors are used in place (code, calldata and the trace's id /
+    addr / val are read by every pass) and the optional *_dev tensors (sized with copy_assign_from_sources_sizes) receive the outputs."""
+    lib = _lib.init(device)
+    outs = (rows_dev, row_flags_dev, table_dev, rw_dev, rw_flags_dev, data_dev)
+    prepared = _copy_sources_args(events, flags, src_ref, dst_ref, sources, randomness, outs)
+    sizes = copy_assign_from_sources_sizes(events, flags, src_ref, dst_ref, sources, device, _prepared=prepared)
+    _check_copy_sources_outs(outs, sizes)
+    t, opts, keep = prepared
+    s = _open(lib, lib.zk_copy_assign_from_sources_open, int(events.shape[0]), (keep, t), ctypes.byref(t), *(ptr(x) for x in keep[-6:]), opts,
+              cls=CopySourcesSession)
+    s.sizes = sizes
+    return s
+
+
 ECDSA_LAYOUT_PACKED = 0  # uint8[n, 5, 32]: pk_x LE, pk_y LE, msg_hash BE, sig_r LE, sig_s LE
 ECDSA_LAYOUT_TX_UNITS = 1   # uint8[n, 9, 32]: the Tx units' byte rows (open_sign's wire["bytes"]; msg_hash little-endian)
 ECDSA_LAYOUT_SIG_UNITS = 2  # the Sig units' byte rows (msg_hash big-endian; v = meta[:, 3])

@@ -219,6 +219,28 @@ def copy_assign(events, flags, data, offsets, randomness, device=None):
     return Result(r), rows, rf, table, rw, rwf
 
 
+def copy_assign_from_sources(events, flags, src_ref, dst_ref, sources, randomness, device=None):
+    """zk_copy_assign_from_sources over copy events, their refs and `sources` (engine._copy_sources_args) -> (Result over the EVENTS,
+    status uint32[n_events], rows, row_flags, table, rw, rw_flags as copy_assign returns them, data uint16[n_data], data_offsets
+    uint64[n_events + 1])"""
+    lib = _lib.init(device)
+    src = {k: _host(sources.get(k)) for k in engine.COPY_SOURCE_KEYS}
+    tr = sources.get("trace")
+    src["trace"] = None if tr is None else {k: (_host(v) if hasattr(v, "shape") else v) for k, v in tr.items()}
+    prepared = engine._copy_sources_args(_host(events), _host(flags, np.uint32), _host(src_ref, np.uint32), _host(dst_ref, np.uint32), src, randomness)
+    n_rows, n_table, n_rw, n_data = engine.copy_assign_from_sources_sizes(None, None, None, None, None, device, _prepared=prepared)
+    t, opts, keep = prepared
+    n = int(t.n_events)
+    rows, rf = np.zeros((20, n_rows, 4), dtype=np.uint64), np.zeros(n_rows + 1, dtype=np.uint32)
+    table = np.zeros((n_table, 14, 4), dtype=np.uint64)
+    rw, rwf = np.zeros((n_rw, 14, 4), dtype=np.uint64), np.zeros(n_rw, dtype=np.uint32)
+    data, offsets, status, r = np.zeros(n_data, dtype=np.uint16), np.zeros(n + 1, dtype=np.uint64), np.zeros(n, dtype=np.uint32), ZkResult()
+    rows_buf = rows if n_rows else np.zeros((20, 1, 4), dtype=np.uint64)  # (events that copy nothing: the entry still wants its row pointers)
+    check(lib.zk_copy_assign_from_sources(ctypes.byref(t), ptr(rows_buf), ptr(rf), ptr(table, n_table), ptr(rw, n_rw), ptr(rwf, n_rw), ptr(data, n_data),
+                                          ptr(offsets), opts, ptr(status), ctypes.byref(r)), "zk_copy_assign_from_sources", lib)
+    return Result(r), status, rows, rf[:n_rows], table, rw, rwf, data, offsets
+
+
 def exp_assign(events, max_exp_steps=0, device=None):
     """zk_exp_assign over EXP events uint64[n, 5, 4] -> (Result or None, rows uint64[21, n_rows, 4], table uint64[n_table, 11, 4]);
     events that expand to no row at all give empty arrays without a pass (Result None).  The host buffers of a one-shot have to be
