@@ -6,6 +6,7 @@
 #include <string.h>
 #include <stdlib.h>
 #include <chrono>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -857,14 +858,82 @@ static int stage(zk_session* s, const void* src, size_t bytes, bool device_ptrs,
     *out = d;
     return 0;
 }
+
+// ---- what every session open, read and one-shot is written with ---------------------------------------------------------------------
+// A session under construction: every early return of its open closes it (zk_close waits for the session's stream first, so a host
+// container that a staged upload reads must be declared BEFORE the guard — it is then destroyed after the close).
+struct SessionCloser { void operator()(zk_session* s) const { zk_close(s); } };
+typedef std::unique_ptr<zk_session, SessionCloser> SessionGuard;
+#define RC_TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
+// ARG_TRY's twin for what the device or the runtime refuses (-2), reported under the entry's own text
+#define DEV_TRY(cond, msg)  \
+    do {                    \
+        if (!(cond)) {      \
+            g_err = msg;    \
+            return -2;      \
+        }                   \
+    } while (0)
+// a buffer the session owns
+template <typename T>
+static int dev_buf(zk_session* s, T*& out, size_t bytes) {
+    void* d = nullptr;
+    RC_TRY(dev_alloc(s, &d, bytes));
+    out = (T*)d;
+    return 0;
+}
+// an input on the device: staged (host callers), or the caller's own pointer
+template <typename T>
+static int stage_in(zk_session* s, const T*& out, const void* src, size_t bytes, bool device_ptrs) {
+    const void* p = nullptr;
+    RC_TRY(stage(s, src, bytes, device_ptrs, &p));
+    out = (const T*)p;
+    return 0;
+}
+// an output: the caller's device buffer if it gave one, else the session's own
+template <typename T, typename U>
+static int out_buf(zk_session* s, T*& out, U* given, size_t bytes) {
+    if (!given) return dev_buf(s, out, bytes);
+    out = (T*)given;
+    return 0;
+}
+// a few words the open needs on the host: read back from a device caller (fetch_small), copied from a host caller
+static int fetch_small(hipStream_t st, void* dst, const void* src, size_t bytes);
+static int host_words(zk_session* s, void* dst, const void* src, size_t bytes, bool device_ptrs, const char* what) {
+    if (!device_ptrs) memcpy(dst, src, bytes);
+    else DEV_TRY(!fetch_small(s->stream, dst, src, bytes), std::string(what) + " download failed");
+    return 0;
+}
+static Fr fr_from_words(const u64* w) {  // (fr_load is device code)
+    Fr r;
+    for (int k = 0; k < 4; k++) { r.v[2 * k] = (u32)w[k]; r.v[2 * k + 1] = (u32)(w[k] >> 32); }
+    return r;
+}
+// the caller's output wire, or one of null members (no out_dev: every output is the session's own)
+template <typename W>
+static W wire_or_nulls(const W* w) { return w ? *w : W{}; }
+// one array of a read: enqueued on the session's stream when the caller wants it and it is not empty (the caller synchronises)
+static int d2h_out(zk_session* s, void* dst, const void* src, size_t bytes) {
+    if (dst && bytes) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s->stream));
+    return 0;
+}
+// One pass of a freshly opened session with its result and statuses (a device caller's statuses are written in place); the session
+// stays open for the entry's own read.  one_shot closes it.
+static int one_shot_pass(zk_session* s, bool dev, uint32_t* status_out, zk_result* result) {
+    RC_TRY(zk_launch(s, (dev && status_out) ? status_out : nullptr));
+    RC_TRY(zk_collect(s, result));
+    if (status_out && !dev) RC_TRY(zk_read_status(s, status_out));
+    return 0;
+}
+static int one_shot(zk_session* s, bool dev, uint32_t* status_out, zk_result* result) {
+    SessionGuard guard(s);
+    return one_shot_pass(s, dev, status_out, result);
+}
+
 // The powers of a keccak randomness (its four words, on the host) on the device: KT_RPOW_ROWS rows (keccak_table.hpp)
 static int keccak_rpow_open(zk_session* s, const u64* rand, const u64** out) {
     u64* d_rpow = nullptr;
-    const int rc = dev_alloc(s, (void**)&d_rpow, KT_RPOW_ROWS * 4 * sizeof(u64));
-    if (rc) return rc;
-    Fr r;  // (fr_load is device code)
-    for (int k = 0; k < 4; k++) { r.v[2 * k] = (u32)rand[k]; r.v[2 * k + 1] = (u32)(rand[k] >> 32); }
-    zk_launch_keccak_rpow(s->stream, r, d_rpow);
+    RC_TRY(dev_buf(s, d_rpow, KT_RPOW_ROWS * 4 * sizeof(u64)));
+    zk_launch_keccak_rpow(s->stream, fr_from_words(rand), d_rpow);
     *out = d_rpow;
     return 0;
 }
@@ -887,7 +956,7 @@ static int secp_lanes_open(zk_session* s, u64 n, const char* entry, SecpLanes& l
     l.lanes_per_sig = f.lanes_per_sig;
     l.qtab_lanes = f.qtab_lanes;
     l.first = 0;
-    return dev_alloc(s, (void**)&l.qtab, (size_t)l.qtab_lanes * 15 * 24 * sizeof(u32));
+    return dev_buf(s, l.qtab, (size_t)l.qtab_lanes * 15 * 24 * sizeof(u32));
 }
 
 // Small device -> host read on the SESSION's stream.  (A plain hipMemcpy runs on the legacy default stream and waits for every
@@ -915,8 +984,7 @@ static int build_index(zk_session* s, ZkTable& t, bool mpt_fingerprints = false,
     u32 cap = 16;
     while (cap < 2 * t.n + 2) cap <<= 1;
     u32* slots = nullptr;
-    int rc = dev_alloc(s, (void**)&slots, (size_t)cap * sizeof(u32));
-    if (rc) return rc;
+    RC_TRY(dev_buf(s, slots, (size_t)cap * sizeof(u32)));
     t.mask = cap - 1;
     t.slots = slots;
     if (unless_dense) hipLaunchKernelGGL(slots_fill_unless_dense_kernel, dim3((cap + 255) / 256), dim3(256), 0, s->stream, slots, cap, unless_dense);
@@ -928,14 +996,11 @@ static int build_index(zk_session* s, ZkTable& t, bool mpt_fingerprints = false,
 }
 
 static int session_common_init(zk_session* s) {
-    int rc = 0;
     if (s->rekey_tally) s->d_tally = s->rekey_tally;  // (rekey_setup: in front of the sweep's error word)
-    else rc = dev_alloc(s, (void**)&s->d_tally, 2 * sizeof(ZkTally));
-    if (rc) return rc;
+    else RC_TRY(dev_buf(s, s->d_tally, 2 * sizeof(ZkTally)));
     hipLaunchKernelGGL(tally_reset_kernel, dim3(1), dim3(2), 0, s->stream, s->d_tally, (u32*)nullptr);
     s->tally_last = s->d_tally;
-    rc = dev_alloc(s, (void**)&s->d_status, (size_t)s->n * sizeof(u32));
-    if (rc) return rc;
+    RC_TRY(dev_buf(s, s->d_status, (size_t)s->n * sizeof(u32)));
     HIP_TRY(hipMemsetAsync(s->d_status, 0, (size_t)s->n * sizeof(u32), s->stream));
     return 0;
 }
@@ -969,31 +1034,24 @@ extern "C" int zk_state_open(const uint64_t* rows, const uint32_t* flags, uint64
     ARG_TRY(n_mpt < (1ull << 31), "zk_state_open: MPT table too large");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     const bool compact = opts & ZK_OPT_STATE_COMPACT;
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_STATE;
     s->n = n;
-    int rc = 0;
-    const void* p = nullptr;
-    if ((rc = stage(s, rows, (size_t)n * (compact ? 15 : ST_NCELLS) * 32, dev, &p))) goto fail;
-    s->state.rows.cells = (const u64*)p;
+    RC_TRY(stage_in(s, s->state.rows.cells, rows, (size_t)n * (compact ? 15 : ST_NCELLS) * 32, dev));
     s->state.rows.skip = compact ? 42u : 0u;
-    if ((rc = stage(s, flags, (size_t)n * 4, dev, &p))) goto fail;
-    s->state.rows.flags = (const u32*)p;
+    RC_TRY(stage_in(s, s->state.rows.flags, flags, (size_t)n * 4, dev));
     s->state.rows.n = n;
     s->state.eval_lo = 0;
     s->state.eval_hi = n;
-    if ((rc = stage(s, mpt, (size_t)n_mpt * MPT_NCELLS * 32, dev, &p))) goto fail;
-    s->state.mpt.cells = (const u64*)p;
+    RC_TRY(stage_in(s, s->state.mpt.cells, mpt, (size_t)n_mpt * MPT_NCELLS * 32, dev));
     s->state.mpt.flags = nullptr;
     s->state.mpt.n = (u32)n_mpt;
     s->state.mpt.ncells = MPT_NCELLS;
-    if ((rc = build_index<state_mpt_key_hash>(s, s->state.mpt, /*mpt_fingerprints=*/true))) goto fail;
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(build_index<state_mpt_key_hash>(s, s->state.mpt, /*mpt_fingerprints=*/true));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 
 static int table_stage(zk_session* s, ZkTable& t, const uint64_t* cells, const uint32_t* flags, uint64_t n,
@@ -1411,36 +1469,25 @@ extern "C" int zk_bytecode_open(const uint64_t* rows, uint64_t n, const uint64_t
     HIP_TRY(hipSetDevice(t_device));
     ARG_TRY(out && rows && randomness && n > 0 && n < (1ull << 32) && n_keccak < (1ull << 31), "zk_bytecode_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_BYTECODE;
     s->n = n;
-    int rc = 0;
-    const void* p = nullptr;
-    u64 rh[4];
-    if ((rc = stage(s, rows, (size_t)n * BC_NCELLS * 32, dev, &p))) goto fail;
-    s->bytecode.rows.cells = (const u64*)p;
+    RC_TRY(stage_in(s, s->bytecode.rows.cells, rows, (size_t)n * BC_NCELLS * 32, dev));
     s->bytecode.rows.flags = nullptr;
     s->bytecode.rows.n = n;
-    if ((rc = table_stage(s, s->bytecode.keccak, keccak, nullptr, n_keccak, KECCAK_NCELLS, dev))) goto fail;
-    if ((rc = build_index<keccak_key_hash>(s, s->bytecode.keccak))) goto fail;
-    if (dev) {
-        if (fetch_small(s->stream, rh, randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
-    } else {
-        memcpy(rh, randomness, 32);
-    }
-    for (int k = 0; k < 4; k++) { s->bytecode.r.v[2 * k] = (u32)rh[k]; s->bytecode.r.v[2 * k + 1] = (u32)(rh[k] >> 32); }
-    {
-        u64* d_rm = nullptr;
-        if ((rc = dev_alloc(s, (void**)&d_rm, 32))) goto fail;
-        zk_launch_fr_to_mont(s->stream, s->bytecode.r, d_rm);
-        s->bytecode.r_mont = d_rm;
-    }
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(table_stage(s, s->bytecode.keccak, keccak, nullptr, n_keccak, KECCAK_NCELLS, dev));
+    RC_TRY(build_index<keccak_key_hash>(s, s->bytecode.keccak));
+    u64 rh[4];
+    RC_TRY(host_words(s, rh, randomness, 32, dev, "randomness"));
+    s->bytecode.r = fr_from_words(rh);
+    u64* d_rm = nullptr;
+    RC_TRY(dev_buf(s, d_rm, 32));
+    zk_launch_fr_to_mont(s->stream, s->bytecode.r, d_rm);
+    s->bytecode.r_mont = d_rm;
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 
 extern "C" int zk_exp_open(const uint64_t* rows, uint64_t n, uint32_t opts, zk_session** out) {
@@ -1448,28 +1495,22 @@ extern "C" int zk_exp_open(const uint64_t* rows, uint64_t n, uint32_t opts, zk_s
     HIP_TRY(hipSetDevice(t_device));
     ARG_TRY(out && rows && n > 0 && n < (1ull << 32), "zk_exp_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_EXP;
     s->n = n;
-    int rc = 0;
-    const void* p = nullptr;
-    if ((rc = stage(s, rows, (size_t)n * EX_NCELLS * 32, dev, &p))) goto fail;
-    s->exp.rows.cells = (const u64*)p;
+    RC_TRY(stage_in(s, s->exp.rows.cells, rows, (size_t)n * EX_NCELLS * 32, dev));
     s->exp.rows.flags = nullptr;
     s->exp.rows.n = n;
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 
 // dense RW-index metadata (see ZkRwMeta), verified on the device
 static int build_rw_meta(zk_session* s, const ZkTable& rw, const ZkRwMeta** out) {
     ZkRwMeta* d_meta = nullptr;
-    int rc = dev_alloc(s, (void**)&d_meta, sizeof(ZkRwMeta));
-    if (rc) return rc;
+    RC_TRY(dev_buf(s, d_meta, sizeof(ZkRwMeta)));
     static const ZkRwMeta init_dense = {1u, 0u, 0ull}, init_empty = {0u, 0u, 0ull};  // static storage: no wait for the copy
     HIP_TRY(hipMemcpyAsync(d_meta, rw.n ? &init_dense : &init_empty, sizeof(ZkRwMeta), hipMemcpyHostToDevice, s->stream));
     if (rw.n) hipLaunchKernelGGL(rw_dense_check_kernel, dim3((rw.n + 255) / 256), dim3(256), 0, s->stream, rw, d_meta);
@@ -1483,40 +1524,30 @@ extern "C" int zk_copy_open(const zk_copy_tables* t, uint32_t opts, zk_session**
     ARG_TRY(t && out && t->rows && t->randomness && t->n_rows > 0 && t->n_rows < (1ull << 32), "zk_copy_open: bad arguments");
     ARG_TRY(t->n_rw < (1ull << 31) && t->n_bytecode < (1ull << 31) && t->n_tx < (1ull << 31), "zk_copy_open: table too large");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_COPY;
     s->n = t->n_rows;
-    int rc = 0;
-    const void* p = nullptr;
-    u64 rh[4];
-    if ((rc = stage(s, t->rows, (size_t)t->n_rows * CP_NCELLS * 32, dev, &p))) goto fail;
-    s->copy.rows.cells = (const u64*)p;
-    if ((rc = stage(s, t->row_flags, (size_t)t->n_rows * 4, dev, &p))) goto fail;
-    s->copy.rows.flags = t->row_flags ? (const u32*)p : nullptr;
+    RC_TRY(stage_in(s, s->copy.rows.cells, t->rows, (size_t)t->n_rows * CP_NCELLS * 32, dev));
+    RC_TRY(stage_in(s, s->copy.rows.flags, t->row_flags, (size_t)t->n_rows * 4, dev));
+    if (!t->row_flags) s->copy.rows.flags = nullptr;
     s->copy.rows.n = t->n_rows;
-    if ((rc = table_stage(s, s->copy.rw, t->rw, t->rw_flags, t->n_rw, RW_NCELLS, dev))) goto fail;
-    if ((rc = table_stage(s, s->copy.bytecode, t->bytecode, nullptr, t->n_bytecode, BYTECODE_NCELLS, dev))) goto fail;
-    if ((rc = table_stage(s, s->copy.tx, t->tx, t->tx_flags, t->n_tx, TX_NCELLS, dev))) goto fail;
+    RC_TRY(table_stage(s, s->copy.rw, t->rw, t->rw_flags, t->n_rw, RW_NCELLS, dev));
+    RC_TRY(table_stage(s, s->copy.bytecode, t->bytecode, nullptr, t->n_bytecode, BYTECODE_NCELLS, dev));
+    RC_TRY(table_stage(s, s->copy.tx, t->tx, t->tx_flags, t->n_tx, TX_NCELLS, dev));
     s->copy.rw_meta = nullptr;
-    if (!(opts & ZK_OPT_GENERIC_INDEX) && (rc = build_rw_meta(s, s->copy.rw, &s->copy.rw_meta))) goto fail;
-    if ((rc = build_index<rw_key_hash>(s, s->copy.rw, false, s->copy.rw_meta))) goto fail;  // (neither filled nor built when the rows are dense)
-    if ((rc = build_index<bc_key_hash>(s, s->copy.bytecode))) goto fail;
-    if ((rc = build_index<tx_key_hash>(s, s->copy.tx))) goto fail;
-    if (dev) {
-        if (fetch_small(s->stream, rh, t->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
-    } else {
-        memcpy(rh, t->randomness, 32);
-    }
-    for (int k = 0; k < 4; k++) { s->copy.r.v[2 * k] = (u32)rh[k]; s->copy.r.v[2 * k + 1] = (u32)(rh[k] >> 32); }
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    if (!(opts & ZK_OPT_GENERIC_INDEX)) RC_TRY(build_rw_meta(s, s->copy.rw, &s->copy.rw_meta));
+    RC_TRY(build_index<rw_key_hash>(s, s->copy.rw, false, s->copy.rw_meta));  // (neither filled nor built when the rows are dense)
+    RC_TRY(build_index<bc_key_hash>(s, s->copy.bytecode));
+    RC_TRY(build_index<tx_key_hash>(s, s->copy.tx));
+    u64 rh[4];
+    RC_TRY(host_words(s, rh, t->randomness, 32, dev, "randomness"));
+    s->copy.r = fr_from_words(rh);
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 
-static int one_shot(zk_session* s, bool dev, uint32_t* status_out, zk_result* result);
 extern "C" int zk_sign_open(const zk_sign_units* t, uint32_t opts, zk_session** out) {
     ARG_TRY(t_device >= 0, "zk_sign_open: call zk_init first");
     HIP_TRY(hipSetDevice(t_device));
@@ -1524,50 +1555,36 @@ extern "C" int zk_sign_open(const zk_sign_units* t, uint32_t opts, zk_session** 
             "zk_sign_open: bad arguments");
     ARG_TRY(t->n_keccak < (1ull << 31) && t->n_tx_rows < (1ull << 32), "zk_sign_open: table too large");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_SIGN;
     s->n = t->n_units;
-    int rc = 0;
-    const void* p = nullptr;
-    u64 rh[4];
-    if ((rc = stage(s, t->bytes, (size_t)t->n_units * SG_NBYTES_ROWS * 32, dev, &p))) goto fail;
-    s->sign.bytes = (const uint8_t*)p;
-    if ((rc = stage(s, t->cells, (size_t)t->n_units * SG_NCELLS * 32, dev, &p))) goto fail;
-    s->sign.cells.cells = (const u64*)p;
+    RC_TRY(stage_in(s, s->sign.bytes, t->bytes, (size_t)t->n_units * SG_NBYTES_ROWS * 32, dev));
+    RC_TRY(stage_in(s, s->sign.cells.cells, t->cells, (size_t)t->n_units * SG_NCELLS * 32, dev));
     s->sign.cells.flags = nullptr;
     s->sign.cells.n = t->n_units;
-    if ((rc = stage(s, t->meta, (size_t)t->n_units * 16, dev, &p))) goto fail;
-    s->sign.meta = (const u32*)p;
-    if ((rc = table_stage(s, s->sign.keccak, t->keccak, nullptr, t->n_keccak, KECCAK_NCELLS, dev))) goto fail;
-    if ((rc = build_index<keccak_key_hash>(s, s->sign.keccak))) goto fail;
-    if ((rc = table_stage(s, s->sign.tx_rows, t->tx_rows, t->tx_flags, t->n_tx_rows, TX_NCELLS, dev))) goto fail;
+    RC_TRY(stage_in(s, s->sign.meta, t->meta, (size_t)t->n_units * 16, dev));
+    RC_TRY(table_stage(s, s->sign.keccak, t->keccak, nullptr, t->n_keccak, KECCAK_NCELLS, dev));
+    RC_TRY(build_index<keccak_key_hash>(s, s->sign.keccak));
+    RC_TRY(table_stage(s, s->sign.tx_rows, t->tx_rows, t->tx_flags, t->n_tx_rows, TX_NCELLS, dev));
     s->sign.tx_rows.slots = nullptr;
     s->sign.tx_rows.mask = 0;
     s->sign.is_sig = t->is_sig ? 1u : 0u;
-    if (dev) {
-        if (fetch_small(s->stream, rh, t->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
-    } else {
-        memcpy(rh, t->randomness, 32);
-    }
-    for (int k = 0; k < 4; k++) { s->sign.r.v[2 * k] = (u32)rh[k]; s->sign.r.v[2 * k + 1] = (u32)(rh[k] >> 32); }
-    {
-        u64* d_rpow = nullptr;
-        if ((rc = dev_alloc(s, (void**)&d_rpow, 64 * 4 * sizeof(u64)))) goto fail;
-        zk_launch_sign_rpow(s->stream, s->sign.r, d_rpow);
-        s->sign.rpow = d_rpow;
-    }
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    u64 rh[4];
+    RC_TRY(host_words(s, rh, t->randomness, 32, dev, "randomness"));
+    s->sign.r = fr_from_words(rh);
+    u64* d_rpow = nullptr;
+    RC_TRY(dev_buf(s, d_rpow, 64 * 4 * sizeof(u64)));
+    zk_launch_sign_rpow(s->stream, s->sign.r, d_rpow);
+    s->sign.rpow = d_rpow;
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_sign_verify(const zk_sign_units* t, uint32_t opts, uint32_t* status_out, zk_result* result) {
     ARG_TRY(result, "zk_sign_verify: result is null");
     zk_session* s = nullptr;
-    int rc = zk_sign_open(t, opts, &s);
-    if (rc) return rc;
+    RC_TRY(zk_sign_open(t, opts, &s));
     return one_shot(s, opts & ZK_OPT_DEVICE_PTRS, status_out, result);
 }
 
@@ -1584,49 +1601,33 @@ extern "C" int zk_keccak_open(const uint8_t* data, uint64_t n_bytes, const uint6
         for (u64 k = 0; k < n_msgs; k++) ARG_TRY(offsets[k] <= offsets[k + 1], "zk_keccak_open: offsets must be non-decreasing");
         ARG_TRY(offsets[n_msgs] <= n_bytes, "zk_keccak_open: offsets exceed the data buffer");
     }
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_KECCAK;
     s->n = n_msgs;
-    int rc = 0;
-    const void* p = nullptr;
-    u64 rh[4];
-    if ((rc = stage(s, data, (size_t)n_bytes, dev, &p))) goto fail;
-    s->keccak_gen.data = (const uint8_t*)p;
-    if ((rc = stage(s, offsets, (size_t)(n_msgs + 1) * 8, dev, &p))) goto fail;
-    s->keccak_gen.offsets = (const u64*)p;
+    RC_TRY(stage_in(s, s->keccak_gen.data, data, (size_t)n_bytes, dev));
+    RC_TRY(stage_in(s, s->keccak_gen.offsets, offsets, (size_t)(n_msgs + 1) * 8, dev));
     s->keccak_gen.n = n_msgs;
     s->keccak_gen.mode = mode;
     s->keccak_gen.long_list = nullptr;
     s->keccak_gen.long_count = nullptr;
     if (mode == KT_MODE_CIRCUIT && !getenv("ZK_KECCAK_NO_GROUPS")) {  // the lane-group kernel's work list (keccak_table.hpp)
         u32* d_list = nullptr;
-        if ((rc = dev_alloc(s, (void**)&d_list, ((size_t)n_msgs + 1) * sizeof(u32)))) goto fail;
+        RC_TRY(dev_buf(s, d_list, ((size_t)n_msgs + 1) * sizeof(u32)));
         s->keccak_gen.long_list = d_list + 1;
         s->keccak_gen.long_count = d_list;
     }
-    if (dev) {
-        if (fetch_small(s->stream, rh, randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
-    } else {
-        memcpy(rh, randomness, 32);
-    }
-    if ((rc = keccak_rpow_open(s, rh, &s->keccak_gen.rpow))) goto fail;
-    if (rows_dev) {
-        s->keccak_gen.rows = rows_dev;
-    } else {
-        u64* d_rows = nullptr;
-        if ((rc = dev_alloc(s, (void**)&d_rows, (size_t)n_msgs * KT_NCELLS * 32))) goto fail;
-        s->keccak_gen.rows = d_rows;
-    }
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    u64 rh[4];
+    RC_TRY(host_words(s, rh, randomness, 32, dev, "randomness"));
+    RC_TRY(keccak_rpow_open(s, rh, &s->keccak_gen.rpow));
+    RC_TRY(out_buf(s, s->keccak_gen.rows, rows_dev, (size_t)n_msgs * KT_NCELLS * 32));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_keccak_read_rows(zk_session* s, uint64_t* rows_host) {
     ARG_TRY(s && rows_host && s->kind == SESSION_KECCAK, "zk_keccak_read_rows: bad arguments");
-    HIP_TRY(hipMemcpyAsync(rows_host, s->keccak_gen.rows, (size_t)s->n * KT_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+    RC_TRY(d2h_out(s, rows_host, s->keccak_gen.rows, (size_t)s->n * KT_NCELLS * 32));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
 }
@@ -1636,14 +1637,10 @@ extern "C" int zk_keccak_table(const uint8_t* data, uint64_t n_bytes, const uint
     ARG_TRY(result && rows_out, "zk_keccak_table: null output");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_keccak_open(data, n_bytes, offsets, n_msgs, randomness, mode, dev ? rows_out : nullptr, opts, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && !dev) rc = zk_keccak_read_rows(s, rows_out);
-    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_keccak_open(data, n_bytes, offsets, n_msgs, randomness, mode, dev ? rows_out : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, status_out, result));
+    return dev ? 0 : zk_keccak_read_rows(s, rows_out);
 }
 
 // ---- State-circuit witness assignment
@@ -1654,53 +1651,43 @@ extern "C" int zk_state_assign_open(const uint64_t* ops, const uint32_t* op_flag
     ARG_TRY(out && ops && op_flags && n > 0 && n < (1ull << 31), "zk_state_assign_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     ARG_TRY(dev || (!rows_dev && !row_flags_dev && !mpt_dev), "zk_state_assign_open: output buffers need ZK_OPT_DEVICE_PTRS");
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_ASSIGN;
     s->n = n;
     AssignArgs& a = s->assign;
-    int rc = 0;
-    const void* p = nullptr;
-    u32 cap = 16;
-    if ((rc = stage(s, ops, (size_t)n * ASG_NSLOTS * 32, dev, &p))) goto fail;
-    a.ops = (const u64*)p;
-    if ((rc = stage(s, op_flags, (size_t)n * 4, dev, &p))) goto fail;
-    a.op_flags = (const u32*)p;
+    RC_TRY(stage_in(s, a.ops, ops, (size_t)n * ASG_NSLOTS * 32, dev));
+    RC_TRY(stage_in(s, a.op_flags, op_flags, (size_t)n * 4, dev));
     a.n = n;
     a.nb = (u32)((n + ASG_BLOCK - 1) / ASG_BLOCK);
-    a.rows = rows_dev;
-    a.row_flags = row_flags_dev;
-    a.mpt = mpt_dev;
     a.compact = (opts & ZK_OPT_STATE_COMPACT) ? 1u : 0u;
-    if (!a.rows && (rc = dev_alloc(s, (void**)&a.rows, (size_t)n * (a.compact ? 15 : ASG_ROW_NCELLS) * 32))) goto fail;
-    if (!a.row_flags && (rc = dev_alloc(s, (void**)&a.row_flags, (size_t)n * 4))) goto fail;
-    if (!a.mpt && (rc = dev_alloc(s, (void**)&a.mpt, (size_t)n * ASG_MPT_NCELLS * 32))) goto fail;
+    RC_TRY(out_buf(s, a.rows, rows_dev, (size_t)n * (a.compact ? 15 : ASG_ROW_NCELLS) * 32));
+    RC_TRY(out_buf(s, a.row_flags, row_flags_dev, (size_t)n * 4));
+    RC_TRY(out_buf(s, a.mpt, mpt_dev, (size_t)n * ASG_MPT_NCELLS * 32));
+    u32 cap = 16;
     while (cap < 2 * n + 2) cap <<= 1;
     a.mask = cap - 1;
-    if ((rc = dev_alloc(s, (void**)&a.slots, (size_t)cap * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.first, (size_t)n * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.rank, (size_t)n * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.blk_cnt, (size_t)(a.nb + 1) * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.blk_next, (size_t)(a.nb + 1) * 4))) goto fail;
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(dev_buf(s, a.slots, (size_t)cap * 4));
+    RC_TRY(dev_buf(s, a.first, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.rank, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.blk_cnt, (size_t)(a.nb + 1) * 4));
+    RC_TRY(dev_buf(s, a.blk_next, (size_t)(a.nb + 1) * 4));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_state_assign_read(zk_session* s, uint64_t* rows_host, uint32_t* row_flags_host, uint64_t* mpt_host,
                                     uint64_t mpt_capacity_rows, uint64_t* n_mpt_out) {
     ARG_TRY(s && s->kind == SESSION_ASSIGN, "zk_state_assign_read: bad arguments");
     const AssignArgs& a = s->assign;
     u32 n_mpt = 0;
-    HIP_TRY(hipMemcpyAsync(&n_mpt, a.blk_cnt + a.nb, 4, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    RC_TRY(d2h_now(s->stream, &n_mpt, a.blk_cnt + a.nb, 4));
     if (n_mpt_out) *n_mpt_out = n_mpt;
-    if (rows_host) HIP_TRY(hipMemcpyAsync(rows_host, a.rows, (size_t)a.n * (a.compact ? 15 : ASG_ROW_NCELLS) * 32, hipMemcpyDeviceToHost, s->stream));
-    if (row_flags_host) HIP_TRY(hipMemcpyAsync(row_flags_host, a.row_flags, (size_t)a.n * 4, hipMemcpyDeviceToHost, s->stream));
+    RC_TRY(d2h_out(s, rows_host, a.rows, (size_t)a.n * (a.compact ? 15 : ASG_ROW_NCELLS) * 32));
+    RC_TRY(d2h_out(s, row_flags_host, a.row_flags, (size_t)a.n * 4));
     if (mpt_host) {
         ARG_TRY(mpt_capacity_rows >= n_mpt, "zk_state_assign_read: mpt buffer too small");
-        if (n_mpt) HIP_TRY(hipMemcpyAsync(mpt_host, a.mpt, (size_t)n_mpt * ASG_MPT_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        RC_TRY(d2h_out(s, mpt_host, a.mpt, (size_t)n_mpt * ASG_MPT_NCELLS * 32));
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
@@ -1711,16 +1698,12 @@ extern "C" int zk_state_assign(const uint64_t* ops, const uint32_t* op_flags, ui
     ARG_TRY(result && n_mpt_out, "zk_state_assign: null output");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_state_assign_open(ops, op_flags, n, dev ? rows_out : nullptr, dev ? row_flags_out : nullptr,
-                                  dev ? mpt_out : nullptr, opts, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc) rc = dev ? zk_state_assign_read(s, nullptr, nullptr, nullptr, 0, n_mpt_out)
-                      : zk_state_assign_read(s, rows_out, row_flags_out, mpt_out, n, n_mpt_out);
-    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_state_assign_open(ops, op_flags, n, dev ? rows_out : nullptr, dev ? row_flags_out : nullptr,
+                                dev ? mpt_out : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, status_out, result));
+    return dev ? zk_state_assign_read(s, nullptr, nullptr, nullptr, 0, n_mpt_out)
+               : zk_state_assign_read(s, rows_out, row_flags_out, mpt_out, n, n_mpt_out);
 }
 
 // ---- RW table -> State-circuit operations (state_rekey.hpp)
@@ -1732,18 +1715,12 @@ static int rekey_setup(zk_session* s, const uint64_t* rw, const uint32_t* rw_fla
                        uint64_t* ops_dev, uint32_t* op_flags_dev) {
     RekeyArgs& a = s->rekey;
     memset(&a, 0, sizeof(a));
-    int rc = 0;
-    const void* p = nullptr;
+    RC_TRY(stage_in(s, a.rw, rw, (size_t)n * RWK_RW_NCELLS * 32, dev));
+    if (rw_flags) RC_TRY(stage_in(s, a.rw_flags, rw_flags, (size_t)n * 4, dev));
+    a.n = n;
     std::vector<u32> h_masks(2 * RWK_MASK_WORDS_H + RWK_NCLASSES);
     const size_t mask_bytes = h_masks.size() * 4;
-    if ((rc = stage(s, rw, (size_t)n * RWK_RW_NCELLS * 32, dev, &p))) return rc;
-    a.rw = (const u64*)p;
-    if (rw_flags) {
-        if ((rc = stage(s, rw_flags, (size_t)n * 4, dev, &p))) return rc;
-        a.rw_flags = (const u32*)p;
-    }
-    a.n = n;
-    if ((rc = dev_alloc(s, (void**)&a.masks, mask_bytes))) return rc;
+    RC_TRY(dev_buf(s, a.masks, mask_bytes));
     HIP_TRY(hipMemsetAsync(a.masks, 0, mask_bytes, s->stream));
     zk_launch_rekey_scan(s->stream, a);
     HIP_TRY(hipMemcpyAsync(h_masks.data(), a.masks, mask_bytes, hipMemcpyDeviceToHost, s->stream));
@@ -1754,7 +1731,6 @@ static int rekey_setup(zk_session* s, const uint64_t* rw, const uint32_t* rw_fla
 static int rekey_plan_setup(zk_session* s, const std::vector<u32>& h_masks, bool want_ops, uint64_t* ops_dev, uint32_t* op_flags_dev) {
     RekeyArgs& a = s->rekey;
     const u64 n = a.n;
-    int rc = 0;
     RwkHostPlan hp;
     RwkPlan* d_plan = nullptr;
     {
@@ -1765,7 +1741,7 @@ static int rekey_plan_setup(zk_session* s, const std::vector<u32>& h_masks, bool
     a.n_passes = hp.plan.n_passes;
     a.n_ops = 1 + hp.n_kept;
     a.ntiles = (u32)((n + 4095) / 4096);
-    if ((rc = dev_alloc(s, (void**)&d_plan, sizeof(RwkPlan)))) return rc;
+    RC_TRY(dev_buf(s, d_plan, sizeof(RwkPlan)));
     s->rekey_plan_host = hp.plan;  // (lives as long as the session: no wait for the copy here — one host round trip less per open)
     HIP_TRY(hipMemcpyAsync(d_plan, &s->rekey_plan_host, sizeof(RwkPlan), hipMemcpyHostToDevice, s->stream));
     a.plan = d_plan;
@@ -1775,35 +1751,33 @@ static int rekey_plan_setup(zk_session* s, const std::vector<u32>& h_masks, bool
         a.fast = (!no_fast && a.key_words <= 2 && a.n_passes <= 8 && n < (1ull << 30)) ? 1u : 0u;
     }
     a.ntiles_fast = (u32)((n + RWK_SW_TILE - 1) / RWK_SW_TILE);
-    if ((rc = dev_alloc(s, (void**)&a.idx_a, (size_t)n * 4))) return rc;
-    if ((rc = dev_alloc(s, (void**)&a.idx_b, (size_t)n * 4))) return rc;
+    RC_TRY(dev_buf(s, a.idx_a, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.idx_b, (size_t)n * 4));
     if (a.fast) {
-        if ((rc = dev_alloc(s, (void**)&a.key64_a, (size_t)n * 8))) return rc;
-        if ((rc = dev_alloc(s, (void**)&a.key64_b, (size_t)n * 8))) return rc;
+        RC_TRY(dev_buf(s, a.key64_a, (size_t)n * 8));
+        RC_TRY(dev_buf(s, a.key64_b, (size_t)n * 8));
         static_assert(2 * sizeof(ZkTally) <= RWK_SWEEP_FRONT * 4, "the two tallies fit in front of the sweep buffer");
         u32* block = nullptr;
-        if ((rc = dev_alloc(s, (void**)&block, ((size_t)RWK_SWEEP_FRONT + RWK_SWEEP_HEAD + (size_t)a.n_passes * a.ntiles_fast * 256) * 4))) return rc;
+        RC_TRY(dev_buf(s, block, ((size_t)RWK_SWEEP_FRONT + RWK_SWEEP_HEAD + (size_t)a.n_passes * a.ntiles_fast * 256) * 4));
         s->rekey_tally = (ZkTally*)block;
         a.sweep = block + RWK_SWEEP_FRONT;
     } else {
-        if ((rc = dev_alloc(s, (void**)&a.keys, (size_t)a.key_words * n * 4))) return rc;
-        if ((rc = dev_alloc(s, (void**)&a.hist, (size_t)a.ntiles * 256 * 4))) return rc;
+        RC_TRY(dev_buf(s, a.keys, (size_t)a.key_words * n * 4));
+        RC_TRY(dev_buf(s, a.hist, (size_t)a.ntiles * 256 * 4));
     }
     a.n_jobs = (u32)hp.jobs.size();
     if (a.n_jobs) {
         u32 members = 0;
         for (u32 j = 0; j < a.n_jobs; j++) { a.jobs[j] = hp.jobs[j]; members += hp.jobs[j].count; }
         for (int f = 0; f < RWK_NFIELDS; f++)
-            if (hp.rank_field[f] && (rc = dev_alloc(s, (void**)&a.ranks[f], (size_t)n * 4))) return rc;
-        if ((rc = dev_alloc(s, (void**)&a.job_cursor, (size_t)RWK_MAX_JOBS * 4))) return rc;
-        if ((rc = dev_alloc(s, (void**)&a.job_rows, (size_t)members * 4))) return rc;
-        if ((rc = dev_alloc(s, (void**)&a.job_vals, (size_t)members * 32))) return rc;
+            if (hp.rank_field[f]) RC_TRY(dev_buf(s, a.ranks[f], (size_t)n * 4));
+        RC_TRY(dev_buf(s, a.job_cursor, (size_t)RWK_MAX_JOBS * 4));
+        RC_TRY(dev_buf(s, a.job_rows, (size_t)members * 4));
+        RC_TRY(dev_buf(s, a.job_vals, (size_t)members * 32));
     }
     if (want_ops) {
-        a.ops = ops_dev;
-        a.op_flags = op_flags_dev;
-        if (!a.ops && (rc = dev_alloc(s, (void**)&a.ops, (size_t)a.n_ops * RWK_NSLOTS * 32))) return rc;
-        if (!a.op_flags && (rc = dev_alloc(s, (void**)&a.op_flags, (size_t)a.n_ops * 4))) return rc;
+        RC_TRY(out_buf(s, a.ops, ops_dev, (size_t)a.n_ops * RWK_NSLOTS * 32));
+        RC_TRY(out_buf(s, a.op_flags, op_flags_dev, (size_t)a.n_ops * 4));
     }
     return 0;
 }
@@ -1817,14 +1791,14 @@ extern "C" int zk_state_ops_from_rw_open(const uint64_t* rw, const uint32_t* rw_
     ARG_TRY(out && rw && n > 0 && n < (1ull << 31), "zk_state_ops_from_rw_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     ARG_TRY(dev || (!ops_dev && !op_flags_dev), "zk_state_ops_from_rw_open: output buffers need ZK_OPT_DEVICE_PTRS");
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_REKEY;
     s->n = n;
-    int rc = rekey_setup(s, rw, rw_flags, n, dev, true, ops_dev, op_flags_dev);
-    if (!rc) rc = session_common_init(s);
-    if (rc) { zk_close(s); return rc; }
+    RC_TRY(rekey_setup(s, rw, rw_flags, n, dev, true, ops_dev, op_flags_dev));
+    RC_TRY(session_common_init(s));
     if (n_ops_out) *n_ops_out = s->rekey.n_ops;
-    *out = s;
+    *out = guard.release();
     return 0;
 }
 // RW table -> State-circuit rows in one session: the re-keying and the sort as above, then the witness assignment reads its ops
@@ -1836,42 +1810,36 @@ extern "C" int zk_state_assign_from_rw_open(const uint64_t* rw, const uint32_t* 
     ARG_TRY(out && rw && n_rw > 0 && n_rw < (1ull << 31) - 1, "zk_state_assign_from_rw_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     ARG_TRY(dev || (!rows_dev && !row_flags_dev && !mpt_dev), "zk_state_assign_from_rw_open: output buffers need ZK_OPT_DEVICE_PTRS");
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_ASSIGN;
-    int rc = rekey_setup(s, rw, rw_flags, n_rw, dev, false, nullptr, nullptr);
-    if (rc) { zk_close(s); return rc; }
+    RC_TRY(rekey_setup(s, rw, rw_flags, n_rw, dev, false, nullptr, nullptr));
     const u64 n = s->rekey.n_ops;
     s->n = n;
     s->assign_from_rw = true;
     AssignArgs& a = s->assign;
-    u32 cap = 16;
     a.n = n;
     a.rw = s->rekey.rw;
     a.rw_flags = s->rekey.rw_flags;
     a.order = rekey_order(s->rekey);
     a.nb = (u32)((n + ASG_BLOCK - 1) / ASG_BLOCK);
-    a.rows = rows_dev;
-    a.row_flags = row_flags_dev;
-    a.mpt = mpt_dev;
     a.compact = (opts & ZK_OPT_STATE_COMPACT) ? 1u : 0u;
-    if (!a.rows && (rc = dev_alloc(s, (void**)&a.rows, (size_t)n * (a.compact ? 15 : ASG_ROW_NCELLS) * 32))) goto fail;
-    if (!a.row_flags && (rc = dev_alloc(s, (void**)&a.row_flags, (size_t)n * 4))) goto fail;
-    if (!a.mpt && (rc = dev_alloc(s, (void**)&a.mpt, (size_t)n * ASG_MPT_NCELLS * 32))) goto fail;
+    RC_TRY(out_buf(s, a.rows, rows_dev, (size_t)n * (a.compact ? 15 : ASG_ROW_NCELLS) * 32));
+    RC_TRY(out_buf(s, a.row_flags, row_flags_dev, (size_t)n * 4));
+    RC_TRY(out_buf(s, a.mpt, mpt_dev, (size_t)n * ASG_MPT_NCELLS * 32));
+    u32 cap = 16;
     while (cap < 2 * n + 2) cap <<= 1;
     a.mask = cap - 1;
-    if ((rc = dev_alloc(s, (void**)&a.slots, (size_t)cap * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.first, (size_t)n * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.rank, (size_t)n * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.blk_cnt, (size_t)(a.nb + 1) * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.blk_next, (size_t)(a.nb + 1) * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&s->rekey_status, (size_t)n_rw * 4))) goto fail;
-    if ((rc = session_common_init(s))) goto fail;
+    RC_TRY(dev_buf(s, a.slots, (size_t)cap * 4));
+    RC_TRY(dev_buf(s, a.first, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.rank, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.blk_cnt, (size_t)(a.nb + 1) * 4));
+    RC_TRY(dev_buf(s, a.blk_next, (size_t)(a.nb + 1) * 4));
+    RC_TRY(dev_buf(s, s->rekey_status, (size_t)n_rw * 4));
+    RC_TRY(session_common_init(s));
     if (n_ops_out) *n_ops_out = n;
-    *out = s;
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 // RW table -> State circuit verdict in one session: the re-keying, the sort and the mock MPT as above; op2row's rows are evaluated in
 // the registers they are computed in (state_fused.hpp) and never stored.
@@ -1881,35 +1849,35 @@ extern "C" int zk_state_verify_from_rw_open(const uint64_t* rw, const uint32_t* 
     HIP_TRY(hipSetDevice(t_device));
     ARG_TRY(out && rw && n_rw > 0 && n_rw < (1ull << 31) - 1, "zk_state_verify_from_rw_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_ASSIGN;
-    int rc = rekey_setup(s, rw, rw_flags, n_rw, dev, false, nullptr, nullptr);
-    if (rc) { zk_close(s); return rc; }
+    RC_TRY(rekey_setup(s, rw, rw_flags, n_rw, dev, false, nullptr, nullptr));
     const u64 n = s->rekey.n_ops;
     s->n = n;
     s->assign_from_rw = true;
     s->fused_verify = true;
     AssignArgs& a = s->assign;
     StateArgs& v = s->state;
-    u32 cap = 16, mcap = 16;
     a.n = n;
     a.rw = s->rekey.rw;
     a.rw_flags = s->rekey.rw_flags;
     a.order = rekey_order(s->rekey);
     a.nb = (u32)((n + ASG_BLOCK - 1) / ASG_BLOCK);
-    if ((rc = dev_alloc(s, (void**)&a.mpt, (size_t)n * ASG_MPT_NCELLS * 32))) goto fail;
+    RC_TRY(dev_buf(s, a.mpt, (size_t)n * ASG_MPT_NCELLS * 32));
+    u32 cap = 16;
     while (cap < 2 * n + 2) cap <<= 1;
-    mcap = cap;  // (as many MPT rows as ops at most)
+    const u32 mcap = cap;  // (as many MPT rows as ops at most)
     a.mask = cap - 1;
     a.mpt_mask = mcap - 1;
-    if ((rc = dev_alloc(s, (void**)&a.slots, ((size_t)cap + mcap) * 4))) goto fail;  // key slots, then the MPT index: one fill
+    RC_TRY(dev_buf(s, a.slots, ((size_t)cap + mcap) * 4));  // key slots, then the MPT index: one fill
     a.mpt_slots = a.slots + cap;
-    if ((rc = dev_alloc(s, (void**)&a.first, (size_t)n * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.rank, (size_t)n * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.root_rank, (size_t)n * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.blk_cnt, (size_t)(a.nb + 1) * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.blk_next, (size_t)(a.nb + 1) * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&s->rekey_status, (size_t)n_rw * 4))) goto fail;
+    RC_TRY(dev_buf(s, a.first, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.rank, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.root_rank, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.blk_cnt, (size_t)(a.nb + 1) * 4));
+    RC_TRY(dev_buf(s, a.blk_next, (size_t)(a.nb + 1) * 4));
+    RC_TRY(dev_buf(s, s->rekey_status, (size_t)n_rw * 4));
     v.rows.cells = nullptr;
     v.rows.flags = nullptr;
     v.rows.n = n;
@@ -1921,33 +1889,25 @@ extern "C" int zk_state_verify_from_rw_open(const uint64_t* rw, const uint32_t* 
     v.mpt.ncells = MPT_NCELLS;
     v.mpt.slots = a.mpt_slots;
     v.mpt.mask = a.mpt_mask;
-    if ((rc = session_common_init(s))) goto fail;
+    RC_TRY(session_common_init(s));
     if (n_ops_out) *n_ops_out = n;
-    *out = s;
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_state_verify_from_rw(const uint64_t* rw, const uint32_t* rw_flags, uint64_t n, uint32_t opts, uint32_t* status_out,
                                        uint64_t* n_ops_out, zk_result* result) {
     ARG_TRY(result, "zk_state_verify_from_rw: result is null");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_state_verify_from_rw_open(rw, rw_flags, n, opts, n_ops_out, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_state_verify_from_rw_open(rw, rw_flags, n, opts, n_ops_out, &s));
+    return one_shot(s, dev, status_out, result);
 }
 extern "C" int zk_state_ops_from_rw_read(zk_session* s, uint64_t* ops_host, uint32_t* op_flags_host, uint64_t* n_ops_out) {
     ARG_TRY(s && s->kind == SESSION_REKEY, "zk_state_ops_from_rw_read: bad arguments");
     const RekeyArgs& a = s->rekey;
     if (n_ops_out) *n_ops_out = a.n_ops;
-    if (ops_host) HIP_TRY(hipMemcpyAsync(ops_host, a.ops, (size_t)a.n_ops * RWK_NSLOTS * 32, hipMemcpyDeviceToHost, s->stream));
-    if (op_flags_host) HIP_TRY(hipMemcpyAsync(op_flags_host, a.op_flags, (size_t)a.n_ops * 4, hipMemcpyDeviceToHost, s->stream));
+    RC_TRY(d2h_out(s, ops_host, a.ops, (size_t)a.n_ops * RWK_NSLOTS * 32));
+    RC_TRY(d2h_out(s, op_flags_host, a.op_flags, (size_t)a.n_ops * 4));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
 }
@@ -1956,14 +1916,10 @@ extern "C" int zk_state_ops_from_rw(const uint64_t* rw, const uint32_t* rw_flags
     ARG_TRY(result && n_ops_out, "zk_state_ops_from_rw: null output");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_state_ops_from_rw_open(rw, rw_flags, n, dev ? ops_out : nullptr, dev ? op_flags_out : nullptr, opts, n_ops_out, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && !dev) rc = zk_state_ops_from_rw_read(s, ops_out, op_flags_out, n_ops_out);
-    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_state_ops_from_rw_open(rw, rw_flags, n, dev ? ops_out : nullptr, dev ? op_flags_out : nullptr, opts, n_ops_out, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, status_out, result));
+    return dev ? 0 : zk_state_ops_from_rw_read(s, ops_out, op_flags_out, n_ops_out);
 }
 
 // ---- secp256k1 ECDSA verification
@@ -1979,12 +1935,11 @@ extern "C" int zk_ecdsa_open_batches(const zk_ecdsa_batch* bt, uint32_t n_batche
         ARG_TRY(!bt[k].out_dev || bt[k].out_stride >= 1, "zk_ecdsa_open: out_stride must be >= 1");
         n += bt[k].n;
     }
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_ECDSA;
     s->n = n;
     EcdsaArgs& a = s->ecdsa;
-    int rc = 0;
-    const void* p = nullptr;
     // layout 0: packed uint8[n][5][32] (msg_hash big-endian); 1 / 2: the Tx / Sig units' byte rows uint8[n][9][32]
     // (rows 2, 3, 5, 7, 8; the Tx chip keeps msg_hash little-endian, the Sig chip big-endian)
     static const u32 OFF[2][5] = {{0, 32, 64, 96, 128}, {64, 96, 160, 224, 256}};
@@ -1995,12 +1950,8 @@ extern "C" int zk_ecdsa_open_batches(const zk_ecdsa_batch* bt, uint32_t n_batche
         const u64 stride = bt[k].layout ? 288 : 160;
         const uint8_t* d_bytes;
         const u32* d_v = nullptr;
-        if ((rc = stage(s, bt[k].bytes, (size_t)bt[k].n * stride, dev, &p))) goto fail;
-        d_bytes = (const uint8_t*)p;
-        if (bt[k].v) {
-            if ((rc = stage(s, bt[k].v, (size_t)bt[k].n * 4 * bt[k].v_stride, dev, &p))) goto fail;
-            d_v = (const u32*)p;
-        }
+        RC_TRY(stage_in(s, d_bytes, bt[k].bytes, (size_t)bt[k].n * stride, dev));
+        if (bt[k].v) RC_TRY(stage_in(s, d_v, bt[k].v, (size_t)bt[k].n * 4 * bt[k].v_stride, dev));
         if (k == 0) {
             a.stride = stride; a.msg_be = bt[k].layout != 1u; a.bytes = d_bytes; a.v = d_v; a.v_stride = bt[k].v_stride;
             a.out = bt[k].out_dev; a.out_stride = bt[k].out_stride;
@@ -2011,13 +1962,10 @@ extern "C" int zk_ecdsa_open_batches(const zk_ecdsa_batch* bt, uint32_t n_batche
             for (int c = 0; c < 5; c++) a.off1[c] = OFF[bt[k].layout ? 1 : 0][c];
         }
     }
-    if ((rc = secp_lanes_open(s, n, "zk_ecdsa_open", a.lanes))) goto fail;
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(secp_lanes_open(s, n, "zk_ecdsa_open", a.lanes));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_ecdsa_open(const uint8_t* bytes, uint32_t layout, const uint32_t* v, uint32_t v_stride, uint64_t n,
                              uint32_t* out_dev, uint32_t out_stride, uint32_t opts, zk_session** out) {
@@ -2029,8 +1977,7 @@ extern "C" int zk_ecdsa_verify(const uint8_t* bytes, uint32_t layout, const uint
                                uint32_t opts, uint32_t* status_out, zk_result* result) {
     ARG_TRY(result, "zk_ecdsa_verify: result is null");
     zk_session* s = nullptr;
-    int rc = zk_ecdsa_open(bytes, layout, v, v_stride, n, nullptr, 0, opts, &s);
-    if (rc) return rc;
+    RC_TRY(zk_ecdsa_open(bytes, layout, v, v_stride, n, nullptr, 0, opts, &s));
     return one_shot(s, opts & ZK_OPT_DEVICE_PTRS, status_out, result);
 }
 
@@ -2044,27 +1991,18 @@ extern "C" int zk_bytecode_assign_open(const uint64_t* in_rows, uint64_t n_rows,
             (n_rows == 0 || in_rows), "zk_bytecode_assign_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     ARG_TRY(dev || !rows_dev, "zk_bytecode_assign_open: rows_dev needs ZK_OPT_DEVICE_PTRS");
-    zk_session* s = new zk_session();
+    std::vector<BcaChunk> chunks;  // (staged below: declared before the session, destroyed after its close)
+    std::vector<u32> code_chunk0((size_t)n_codes + 1, 0);
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_BCA;
     s->n = 1ull << k;
     BcaArgs& a = s->bca;
-    int rc = 0;
-    const void* p = nullptr;
-    std::vector<u64> h_off((size_t)n_codes + 1, 0);
-    std::vector<BcaChunk> chunks;
-    std::vector<u32> code_chunk0((size_t)n_codes + 1, 0);
-    u64 rh[4];
-    Fr r;
     // the chunk table is index plumbing over the row offsets (not witness data): built on the host
-    if (n_codes) {
-        if (dev) {
-            if (fetch_small(s->stream, h_off.data(), offsets, (n_codes + 1) * 8)) { rc = -2; g_err = "offsets download failed"; goto fail; }
-        } else {
-            memcpy(h_off.data(), offsets, (n_codes + 1) * 8);
-        }
-    }
+    std::vector<u64> h_off((size_t)n_codes + 1, 0);
+    if (n_codes) RC_TRY(host_words(s, h_off.data(), offsets, (n_codes + 1) * 8, dev, "offsets"));
     for (u64 j = 0; j < n_codes; j++) {
-        if (h_off[j] > h_off[j + 1] || h_off[j + 1] > n_rows) { rc = -1; g_err = "zk_bytecode_assign_open: offsets must be non-decreasing and within the rows"; goto fail; }
+        ARG_TRY(h_off[j] <= h_off[j + 1] && h_off[j + 1] <= n_rows, "zk_bytecode_assign_open: offsets must be non-decreasing and within the rows");
         code_chunk0[j] = (u32)chunks.size();
         for (u64 g = h_off[j]; g < h_off[j + 1]; g += BCA_CHUNK) {
             BcaChunk c;
@@ -2075,63 +2013,38 @@ extern "C" int zk_bytecode_assign_open(const uint64_t* in_rows, uint64_t n_rows,
         }
     }
     code_chunk0[n_codes] = (u32)chunks.size();
-    if (n_codes && (h_off[0] != 0 || h_off[n_codes] != n_rows)) { rc = -1; g_err = "zk_bytecode_assign_open: offsets must cover every row"; goto fail; }
-    if ((rc = stage(s, in_rows, (size_t)n_rows * BCA_IN_NCELLS * 32, dev, &p))) goto fail;
-    a.in_rows = (const u64*)p;
-    if ((rc = stage(s, n_codes ? offsets : nullptr, (size_t)(n_codes + 1) * 8, dev, &p))) goto fail;
-    a.offsets = (const u64*)p;
-    if ((rc = stage(s, lengths, (size_t)n_codes * 8, dev, &p))) goto fail;
-    a.lengths = (const u64*)p;
+    ARG_TRY(!n_codes || (h_off[0] == 0 && h_off[n_codes] == n_rows), "zk_bytecode_assign_open: offsets must cover every row");
+    RC_TRY(stage_in(s, a.in_rows, in_rows, (size_t)n_rows * BCA_IN_NCELLS * 32, dev));
+    RC_TRY(stage_in(s, a.offsets, n_codes ? offsets : nullptr, (size_t)(n_codes + 1) * 8, dev));
+    RC_TRY(stage_in(s, a.lengths, lengths, (size_t)n_codes * 8, dev));
     a.n_in = n_rows; a.n_codes = n_codes; a.n_out = 1ull << k; a.n_chunks = chunks.size();
-    if (dev) {
-        if (fetch_small(s->stream, rh, randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
-    } else {
-        memcpy(rh, randomness, 32);
-    }
-    for (int q = 0; q < 4; q++) { r.v[2 * q] = (u32)rh[q]; r.v[2 * q + 1] = (u32)(rh[q] >> 32); }
-    {
-        u64* d_rpow = nullptr;
-        void* d = nullptr;
-        if ((rc = dev_alloc(s, (void**)&d_rpow, BCA_RPOW_ROWS * 32))) goto fail;
-        zk_launch_bca_rpow(s->stream, r, d_rpow);
-        a.rpow = d_rpow;
-        if ((rc = stage(s, chunks.empty() ? nullptr : chunks.data(), chunks.size() * sizeof(BcaChunk), false, &p))) goto fail;
-        a.chunks = (const BcaChunk*)p;
-        if ((rc = stage(s, code_chunk0.data(), code_chunk0.size() * 4, false, &p))) goto fail;
-        a.code_chunk0 = (const u32*)p;
-        // the host vectors above go out of scope with this call
-        if (hipStreamSynchronize(s->stream) != hipSuccess) { rc = -2; g_err = "zk_bytecode_assign_open: upload failed"; goto fail; }
-        if ((rc = dev_alloc(s, &d, (size_t)n_rows * 2))) goto fail;
-        a.track = (uint8_t*)d;
-        if ((rc = dev_alloc(s, &d, chunks.size() * 32))) goto fail;
-        a.chunk_acc = (u64*)d;
-        if ((rc = dev_alloc(s, &d, chunks.size() * 4))) goto fail;
-        a.chunk_m = (u32*)d;
-        if ((rc = dev_alloc(s, &d, chunks.size() * (size_t)BCA_MAP_STRIDE))) goto fail;
-        a.chunk_map = (uint8_t*)d;
-        if ((rc = dev_alloc(s, &d, chunks.size() * 4))) goto fail;
-        a.chunk_state = (u32*)d;
-        if ((rc = dev_alloc(s, &d, chunks.size() * 32))) goto fail;
-        a.chunk_in = (u64*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)n_rows * 32))) goto fail;
-        a.rlc = (u64*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)n_rows * 4))) goto fail;
-        a.row_code = (u32*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)n_rows * 4))) goto fail;
-        a.row_chunk = (u32*)d;
-    }
-    a.rows = rows_dev;
-    if (!a.rows && (rc = dev_alloc(s, (void**)&a.rows, (size_t)a.n_out * BCA_OUT_NCELLS * 32))) goto fail;
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    u64 rh[4];
+    RC_TRY(host_words(s, rh, randomness, 32, dev, "randomness"));
+    u64* d_rpow = nullptr;
+    RC_TRY(dev_buf(s, d_rpow, BCA_RPOW_ROWS * 32));
+    zk_launch_bca_rpow(s->stream, fr_from_words(rh), d_rpow);
+    a.rpow = d_rpow;
+    RC_TRY(stage_in(s, a.chunks, chunks.empty() ? nullptr : chunks.data(), chunks.size() * sizeof(BcaChunk), false));
+    RC_TRY(stage_in(s, a.code_chunk0, code_chunk0.data(), code_chunk0.size() * 4, false));
+    // the host vectors above go out of scope with this call
+    DEV_TRY(hipStreamSynchronize(s->stream) == hipSuccess, "zk_bytecode_assign_open: upload failed");
+    RC_TRY(dev_buf(s, a.track, (size_t)n_rows * 2));
+    RC_TRY(dev_buf(s, a.chunk_acc, chunks.size() * 32));
+    RC_TRY(dev_buf(s, a.chunk_m, chunks.size() * 4));
+    RC_TRY(dev_buf(s, a.chunk_map, chunks.size() * (size_t)BCA_MAP_STRIDE));
+    RC_TRY(dev_buf(s, a.chunk_state, chunks.size() * 4));
+    RC_TRY(dev_buf(s, a.chunk_in, chunks.size() * 32));
+    RC_TRY(dev_buf(s, a.rlc, (size_t)n_rows * 32));
+    RC_TRY(dev_buf(s, a.row_code, (size_t)n_rows * 4));
+    RC_TRY(dev_buf(s, a.row_chunk, (size_t)n_rows * 4));
+    RC_TRY(out_buf(s, a.rows, rows_dev, (size_t)a.n_out * BCA_OUT_NCELLS * 32));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_bytecode_assign_read(zk_session* s, uint64_t* rows_host) {
     ARG_TRY(s && rows_host && s->kind == SESSION_BCA, "zk_bytecode_assign_read: bad arguments");
-    HIP_TRY(hipMemcpyAsync(rows_host, s->bca.rows, (size_t)s->bca.n_out * BCA_OUT_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+    RC_TRY(d2h_out(s, rows_host, s->bca.rows, (size_t)s->bca.n_out * BCA_OUT_NCELLS * 32));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
 }
@@ -2141,13 +2054,10 @@ extern "C" int zk_bytecode_assign(const uint64_t* in_rows, uint64_t n_rows, cons
     ARG_TRY(result && rows_out, "zk_bytecode_assign: null output");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_bytecode_assign_open(in_rows, n_rows, offsets, lengths, n_codes, k, randomness, dev ? rows_out : nullptr, opts, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && !dev) rc = zk_bytecode_assign_read(s, rows_out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_bytecode_assign_open(in_rows, n_rows, offsets, lengths, n_codes, k, randomness, dev ? rows_out : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, nullptr, result));
+    return dev ? 0 : zk_bytecode_assign_read(s, rows_out);
 }
 
 
@@ -2175,10 +2085,9 @@ extern "C" int zk_copy_assign_sizes(const zk_copy_events* t, uint32_t opts, uint
     std::vector<u32> flags;
     const u64 *pc, *po;
     const u32* pf;
-    int rc = cpa_fetch(t, opts & ZK_OPT_DEVICE_PTRS, cells, flags, offs, &pc, &pf, &po);
-    if (rc) return rc;
+    RC_TRY(cpa_fetch(t, opts & ZK_OPT_DEVICE_PTRS, cells, flags, offs, &pc, &pf, &po));
     CpaPlan pl;
-    if ((rc = cpa_plan(pc, pf, po, t->n_events, pl))) return rc;
+    RC_TRY(cpa_plan(pc, pf, po, t->n_events, pl));
     if (n_rows) *n_rows = pl.n_rows;
     if (n_table) *n_table = pl.n_table;
     if (n_rw) *n_rw = pl.n_rw;
@@ -2195,77 +2104,58 @@ extern "C" int zk_copy_assign_open(const zk_copy_events* t, uint64_t* rows_dev, 
     std::vector<u32> flags;
     const u64 *pc, *po;
     const u32* pf;
-    int rc = cpa_fetch(t, dev, cells, flags, offs, &pc, &pf, &po);
-    if (rc) return rc;
+    RC_TRY(cpa_fetch(t, dev, cells, flags, offs, &pc, &pf, &po));
     CpaPlan pl;
-    if ((rc = cpa_plan(pc, pf, po, t->n_events, pl))) return rc;
-    zk_session* s = new zk_session();
+    RC_TRY(cpa_plan(pc, pf, po, t->n_events, pl));
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_CPA;
     s->n = pl.n_rows;
     s->cpa_n_table = pl.n_table;
     s->cpa_n_rw = pl.n_rw;
     CpaArgs& a = s->cpa;
-    const void* p = nullptr;
-    void* d = nullptr;
-    u64 rh[4];
-    Fr r;
-    if ((rc = stage(s, t->events, (size_t)t->n_events * CPA_EV_NCELLS * 32, dev, &p))) goto fail;
-    a.events = (const u64*)p;
-    if ((rc = stage(s, t->data, (size_t)pl.n_data * 2, dev, &p))) goto fail;
-    a.data = (const uint16_t*)p;
-    if ((rc = stage(s, pl.ev.data(), pl.ev.size() * sizeof(CpaEvent), false, &p))) goto fail;
-    a.ev = (const CpaEvent*)p;
-    if ((rc = stage(s, pl.row0.data(), pl.row0.size() * 8, false, &p))) goto fail;
-    a.row0 = (const u64*)p;
-    if ((rc = stage(s, pl.chunks.empty() ? nullptr : pl.chunks.data(), pl.chunks.size() * sizeof(CpaChunk), false, &p))) goto fail;
-    a.chunks = (const CpaChunk*)p;
+    RC_TRY(stage_in(s, a.events, t->events, (size_t)t->n_events * CPA_EV_NCELLS * 32, dev));
+    RC_TRY(stage_in(s, a.data, t->data, (size_t)pl.n_data * 2, dev));
+    RC_TRY(stage_in(s, a.ev, pl.ev.data(), pl.ev.size() * sizeof(CpaEvent), false));
+    RC_TRY(stage_in(s, a.row0, pl.row0.data(), pl.row0.size() * 8, false));
+    RC_TRY(stage_in(s, a.chunks, pl.chunks.empty() ? nullptr : pl.chunks.data(), pl.chunks.size() * sizeof(CpaChunk), false));
     a.n_events = t->n_events; a.n_rows = pl.n_rows; a.n_chunks = pl.chunks.size();
-    if (dev) {
-        if (fetch_small(s->stream, rh, t->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
-    } else {
-        memcpy(rh, t->randomness, 32);
-    }
-    for (int q = 0; q < 4; q++) { r.v[2 * q] = (u32)rh[q]; r.v[2 * q + 1] = (u32)(rh[q] >> 32); }
-    if ((rc = dev_alloc(s, &d, CPA_RPOW_ROWS * 32))) goto fail;
-    a.rpow = (const u64*)d;
-    zk_launch_cpa_rpow(s->stream, r, (u64*)d);
+    u64 rh[4];
+    RC_TRY(host_words(s, rh, t->randomness, 32, dev, "randomness"));
+    u64* d_rpow = nullptr;
+    RC_TRY(dev_buf(s, d_rpow, CPA_RPOW_ROWS * 32));
+    a.rpow = d_rpow;
+    zk_launch_cpa_rpow(s->stream, fr_from_words(rh), d_rpow);
     // the plan vectors go out of scope with this call
-    if (hipStreamSynchronize(s->stream) != hipSuccess) { rc = -2; g_err = "zk_copy_assign_open: upload failed"; goto fail; }
-    if ((rc = dev_alloc(s, &d, pl.chunks.size() * 32))) goto fail;
-    a.chunk_acc = (u64*)d;
-    if ((rc = dev_alloc(s, &d, pl.chunks.size() * 32))) goto fail;
-    a.chunk_in = (u64*)d;
-    if ((rc = dev_alloc(s, &d, (size_t)t->n_events * 32))) goto fail;
-    a.ev_rlc = (u64*)d;
+    DEV_TRY(hipStreamSynchronize(s->stream) == hipSuccess, "zk_copy_assign_open: upload failed");
+    RC_TRY(dev_buf(s, a.chunk_acc, pl.chunks.size() * 32));
+    RC_TRY(dev_buf(s, a.chunk_in, pl.chunks.size() * 32));
+    RC_TRY(dev_buf(s, a.ev_rlc, (size_t)t->n_events * 32));
     a.rlc = nullptr;  // the row lanes compute the running values themselves (copy_assign.hpp cpa_rlc_value)
-    a.rows = rows_dev; a.row_flags = row_flags_dev; a.table = table_dev; a.rw = rw_dev; a.rw_flags = rw_flags_dev;
-    if (!a.rows && (rc = dev_alloc(s, (void**)&a.rows, (size_t)pl.n_rows * CPA_ROW_NCELLS * 32))) goto fail;
-    if (!a.row_flags && (rc = dev_alloc(s, (void**)&a.row_flags, (size_t)pl.n_rows * 4))) goto fail;
-    if (!a.table && (rc = dev_alloc(s, (void**)&a.table, (size_t)pl.n_table * CPA_TABLE_NCELLS * 32))) goto fail;
-    if (!a.rw && (rc = dev_alloc(s, (void**)&a.rw, (size_t)pl.n_rw * CPA_RW_NCELLS * 32))) goto fail;
-    if (!a.rw_flags && (rc = dev_alloc(s, (void**)&a.rw_flags, (size_t)pl.n_rw * 4))) goto fail;
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(out_buf(s, a.rows, rows_dev, (size_t)pl.n_rows * CPA_ROW_NCELLS * 32));
+    RC_TRY(out_buf(s, a.row_flags, row_flags_dev, (size_t)pl.n_rows * 4));
+    RC_TRY(out_buf(s, a.table, table_dev, (size_t)pl.n_table * CPA_TABLE_NCELLS * 32));
+    RC_TRY(out_buf(s, a.rw, rw_dev, (size_t)pl.n_rw * CPA_RW_NCELLS * 32));
+    RC_TRY(out_buf(s, a.rw_flags, rw_flags_dev, (size_t)pl.n_rw * 4));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 // the copies of a read, enqueued on the session's stream (the caller synchronises)
 static int cpa_read_enqueue(zk_session* s, uint64_t* rows_host, uint32_t* row_flags_host, uint64_t* table_host, uint64_t* rw_host, uint32_t* rw_flags_host) {
     const CpaArgs& a = s->cpa;
-    if (rows_host) HIP_TRY(hipMemcpyAsync(rows_host, a.rows, (size_t)a.n_rows * CPA_ROW_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
-    if (row_flags_host) HIP_TRY(hipMemcpyAsync(row_flags_host, a.row_flags, (size_t)a.n_rows * 4, hipMemcpyDeviceToHost, s->stream));
-    if (table_host && s->cpa_n_table) HIP_TRY(hipMemcpyAsync(table_host, a.table, (size_t)s->cpa_n_table * CPA_TABLE_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
-    if (rw_host && s->cpa_n_rw) HIP_TRY(hipMemcpyAsync(rw_host, a.rw, (size_t)s->cpa_n_rw * CPA_RW_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
-    if (rw_flags_host && s->cpa_n_rw) HIP_TRY(hipMemcpyAsync(rw_flags_host, a.rw_flags, (size_t)s->cpa_n_rw * 4, hipMemcpyDeviceToHost, s->stream));
+    RC_TRY(d2h_out(s, rows_host, a.rows, (size_t)a.n_rows * CPA_ROW_NCELLS * 32));
+    RC_TRY(d2h_out(s, row_flags_host, a.row_flags, (size_t)a.n_rows * 4));
+    RC_TRY(d2h_out(s, table_host, a.table, (size_t)s->cpa_n_table * CPA_TABLE_NCELLS * 32));
+    RC_TRY(d2h_out(s, rw_host, a.rw, (size_t)s->cpa_n_rw * CPA_RW_NCELLS * 32));
+    RC_TRY(d2h_out(s, rw_flags_host, a.rw_flags, (size_t)s->cpa_n_rw * 4));
     return 0;
 }
 extern "C" int zk_copy_assign_read(zk_session* s, uint64_t* rows_host, uint32_t* row_flags_host, uint64_t* table_host,
                                    uint64_t* rw_host, uint32_t* rw_flags_host) {
     ARG_TRY(s && s->kind == SESSION_CPA, "zk_copy_assign_read: bad arguments");
     HIP_TRY(hipSetDevice(s->device));
-    if (int rc = cpa_read_enqueue(s, rows_host, row_flags_host, table_host, rw_host, rw_flags_host)) return rc;
+    RC_TRY(cpa_read_enqueue(s, rows_host, row_flags_host, table_host, rw_host, rw_flags_host));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
 }
@@ -2274,14 +2164,11 @@ extern "C" int zk_copy_assign(const zk_copy_events* t, uint64_t* rows_out, uint3
     ARG_TRY(result && rows_out && row_flags_out, "zk_copy_assign: null output");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_copy_assign_open(t, dev ? rows_out : nullptr, dev ? row_flags_out : nullptr, dev ? table_out : nullptr,
-                                 dev ? rw_out : nullptr, dev ? rw_flags_out : nullptr, opts, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && !dev) rc = zk_copy_assign_read(s, rows_out, row_flags_out, table_out, rw_out, rw_flags_out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_copy_assign_open(t, dev ? rows_out : nullptr, dev ? row_flags_out : nullptr, dev ? table_out : nullptr,
+                               dev ? rw_out : nullptr, dev ? rw_flags_out : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, nullptr, result));
+    return dev ? 0 : zk_copy_assign_read(s, rows_out, row_flags_out, table_out, rw_out, rw_flags_out);
 }
 
 // ---- Copy-circuit witness assignment from raw sources (copy_sources.hpp, k_copy_sources.hip): the `data` array gathered on the device from
@@ -2315,19 +2202,19 @@ static int cps_open(const zk_copy_sources* t, uint64_t* rows_dev, uint32_t* row_
     std::vector<u32> k_flags, k_src, k_dst;
     const u64 *cells, *code_off, *cd_off;
     const u32 *flags, *src_ref, *dst_ref;
-    int rc = 0;
-    if ((rc = cps_host_view(t->events, (size_t)t->n_events * CPA_EV_NCELLS * 4, dev, k_cells, &cells))) return rc;
-    if ((rc = cps_host_view(t->flags, (size_t)t->n_events, dev, k_flags, &flags))) return rc;
-    if ((rc = cps_host_view(t->src_ref, (size_t)t->n_events, dev, k_src, &src_ref))) return rc;
-    if ((rc = cps_host_view(t->dst_ref, (size_t)t->n_events, dev, k_dst, &dst_ref))) return rc;
-    if ((rc = cps_host_view(t->code_offsets, t->n_codes ? (size_t)t->n_codes + 1 : 0, dev, k_code_off, &code_off))) return rc;
-    if ((rc = cps_host_view(t->calldata_offsets, t->n_txs ? (size_t)t->n_txs + 1 : 0, dev, k_cd_off, &cd_off))) return rc;
+    RC_TRY(cps_host_view(t->events, (size_t)t->n_events * CPA_EV_NCELLS * 4, dev, k_cells, &cells));
+    RC_TRY(cps_host_view(t->flags, (size_t)t->n_events, dev, k_flags, &flags));
+    RC_TRY(cps_host_view(t->src_ref, (size_t)t->n_events, dev, k_src, &src_ref));
+    RC_TRY(cps_host_view(t->dst_ref, (size_t)t->n_events, dev, k_dst, &dst_ref));
+    RC_TRY(cps_host_view(t->code_offsets, t->n_codes ? (size_t)t->n_codes + 1 : 0, dev, k_code_off, &code_off));
+    RC_TRY(cps_host_view(t->calldata_offsets, t->n_txs ? (size_t)t->n_txs + 1 : 0, dev, k_cd_off, &cd_off));
     CpsPlan pl;
-    if ((rc = cps_plan(cells, flags, src_ref, dst_ref, t->n_events, code_off, t->n_codes, t->n_code_bytes, cd_off, t->n_txs, pl))) return rc;
+    RC_TRY(cps_plan(cells, flags, src_ref, dst_ref, t->n_events, code_off, t->n_codes, t->n_code_bytes, cd_off, t->n_txs, pl));
     const u64 n_cd_bytes = t->n_txs ? cd_off[t->n_txs] : 0;
     ARG_TRY(n_cd_bytes == 0 || t->calldata, "zk_copy_assign_from_sources: calldata is null");
     const u64 n = tr.n_rw, n_data = pl.data0[t->n_events];
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_CPS;
     s->n = t->n_events;
     s->cpa_n_table = pl.cpa.n_table;
@@ -2340,115 +2227,73 @@ static int cps_open(const zk_copy_sources* t, uint64_t* rows_dev, uint32_t* row_
     memset(&g, 0, sizeof(g));
     memset(&c, 0, sizeof(c));
     memset(&w, 0, sizeof(w));
-    const void* p = nullptr;
-    void* d = nullptr;
-    u64 v[TRW_V_WORDS], rh[4];
-    Fr r;
     // the trace's heads and counters: checked as zk_evm_witness_from_trace_open checks them, the session keeps its own copies
-    if ((rc = stage(s, tr.head, (size_t)n * 4, dev, &p))) goto fail;
-    w.head_in = (const u32*)p;
-    if (tr.rw_counter && n) {
-        if ((rc = stage(s, tr.rw_counter, (size_t)n * 8, dev, &p))) goto fail;
-        w.ctr_in = (const u64*)p;
-    }
+    RC_TRY(stage_in(s, w.head_in, tr.head, (size_t)n * 4, dev));
+    if (tr.rw_counter && n) RC_TRY(stage_in(s, w.ctr_in, tr.rw_counter, (size_t)n * 8, dev));
     w.n_rw = n; w.rw_base = tr.rw_base;
-    if ((rc = dev_alloc(s, &d, (size_t)n * 4 + 4))) goto fail;
-    w.head = (u32*)d;
-    if (w.ctr_in) {
-        if ((rc = dev_alloc(s, &d, (size_t)n * 8))) goto fail;
-        w.ctr = (u64*)d;
-    }
-    if ((rc = dev_alloc(s, &d, TRW_V_WORDS * 8))) goto fail;
-    w.verdict = (u64*)d;
+    RC_TRY(dev_buf(s, w.head, (size_t)n * 4 + 4));
+    if (w.ctr_in) RC_TRY(dev_buf(s, w.ctr, (size_t)n * 8));
+    RC_TRY(dev_buf(s, w.verdict, TRW_V_WORDS * 8));
     zk_launch_trace_witness_check(s->stream, w, false);  // (no pool offsets: the pool is not read, the verdict's pool word stays 0)
-    if (hipGetLastError() != hipSuccess) { rc = -2; g_err = "zk_copy_assign_from_sources: the open's check launch failed"; goto fail; }
-    if ((rc = d2h_now(s->stream, v, w.verdict, sizeof v))) goto fail;
-    if ((rc = trw_verdict_error(v, 0, msg, sizeof msg))) { g_err = msg; cps_retitle(name); goto fail; }
+    DEV_TRY(hipGetLastError() == hipSuccess, "zk_copy_assign_from_sources: the open's check launch failed");
+    u64 v[TRW_V_WORDS];
+    RC_TRY(d2h_now(s->stream, v, w.verdict, sizeof v));
+    if (int rc = trw_verdict_error(v, 0, msg, sizeof msg)) { g_err = msg; cps_retitle(name); return rc; }
     if (counts) { counts[0] = pl.cpa.n_rows; counts[1] = pl.cpa.n_table; counts[2] = pl.cpa.n_rw; counts[3] = n_data; }
-    if (check_only) {
-        zk_close(s);
-        return 0;
-    }
+    if (check_only) return 0;
     // the Copy assignment's arguments, as zk_copy_assign_open sets them, over the gathered array
-    if ((rc = stage(s, t->events, (size_t)t->n_events * CPA_EV_NCELLS * 32, dev, &p))) goto fail;
-    a.events = g.events = (const u64*)p;
-    if ((rc = stage(s, pl.cpa.ev.data(), pl.cpa.ev.size() * sizeof(CpaEvent), false, &p))) goto fail;
-    a.ev = g.ev = (const CpaEvent*)p;
-    if ((rc = stage(s, pl.cpa.row0.data(), pl.cpa.row0.size() * 8, false, &p))) goto fail;
-    a.row0 = (const u64*)p;
-    if ((rc = stage(s, pl.cpa.chunks.empty() ? nullptr : pl.cpa.chunks.data(), pl.cpa.chunks.size() * sizeof(CpaChunk), false, &p))) goto fail;
-    a.chunks = (const CpaChunk*)p;
+    RC_TRY(stage_in(s, a.events, t->events, (size_t)t->n_events * CPA_EV_NCELLS * 32, dev));
+    g.events = a.events;
+    RC_TRY(stage_in(s, a.ev, pl.cpa.ev.data(), pl.cpa.ev.size() * sizeof(CpaEvent), false));
+    g.ev = a.ev;
+    RC_TRY(stage_in(s, a.row0, pl.cpa.row0.data(), pl.cpa.row0.size() * 8, false));
+    RC_TRY(stage_in(s, a.chunks, pl.cpa.chunks.empty() ? nullptr : pl.cpa.chunks.data(), pl.cpa.chunks.size() * sizeof(CpaChunk), false));
     a.n_events = g.n_events = t->n_events; a.n_rows = pl.cpa.n_rows; a.n_chunks = pl.cpa.chunks.size();
-    if (dev) {
-        if (fetch_small(s->stream, rh, t->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
-    } else {
-        memcpy(rh, t->randomness, 32);
-    }
-    for (int q = 0; q < 4; q++) { r.v[2 * q] = (u32)rh[q]; r.v[2 * q + 1] = (u32)(rh[q] >> 32); }
-    if ((rc = dev_alloc(s, &d, CPA_RPOW_ROWS * 32))) goto fail;
-    a.rpow = (const u64*)d;
-    zk_launch_cpa_rpow(s->stream, r, (u64*)d);
+    u64 rh[4];
+    RC_TRY(host_words(s, rh, t->randomness, 32, dev, "randomness"));
+    u64* d_rpow = nullptr;
+    RC_TRY(dev_buf(s, d_rpow, CPA_RPOW_ROWS * 32));
+    a.rpow = d_rpow;
+    zk_launch_cpa_rpow(s->stream, fr_from_words(rh), d_rpow);
     // the gather's: the plan's tables (the session's copies of everything a store or a load is indexed by) and the caller's bytes
-    if ((rc = stage(s, pl.sev.data(), pl.sev.size() * sizeof(CpsEv), false, &p))) goto fail;
-    g.sev = (const CpsEv*)p;
-    if ((rc = stage(s, pl.data0.data(), pl.data0.size() * 8, false, &p))) goto fail;
-    g.data0 = (const u64*)p;
+    RC_TRY(stage_in(s, g.sev, pl.sev.data(), pl.sev.size() * sizeof(CpsEv), false));
+    RC_TRY(stage_in(s, g.data0, pl.data0.data(), pl.data0.size() * 8, false));
     g.n_data = n_data;
-    if ((rc = stage(s, t->code, (size_t)t->n_code_bytes, dev, &p))) goto fail;
-    g.code = c.code = (const uint8_t*)p;
-    if ((rc = stage(s, t->calldata, (size_t)n_cd_bytes, dev, &p))) goto fail;
-    g.calldata = (const uint8_t*)p;
-    if ((rc = stage(s, tr.id, (size_t)n * 8, dev, &p))) goto fail;
-    g.id = (const u64*)p;
-    if ((rc = stage(s, tr.addr, (size_t)n * 8, dev, &p))) goto fail;
-    g.addr = (const u64*)p;
-    if ((rc = stage(s, tr.val, (size_t)n * 8, dev, &p))) goto fail;
-    g.val = (const u64*)p;
+    RC_TRY(stage_in(s, g.code, t->code, (size_t)t->n_code_bytes, dev));
+    c.code = g.code;
+    RC_TRY(stage_in(s, g.calldata, t->calldata, (size_t)n_cd_bytes, dev));
+    RC_TRY(stage_in(s, g.id, tr.id, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, g.addr, tr.addr, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, g.val, tr.val, (size_t)n * 8, dev));
     g.head = w.head; g.ctr = w.ctr; g.n_rw = n; g.rw_base = tr.rw_base;
     if (pl.any_code) {  // the is_code scan of the code set (every pass: the code bytes are the caller's)
-        if ((rc = stage(s, code_off, ((size_t)t->n_codes + 1) * 8, false, &p))) goto fail;
-        c.offsets = (const u64*)p;
-        if ((rc = stage(s, pl.chunk0.data(), pl.chunk0.size() * 4, false, &p))) goto fail;
-        c.chunk0 = (const u32*)p;
-        if ((rc = stage(s, pl.seg0.data(), pl.seg0.size() * 4, false, &p))) goto fail;
-        c.seg0 = (const u32*)p;
+        RC_TRY(stage_in(s, c.offsets, code_off, ((size_t)t->n_codes + 1) * 8, false));
+        RC_TRY(stage_in(s, c.chunk0, pl.chunk0.data(), pl.chunk0.size() * 4, false));
+        RC_TRY(stage_in(s, c.seg0, pl.seg0.data(), pl.seg0.size() * 4, false));
         c.n_codes = (u32)t->n_codes; c.n_segs = (u32)pl.n_segs; c.n_chunks = pl.n_chunks;
-        if ((rc = dev_alloc(s, &d, (size_t)pl.n_chunks * CPS_MAP_STRIDE))) goto fail;
-        c.chunk_in = (uint8_t*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)pl.n_segs * CPS_MAP_STRIDE))) goto fail;
-        c.seg_map = (uint8_t*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)pl.n_segs))) goto fail;
-        c.seg_state = (uint8_t*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)pl.n_chunks * 8))) goto fail;
-        c.mask = (u64*)d;
+        RC_TRY(dev_buf(s, c.chunk_in, (size_t)pl.n_chunks * CPS_MAP_STRIDE));
+        RC_TRY(dev_buf(s, c.seg_map, (size_t)pl.n_segs * CPS_MAP_STRIDE));
+        RC_TRY(dev_buf(s, c.seg_state, (size_t)pl.n_segs));
+        RC_TRY(dev_buf(s, c.mask, (size_t)pl.n_chunks * 8));
         g.code_mask = c.mask;
     }
     // the plan vectors and the host views go out of scope with this call
-    if (hipStreamSynchronize(s->stream) != hipSuccess) { rc = -2; g_err = "zk_copy_assign_from_sources_open: upload failed"; goto fail; }
-    if ((rc = dev_alloc(s, &d, (size_t)t->n_events * 8))) goto fail;
-    g.ev_fail = (unsigned long long*)d;
-    g.data = data_dev;
-    if (!g.data && (rc = dev_alloc(s, (void**)&g.data, (size_t)n_data * 2))) goto fail;
+    DEV_TRY(hipStreamSynchronize(s->stream) == hipSuccess, "zk_copy_assign_from_sources_open: upload failed");
+    RC_TRY(dev_buf(s, g.ev_fail, (size_t)t->n_events * 8));
+    RC_TRY(out_buf(s, g.data, data_dev, (size_t)n_data * 2));
     a.data = g.data;
-    if ((rc = dev_alloc(s, &d, pl.cpa.chunks.size() * 32))) goto fail;
-    a.chunk_acc = (u64*)d;
-    if ((rc = dev_alloc(s, &d, pl.cpa.chunks.size() * 32))) goto fail;
-    a.chunk_in = (u64*)d;
-    if ((rc = dev_alloc(s, &d, (size_t)t->n_events * 32))) goto fail;
-    a.ev_rlc = (u64*)d;
-    a.rows = rows_dev; a.row_flags = row_flags_dev; a.table = table_dev; a.rw = rw_dev; a.rw_flags = rw_flags_dev;
-    if (!a.rows && (rc = dev_alloc(s, (void**)&a.rows, (size_t)pl.cpa.n_rows * CPA_ROW_NCELLS * 32))) goto fail;
-    if (!a.row_flags && (rc = dev_alloc(s, (void**)&a.row_flags, (size_t)pl.cpa.n_rows * 4))) goto fail;
-    if (!a.table && (rc = dev_alloc(s, (void**)&a.table, (size_t)pl.cpa.n_table * CPA_TABLE_NCELLS * 32))) goto fail;
-    if (!a.rw && (rc = dev_alloc(s, (void**)&a.rw, (size_t)pl.cpa.n_rw * CPA_RW_NCELLS * 32))) goto fail;
-    if (!a.rw_flags && (rc = dev_alloc(s, (void**)&a.rw_flags, (size_t)pl.cpa.n_rw * 4))) goto fail;
+    RC_TRY(dev_buf(s, a.chunk_acc, pl.cpa.chunks.size() * 32));
+    RC_TRY(dev_buf(s, a.chunk_in, pl.cpa.chunks.size() * 32));
+    RC_TRY(dev_buf(s, a.ev_rlc, (size_t)t->n_events * 32));
+    RC_TRY(out_buf(s, a.rows, rows_dev, (size_t)pl.cpa.n_rows * CPA_ROW_NCELLS * 32));
+    RC_TRY(out_buf(s, a.row_flags, row_flags_dev, (size_t)pl.cpa.n_rows * 4));
+    RC_TRY(out_buf(s, a.table, table_dev, (size_t)pl.cpa.n_table * CPA_TABLE_NCELLS * 32));
+    RC_TRY(out_buf(s, a.rw, rw_dev, (size_t)pl.cpa.n_rw * CPA_RW_NCELLS * 32));
+    RC_TRY(out_buf(s, a.rw_flags, rw_flags_dev, (size_t)pl.cpa.n_rw * 4));
     s->cps_data0.swap(pl.data0);
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_copy_assign_from_sources_sizes(const zk_copy_sources* t, uint32_t opts, uint64_t* n_rows, uint64_t* n_table, uint64_t* n_rw,
                                                  uint64_t* n_data) {
@@ -2456,8 +2301,7 @@ extern "C" int zk_copy_assign_from_sources_sizes(const zk_copy_sources* t, uint3
     HIP_TRY(hipSetDevice(t_device));
     ARG_TRY(CPS_ARGS_OK(t), "zk_copy_assign_from_sources_sizes: bad arguments");
     u64 counts[4];
-    const int rc = cps_open(t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, opts, true, counts, nullptr);
-    if (rc) return rc;
+    RC_TRY(cps_open(t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, opts, true, counts, nullptr));
     if (n_rows) *n_rows = counts[0];
     if (n_table) *n_table = counts[1];
     if (n_rw) *n_rw = counts[2];
@@ -2477,8 +2321,8 @@ extern "C" int zk_copy_assign_from_sources_read(zk_session* s, uint64_t* rows_ho
                                                 uint64_t* rw_host, uint32_t* rw_flags_host, uint16_t* data_host, uint64_t* data_offsets_host) {
     ARG_TRY(s && s->kind == SESSION_CPS, "zk_copy_assign_from_sources_read: bad arguments");
     HIP_TRY(hipSetDevice(s->device));
-    if (int rc = cpa_read_enqueue(s, rows_host, row_flags_host, table_host, rw_host, rw_flags_host)) return rc;
-    if (data_host && s->cps.n_data) HIP_TRY(hipMemcpyAsync(data_host, s->cps.data, (size_t)s->cps.n_data * 2, hipMemcpyDeviceToHost, s->stream));
+    RC_TRY(cpa_read_enqueue(s, rows_host, row_flags_host, table_host, rw_host, rw_flags_host));
+    RC_TRY(d2h_out(s, data_host, s->cps.data, (size_t)s->cps.n_data * 2));
     HIP_TRY(hipStreamSynchronize(s->stream));
     if (data_offsets_host) memcpy(data_offsets_host, s->cps_data0.data(), s->cps_data0.size() * 8);
     return 0;
@@ -2489,17 +2333,13 @@ extern "C" int zk_copy_assign_from_sources(const zk_copy_sources* t, uint64_t* r
     ARG_TRY(result && rows_out && row_flags_out, "zk_copy_assign_from_sources: null output");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_copy_assign_from_sources_open(t, dev ? rows_out : nullptr, dev ? row_flags_out : nullptr, dev ? table_out : nullptr,
-                                              dev ? rw_out : nullptr, dev ? rw_flags_out : nullptr, dev ? data_out : nullptr, opts, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, dev ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && !dev && status_out) rc = zk_read_status(s, status_out);
+    RC_TRY(zk_copy_assign_from_sources_open(t, dev ? rows_out : nullptr, dev ? row_flags_out : nullptr, dev ? table_out : nullptr,
+                                            dev ? rw_out : nullptr, dev ? rw_flags_out : nullptr, dev ? data_out : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, status_out, result));
     // (data_offsets_out is host arithmetic over the events: a HOST array of n_events + 1 entries in either mode)
-    if (!rc) rc = dev ? zk_copy_assign_from_sources_read(s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, data_offsets_out)
-                      : zk_copy_assign_from_sources_read(s, rows_out, row_flags_out, table_out, rw_out, rw_flags_out, data_out, data_offsets_out);
-    zk_close(s);
-    return rc;
+    return dev ? zk_copy_assign_from_sources_read(s, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, data_offsets_out)
+               : zk_copy_assign_from_sources_read(s, rows_out, row_flags_out, table_out, rw_out, rw_flags_out, data_out, data_offsets_out);
 }
 
 // ---- Exp-circuit witness assignment
@@ -2507,22 +2347,19 @@ extern "C" int zk_copy_assign_from_sources(const zk_copy_sources* t, uint64_t* r
 // read back (the one wait of the open).  `s` owns the buffers; on a rejected event the error code is returned with its text.
 static int exa_size_pass(const zk_exp_events* t, bool dev, zk_session* s, ExaSizes& z) {
     ExaArgs& a = s->exa;
-    const void* p = nullptr;
-    int rc = stage(s, t->n_events ? t->events : nullptr, (size_t)t->n_events * EXA_EV_NCELLS * 32, dev, &p);
-    if (rc) return rc;
-    a.events = (const u64*)p;
+    RC_TRY(stage_in(s, a.events, t->n_events ? t->events : nullptr, (size_t)t->n_events * EXA_EV_NCELLS * 32, dev));
     a.n_events = t->n_events;
-    if ((rc = dev_alloc(s, (void**)&a.count, (size_t)(t->n_events + 1) * 4))) return rc;
-    if ((rc = dev_alloc(s, (void**)&a.row0, (size_t)(t->n_events + 1) * 8))) return rc;
-    if ((rc = dev_alloc(s, (void**)&a.meta, 16))) return rc;
+    RC_TRY(dev_buf(s, a.count, (size_t)(t->n_events + 1) * 4));
+    RC_TRY(dev_buf(s, a.row0, (size_t)(t->n_events + 1) * 8));
+    RC_TRY(dev_buf(s, a.meta, 16));
     u64 meta[2] = {EXA_NO_REJECT, 0};
     HIP_TRY(hipMemcpyAsync(a.meta, meta, 16, hipMemcpyHostToDevice, s->stream));
     HIP_TRY(hipMemsetAsync(a.row0, 0, (size_t)(t->n_events + 1) * 8, s->stream));
     zk_launch_exp_assign_sizes(s->stream, a);
     HIP_TRY(hipGetLastError());
-    if ((rc = d2h_now(s->stream, meta, a.meta, 16))) return rc;
+    RC_TRY(d2h_now(s->stream, meta, a.meta, 16));
     char msg[256];
-    if ((rc = exa_sizes_of(meta[0], meta[1], t->max_exp_steps, z, msg, sizeof msg))) { g_err = msg; return rc; }
+    if (int rc = exa_sizes_of(meta[0], meta[1], t->max_exp_steps, z, msg, sizeof msg)) { g_err = msg; return rc; }
     a.n_step = z.n_step;
     a.n_rows = z.n_rows;
     return 0;
@@ -2531,12 +2368,11 @@ extern "C" int zk_exp_assign_sizes(const zk_exp_events* t, uint32_t opts, uint64
     ARG_TRY(t_device >= 0, "zk_exp_assign_sizes: call zk_init first");
     HIP_TRY(hipSetDevice(t_device));
     ARG_TRY(t && (t->events || t->n_events == 0) && t->n_events < (1ull << 31), "zk_exp_assign_sizes: bad arguments");
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_EXA;
     ExaSizes z;
-    const int rc = exa_size_pass(t, opts & ZK_OPT_DEVICE_PTRS, s, z);
-    zk_close(s);
-    if (rc) return rc;
+    RC_TRY(exa_size_pass(t, opts & ZK_OPT_DEVICE_PTRS, s, z));
     if (n_rows) *n_rows = z.n_rows;
     if (n_step_rows) *n_step_rows = z.n_step;
     if (n_table) *n_table = z.n_table;
@@ -2549,26 +2385,22 @@ static int exa_open(const zk_exp_events* t, uint64_t* rows_dev, uint64_t* table_
     ARG_TRY(t && out && (t->events || t->n_events == 0) && t->n_events < (1ull << 31), "zk_exp_assign_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     ARG_TRY(dev || (!rows_dev && !table_dev), "zk_exp_assign_open: output buffers need ZK_OPT_DEVICE_PTRS");
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_EXA;
     ExaArgs& a = s->exa;
     ExaSizes z;
-    int rc = exa_size_pass(t, dev, s, z);
-    if (rc) goto fail;
-    if (z.n_rows == 0 && allow_empty) { zk_close(s); *out = nullptr; return 0; }
-    if (z.n_rows == 0) { rc = -1; g_err = "zk_exp_assign_open: no rows (every exponent is 0 or 1 and max_exp_steps is 0)"; goto fail; }
+    RC_TRY(exa_size_pass(t, dev, s, z));
+    if (z.n_rows == 0 && allow_empty) { *out = nullptr; return 0; }
+    ARG_TRY(z.n_rows != 0, "zk_exp_assign_open: no rows (every exponent is 0 or 1 and max_exp_steps is 0)");
     s->n = z.n_rows;
     s->exa_n_table = z.n_table;
-    if ((rc = dev_alloc(s, (void**)&a.d, (size_t)(z.n_step + 1) * 32))) goto fail;
-    a.rows = rows_dev; a.table = table_dev;
-    if (!a.rows && (rc = dev_alloc(s, (void**)&a.rows, (size_t)z.n_rows * EXA_ROW_NCELLS * 32))) goto fail;
-    if (!a.table && (rc = dev_alloc(s, (void**)&a.table, (size_t)z.n_table * EXA_TABLE_NCELLS * 32))) goto fail;
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(dev_buf(s, a.d, (size_t)(z.n_step + 1) * 32));
+    RC_TRY(out_buf(s, a.rows, rows_dev, (size_t)z.n_rows * EXA_ROW_NCELLS * 32));
+    RC_TRY(out_buf(s, a.table, table_dev, (size_t)z.n_table * EXA_TABLE_NCELLS * 32));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_exp_assign_open(const zk_exp_events* t, uint64_t* rows_dev, uint64_t* table_dev, uint32_t opts, zk_session** out) {
     return exa_open(t, rows_dev, table_dev, opts, out, false);
@@ -2584,8 +2416,8 @@ extern "C" int zk_exp_assign_read(zk_session* s, uint64_t* rows_host, uint64_t* 
     ARG_TRY(s && s->kind == SESSION_EXA, "zk_exp_assign_read: bad arguments");
     HIP_TRY(hipSetDevice(s->device));
     const ExaArgs& a = s->exa;
-    if (rows_host) HIP_TRY(hipMemcpyAsync(rows_host, a.rows, (size_t)a.n_rows * EXA_ROW_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
-    if (table_host && s->exa_n_table) HIP_TRY(hipMemcpyAsync(table_host, a.table, (size_t)s->exa_n_table * EXA_TABLE_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+    RC_TRY(d2h_out(s, rows_host, a.rows, (size_t)a.n_rows * EXA_ROW_NCELLS * 32));
+    RC_TRY(d2h_out(s, table_host, a.table, (size_t)s->exa_n_table * EXA_TABLE_NCELLS * 32));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
 }
@@ -2593,13 +2425,10 @@ extern "C" int zk_exp_assign(const zk_exp_events* t, uint64_t* rows_out, uint64_
     ARG_TRY(result && rows_out, "zk_exp_assign: null output");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_exp_assign_open(t, dev ? rows_out : nullptr, dev ? table_out : nullptr, opts, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && !dev) rc = zk_exp_assign_read(s, rows_out, table_out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_exp_assign_open(t, dev ? rows_out : nullptr, dev ? table_out : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, nullptr, result));
+    return dev ? 0 : zk_exp_assign_read(s, rows_out, table_out);
 }
 
 // ---- PI-circuit witness assignment
@@ -2610,63 +2439,50 @@ extern "C" int zk_exp_assign(const zk_exp_events* t, uint64_t* rows_out, uint64_
 static int pia_prepare(const zk_pi_inputs* t, bool dev, zk_session* s, PiaSizes& z) {
     PiaArgs& a = s->pia;
     char msg[256];
-    u64 total = 0, rh[8];
-    int rc = 0;
-    if (dev) { if ((rc = fetch_small(s->stream, &total, t->calldata_offsets + t->n_txs, 8))) return rc; }
+    u64 total = 0;
+    if (dev) RC_TRY(fetch_small(s->stream, &total, t->calldata_offsets + t->n_txs, 8));
     else total = t->calldata_offsets[t->n_txs];
-    if ((rc = pia_sizes_of(t->n_txs, t->n_withdrawals, total, t->max_txs, t->max_calldata_bytes, t->max_withdrawals, z, msg, sizeof msg))) { g_err = msg; return rc; }
+    if (int rc = pia_sizes_of(t->n_txs, t->n_withdrawals, total, t->max_txs, t->max_calldata_bytes, t->max_withdrawals, z, msg, sizeof msg)) {
+        g_err = msg;
+        return rc;
+    }
     ARG_TRY(t->calldata || total == 0, "zk_pi_assign: calldata is null");
-    const void* p = nullptr;
-    if ((rc = stage(s, t->block, PIA_NBLOCK_FIELDS * 32, dev, &p))) return rc;
-    a.block = (const u64*)p;
-    if ((rc = stage(s, t->state_root_prev, 32, dev, &p))) return rc;
-    a.srp = (const u64*)p;
-    if ((rc = stage(s, t->block_hashes, 256 * 32, dev, &p))) return rc;
-    a.hashes = (const u64*)p;
-    if ((rc = stage(s, t->tx_fields, (size_t)t->n_txs * PIA_NTX_FIELDS * 32, dev, &p))) return rc;
-    a.txf = (const u64*)p;
-    if ((rc = stage(s, t->to_is_none, (size_t)t->n_txs * 4, dev, &p))) return rc;
-    a.to_none = (const u32*)p;
-    if ((rc = stage(s, t->calldata, (size_t)total, dev, &p))) return rc;
-    a.calldata = (const uint8_t*)p;
-    if ((rc = stage(s, t->calldata_offsets, (size_t)(t->n_txs + 1) * 8, dev, &p))) return rc;
-    a.offs = (const u64*)p;
-    if ((rc = stage(s, t->withdrawals, (size_t)t->n_withdrawals * PIA_NWD_FIELDS * 32, dev, &p))) return rc;
-    a.wd = (const u64*)p;
+    RC_TRY(stage_in(s, a.block, t->block, PIA_NBLOCK_FIELDS * 32, dev));
+    RC_TRY(stage_in(s, a.srp, t->state_root_prev, 32, dev));
+    RC_TRY(stage_in(s, a.hashes, t->block_hashes, 256 * 32, dev));
+    RC_TRY(stage_in(s, a.txf, t->tx_fields, (size_t)t->n_txs * PIA_NTX_FIELDS * 32, dev));
+    RC_TRY(stage_in(s, a.to_none, t->to_is_none, (size_t)t->n_txs * 4, dev));
+    RC_TRY(stage_in(s, a.calldata, t->calldata, (size_t)total, dev));
+    RC_TRY(stage_in(s, a.offs, t->calldata_offsets, (size_t)(t->n_txs + 1) * 8, dev));
+    RC_TRY(stage_in(s, a.wd, t->withdrawals, (size_t)t->n_withdrawals * PIA_NWD_FIELDS * 32, dev));
     a.chain_id = t->chain_id;
     a.n_txs = t->n_txs; a.n_wd = t->n_withdrawals; a.max_txs = t->max_txs; a.max_cd = t->max_calldata_bytes; a.max_wd = t->max_withdrawals;
     a.total_cd = total;
     pia_set_layout(a, z);
-    if (dev) {
-        if (fetch_small(s->stream, rh, t->keccak_rand, 32) || fetch_small(s->stream, rh + 4, t->byte_pow_base, 32)) { g_err = "zk_pi_assign: randomness download failed"; return -2; }
-    } else {
-        memcpy(rh, t->keccak_rand, 32);
-        memcpy(rh + 4, t->byte_pow_base, 32);
-    }
-    Fr r, b;
-    for (int q = 0; q < 4; q++) { r.v[2 * q] = (u32)rh[q]; r.v[2 * q + 1] = (u32)(rh[q] >> 32); b.v[2 * q] = (u32)rh[4 + q]; b.v[2 * q + 1] = (u32)(rh[4 + q] >> 32); }
-    a.rand = r;
-    a.base = b;
-    if ((rc = dev_alloc(s, (void**)&a.meta, 32))) return rc;
+    u64 rh[8];
+    RC_TRY(host_words(s, rh, t->keccak_rand, 32, dev, "zk_pi_assign: randomness"));
+    RC_TRY(host_words(s, rh + 4, t->byte_pow_base, 32, dev, "zk_pi_assign: randomness"));
+    a.rand = fr_from_words(rh);
+    a.base = fr_from_words(rh + 4);
+    RC_TRY(dev_buf(s, a.meta, 32));
     s->pia_host[0] = PIA_NO_REJECT;
     HIP_TRY(hipMemcpyAsync(a.meta, s->pia_host, 8, hipMemcpyHostToDevice, s->stream));
     zk_launch_pi_assign_check(s->stream, a);
     HIP_TRY(hipGetLastError());
     u64 meta = PIA_NO_REJECT;
-    if ((rc = d2h_now(s->stream, &meta, a.meta, 8))) return rc;  // the one wait of sizes / open
-    if (meta != PIA_NO_REJECT) { rc = pia_reject_text(meta, msg, sizeof msg); g_err = msg; return rc; }
+    RC_TRY(d2h_now(s->stream, &meta, a.meta, 8));  // the one wait of sizes / open
+    if (meta != PIA_NO_REJECT) { const int rc = pia_reject_text(meta, msg, sizeof msg); g_err = msg; return rc; }
     return 0;
 }
 // what only an open needs: the power table, the small inverses, and the keccak kernels' arguments (one message: the generation-order buffer)
 static int pia_tables(zk_session* s, const PiaSizes& z) {
     PiaArgs& a = s->pia;
-    int rc = 0;
-    if ((rc = dev_alloc(s, (void**)&a.rpow, ((size_t)PIA_TILE + 1) * 32))) return rc;
-    if ((rc = dev_alloc(s, (void**)&a.inv_small, (size_t)a.n_inv * 32))) return rc;
+    RC_TRY(dev_buf(s, a.rpow, ((size_t)PIA_TILE + 1) * 32));
+    RC_TRY(dev_buf(s, a.inv_small, (size_t)a.n_inv * 32));
     zk_launch_pi_assign_tables(s->stream, a);
     u64* kbuf = nullptr;
-    if ((rc = dev_alloc(s, (void**)&kbuf, (KT_NCELLS * 4 + (size_t)KT_RPOW_ROWS * 4 + 4) * 8))) return rc;
-    if ((rc = dev_alloc(s, (void**)&a.gen, (size_t)z.n + 8))) return rc;
+    RC_TRY(dev_buf(s, kbuf, (KT_NCELLS * 4 + (size_t)KT_RPOW_ROWS * 4 + 4) * 8));
+    RC_TRY(dev_buf(s, a.gen, (size_t)z.n + 8));
     a.krow = kbuf;
     KeccakGenArgs& g = s->pia_kgen;
     u64* offs = kbuf + KT_NCELLS * 4 + (size_t)KT_RPOW_ROWS * 4;
@@ -2683,12 +2499,11 @@ extern "C" int zk_pi_assign_sizes(const zk_pi_inputs* t, uint32_t opts, uint64_t
     ARG_TRY(t_device >= 0, "zk_pi_assign_sizes: call zk_init first");
     HIP_TRY(hipSetDevice(t_device));
     ARG_TRY(PIA_ARGS_OK(t), "zk_pi_assign_sizes: bad arguments");
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_PIA;
     PiaSizes z;
-    const int rc = pia_prepare(t, opts & ZK_OPT_DEVICE_PTRS, s, z);
-    zk_close(s);
-    if (rc) return rc;
+    RC_TRY(pia_prepare(t, opts & ZK_OPT_DEVICE_PTRS, s, z));
     if (circuit_len) *circuit_len = z.n;
     if (n_gas) *n_gas = z.n_gas;
     if (n_constraints) *n_constraints = z.n_cc;
@@ -2700,71 +2515,58 @@ extern "C" int zk_pi_assign_open(const zk_pi_inputs* t, const zk_pi_wire* out_de
     ARG_TRY(PIA_ARGS_OK(t) && out, "zk_pi_assign_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     ARG_TRY(dev || !out_dev, "zk_pi_assign_open: output buffers need ZK_OPT_DEVICE_PTRS");
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_PIA;
     PiaArgs& a = s->pia;
     PiaSizes& z = s->pia_sizes;
-    int rc = pia_prepare(t, dev, s, z);
-    if (rc) goto fail;
-    if ((rc = pia_tables(s, z))) goto fail;
+    RC_TRY(pia_prepare(t, dev, s, z));
+    RC_TRY(pia_tables(s, z));
     s->n = z.n;
-    if ((rc = dev_alloc(s, (void**)&a.gas_local, ((size_t)a.total_cd + 1) * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.gas_tile, ((size_t)a.n_gas_tiles + 1) * 8))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.inv_txlo, ((size_t)PIA_TX_LEN * a.max_txs + 1) * 32))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.slice_acc, (size_t)a.n_tiles * 256 * 32))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.tile_acc, ((size_t)a.n_tiles + 1) * 32))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.carry, ((size_t)a.n_tiles + 1) * 32))) goto fail;
-    if (out_dev) {
-        a.rows = out_dev->rows; a.gas = out_dev->gas; a.keccak = out_dev->keccak; a.cc_cells = out_dev->cc_cells; a.cc_bytes = out_dev->cc_bytes;
-        a.cc_lens = out_dev->cc_lens; a.block_table = out_dev->block_table; a.block_flags = out_dev->block_flags; a.tx_table = out_dev->tx_table;
-        a.tx_flags = out_dev->tx_flags; a.wd_table = out_dev->wd_table; a.public_inputs = out_dev->public_inputs; a.raw_bytes = out_dev->raw_bytes;
-        a.raw_lens = out_dev->raw_lens;
-    } else {
-        a.rows = a.gas = a.keccak = a.cc_cells = a.block_table = a.tx_table = a.wd_table = a.public_inputs = nullptr;
-        a.cc_bytes = a.raw_bytes = nullptr;
-        a.cc_lens = a.block_flags = a.tx_flags = a.raw_lens = nullptr;
-    }
-    if (!a.rows && (rc = dev_alloc(s, (void**)&a.rows, (size_t)z.n * PI_NCELLS * 32))) goto fail;
-    if (!a.gas && (rc = dev_alloc(s, (void**)&a.gas, (size_t)z.n_gas * PI_GAS_NCELLS * 32))) goto fail;
-    if (!a.keccak && (rc = dev_alloc(s, (void**)&a.keccak, 2 * 5 * 32))) goto fail;
-    if (!a.cc_cells && (rc = dev_alloc(s, (void**)&a.cc_cells, (size_t)z.n_cc * 32))) goto fail;
-    if (!a.cc_bytes && (rc = dev_alloc(s, (void**)&a.cc_bytes, (size_t)z.n_cc * 32))) goto fail;
-    if (!a.cc_lens && (rc = dev_alloc(s, (void**)&a.cc_lens, (size_t)z.n_cc * 4))) goto fail;
-    if (!a.block_table && (rc = dev_alloc(s, (void**)&a.block_table, (size_t)PIA_BLOCK_ENTRIES * 2 * 32))) goto fail;
-    if (!a.block_flags && (rc = dev_alloc(s, (void**)&a.block_flags, (size_t)PIA_BLOCK_ENTRIES * 4))) goto fail;
-    if (!a.tx_table && (rc = dev_alloc(s, (void**)&a.tx_table, (size_t)z.tx_table_rows * 5 * 32))) goto fail;
-    if (!a.tx_flags && (rc = dev_alloc(s, (void**)&a.tx_flags, (size_t)z.tx_table_rows * 4))) goto fail;
-    if (!a.wd_table && (rc = dev_alloc(s, (void**)&a.wd_table, (size_t)a.max_wd * 5 * 32))) goto fail;
-    if (!a.public_inputs && (rc = dev_alloc(s, (void**)&a.public_inputs, 4 * 2 * 32))) goto fail;
-    if (!a.raw_bytes && (rc = dev_alloc(s, (void**)&a.raw_bytes, (size_t)z.n))) goto fail;
-    if (!a.raw_lens && (rc = dev_alloc(s, (void**)&a.raw_lens, (size_t)z.n_values * 4))) goto fail;
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(dev_buf(s, a.gas_local, ((size_t)a.total_cd + 1) * 4));
+    RC_TRY(dev_buf(s, a.gas_tile, ((size_t)a.n_gas_tiles + 1) * 8));
+    RC_TRY(dev_buf(s, a.inv_txlo, ((size_t)PIA_TX_LEN * a.max_txs + 1) * 32));
+    RC_TRY(dev_buf(s, a.slice_acc, (size_t)a.n_tiles * 256 * 32));
+    RC_TRY(dev_buf(s, a.tile_acc, ((size_t)a.n_tiles + 1) * 32));
+    RC_TRY(dev_buf(s, a.carry, ((size_t)a.n_tiles + 1) * 32));
+    const zk_pi_wire o = wire_or_nulls(out_dev);
+    RC_TRY(out_buf(s, a.rows, o.rows, (size_t)z.n * PI_NCELLS * 32));
+    RC_TRY(out_buf(s, a.gas, o.gas, (size_t)z.n_gas * PI_GAS_NCELLS * 32));
+    RC_TRY(out_buf(s, a.keccak, o.keccak, 2 * 5 * 32));
+    RC_TRY(out_buf(s, a.cc_cells, o.cc_cells, (size_t)z.n_cc * 32));
+    RC_TRY(out_buf(s, a.cc_bytes, o.cc_bytes, (size_t)z.n_cc * 32));
+    RC_TRY(out_buf(s, a.cc_lens, o.cc_lens, (size_t)z.n_cc * 4));
+    RC_TRY(out_buf(s, a.block_table, o.block_table, (size_t)PIA_BLOCK_ENTRIES * 2 * 32));
+    RC_TRY(out_buf(s, a.block_flags, o.block_flags, (size_t)PIA_BLOCK_ENTRIES * 4));
+    RC_TRY(out_buf(s, a.tx_table, o.tx_table, (size_t)z.tx_table_rows * 5 * 32));
+    RC_TRY(out_buf(s, a.tx_flags, o.tx_flags, (size_t)z.tx_table_rows * 4));
+    RC_TRY(out_buf(s, a.wd_table, o.wd_table, (size_t)a.max_wd * 5 * 32));
+    RC_TRY(out_buf(s, a.public_inputs, o.public_inputs, 4 * 2 * 32));
+    RC_TRY(out_buf(s, a.raw_bytes, o.raw_bytes, (size_t)z.n));
+    RC_TRY(out_buf(s, a.raw_lens, o.raw_lens, (size_t)z.n_values * 4));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
-#define PIA_D2H(dst, src, bytes) do { if (dst) HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s->stream)); } while (0)
 extern "C" int zk_pi_assign_read(zk_session* s, const zk_pi_wire* h) {
     ARG_TRY(s && h && s->kind == SESSION_PIA, "zk_pi_assign_read: bad arguments");
     HIP_TRY(hipSetDevice(s->device));
     const PiaArgs& a = s->pia;
     const PiaSizes& z = s->pia_sizes;
-    PIA_D2H(h->rows, a.rows, (size_t)z.n * PI_NCELLS * 32);
-    PIA_D2H(h->gas, a.gas, (size_t)z.n_gas * PI_GAS_NCELLS * 32);
-    PIA_D2H(h->keccak, a.keccak, 2 * 5 * 32);
-    PIA_D2H(h->cc_cells, a.cc_cells, (size_t)z.n_cc * 32);
-    PIA_D2H(h->cc_bytes, a.cc_bytes, (size_t)z.n_cc * 32);
-    PIA_D2H(h->cc_lens, a.cc_lens, (size_t)z.n_cc * 4);
-    PIA_D2H(h->block_table, a.block_table, (size_t)PIA_BLOCK_ENTRIES * 2 * 32);
-    PIA_D2H(h->block_flags, a.block_flags, (size_t)PIA_BLOCK_ENTRIES * 4);
-    PIA_D2H(h->tx_table, a.tx_table, (size_t)z.tx_table_rows * 5 * 32);
-    PIA_D2H(h->tx_flags, a.tx_flags, (size_t)z.tx_table_rows * 4);
-    PIA_D2H(h->wd_table, a.wd_table, (size_t)a.max_wd * 5 * 32);
-    PIA_D2H(h->public_inputs, a.public_inputs, 4 * 2 * 32);
-    PIA_D2H(h->raw_bytes, a.raw_bytes, (size_t)z.n);
-    PIA_D2H(h->raw_lens, a.raw_lens, (size_t)z.n_values * 4);
+    RC_TRY(d2h_out(s, h->rows, a.rows, (size_t)z.n * PI_NCELLS * 32));
+    RC_TRY(d2h_out(s, h->gas, a.gas, (size_t)z.n_gas * PI_GAS_NCELLS * 32));
+    RC_TRY(d2h_out(s, h->keccak, a.keccak, 2 * 5 * 32));
+    RC_TRY(d2h_out(s, h->cc_cells, a.cc_cells, (size_t)z.n_cc * 32));
+    RC_TRY(d2h_out(s, h->cc_bytes, a.cc_bytes, (size_t)z.n_cc * 32));
+    RC_TRY(d2h_out(s, h->cc_lens, a.cc_lens, (size_t)z.n_cc * 4));
+    RC_TRY(d2h_out(s, h->block_table, a.block_table, (size_t)PIA_BLOCK_ENTRIES * 2 * 32));
+    RC_TRY(d2h_out(s, h->block_flags, a.block_flags, (size_t)PIA_BLOCK_ENTRIES * 4));
+    RC_TRY(d2h_out(s, h->tx_table, a.tx_table, (size_t)z.tx_table_rows * 5 * 32));
+    RC_TRY(d2h_out(s, h->tx_flags, a.tx_flags, (size_t)z.tx_table_rows * 4));
+    RC_TRY(d2h_out(s, h->wd_table, a.wd_table, (size_t)a.max_wd * 5 * 32));
+    RC_TRY(d2h_out(s, h->public_inputs, a.public_inputs, 4 * 2 * 32));
+    RC_TRY(d2h_out(s, h->raw_bytes, a.raw_bytes, (size_t)z.n));
+    RC_TRY(d2h_out(s, h->raw_lens, a.raw_lens, (size_t)z.n_values * 4));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
 }
@@ -2772,13 +2574,10 @@ extern "C" int zk_pi_assign(const zk_pi_inputs* t, const zk_pi_wire* out_wire, u
     ARG_TRY(result && out_wire && out_wire->rows, "zk_pi_assign: null output");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_pi_assign_open(t, dev ? out_wire : nullptr, opts, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && !dev) rc = zk_pi_assign_read(s, out_wire);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_pi_assign_open(t, dev ? out_wire : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, nullptr, result));
+    return dev ? 0 : zk_pi_assign_read(s, out_wire);
 }
 
 // ---- Public-inputs circuit
@@ -2788,54 +2587,36 @@ extern "C" int zk_pi_open(const uint64_t* rows, uint64_t n, const uint64_t* kecc
     HIP_TRY(hipSetDevice(t_device));
     ARG_TRY(out && rows && keccak_rand && byte_pow_base && n > 0 && n < (1ull << 32) && n_keccak < (1ull << 31) && n_gas < (1ull << 31), "zk_pi_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_PI;
     s->n = n;
-    int rc = 0;
-    const void* p = nullptr;
-    u64 rh[8];
-    if ((rc = stage(s, rows, (size_t)n * PI_NCELLS * 32, dev, &p))) goto fail;
-    s->pi.rows.cells = (const u64*)p;
+    RC_TRY(stage_in(s, s->pi.rows.cells, rows, (size_t)n * PI_NCELLS * 32, dev));
     s->pi.rows.flags = nullptr;
     s->pi.rows.n = n;
-    if ((rc = table_stage(s, s->pi.keccak, keccak, nullptr, n_keccak, KECCAK_NCELLS, dev))) goto fail;
-    if ((rc = build_index<keccak_key_hash>(s, s->pi.keccak))) goto fail;
-    if ((rc = table_stage(s, s->pi.gas, gas, nullptr, n_gas, PI_GAS_NCELLS, dev))) goto fail;
-    if ((rc = build_index<pi_gas_key_hash>(s, s->pi.gas))) goto fail;
+    RC_TRY(table_stage(s, s->pi.keccak, keccak, nullptr, n_keccak, KECCAK_NCELLS, dev));
+    RC_TRY(build_index<keccak_key_hash>(s, s->pi.keccak));
+    RC_TRY(table_stage(s, s->pi.gas, gas, nullptr, n_gas, PI_GAS_NCELLS, dev));
+    RC_TRY(build_index<pi_gas_key_hash>(s, s->pi.gas));
+    u64 rh[8];
     if (dev) {
-        if (d2h_now(s->stream, rh, keccak_rand, 32) || d2h_now(s->stream, rh + 4, byte_pow_base, 32)) {
-            rc = -2; g_err = "randomness download failed"; goto fail;
-        }
+        DEV_TRY(!d2h_now(s->stream, rh, keccak_rand, 32) && !d2h_now(s->stream, rh + 4, byte_pow_base, 32), "randomness download failed");
     } else {
         memcpy(rh, keccak_rand, 32);
         memcpy(rh + 4, byte_pow_base, 32);
     }
-    {
-        Fr kr, bp;
-        for (int k = 0; k < 4; k++) {
-            kr.v[2 * k] = (u32)rh[k]; kr.v[2 * k + 1] = (u32)(rh[k] >> 32);
-            bp.v[2 * k] = (u32)rh[4 + k]; bp.v[2 * k + 1] = (u32)(rh[4 + k] >> 32);
-        }
-        u64* d_m = nullptr;
-        u64 hm[8];
-        if ((rc = dev_alloc(s, (void**)&d_m, 64))) goto fail;
-        zk_launch_fr_to_mont(s->stream, kr, d_m);
-        zk_launch_fr_to_mont(s->stream, bp, d_m + 4);
-        if (hipMemcpyAsync(hm, d_m, 64, hipMemcpyDeviceToHost, s->stream) != hipSuccess || hipStreamSynchronize(s->stream) != hipSuccess) {
-            rc = -2; g_err = "constant download failed"; goto fail;
-        }
-        for (int k = 0; k < 4; k++) {
-            s->pi.keccak_rand_m.v[2 * k] = (u32)hm[k]; s->pi.keccak_rand_m.v[2 * k + 1] = (u32)(hm[k] >> 32);
-            s->pi.byte_pow_base_m.v[2 * k] = (u32)hm[4 + k]; s->pi.byte_pow_base_m.v[2 * k + 1] = (u32)(hm[4 + k] >> 32);
-        }
-    }
+    u64* d_m = nullptr;
+    RC_TRY(dev_buf(s, d_m, 64));
+    zk_launch_fr_to_mont(s->stream, fr_from_words(rh), d_m);
+    zk_launch_fr_to_mont(s->stream, fr_from_words(rh + 4), d_m + 4);
+    u64 hm[8];
+    DEV_TRY(!d2h_now(s->stream, hm, d_m, 64), "constant download failed");
+    s->pi.keccak_rand_m = fr_from_words(hm);
+    s->pi.byte_pow_base_m = fr_from_words(hm + 4);
     s->pi.circuit_len = Fr{{(u32)circuit_len, (u32)(circuit_len >> 32), 0, 0, 0, 0, 0, 0}};
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 // PI circuit copy constraints (pi_circuit.py:355-445; csrc/pi_circuit.hpp pi_copy_check)
 extern "C" int zk_pi_copy_open(const uint64_t* cells, const uint8_t* bytes, const uint32_t* lens, uint64_t n, uint32_t opts, zk_session** out) {
@@ -2843,76 +2624,53 @@ extern "C" int zk_pi_copy_open(const uint64_t* cells, const uint8_t* bytes, cons
     HIP_TRY(hipSetDevice(t_device));
     ARG_TRY(out && cells && bytes && lens && n > 0 && n < (1ull << 32), "zk_pi_copy_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_PICOPY;
     s->n = n;
-    int rc = 0;
-    const void* p = nullptr;
-    if ((rc = stage(s, cells, (size_t)n * 32, dev, &p))) goto fail;
-    s->picopy.cells = (const u64*)p;
-    if ((rc = stage(s, bytes, (size_t)n * 32, dev, &p))) goto fail;
-    s->picopy.bytes = (const uint8_t*)p;
-    if ((rc = stage(s, lens, (size_t)n * 4, dev, &p))) goto fail;
-    s->picopy.lens = (const u32*)p;
+    RC_TRY(stage_in(s, s->picopy.cells, cells, (size_t)n * 32, dev));
+    RC_TRY(stage_in(s, s->picopy.bytes, bytes, (size_t)n * 32, dev));
+    RC_TRY(stage_in(s, s->picopy.lens, lens, (size_t)n * 4, dev));
     s->picopy.n = n;
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_pi_copy_verify(const uint64_t* cells, const uint8_t* bytes, const uint32_t* lens, uint64_t n, uint32_t opts, uint32_t* status_out,
                                  zk_result* result) {
     ARG_TRY(result, "zk_pi_copy_verify: result is null");
     zk_session* s = nullptr;
-    int rc = zk_pi_copy_open(cells, bytes, lens, n, opts, &s);
-    if (rc) return rc;
+    RC_TRY(zk_pi_copy_open(cells, bytes, lens, n, opts, &s));
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
-    rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
-    zk_close(s);
-    return rc;
+    return one_shot(s, dev, status_out, result);
 }
 extern "C" int zk_pi_verify(const uint64_t* rows, uint64_t n, const uint64_t* keccak, uint64_t n_keccak, const uint64_t* gas, uint64_t n_gas,
                             uint64_t circuit_len, const uint64_t* keccak_rand, const uint64_t* byte_pow_base, uint32_t opts,
                             uint32_t* status_out, zk_result* result) {
     ARG_TRY(result, "zk_pi_verify: result is null");
     zk_session* s = nullptr;
-    int rc = zk_pi_open(rows, n, keccak, n_keccak, gas, n_gas, circuit_len, keccak_rand, byte_pow_base, opts, &s);
-    if (rc) return rc;
+    RC_TRY(zk_pi_open(rows, n, keccak, n_keccak, gas, n_gas, circuit_len, keccak_rand, byte_pow_base, opts, &s));
     return one_shot(s, opts & ZK_OPT_DEVICE_PTRS, status_out, result);
 }
 
 extern "C" int zk_copy_verify(const zk_copy_tables* t, uint32_t opts, uint32_t* status_out, zk_result* result) {
     ARG_TRY(result, "zk_copy_verify: result is null");
     zk_session* s = nullptr;
-    int rc = zk_copy_open(t, opts, &s);
-    if (rc) return rc;
+    RC_TRY(zk_copy_open(t, opts, &s));
     return one_shot(s, opts & ZK_OPT_DEVICE_PTRS, status_out, result);
 }
 
-static int one_shot(zk_session* s, bool dev, uint32_t* status_out, zk_result* result) {
-    int rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
-    zk_close(s);
-    return rc;
-}
 extern "C" int zk_bytecode_verify(const uint64_t* rows, uint64_t n, const uint64_t* keccak, uint64_t n_keccak,
                                   const uint64_t* randomness, uint32_t opts, uint32_t* status_out, zk_result* result) {
     ARG_TRY(result, "zk_bytecode_verify: result is null");
     zk_session* s = nullptr;
-    int rc = zk_bytecode_open(rows, n, keccak, n_keccak, randomness, opts, &s);
-    if (rc) return rc;
+    RC_TRY(zk_bytecode_open(rows, n, keccak, n_keccak, randomness, opts, &s));
     return one_shot(s, opts & ZK_OPT_DEVICE_PTRS, status_out, result);
 }
 extern "C" int zk_exp_verify(const uint64_t* rows, uint64_t n, uint32_t opts, uint32_t* status_out, zk_result* result) {
     ARG_TRY(result, "zk_exp_verify: result is null");
     zk_session* s = nullptr;
-    int rc = zk_exp_open(rows, n, opts, &s);
-    if (rc) return rc;
+    RC_TRY(zk_exp_open(rows, n, opts, &s));
     return one_shot(s, opts & ZK_OPT_DEVICE_PTRS, status_out, result);
 }
 
@@ -3471,14 +3229,9 @@ extern "C" int zk_state_verify(const uint64_t* rows, const uint32_t* flags, uint
                                uint64_t n_mpt, uint32_t opts, uint32_t* status_out, zk_result* result) {
     ARG_TRY(result, "zk_state_verify: result is null");
     zk_session* s = nullptr;
-    int rc = zk_state_open(rows, flags, n, mpt, n_mpt, opts, &s);
-    if (rc) return rc;
+    RC_TRY(zk_state_open(rows, flags, n, mpt, n_mpt, opts, &s));
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
-    rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
-    zk_close(s);
-    return rc;
+    return one_shot(s, dev, status_out, result);
 }
 
 extern "C" int zk_fr_op(int op, const uint64_t* a, const uint64_t* b, uint64_t* out, uint64_t n, uint32_t opts) {
@@ -4089,16 +3842,10 @@ static int ecc_session_ops(zk_session* s, const zk_ecc_ops* ops, bool dev, const
     EccArgs& a = s->ecc.a;
     if (const char* err = ecc_args_from_ops(&h, a)) return fail(err);
     const u64 np = a.n_add + a.n_mul, n_pp = s->ecc_pair_off[a.n_pairing];
-    int rc;
-    const void* p = nullptr;
-    if ((rc = stage(s, ops->points, (size_t)np * 192, dev, &p))) return rc;
-    a.pts = (const u64*)p;
-    if ((rc = stage(s, ops->pair_pts, (size_t)n_pp * 192, dev, &p))) return rc;
-    a.pair_pts = (const u64*)p;
-    if ((rc = stage(s, ops->pair_out, (size_t)a.n_pairing * 32, dev, &p))) return rc;
-    a.pair_out = (const u64*)p;
-    if ((rc = stage(s, ops->pair_off, a.n_pairing ? (size_t)(a.n_pairing + 1) * 4 : 0, dev, &p))) return rc;
-    a.pair_off = (const u32*)p;
+    RC_TRY(stage_in(s, a.pts, ops->points, (size_t)np * 192, dev));
+    RC_TRY(stage_in(s, a.pair_pts, ops->pair_pts, (size_t)n_pp * 192, dev));
+    RC_TRY(stage_in(s, a.pair_out, ops->pair_out, (size_t)a.n_pairing * 32, dev));
+    RC_TRY(stage_in(s, a.pair_off, ops->pair_off, a.n_pairing ? (size_t)(a.n_pairing + 1) * 4 : 0, dev));
     s->n = np + a.n_pairing;
     return 0;
 }
@@ -4108,24 +3855,18 @@ extern "C" int zk_ecc_open(const zk_ecc_ops* ops, const uint64_t* rows, uint32_t
     ARG_TRY(out, "zk_ecc_open: out is null");
     ARG_TRY(rows, "zk_ecc_open: rows is null");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_ECC;
-    int rc = ecc_session_ops(s, ops, dev, "zk_ecc_open");
-    const void* p = nullptr;
-    if (rc) goto fail;
-    if ((rc = stage(s, rows, (size_t)s->n * ECC_NCELLS * 32, dev, &p))) goto fail;
-    s->ecc.a.rows = (const u64*)p;
-    {   // the per-pair records of the two-stage pairing pass (written by stage 1 of every pass before stage 2 reads them)
-        const u64 n_pp = s->ecc_pair_off[s->ecc.a.n_pairing];
-        if ((rc = dev_alloc(s, (void**)&s->ecc.pair_flags, (size_t)(n_pp ? n_pp : 1) * sizeof(u32)))) goto fail;
-        if ((rc = dev_alloc(s, (void**)&s->ecc.pair_f, (size_t)(n_pp ? n_pp : 1) * sizeof(bn::Fq12)))) goto fail;
-    }
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(ecc_session_ops(s, ops, dev, "zk_ecc_open"));
+    RC_TRY(stage_in(s, s->ecc.a.rows, rows, (size_t)s->n * ECC_NCELLS * 32, dev));
+    // the per-pair records of the two-stage pairing pass (written by stage 1 of every pass before stage 2 reads them)
+    const u64 n_pp = s->ecc_pair_off[s->ecc.a.n_pairing];
+    RC_TRY(dev_buf(s, s->ecc.pair_flags, (size_t)(n_pp ? n_pp : 1) * sizeof(u32)));
+    RC_TRY(dev_buf(s, s->ecc.pair_f, (size_t)(n_pp ? n_pp : 1) * sizeof(bn::Fq12)));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_ecc_assign_open(const zk_ecc_ops* ops, uint64_t* rows_dev, uint32_t opts, zk_session** out) {
     ARG_TRY(t_device >= 0, "zk_ecc_assign_open: call zk_init first");
@@ -4133,25 +3874,21 @@ extern "C" int zk_ecc_assign_open(const zk_ecc_ops* ops, uint64_t* rows_dev, uin
     ARG_TRY(out, "zk_ecc_assign_open: out is null");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     ARG_TRY(dev || !rows_dev, "zk_ecc_assign_open: rows_dev needs ZK_OPT_DEVICE_PTRS");
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_ECC_ASSIGN;
-    int rc = ecc_session_ops(s, ops, dev, "zk_ecc_assign_open");
-    if (rc) goto fail;
-    s->ecc.a.rows_out = rows_dev;
-    if (!rows_dev && (rc = dev_alloc(s, (void**)&s->ecc.a.rows_out, (size_t)s->n * ECC_NCELLS * 32))) goto fail;
+    RC_TRY(ecc_session_ops(s, ops, dev, "zk_ecc_assign_open"));
+    RC_TRY(out_buf(s, s->ecc.a.rows_out, rows_dev, (size_t)s->n * ECC_NCELLS * 32));
     s->ecc.pair_flags = nullptr;
     s->ecc.pair_f = nullptr;
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_ecc_assign_read(zk_session* s, uint64_t* rows_host) {
     ARG_TRY(s && rows_host && s->kind == SESSION_ECC_ASSIGN, "zk_ecc_assign_read: bad arguments");
     HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipMemcpyAsync(rows_host, s->ecc.a.rows_out, (size_t)s->n * ECC_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+    RC_TRY(d2h_out(s, rows_host, s->ecc.a.rows_out, (size_t)s->n * ECC_NCELLS * 32));
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
 }
@@ -4182,50 +3919,37 @@ extern "C" int zk_withdrawal_open(const zk_withdrawal_witness* w, uint32_t opts,
     a.max_w = w->max_withdrawals;
     const u64 n = wd_eval_rows(a);
     ARG_TRY(n > 0, "zk_withdrawal_open: row_base lies beyond the evaluated rows");
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_WITHDRAWAL;
     s->n = n;
-    int rc = 0;
-    const void* p = nullptr;
-    u64 rh[4];
-    if ((rc = stage(s, w->rows, (size_t)w->n_rows * WD_NCELLS * 32, dev, &p))) goto fail;
-    a.rows = (const u64*)p;
-    if ((rc = table_stage(s, a.keccak, w->keccak, nullptr, w->n_keccak, KECCAK_NCELLS, dev))) goto fail;
-    if ((rc = build_index<keccak_key_hash>(s, a.keccak))) goto fail;
-    if ((rc = table_stage(s, a.mpt, w->mpt, nullptr, w->n_mpt, MPT_NCELLS, dev))) goto fail;
-    {
-        u32 cap = 16;
-        while (cap < 2 * a.mpt.n + 2) cap <<= 1;
-        u32* slots = nullptr;
-        if ((rc = dev_alloc(s, (void**)&slots, (size_t)cap * sizeof(u32)))) goto fail;
-        a.mpt.mask = cap - 1;
-        a.mpt.slots = slots;
-        hipLaunchKernelGGL(slots_fill_kernel, dim3((cap + 255) / 256), dim3(256), 0, s->stream, slots, cap);
-        if (a.mpt.n) hipLaunchKernelGGL(wd_mpt_index_kernel, dim3((a.mpt.n + 255) / 256), dim3(256), 0, s->stream, a.mpt, slots);
-        if (hipGetLastError() != hipSuccess) { rc = -2; g_err = "zk_withdrawal_open: MPT index launch failed"; goto fail; }
-    }
-    if ((rc = stage(s, w->block, (size_t)w->n_block * WD_BLOCK_NCELLS * 32, dev, &p))) goto fail;
-    a.block = (const u64*)p;
+    RC_TRY(stage_in(s, a.rows, w->rows, (size_t)w->n_rows * WD_NCELLS * 32, dev));
+    RC_TRY(table_stage(s, a.keccak, w->keccak, nullptr, w->n_keccak, KECCAK_NCELLS, dev));
+    RC_TRY(build_index<keccak_key_hash>(s, a.keccak));
+    RC_TRY(table_stage(s, a.mpt, w->mpt, nullptr, w->n_mpt, MPT_NCELLS, dev));
+    u32 cap = 16;
+    while (cap < 2 * a.mpt.n + 2) cap <<= 1;
+    u32* slots = nullptr;
+    RC_TRY(dev_buf(s, slots, (size_t)cap * sizeof(u32)));
+    a.mpt.mask = cap - 1;
+    a.mpt.slots = slots;
+    hipLaunchKernelGGL(slots_fill_kernel, dim3((cap + 255) / 256), dim3(256), 0, s->stream, slots, cap);
+    if (a.mpt.n) hipLaunchKernelGGL(wd_mpt_index_kernel, dim3((a.mpt.n + 255) / 256), dim3(256), 0, s->stream, a.mpt, slots);
+    DEV_TRY(hipGetLastError() == hipSuccess, "zk_withdrawal_open: MPT index launch failed");
+    RC_TRY(stage_in(s, a.block, w->block, (size_t)w->n_block * WD_BLOCK_NCELLS * 32, dev));
     a.n_block = w->n_block;
-    if (dev) {
-        if (fetch_small(s->stream, rh, w->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
-    } else {
-        memcpy(rh, w->randomness, 32);
-    }
-    for (int k = 0; k < 4; k++) { a.r.v[2 * k] = (u32)rh[k]; a.r.v[2 * k + 1] = (u32)(rh[k] >> 32); }
+    u64 rh[4];
+    RC_TRY(host_words(s, rh, w->randomness, 32, dev, "randomness"));
+    a.r = fr_from_words(rh);
     s->withdrawal = a;
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_withdrawal_verify(const zk_withdrawal_witness* w, uint32_t opts, uint32_t* status_out, zk_result* result) {
     ARG_TRY(result, "zk_withdrawal_verify: result is null");
     zk_session* s = nullptr;
-    int rc = zk_withdrawal_open(w, opts, &s);
-    if (rc) return rc;
+    RC_TRY(zk_withdrawal_open(w, opts, &s));
     return one_shot(s, opts & ZK_OPT_DEVICE_PTRS, status_out, result);
 }
 extern "C" int zk_withdrawal_assign(const uint64_t* withdrawals, uint64_t n, uint64_t max_withdrawals, const uint64_t* randomness,
@@ -4276,84 +4000,54 @@ extern "C" int zk_tx_assign_open(const zk_tx_inputs* in, const zk_tx_wire* out_d
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     ARG_TRY(dev || !out_dev, "zk_tx_assign_open: out_dev needs ZK_OPT_DEVICE_PTRS");
     const u64 n = in->n_txs, mt = in->max_txs, mc = in->max_calldata_bytes;
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_TXA;
     s->n = n;
     TxAssignArgs& a = s->txa;
     memset(&a, 0, sizeof(a));
-    int rc = 0;
-    const void* p = nullptr;
-    u64 rh[4];
-    std::vector<u64> h_off((size_t)n + 1, 0);
     // the offsets are validated on the host (a device caller's are read back once)
-    if (dev) {
-        if (fetch_small(s->stream, h_off.data(), in->calldata_offsets, (n + 1) * 8)) { rc = -2; g_err = "offsets download failed"; goto fail; }
-        if (fetch_small(s->stream, rh, in->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
-    } else {
-        memcpy(h_off.data(), in->calldata_offsets, (n + 1) * 8);
-        memcpy(rh, in->randomness, 32);
-    }
-    if (h_off[0] != 0) { rc = -1; g_err = "zk_tx_assign_open: calldata offsets must start at 0"; goto fail; }
-    for (u64 j = 0; j < n; j++)
-        if (h_off[j] > h_off[j + 1]) { rc = -1; g_err = "zk_tx_assign_open: calldata offsets must be non-decreasing"; goto fail; }
-    if (h_off[n] > mc) { rc = -1; g_err = "zk_tx_assign_open: more calldata bytes than max_calldata_bytes"; goto fail; }
-    if (h_off[n] && !in->calldata) { rc = -1; g_err = "zk_tx_assign_open: calldata is null"; goto fail; }
-    if ((rc = stage(s, in->fields, (size_t)n * TX_NFIELDS * 32, dev, &p))) goto fail;
-    a.fields = (const u64*)p;
-    if ((rc = stage(s, in->to_is_none, (size_t)n * 4, dev, &p))) goto fail;
-    a.to_none = (const u32*)p;
-    if ((rc = stage(s, in->calldata_offsets, (size_t)(n + 1) * 8, dev, &p))) goto fail;
-    a.off = (const u64*)p;
+    std::vector<u64> h_off((size_t)n + 1, 0);
+    u64 rh[4];
+    RC_TRY(host_words(s, h_off.data(), in->calldata_offsets, (n + 1) * 8, dev, "offsets"));
+    RC_TRY(host_words(s, rh, in->randomness, 32, dev, "randomness"));
+    ARG_TRY(h_off[0] == 0, "zk_tx_assign_open: calldata offsets must start at 0");
+    for (u64 j = 0; j < n; j++) ARG_TRY(h_off[j] <= h_off[j + 1], "zk_tx_assign_open: calldata offsets must be non-decreasing");
+    ARG_TRY(h_off[n] <= mc, "zk_tx_assign_open: more calldata bytes than max_calldata_bytes");
+    ARG_TRY(!h_off[n] || in->calldata, "zk_tx_assign_open: calldata is null");
+    RC_TRY(stage_in(s, a.fields, in->fields, (size_t)n * TX_NFIELDS * 32, dev));
+    RC_TRY(stage_in(s, a.to_none, in->to_is_none, (size_t)n * 4, dev));
+    RC_TRY(stage_in(s, a.off, in->calldata_offsets, (size_t)(n + 1) * 8, dev));
     if (dev || !h_off[n]) {
-        if ((rc = stage(s, h_off[n] ? in->calldata : nullptr, (size_t)h_off[n], dev, &p))) goto fail;
-        a.data = (const uint8_t*)p;
+        RC_TRY(stage_in(s, a.data, h_off[n] ? in->calldata : nullptr, (size_t)h_off[n], dev));
     } else {  // staged with its last aligned word whole (the sponge reads whole aligned words)
-        void* d = nullptr;
-        if ((rc = dev_alloc(s, &d, (size_t)((h_off[n] + 15) & ~7ull)))) goto fail;
-        if (hipMemcpyAsync(d, in->calldata, (size_t)h_off[n], hipMemcpyHostToDevice, s->stream) != hipSuccess) { rc = -2; g_err = "zk_tx_assign_open: calldata upload failed"; goto fail; }
-        a.data = (const uint8_t*)d;
+        uint8_t* d_data = nullptr;
+        RC_TRY(dev_buf(s, d_data, (size_t)((h_off[n] + 15) & ~7ull)));
+        DEV_TRY(hipMemcpyAsync(d_data, in->calldata, (size_t)h_off[n], hipMemcpyHostToDevice, s->stream) == hipSuccess,
+                "zk_tx_assign_open: calldata upload failed");
+        a.data = d_data;
     }
     a.n = n; a.max_txs = mt; a.max_calldata = mc; a.chain_id = in->chain_id;
-    if ((rc = keccak_rpow_open(s, rh, &a.rpow))) goto fail;
-    {
-        void* d = nullptr;
-        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 32))) goto fail;
-        a.hash = (u64*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 8))) goto fail;
-        a.gas_cost = (u64*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 64))) goto fail;
-        a.pk = (u64*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 4))) goto fail;
-        a.status = (u32*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * KT_NCELLS * 32))) goto fail;
-        a.kcand = (u64*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 4))) goto fail;
-        a.kfirst = (u32*)d;
-        if ((rc = dev_alloc(s, &d, 64))) goto fail;
-        a.n_keccak = (u32*)d;
-    }
-    if ((rc = secp_lanes_open(s, n, "zk_tx_assign_open", a.lanes))) goto fail;
-    {
-        const zk_tx_wire* o = out_dev;
-        void* d = nullptr;
-        const u64 rows = mt * TX_FIXED_ROWS + mc;
-#define TXA_OUT(field, member, type, bytes)                                               \
-        if (o && o->field) a.member = (type)o->field;                                     \
-        else { if ((rc = dev_alloc(s, &d, (size_t)(bytes)))) goto fail; a.member = (type)d; }
-        TXA_OUT(tx_rows, tx_rows, u64*, rows * TX_ROW_CELLS * 32 + 32)
-        TXA_OUT(tx_flags, tx_flags, u32*, rows * 4 + 4)
-        TXA_OUT(bytes, bytes, uint8_t*, mt * TX_UNIT_BYTES + 32)
-        TXA_OUT(cells, cells, u64*, mt * TX_UNIT_CELLS * 32 + 32)
-        TXA_OUT(meta, meta, u32*, mt * 16 + 16)
-        TXA_OUT(keccak, keccak, u64*, (n + 1) * KT_NCELLS * 32)
-#undef TXA_OUT
-    }
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(keccak_rpow_open(s, rh, &a.rpow));
+    RC_TRY(dev_buf(s, a.hash, (size_t)(n + 1) * 32));
+    RC_TRY(dev_buf(s, a.gas_cost, (size_t)(n + 1) * 8));
+    RC_TRY(dev_buf(s, a.pk, (size_t)(n + 1) * 64));
+    RC_TRY(dev_buf(s, a.status, (size_t)(n + 1) * 4));
+    RC_TRY(dev_buf(s, a.kcand, (size_t)(n + 1) * KT_NCELLS * 32));
+    RC_TRY(dev_buf(s, a.kfirst, (size_t)(n + 1) * 4));
+    RC_TRY(dev_buf(s, a.n_keccak, 64));
+    RC_TRY(secp_lanes_open(s, n, "zk_tx_assign_open", a.lanes));
+    const zk_tx_wire o = wire_or_nulls(out_dev);
+    const u64 rows = mt * TX_FIXED_ROWS + mc;
+    RC_TRY(out_buf(s, a.tx_rows, o.tx_rows, rows * TX_ROW_CELLS * 32 + 32));
+    RC_TRY(out_buf(s, a.tx_flags, o.tx_flags, rows * 4 + 4));
+    RC_TRY(out_buf(s, a.bytes, o.bytes, mt * TX_UNIT_BYTES + 32));
+    RC_TRY(out_buf(s, a.cells, o.cells, mt * TX_UNIT_CELLS * 32 + 32));
+    RC_TRY(out_buf(s, a.meta, o.meta, mt * 16 + 16));
+    RC_TRY(out_buf(s, a.keccak, o.keccak, (n + 1) * KT_NCELLS * 32));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_tx_assign_read(zk_session* s, const zk_tx_wire* host, uint64_t* n_keccak_out) {
     ARG_TRY(s && s->kind == SESSION_TXA, "zk_tx_assign_read: bad arguments");
@@ -4361,15 +4055,14 @@ extern "C" int zk_tx_assign_read(zk_session* s, const zk_tx_wire* host, uint64_t
     const TxAssignArgs& a = s->txa;
     const u64 rows = a.max_txs * TX_FIXED_ROWS + a.max_calldata;
     u32 nk = 0;
-    HIP_TRY(hipMemcpyAsync(&nk, a.n_keccak, 4, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    RC_TRY(d2h_now(s->stream, &nk, a.n_keccak, 4));
     if (host) {
-        if (host->tx_rows) HIP_TRY(hipMemcpyAsync(host->tx_rows, a.tx_rows, (size_t)rows * TX_ROW_CELLS * 32, hipMemcpyDeviceToHost, s->stream));
-        if (host->tx_flags) HIP_TRY(hipMemcpyAsync(host->tx_flags, a.tx_flags, (size_t)rows * 4, hipMemcpyDeviceToHost, s->stream));
-        if (host->bytes) HIP_TRY(hipMemcpyAsync(host->bytes, a.bytes, (size_t)a.max_txs * TX_UNIT_BYTES, hipMemcpyDeviceToHost, s->stream));
-        if (host->cells) HIP_TRY(hipMemcpyAsync(host->cells, a.cells, (size_t)a.max_txs * TX_UNIT_CELLS * 32, hipMemcpyDeviceToHost, s->stream));
-        if (host->meta) HIP_TRY(hipMemcpyAsync(host->meta, a.meta, (size_t)a.max_txs * 16, hipMemcpyDeviceToHost, s->stream));
-        if (host->keccak) HIP_TRY(hipMemcpyAsync(host->keccak, a.keccak, (size_t)nk * KT_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        RC_TRY(d2h_out(s, host->tx_rows, a.tx_rows, (size_t)rows * TX_ROW_CELLS * 32));
+        RC_TRY(d2h_out(s, host->tx_flags, a.tx_flags, (size_t)rows * 4));
+        RC_TRY(d2h_out(s, host->bytes, a.bytes, (size_t)a.max_txs * TX_UNIT_BYTES));
+        RC_TRY(d2h_out(s, host->cells, a.cells, (size_t)a.max_txs * TX_UNIT_CELLS * 32));
+        RC_TRY(d2h_out(s, host->meta, a.meta, (size_t)a.max_txs * 16));
+        RC_TRY(d2h_out(s, host->keccak, a.keccak, (size_t)nk * KT_NCELLS * 32));
         HIP_TRY(hipStreamSynchronize(s->stream));
     }
     if (n_keccak_out) *n_keccak_out = nk;
@@ -4380,14 +4073,10 @@ extern "C" int zk_tx_assign(const zk_tx_inputs* in, const zk_tx_wire* out, uint3
     ARG_TRY(result && out, "zk_tx_assign: null output");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_tx_assign_open(in, dev ? out : nullptr, opts, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, dev ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && !dev && status_out) rc = zk_read_status(s, status_out);
-    if (!rc) rc = zk_tx_assign_read(s, dev ? nullptr : out, n_keccak_out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_tx_assign_open(in, dev ? out : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, status_out, result));
+    return zk_tx_assign_read(s, dev ? nullptr : out, n_keccak_out);
 }
 
 // ---- Sig circuit witness assignment (sig_assign.hpp, k_sig_assign.hip)
@@ -4398,85 +4087,54 @@ extern "C" int zk_sig_assign_open(const zk_sig_inputs* in, const zk_sig_wire* ou
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     ARG_TRY(dev || !out_dev, "zk_sig_assign_open: out_dev needs ZK_OPT_DEVICE_PTRS");
     const u64 n = in->n;
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_SGA;
     s->n = n;
     SigAssignArgs& a = s->sga;
     memset(&a, 0, sizeof(a));
-    int rc = 0;
-    const void* p = nullptr;
-    if (dev) {
-        if (fetch_small(s->stream, a.rand, in->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
-    } else {
-        memcpy(a.rand, in->randomness, 32);
-    }
-    if ((rc = stage(s, in->fields, (size_t)n * SIG_NFIELDS * 32, dev, &p))) goto fail;
-    a.fields = (const u64*)p;
-    if (in->addr && n) {
-        if ((rc = stage(s, in->addr, (size_t)n * 32, dev, &p))) goto fail;
-        a.addr = (const u64*)p;
-    }
+    RC_TRY(host_words(s, a.rand, in->randomness, 32, dev, "randomness"));
+    RC_TRY(stage_in(s, a.fields, in->fields, (size_t)n * SIG_NFIELDS * 32, dev));
+    if (in->addr && n) RC_TRY(stage_in(s, a.addr, in->addr, (size_t)n * 32, dev));
     if (in->expect_valid && n) {
-        if ((rc = stage(s, in->expect_valid, (size_t)n * 4, dev, &p))) goto fail;
-        a.expect_valid = (const u32*)p;
+        RC_TRY(stage_in(s, a.expect_valid, in->expect_valid, (size_t)n * 4, dev));
     }
     a.n = n; a.v_offset = in->v_offset;
-    if ((rc = keccak_rpow_open(s, a.rand, &a.rpow))) goto fail;
-    {
-        void* d = nullptr;
-        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 64))) goto fail;
-        a.pk = (u64*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 4))) goto fail;
-        a.status = (u32*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * KT_NCELLS * 32))) goto fail;
-        a.kcand = (u64*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 4))) goto fail;
-        a.kfirst = (u32*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * SIG_TABLE_CELLS * 32))) goto fail;
-        a.scand = (u64*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)(n + 1) * 4))) goto fail;
-        a.sdup = (u32*)d;
-        if ((rc = dev_alloc(s, &d, 64))) goto fail;
-        a.n_keccak = (u32*)d;
-        a.n_sig_rows = (u32*)d + 1;
-        if (hipMemsetAsync(d, 0, 64, s->stream) != hipSuccess) { rc = -2; g_err = "zk_sig_assign_open: counter reset failed"; goto fail; }  // (a read before any pass: no rows)
-    }
-    if ((rc = secp_lanes_open(s, n, "zk_sig_assign_open", a.lanes))) goto fail;
-    {
-        const zk_sig_wire* o = out_dev;
-        void* d = nullptr;
-#define SGA_OUT(field, type, bytes)                                                       \
-        if (o && o->field) a.field = (type)o->field;                                      \
-        else { if ((rc = dev_alloc(s, &d, (size_t)(bytes)))) goto fail; a.field = (type)d; }
-        SGA_OUT(bytes, uint8_t*, n * TX_UNIT_BYTES + 32)
-        SGA_OUT(cells, u64*, n * TX_UNIT_CELLS * 32 + 32)
-        SGA_OUT(meta, u32*, n * 16 + 16)
-        SGA_OUT(keccak, u64*, (n + 1) * KT_NCELLS * 32)
-        SGA_OUT(sig_table, u64*, n * SIG_TABLE_CELLS * 32 + 32)
-        SGA_OUT(aux, u64*, n * SIG_AUX_CELLS * 32 + 32)
-#undef SGA_OUT
-    }
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(keccak_rpow_open(s, a.rand, &a.rpow));
+    RC_TRY(dev_buf(s, a.pk, (size_t)(n + 1) * 64));
+    RC_TRY(dev_buf(s, a.status, (size_t)(n + 1) * 4));
+    RC_TRY(dev_buf(s, a.kcand, (size_t)(n + 1) * KT_NCELLS * 32));
+    RC_TRY(dev_buf(s, a.kfirst, (size_t)(n + 1) * 4));
+    RC_TRY(dev_buf(s, a.scand, (size_t)(n + 1) * SIG_TABLE_CELLS * 32));
+    RC_TRY(dev_buf(s, a.sdup, (size_t)(n + 1) * 4));
+    RC_TRY(dev_buf(s, a.n_keccak, 64));
+    a.n_sig_rows = a.n_keccak + 1;
+    DEV_TRY(hipMemsetAsync(a.n_keccak, 0, 64, s->stream) == hipSuccess, "zk_sig_assign_open: counter reset failed");  // (a read before any pass: no rows)
+    RC_TRY(secp_lanes_open(s, n, "zk_sig_assign_open", a.lanes));
+    const zk_sig_wire o = wire_or_nulls(out_dev);
+    RC_TRY(out_buf(s, a.bytes, o.bytes, n * TX_UNIT_BYTES + 32));
+    RC_TRY(out_buf(s, a.cells, o.cells, n * TX_UNIT_CELLS * 32 + 32));
+    RC_TRY(out_buf(s, a.meta, o.meta, n * 16 + 16));
+    RC_TRY(out_buf(s, a.keccak, o.keccak, (n + 1) * KT_NCELLS * 32));
+    RC_TRY(out_buf(s, a.sig_table, o.sig_table, n * SIG_TABLE_CELLS * 32 + 32));
+    RC_TRY(out_buf(s, a.aux, o.aux, n * SIG_AUX_CELLS * 32 + 32));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_sig_assign_read(zk_session* s, const zk_sig_wire* host, uint64_t* n_keccak_out, uint64_t* n_sig_rows_out) {
     ARG_TRY(s && s->kind == SESSION_SGA, "zk_sig_assign_read: bad arguments");
     HIP_TRY(hipSetDevice(s->device));
     const SigAssignArgs& a = s->sga;
     u32 cnt[2] = {0, 0};  // n_keccak, n_sig_rows: adjacent words
-    HIP_TRY(hipMemcpyAsync(cnt, a.n_keccak, 8, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    RC_TRY(d2h_now(s->stream, cnt, a.n_keccak, 8));
     if (host) {
-        if (host->bytes) HIP_TRY(hipMemcpyAsync(host->bytes, a.bytes, (size_t)a.n * TX_UNIT_BYTES, hipMemcpyDeviceToHost, s->stream));
-        if (host->cells) HIP_TRY(hipMemcpyAsync(host->cells, a.cells, (size_t)a.n * TX_UNIT_CELLS * 32, hipMemcpyDeviceToHost, s->stream));
-        if (host->meta) HIP_TRY(hipMemcpyAsync(host->meta, a.meta, (size_t)a.n * 16, hipMemcpyDeviceToHost, s->stream));
-        if (host->keccak) HIP_TRY(hipMemcpyAsync(host->keccak, a.keccak, (size_t)cnt[0] * KT_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
-        if (host->sig_table) HIP_TRY(hipMemcpyAsync(host->sig_table, a.sig_table, (size_t)cnt[1] * SIG_TABLE_CELLS * 32, hipMemcpyDeviceToHost, s->stream));
-        if (host->aux) HIP_TRY(hipMemcpyAsync(host->aux, a.aux, (size_t)a.n * SIG_AUX_CELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        RC_TRY(d2h_out(s, host->bytes, a.bytes, (size_t)a.n * TX_UNIT_BYTES));
+        RC_TRY(d2h_out(s, host->cells, a.cells, (size_t)a.n * TX_UNIT_CELLS * 32));
+        RC_TRY(d2h_out(s, host->meta, a.meta, (size_t)a.n * 16));
+        RC_TRY(d2h_out(s, host->keccak, a.keccak, (size_t)cnt[0] * KT_NCELLS * 32));
+        RC_TRY(d2h_out(s, host->sig_table, a.sig_table, (size_t)cnt[1] * SIG_TABLE_CELLS * 32));
+        RC_TRY(d2h_out(s, host->aux, a.aux, (size_t)a.n * SIG_AUX_CELLS * 32));
         HIP_TRY(hipStreamSynchronize(s->stream));
     }
     if (n_keccak_out) *n_keccak_out = cnt[0];
@@ -4488,14 +4146,10 @@ extern "C" int zk_sig_assign(const zk_sig_inputs* in, const zk_sig_wire* out, ui
     ARG_TRY(result && out, "zk_sig_assign: null output");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_sig_assign_open(in, dev ? out : nullptr, opts, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, dev ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && !dev && status_out) rc = zk_read_status(s, status_out);
-    if (!rc) rc = zk_sig_assign_read(s, dev ? nullptr : out, n_keccak_out, n_sig_rows_out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_sig_assign_open(in, dev ? out : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, status_out, result));
+    return zk_sig_assign_read(s, dev ? nullptr : out, n_keccak_out, n_sig_rows_out);
 }
 
 // ---- ECC precompile calls (ecc_calls.hpp, k_ecc_calls.hip)
@@ -4505,75 +4159,55 @@ extern "C" int zk_ecc_from_calls_open(const zk_ecc_calls* in, const zk_ecc_call_
     ARG_TRY(in && out, "zk_ecc_from_calls_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     ARG_TRY(dev || !out_dev, "zk_ecc_from_calls_open: out_dev needs ZK_OPT_DEVICE_PTRS");
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_ECL;
     EccCallArgs& a = s->ecl;
     memset(&a, 0, sizeof(a));
-    int rc = 0;
-    const void* p = nullptr;
-    {   // pair_off and the randomness cell are what the host looks at: ecc_calls_check reads them through `h`, every other pointer
-        // it only compares with null (an op count that is out of range is refused before pair_off is fetched)
-        zk_ecc_calls h = *in;
-        u64 rh[4] = {0, 0, 0, 0};
-        std::vector<u32> off;
-        const bool counts_ok = in->n_pairing < (1ull << 31);
-        if (dev && in->randomness) {
-            if (fetch_small(s->stream, rh, in->randomness, 32)) { rc = -2; g_err = "zk_ecc_from_calls_open: randomness download failed"; goto fail; }
-            h.randomness = rh;
-        }
-        if (dev && counts_ok && in->n_pairing && in->pair_off) {
-            off.assign(in->n_pairing + 1, 0u);
-            if (d2h_now(s->stream, off.data(), in->pair_off, (in->n_pairing + 1) * 4)) { rc = -2; g_err = "zk_ecc_from_calls_open: pair_off download failed"; goto fail; }
-            h.pair_off = off.data();
-        }
-        const char* err = nullptr;
-        if ((rc = ecc_calls_check(&h, a, &err))) { g_err = std::string("zk_ecc_from_calls_open: ") + err; goto fail; }
-        s->ecl_n_pairs = in->n_pairing ? h.pair_off[in->n_pairing] : 0u;
-        // the validated offsets stay with the session, on the host and in a device buffer of its own: a caller that rewrites its
-        // pair_off between passes cannot move a lane's reads or stores
-        if (in->n_pairing) s->ecc_pair_off.assign(h.pair_off, h.pair_off + in->n_pairing + 1);
+    // pair_off and the randomness cell are what the host looks at: ecc_calls_check reads them through `h`, every other pointer
+    // it only compares with null (an op count that is out of range is refused before pair_off is fetched)
+    zk_ecc_calls h = *in;
+    u64 rh[4] = {0, 0, 0, 0};
+    std::vector<u32> off;
+    const bool counts_ok = in->n_pairing < (1ull << 31);
+    if (dev && in->randomness) {
+        RC_TRY(host_words(s, rh, in->randomness, 32, dev, "zk_ecc_from_calls_open: randomness"));
+        h.randomness = rh;
     }
-    {
-        const u64 np = a.n_add + a.n_mul, n = np + a.n_pairing, n_pp = s->ecl_n_pairs;
-        s->n = n;
-        if ((rc = stage(s, in->add_in, (size_t)a.n_add * 128, dev, &p))) goto fail;
-        a.add_in = (const u64*)p;
-        if ((rc = stage(s, in->mul_in, (size_t)a.n_mul * 96, dev, &p))) goto fail;
-        a.mul_in = (const u64*)p;
-        if ((rc = stage(s, in->pair_pts, (size_t)n_pp * 192, dev, &p))) goto fail;
-        a.pair_pts = (const u64*)p;
-        if ((rc = stage(s, a.n_pairing ? s->ecc_pair_off.data() : nullptr, a.n_pairing ? (size_t)(a.n_pairing + 1) * 4 : 0, false, &p))) goto fail;
-        a.pair_off = (const u32*)p;
-        void* d = nullptr;
-        if ((rc = dev_alloc(s, &d, (size_t)n * ECL_ROW_WORDS * 8))) goto fail;
-        a.tcand = (u64*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)n * 4))) goto fail;
-        a.tdup = (u32*)d;
-        if ((rc = dev_alloc(s, &d, 64))) goto fail;
-        a.n_table = (u32*)d;
-        if (hipMemsetAsync(d, 0, 64, s->stream) != hipSuccess) { rc = -2; g_err = "zk_ecc_from_calls_open: counter reset failed"; goto fail; }  // (a read before any pass: no rows)
-        if ((rc = dev_alloc(s, &d, (size_t)(n_pp ? n_pp : 1) * sizeof(u32)))) goto fail;
-        a.pair_flags = (u32*)d;
-        if ((rc = dev_alloc(s, &d, (size_t)(n_pp ? n_pp : 1) * sizeof(bn::Fq12)))) goto fail;
-        a.pair_f = (bn::Fq12*)d;
-        const zk_ecc_call_wire* o = out_dev;
-#define ECL_OUT(field, type, bytes)                                                       \
-        if (o && o->field) a.field = (type)o->field;                                      \
-        else { if ((rc = dev_alloc(s, &d, (size_t)(bytes) + 32))) goto fail; a.field = (type)d; }
-        ECL_OUT(points, u64*, np * 192)
-        ECL_OUT(pair_out, u64*, a.n_pairing * 32)
-        ECL_OUT(rows, u64*, n * ECL_ROW_WORDS * 8)
-        ECL_OUT(ecc_table, u64*, n * ECL_ROW_WORDS * 8)
-        ECL_OUT(aux, u64*, n * ECL_AUX_CELLS * 32)
-        ECL_OUT(aux_kind, u32*, n * 4)
-#undef ECL_OUT
+    if (dev && counts_ok && in->n_pairing && in->pair_off) {
+        off.assign(in->n_pairing + 1, 0u);
+        DEV_TRY(!d2h_now(s->stream, off.data(), in->pair_off, (in->n_pairing + 1) * 4), "zk_ecc_from_calls_open: pair_off download failed");
+        h.pair_off = off.data();
     }
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    const char* err = nullptr;
+    if (int rc = ecc_calls_check(&h, a, &err)) { g_err = std::string("zk_ecc_from_calls_open: ") + err; return rc; }
+    s->ecl_n_pairs = in->n_pairing ? h.pair_off[in->n_pairing] : 0u;
+    // the validated offsets stay with the session, on the host and in a device buffer of its own: a caller that rewrites its
+    // pair_off between passes cannot move a lane's reads or stores
+    if (in->n_pairing) s->ecc_pair_off.assign(h.pair_off, h.pair_off + in->n_pairing + 1);
+    const u64 np = a.n_add + a.n_mul, n = np + a.n_pairing, n_pp = s->ecl_n_pairs;
+    s->n = n;
+    RC_TRY(stage_in(s, a.add_in, in->add_in, (size_t)a.n_add * 128, dev));
+    RC_TRY(stage_in(s, a.mul_in, in->mul_in, (size_t)a.n_mul * 96, dev));
+    RC_TRY(stage_in(s, a.pair_pts, in->pair_pts, (size_t)n_pp * 192, dev));
+    RC_TRY(stage_in(s, a.pair_off, a.n_pairing ? s->ecc_pair_off.data() : nullptr, a.n_pairing ? (size_t)(a.n_pairing + 1) * 4 : 0, false));
+    RC_TRY(dev_buf(s, a.tcand, (size_t)n * ECL_ROW_WORDS * 8));
+    RC_TRY(dev_buf(s, a.tdup, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.n_table, 64));
+    DEV_TRY(hipMemsetAsync(a.n_table, 0, 64, s->stream) == hipSuccess, "zk_ecc_from_calls_open: counter reset failed");  // (a read before any pass: no rows)
+    RC_TRY(dev_buf(s, a.pair_flags, (size_t)(n_pp ? n_pp : 1) * sizeof(u32)));
+    RC_TRY(dev_buf(s, a.pair_f, (size_t)(n_pp ? n_pp : 1) * sizeof(bn::Fq12)));
+    // every output with 32 bytes of slack behind it
+    const zk_ecc_call_wire o = wire_or_nulls(out_dev);
+    RC_TRY(out_buf(s, a.points, o.points, np * 192 + 32));
+    RC_TRY(out_buf(s, a.pair_out, o.pair_out, a.n_pairing * 32 + 32));
+    RC_TRY(out_buf(s, a.rows, o.rows, n * ECL_ROW_WORDS * 8 + 32));
+    RC_TRY(out_buf(s, a.ecc_table, o.ecc_table, n * ECL_ROW_WORDS * 8 + 32));
+    RC_TRY(out_buf(s, a.aux, o.aux, n * ECL_AUX_CELLS * 32 + 32));
+    RC_TRY(out_buf(s, a.aux_kind, o.aux_kind, n * 4 + 32));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_ecc_from_calls_read(zk_session* s, const zk_ecc_call_wire* host, uint64_t* n_table_rows_out) {
     ARG_TRY(s && s->kind == SESSION_ECL, "zk_ecc_from_calls_read: bad arguments");
@@ -4581,15 +4215,14 @@ extern "C" int zk_ecc_from_calls_read(zk_session* s, const zk_ecc_call_wire* hos
     const EccCallArgs& a = s->ecl;
     const u64 np = a.n_add + a.n_mul, n = np + a.n_pairing;
     u32 cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, a.n_table, 4, hipMemcpyDeviceToHost, s->stream));
-    HIP_TRY(hipStreamSynchronize(s->stream));
+    RC_TRY(d2h_now(s->stream, &cnt, a.n_table, 4));
     if (host) {
-        if (host->points && np) HIP_TRY(hipMemcpyAsync(host->points, a.points, (size_t)np * 192, hipMemcpyDeviceToHost, s->stream));
-        if (host->pair_out && a.n_pairing) HIP_TRY(hipMemcpyAsync(host->pair_out, a.pair_out, (size_t)a.n_pairing * 32, hipMemcpyDeviceToHost, s->stream));
-        if (host->rows) HIP_TRY(hipMemcpyAsync(host->rows, a.rows, (size_t)n * ECL_ROW_WORDS * 8, hipMemcpyDeviceToHost, s->stream));
-        if (host->ecc_table && cnt) HIP_TRY(hipMemcpyAsync(host->ecc_table, a.ecc_table, (size_t)cnt * ECL_ROW_WORDS * 8, hipMemcpyDeviceToHost, s->stream));
-        if (host->aux) HIP_TRY(hipMemcpyAsync(host->aux, a.aux, (size_t)n * ECL_AUX_CELLS * 32, hipMemcpyDeviceToHost, s->stream));
-        if (host->aux_kind) HIP_TRY(hipMemcpyAsync(host->aux_kind, a.aux_kind, (size_t)n * 4, hipMemcpyDeviceToHost, s->stream));
+        RC_TRY(d2h_out(s, host->points, a.points, (size_t)np * 192));
+        RC_TRY(d2h_out(s, host->pair_out, a.pair_out, (size_t)a.n_pairing * 32));
+        RC_TRY(d2h_out(s, host->rows, a.rows, (size_t)n * ECL_ROW_WORDS * 8));
+        RC_TRY(d2h_out(s, host->ecc_table, a.ecc_table, (size_t)cnt * ECL_ROW_WORDS * 8));
+        RC_TRY(d2h_out(s, host->aux, a.aux, (size_t)n * ECL_AUX_CELLS * 32));
+        RC_TRY(d2h_out(s, host->aux_kind, a.aux_kind, (size_t)n * 4));
         HIP_TRY(hipStreamSynchronize(s->stream));
     }
     if (n_table_rows_out) *n_table_rows_out = cnt;
@@ -4600,14 +4233,10 @@ extern "C" int zk_ecc_from_calls(const zk_ecc_calls* in, const zk_ecc_call_wire*
     ARG_TRY(result && out, "zk_ecc_from_calls: null output");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_ecc_from_calls_open(in, dev ? out : nullptr, opts, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, dev ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && !dev && status_out) rc = zk_read_status(s, status_out);
-    if (!rc) rc = zk_ecc_from_calls_read(s, dev ? nullptr : out, n_table_rows_out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_ecc_from_calls_open(in, dev ? out : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, status_out, result));
+    return zk_ecc_from_calls_read(s, dev ? nullptr : out, n_table_rows_out);
 }
 
 // ---- Bytecode table + Bytecode-circuit witness + keccak rows from raw contract code (bytecode_code.hpp, k_bytecode_code.hip)
@@ -4622,33 +4251,24 @@ extern "C" int zk_bytecode_from_code_open(const zk_code_set* in, const zk_code_w
     ARG_TRY(dev || !out_dev, "zk_bytecode_from_code_open: out_dev needs ZK_OPT_DEVICE_PTRS");
     ARG_TRY(in->k > 0 || !(out_dev && out_dev->rows), "zk_bytecode_from_code_open: rows asked for with k == 0");
     const u64 n_codes = in->n_codes, n_bytes = in->n_bytes, n_rows = n_bytes + n_codes;
-    zk_session* s = new zk_session();
+    std::vector<BcaChunk> chunks;  // (staged below: declared before the session, destroyed after its close)
+    std::vector<u32> code_chunk0((size_t)n_codes + 1, 0), row_off((size_t)n_codes + 1, 0);
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_BCC;
     s->n = n_rows;
     BccArgs& a = s->bcc;
     KeccakGenArgs& g = s->bcc_kgen;
     memset(&a, 0, sizeof(a));
     memset(&g, 0, sizeof(g));
-    int rc = 0;
-    const void* p = nullptr;
-    void* d = nullptr;
-    u64 rh[4];
-    Fr r;
-    std::vector<u64> h_off((size_t)n_codes + 1, 0);
-    std::vector<BcaChunk> chunks;
-    std::vector<u32> code_chunk0((size_t)n_codes + 1, 0), row_off((size_t)n_codes + 1, 0);
     // the offsets are validated on the host (a device caller's are read back once); the chunk table over them is index plumbing
-    if (dev) {
-        if (fetch_small(s->stream, h_off.data(), in->offsets, (n_codes + 1) * 8)) { rc = -2; g_err = "offsets download failed"; goto fail; }
-        if (fetch_small(s->stream, rh, in->randomness, 32)) { rc = -2; g_err = "randomness download failed"; goto fail; }
-    } else {
-        memcpy(h_off.data(), in->offsets, (n_codes + 1) * 8);
-        memcpy(rh, in->randomness, 32);
-    }
-    if (h_off[0] != 0) { rc = -1; g_err = "zk_bytecode_from_code_open: offsets must start at 0"; goto fail; }
-    for (u64 j = 0; j < n_codes; j++)
-        if (h_off[j] > h_off[j + 1]) { rc = -1; g_err = "zk_bytecode_from_code_open: offsets must be non-decreasing"; goto fail; }
-    if (h_off[n_codes] != n_bytes) { rc = -1; g_err = "zk_bytecode_from_code_open: offsets must end at n_bytes"; goto fail; }
+    std::vector<u64> h_off((size_t)n_codes + 1, 0);
+    u64 rh[4];
+    RC_TRY(host_words(s, h_off.data(), in->offsets, (n_codes + 1) * 8, dev, "offsets"));
+    RC_TRY(host_words(s, rh, in->randomness, 32, dev, "randomness"));
+    ARG_TRY(h_off[0] == 0, "zk_bytecode_from_code_open: offsets must start at 0");
+    for (u64 j = 0; j < n_codes; j++) ARG_TRY(h_off[j] <= h_off[j + 1], "zk_bytecode_from_code_open: offsets must be non-decreasing");
+    ARG_TRY(h_off[n_codes] == n_bytes, "zk_bytecode_from_code_open: offsets must end at n_bytes");
     for (u64 j = 0; j < n_codes; j++) {
         code_chunk0[j] = (u32)chunks.size();
         row_off[j] = (u32)(h_off[j] + j);
@@ -4663,44 +4283,32 @@ extern "C" int zk_bytecode_from_code_open(const zk_code_set* in, const zk_code_w
     code_chunk0[n_codes] = (u32)chunks.size();
     row_off[n_codes] = (u32)n_rows;
     if (dev || !n_bytes) {
-        if ((rc = stage(s, n_bytes ? in->code : nullptr, (size_t)n_bytes, dev, &p))) goto fail;
-        a.code = (const uint8_t*)p;
+        RC_TRY(stage_in(s, a.code, n_bytes ? in->code : nullptr, (size_t)n_bytes, dev));
     } else {  // staged with its last aligned word whole (the sponge reads whole aligned words)
-        if ((rc = dev_alloc(s, &d, (size_t)((n_bytes + 15) & ~7ull)))) goto fail;
-        if (hipMemcpyAsync(d, in->code, (size_t)n_bytes, hipMemcpyHostToDevice, s->stream) != hipSuccess) { rc = -2; g_err = "zk_bytecode_from_code_open: code upload failed"; goto fail; }
-        a.code = (const uint8_t*)d;
+        uint8_t* d_code = nullptr;
+        RC_TRY(dev_buf(s, d_code, (size_t)((n_bytes + 15) & ~7ull)));
+        DEV_TRY(hipMemcpyAsync(d_code, in->code, (size_t)n_bytes, hipMemcpyHostToDevice, s->stream) == hipSuccess,
+                "zk_bytecode_from_code_open: code upload failed");
+        a.code = d_code;
     }
-    if ((rc = stage(s, in->offsets, (size_t)(n_codes + 1) * 8, dev, &p))) goto fail;
-    a.offsets = (const u64*)p;
-    if ((rc = stage(s, row_off.data(), row_off.size() * 4, false, &p))) goto fail;
-    a.row_off = (const u32*)p;
-    if ((rc = stage(s, chunks.empty() ? nullptr : chunks.data(), chunks.size() * sizeof(BcaChunk), false, &p))) goto fail;
-    a.p.chunks = (const BcaChunk*)p;
-    if ((rc = stage(s, code_chunk0.data(), code_chunk0.size() * 4, false, &p))) goto fail;
-    a.p.code_chunk0 = (const u32*)p;
+    RC_TRY(stage_in(s, a.offsets, in->offsets, (size_t)(n_codes + 1) * 8, dev));
+    RC_TRY(stage_in(s, a.row_off, row_off.data(), row_off.size() * 4, false));
+    RC_TRY(stage_in(s, a.p.chunks, chunks.empty() ? nullptr : chunks.data(), chunks.size() * sizeof(BcaChunk), false));
+    RC_TRY(stage_in(s, a.p.code_chunk0, code_chunk0.data(), code_chunk0.size() * 4, false));
     a.n_bytes = n_bytes; a.n_codes = n_codes; a.n_rows = n_rows; a.n_out = in->k ? 1ull << in->k : 0;
     a.p.n_codes = n_codes; a.p.n_chunks = chunks.size();
-    for (int q = 0; q < 4; q++) { r.v[2 * q] = (u32)rh[q]; r.v[2 * q + 1] = (u32)(rh[q] >> 32); }
-    {
-        u64* d_rpow = nullptr;
-        if ((rc = dev_alloc(s, (void**)&d_rpow, BCA_RPOW_ROWS * 32))) goto fail;
-        zk_launch_bca_rpow(s->stream, r, d_rpow);
-        a.p.rpow = d_rpow;
-    }
+    u64* d_rpow = nullptr;
+    RC_TRY(dev_buf(s, d_rpow, BCA_RPOW_ROWS * 32));
+    zk_launch_bca_rpow(s->stream, fr_from_words(rh), d_rpow);
+    a.p.rpow = d_rpow;
     // the host vectors above go out of scope with this call
-    if (hipStreamSynchronize(s->stream) != hipSuccess) { rc = -2; g_err = "zk_bytecode_from_code_open: upload failed"; goto fail; }
-    if ((rc = dev_alloc(s, &d, chunks.size() * 32))) goto fail;
-    a.p.chunk_acc = (u64*)d;
-    if ((rc = dev_alloc(s, &d, chunks.size() * 4))) goto fail;
-    a.p.chunk_m = (u32*)d;
-    if ((rc = dev_alloc(s, &d, chunks.size() * (size_t)BCA_MAP_STRIDE))) goto fail;
-    a.p.chunk_map = (uint8_t*)d;
-    if ((rc = dev_alloc(s, &d, chunks.size() * 4))) goto fail;
-    a.p.chunk_state = (u32*)d;
-    if ((rc = dev_alloc(s, &d, chunks.size() * 32))) goto fail;
-    a.p.chunk_in = (u64*)d;
-    if ((rc = dev_alloc(s, &d, (size_t)n_bytes * 32))) goto fail;
-    a.part = (u64*)d;
+    DEV_TRY(hipStreamSynchronize(s->stream) == hipSuccess, "zk_bytecode_from_code_open: upload failed");
+    RC_TRY(dev_buf(s, a.p.chunk_acc, chunks.size() * 32));
+    RC_TRY(dev_buf(s, a.p.chunk_m, chunks.size() * 4));
+    RC_TRY(dev_buf(s, a.p.chunk_map, chunks.size() * (size_t)BCA_MAP_STRIDE));
+    RC_TRY(dev_buf(s, a.p.chunk_state, chunks.size() * 4));
+    RC_TRY(dev_buf(s, a.p.chunk_in, chunks.size() * 32));
+    RC_TRY(dev_buf(s, a.part, (size_t)n_bytes * 32));
     // the keccak pass over the same bytes (KeccakCircuit.add mode), as zk_keccak_open sets it up
     g.data = a.code;
     g.offsets = a.offsets;
@@ -4708,26 +4316,19 @@ extern "C" int zk_bytecode_from_code_open(const zk_code_set* in, const zk_code_w
     g.mode = KT_MODE_CIRCUIT;
     if (!getenv("ZK_KECCAK_NO_GROUPS")) {
         u32* d_list = nullptr;
-        if ((rc = dev_alloc(s, (void**)&d_list, ((size_t)n_codes + 1) * sizeof(u32)))) goto fail;
+        RC_TRY(dev_buf(s, d_list, ((size_t)n_codes + 1) * sizeof(u32)));
         g.long_list = d_list + 1;
         g.long_count = d_list;
     }
-    if ((rc = keccak_rpow_open(s, rh, &g.rpow))) goto fail;
-#define BCC_OUT_BUF(field, bytes)                                                     \
-    if (out_dev && out_dev->field) a.field = out_dev->field;                          \
-    else { if ((rc = dev_alloc(s, &d, (size_t)(bytes)))) goto fail; a.field = (u64*)d; }
-    BCC_OUT_BUF(table, n_rows * BCC_TABLE_NCELLS * 32)
-    BCC_OUT_BUF(rows, a.n_out * BCA_OUT_NCELLS * 32)
-#undef BCC_OUT_BUF
-    if (out_dev && out_dev->keccak) g.rows = out_dev->keccak;
-    else { if ((rc = dev_alloc(s, &d, (size_t)n_codes * KT_NCELLS * 32))) goto fail; g.rows = (u64*)d; }
+    RC_TRY(keccak_rpow_open(s, rh, &g.rpow));
+    const zk_code_wire o = wire_or_nulls(out_dev);
+    RC_TRY(out_buf(s, a.table, o.table, n_rows * BCC_TABLE_NCELLS * 32));
+    RC_TRY(out_buf(s, a.rows, o.rows, a.n_out * BCA_OUT_NCELLS * 32));
+    RC_TRY(out_buf(s, g.rows, o.keccak, (size_t)n_codes * KT_NCELLS * 32));
     a.keccak = g.rows;
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_bytecode_from_code_read(zk_session* s, const zk_code_wire* host) {
     ARG_TRY(s && s->kind == SESSION_BCC, "zk_bytecode_from_code_read: bad arguments");
@@ -4735,9 +4336,9 @@ extern "C" int zk_bytecode_from_code_read(zk_session* s, const zk_code_wire* hos
     const BccArgs& a = s->bcc;
     ARG_TRY(!(host && host->rows) || a.n_out, "zk_bytecode_from_code_read: rows asked for with k == 0");
     if (host) {
-        if (host->table && a.n_rows) HIP_TRY(hipMemcpyAsync(host->table, a.table, (size_t)a.n_rows * BCC_TABLE_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
-        if (host->rows) HIP_TRY(hipMemcpyAsync(host->rows, a.rows, (size_t)a.n_out * BCA_OUT_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
-        if (host->keccak && a.n_codes) HIP_TRY(hipMemcpyAsync(host->keccak, a.keccak, (size_t)a.n_codes * KT_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        RC_TRY(d2h_out(s, host->table, a.table, (size_t)a.n_rows * BCC_TABLE_NCELLS * 32));
+        RC_TRY(d2h_out(s, host->rows, a.rows, (size_t)a.n_out * BCA_OUT_NCELLS * 32));
+        RC_TRY(d2h_out(s, host->keccak, a.keccak, (size_t)a.n_codes * KT_NCELLS * 32));
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
@@ -4747,13 +4348,10 @@ extern "C" int zk_bytecode_from_code(const zk_code_set* in, const zk_code_wire* 
     ARG_TRY(in->k > 0 || !out->rows, "zk_bytecode_from_code: rows asked for with k == 0");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_bytecode_from_code_open(in, dev ? out : nullptr, opts, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc) rc = zk_bytecode_from_code_read(s, dev ? nullptr : out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_bytecode_from_code_open(in, dev ? out : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, nullptr, result));
+    return zk_bytecode_from_code_read(s, dev ? nullptr : out);
 }
 
 // ---- EVM circuit tx / block / withdrawal tables from raw block data (block_tables.hpp, k_block_tables.hip)
@@ -4796,8 +4394,7 @@ extern "C" int zk_evm_tables_from_block_sizes(const zk_block_data* t, uint32_t o
     HIP_TRY(hipSetDevice(t_device));
     ARG_TRY(BTB_ARGS_OK(t), "zk_evm_tables_from_block_sizes: bad arguments");
     BtbHost h;
-    const int rc = btb_prepare(t, opts & ZK_OPT_DEVICE_PTRS, t_stream ? t_stream : g_own_stream[t_device], h);
-    if (rc) return rc;
+    RC_TRY(btb_prepare(t, opts & ZK_OPT_DEVICE_PTRS, t_stream ? t_stream : g_own_stream[t_device], h));
     if (n_tx_rows) *n_tx_rows = h.z.n_tx_rows;
     if (n_block_rows) *n_block_rows = h.z.n_block_rows;
     if (n_withdrawal_rows) *n_withdrawal_rows = t->n_withdrawals;
@@ -4809,88 +4406,65 @@ extern "C" int zk_evm_tables_from_block_open(const zk_block_data* t, const zk_bl
     ARG_TRY(BTB_ARGS_OK(t) && out, "zk_evm_tables_from_block_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     ARG_TRY(dev || !out_dev, "zk_evm_tables_from_block_open: out_dev needs ZK_OPT_DEVICE_PTRS");
-    zk_session* s = new zk_session();
+    BtbHost h;  // (the host arrays the staged uploads read: declared before the session, destroyed after its close)
+    std::vector<u64> ids, wd_ids;
+    std::vector<u32> wave_tx;
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_BTB;
     BtbArgs& a = s->btb;
     memset(&a, 0, sizeof(a));
-    BtbHost h;
-    std::vector<u64> ids, wd_ids;
-    std::vector<u32> wave_tx;
-    const void* p = nullptr;
-    void* d = nullptr;
     const u64 n = t->n_txs, nw = t->n_withdrawals, nh = t->n_history;
-    int rc = btb_prepare(t, dev, s->stream, h);
-    if (rc) goto fail;
-    {
-        const BtbPlan& z = h.z;
-        s->n = z.n_tx_rows;
-        ids.assign((size_t)n * 4 + 4, 0);
-        wd_ids.assign((size_t)nw * 4 + 4, 0);
-        for (u64 i = 0; i < n; i++) memcpy(ids.data() + 4 * i, h.txf.data() + i * BTB_NTX_FIELDS * 4, 32);
-        for (u64 i = 0; i < nw; i++) memcpy(wd_ids.data() + 4 * i, h.wd.data() + i * BTB_WD_NCELLS * 4, 32);
-        if ((rc = stage(s, t->tx_fields, (size_t)n * BTB_NTX_FIELDS * 32, dev, &p))) goto fail;
-        a.txf = (const u64*)p;
-        if ((rc = stage(s, t->to_is_none, (size_t)n * 4, dev, &p))) goto fail;
-        a.to_none = (const u32*)p;
-        if ((rc = stage(s, t->access_list, (size_t)n * 8, dev, &p))) goto fail;
-        a.access = (const u32*)p;
-        if ((rc = stage(s, z.n_bytes ? t->calldata : nullptr, (size_t)z.n_bytes, dev, &p))) goto fail;
-        a.calldata = (const uint8_t*)p;
-        if ((rc = stage(s, t->block, t->block ? BTB_NBLOCK_FIELDS * 32 : 0, dev, &p))) goto fail;
-        a.block = (const u64*)p;
-        if ((rc = stage(s, t->history_hashes, (size_t)nh * 32, dev, &p))) goto fail;
-        a.hashes = (const u64*)p;
-        if ((rc = stage(s, t->withdrawals, (size_t)nw * BTB_WD_NCELLS * 32, dev, &p))) goto fail;
-        a.wd = (const u64*)p;
-        // the session's own copies of what was checked (fixed for the session: a caller that rewrites its offsets cannot move a store)
-        if ((rc = stage(s, h.offs.data(), ((size_t)n + 1) * 8, false, &p))) goto fail;
-        a.offs = (const u64*)p;
-        if ((rc = stage(s, ids.data(), (size_t)n * 32, false, &p))) goto fail;
-        a.ids = (const u64*)p;
-        if ((rc = stage(s, wd_ids.data(), (size_t)nw * 32, false, &p))) goto fail;
-        a.wd_ids = (const u64*)p;
-        wave_tx.assign((size_t)((z.n_tx_rows * BTB_TX_PIECES + 63) / 64) + 1, 0);
-        btb_wave_index(h.offs.data(), n, z.n_tx_rows, wave_tx.data());
-        if ((rc = stage(s, wave_tx.data(), wave_tx.size() * 4, false, &p))) goto fail;
-        a.wave_tx = (const u32*)p;
-        a.n_txs = n; a.n_bytes = z.n_bytes; a.n_tx_rows = z.n_tx_rows; a.n_hist = nh; a.n_block_rows = z.n_block_rows; a.n_wd = nw;
-        if (t->block) memcpy(a.number, h.block.data() + 4 * 2, 32);
-        a.mis = z.n_bytes ? (u32)((uintptr_t)a.calldata & 15u) : 0u;
-        a.hist_rot = z.hist_rot;
-        a.n_gas_blocks = z.n_bytes ? (a.mis + z.n_bytes + BTB_GAS_BLOCK - 1) / BTB_GAS_BLOCK : 0;
-        // the host vectors above go out of scope with this call
-        if (hipStreamSynchronize(s->stream) != hipSuccess) { rc = -2; g_err = "zk_evm_tables_from_block_open: upload failed"; goto fail; }
-        if ((rc = dev_alloc(s, &d, ((size_t)a.n_gas_blocks + 1) * 4))) goto fail;
-        a.gas_part = (u32*)d;
-        if ((rc = dev_alloc(s, &d, ((size_t)a.n_gas_blocks + 1) * 4))) goto fail;
-        a.gas_pre = (u32*)d;
-#define BTB_OUT_BUF(member, field, type, bytes)                                             \
-    if (out_dev && out_dev->member) a.field = out_dev->member;                              \
-    else { if ((rc = dev_alloc(s, &d, (size_t)(bytes)))) goto fail; a.field = (type*)d; }
-        BTB_OUT_BUF(tx, tx, u64, z.n_tx_rows * BTB_TX_NCELLS * 32)
-        BTB_OUT_BUF(tx_flags, tx_flags, u32, z.n_tx_rows * 4)
-        BTB_OUT_BUF(block, blk, u64, z.n_block_rows * BTB_BLOCK_NCELLS * 32)
-        BTB_OUT_BUF(block_flags, blk_flags, u32, z.n_block_rows * 4)
-        BTB_OUT_BUF(withdrawals, wdt, u64, nw * BTB_WD_NCELLS * 32)
-#undef BTB_OUT_BUF
-    }
-    if ((rc = session_common_init(s))) goto fail;
-    *out = s;
+    RC_TRY(btb_prepare(t, dev, s->stream, h));
+    const BtbPlan& z = h.z;
+    s->n = z.n_tx_rows;
+    ids.assign((size_t)n * 4 + 4, 0);
+    wd_ids.assign((size_t)nw * 4 + 4, 0);
+    for (u64 i = 0; i < n; i++) memcpy(ids.data() + 4 * i, h.txf.data() + i * BTB_NTX_FIELDS * 4, 32);
+    for (u64 i = 0; i < nw; i++) memcpy(wd_ids.data() + 4 * i, h.wd.data() + i * BTB_WD_NCELLS * 4, 32);
+    RC_TRY(stage_in(s, a.txf, t->tx_fields, (size_t)n * BTB_NTX_FIELDS * 32, dev));
+    RC_TRY(stage_in(s, a.to_none, t->to_is_none, (size_t)n * 4, dev));
+    RC_TRY(stage_in(s, a.access, t->access_list, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, a.calldata, z.n_bytes ? t->calldata : nullptr, (size_t)z.n_bytes, dev));
+    RC_TRY(stage_in(s, a.block, t->block, t->block ? BTB_NBLOCK_FIELDS * 32 : 0, dev));
+    RC_TRY(stage_in(s, a.hashes, t->history_hashes, (size_t)nh * 32, dev));
+    RC_TRY(stage_in(s, a.wd, t->withdrawals, (size_t)nw * BTB_WD_NCELLS * 32, dev));
+    // the session's own copies of what was checked (fixed for the session: a caller that rewrites its offsets cannot move a store)
+    RC_TRY(stage_in(s, a.offs, h.offs.data(), ((size_t)n + 1) * 8, false));
+    RC_TRY(stage_in(s, a.ids, ids.data(), (size_t)n * 32, false));
+    RC_TRY(stage_in(s, a.wd_ids, wd_ids.data(), (size_t)nw * 32, false));
+    wave_tx.assign((size_t)((z.n_tx_rows * BTB_TX_PIECES + 63) / 64) + 1, 0);
+    btb_wave_index(h.offs.data(), n, z.n_tx_rows, wave_tx.data());
+    RC_TRY(stage_in(s, a.wave_tx, wave_tx.data(), wave_tx.size() * 4, false));
+    a.n_txs = n; a.n_bytes = z.n_bytes; a.n_tx_rows = z.n_tx_rows; a.n_hist = nh; a.n_block_rows = z.n_block_rows; a.n_wd = nw;
+    if (t->block) memcpy(a.number, h.block.data() + 4 * 2, 32);
+    a.mis = z.n_bytes ? (u32)((uintptr_t)a.calldata & 15u) : 0u;
+    a.hist_rot = z.hist_rot;
+    a.n_gas_blocks = z.n_bytes ? (a.mis + z.n_bytes + BTB_GAS_BLOCK - 1) / BTB_GAS_BLOCK : 0;
+    // the host vectors above go out of scope with this call
+    DEV_TRY(hipStreamSynchronize(s->stream) == hipSuccess, "zk_evm_tables_from_block_open: upload failed");
+    RC_TRY(dev_buf(s, a.gas_part, ((size_t)a.n_gas_blocks + 1) * 4));
+    RC_TRY(dev_buf(s, a.gas_pre, ((size_t)a.n_gas_blocks + 1) * 4));
+    const zk_block_tables o = wire_or_nulls(out_dev);
+    RC_TRY(out_buf(s, a.tx, o.tx, z.n_tx_rows * BTB_TX_NCELLS * 32));
+    RC_TRY(out_buf(s, a.tx_flags, o.tx_flags, z.n_tx_rows * 4));
+    RC_TRY(out_buf(s, a.blk, o.block, z.n_block_rows * BTB_BLOCK_NCELLS * 32));
+    RC_TRY(out_buf(s, a.blk_flags, o.block_flags, z.n_block_rows * 4));
+    RC_TRY(out_buf(s, a.wdt, o.withdrawals, nw * BTB_WD_NCELLS * 32));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_evm_tables_from_block_read(zk_session* s, const zk_block_tables* host) {
     ARG_TRY(s && s->kind == SESSION_BTB, "zk_evm_tables_from_block_read: bad arguments");
     HIP_TRY(hipSetDevice(s->device));
     const BtbArgs& a = s->btb;
     if (host) {
-        if (host->tx && a.n_tx_rows) HIP_TRY(hipMemcpyAsync(host->tx, a.tx, (size_t)a.n_tx_rows * BTB_TX_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
-        if (host->tx_flags && a.n_tx_rows) HIP_TRY(hipMemcpyAsync(host->tx_flags, a.tx_flags, (size_t)a.n_tx_rows * 4, hipMemcpyDeviceToHost, s->stream));
-        if (host->block && a.n_block_rows) HIP_TRY(hipMemcpyAsync(host->block, a.blk, (size_t)a.n_block_rows * BTB_BLOCK_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
-        if (host->block_flags && a.n_block_rows) HIP_TRY(hipMemcpyAsync(host->block_flags, a.blk_flags, (size_t)a.n_block_rows * 4, hipMemcpyDeviceToHost, s->stream));
-        if (host->withdrawals && a.n_wd) HIP_TRY(hipMemcpyAsync(host->withdrawals, a.wdt, (size_t)a.n_wd * BTB_WD_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        RC_TRY(d2h_out(s, host->tx, a.tx, (size_t)a.n_tx_rows * BTB_TX_NCELLS * 32));
+        RC_TRY(d2h_out(s, host->tx_flags, a.tx_flags, (size_t)a.n_tx_rows * 4));
+        RC_TRY(d2h_out(s, host->block, a.blk, (size_t)a.n_block_rows * BTB_BLOCK_NCELLS * 32));
+        RC_TRY(d2h_out(s, host->block_flags, a.blk_flags, (size_t)a.n_block_rows * 4));
+        RC_TRY(d2h_out(s, host->withdrawals, a.wdt, (size_t)a.n_wd * BTB_WD_NCELLS * 32));
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
@@ -4899,93 +4473,62 @@ extern "C" int zk_evm_tables_from_block(const zk_block_data* t, const zk_block_t
     ARG_TRY(result && out_wire && t, "zk_evm_tables_from_block: null argument");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_evm_tables_from_block_open(t, dev ? out_wire : nullptr, opts, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc) rc = zk_evm_tables_from_block_read(s, dev ? nullptr : out_wire);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_evm_tables_from_block_open(t, dev ? out_wire : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, nullptr, result));
+    return zk_evm_tables_from_block_read(s, dev ? nullptr : out_wire);
 }
 
 // ---- EVM circuit witness from compact trace records (trace_witness.hpp, k_trace_witness.hip)
 #define TRW_ARGS_OK(t) ((t) && ((t)->n_rw == 0 || ((t)->head && (t)->id && (t)->addr && (t)->val && (t)->prev)) && ((t)->n_pool == 0 || (t)->pool) && \
                         ((t)->n_steps == 0 || (t)->steps))
 // Open a session over the records: the inputs staged (host callers) or used in place, the checks and the pool offsets run on the device,
-// the 32-byte verdict block read back (one wait).  check_only: no output buffers (zk_evm_witness_from_trace_sizes closes the session).
+// the 32-byte verdict block read back (one wait).  check_only: the checks alone, no session is handed out (zk_evm_witness_from_trace_sizes).
 static int trw_open(const zk_trace* t, const zk_trace_witness* out_dev, uint32_t opts, bool check_only, zk_session** out) {
     char msg[256];
     if (int rc = trw_plan_counts(t->n_rw, t->n_steps, t->rw_base, t->rw_counter != nullptr, msg, sizeof msg)) { g_err = msg; return rc; }  // (before anything is read or allocated)
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_TRW;
     s->n = t->n_rw;
     TrwArgs& a = s->trw;
     memset(&a, 0, sizeof(a));
-    const void* p = nullptr;
-    void* d = nullptr;
     const u64 n = t->n_rw, ns = t->n_steps;
-    u64 v[TRW_V_WORDS];
-    int rc = 0;
-    if ((rc = stage(s, t->head, (size_t)n * 4, dev, &p))) goto fail;
-    a.head_in = (const u32*)p;
-    if (t->rw_counter && n) {
-        if ((rc = stage(s, t->rw_counter, (size_t)n * 8, dev, &p))) goto fail;
-        a.ctr_in = (const u64*)p;
-    }
-    if ((rc = stage(s, t->id, (size_t)n * 8, dev, &p))) goto fail;
-    a.id = (const u64*)p;
-    if ((rc = stage(s, t->addr, (size_t)n * 8, dev, &p))) goto fail;
-    a.addr = (const u64*)p;
-    if ((rc = stage(s, t->val, (size_t)n * 8, dev, &p))) goto fail;
-    a.val = (const u64*)p;
-    if ((rc = stage(s, t->prev, (size_t)n * 8, dev, &p))) goto fail;
-    a.prev = (const u64*)p;
-    if ((rc = stage(s, t->pool, (size_t)t->n_pool * 32, dev, &p))) goto fail;
-    a.pool = (const u64*)p;
-    if ((rc = stage(s, t->steps, (size_t)ns * TRW_STEP_WORDS * 8, dev, &p))) goto fail;
-    a.steps_in = (const u64*)p;
+    RC_TRY(stage_in(s, a.head_in, t->head, (size_t)n * 4, dev));
+    if (t->rw_counter && n) RC_TRY(stage_in(s, a.ctr_in, t->rw_counter, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, a.id, t->id, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, a.addr, t->addr, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, a.val, t->val, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, a.prev, t->prev, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, a.pool, t->pool, (size_t)t->n_pool * 32, dev));
+    RC_TRY(stage_in(s, a.steps_in, t->steps, (size_t)ns * TRW_STEP_WORDS * 8, dev));
     a.n_rw = n; a.n_pool = t->n_pool; a.n_steps = ns; a.rw_base = t->rw_base;
     // the session's own copies of what is checked (fixed for the session: a caller that rewrites a head cannot move a store)
-    if ((rc = dev_alloc(s, &d, (size_t)n * 4 + 4))) goto fail;
-    a.head = (u32*)d;
-    if (a.ctr_in) {
-        if ((rc = dev_alloc(s, &d, (size_t)n * 8))) goto fail;
-        a.ctr = (u64*)d;
-    }
-    if ((rc = dev_alloc(s, &d, (size_t)n * 8 + 8))) goto fail;
-    a.off = (u64*)d;
-    if ((rc = dev_alloc(s, &d, TRW_V_WORDS * 8))) goto fail;
-    a.verdict = (u64*)d;
+    RC_TRY(dev_buf(s, a.head, (size_t)n * 4 + 4));
+    if (a.ctr_in) RC_TRY(dev_buf(s, a.ctr, (size_t)n * 8));
+    RC_TRY(dev_buf(s, a.off, (size_t)n * 8 + 8));
+    RC_TRY(dev_buf(s, a.verdict, TRW_V_WORDS * 8));
     zk_launch_trace_witness_check(s->stream, a);
-    if (hipGetLastError() != hipSuccess) { rc = -2; g_err = "zk_evm_witness_from_trace: the open's check launch failed"; goto fail; }
-    if ((rc = d2h_now(s->stream, v, a.verdict, sizeof v))) goto fail;  // (also: the staged host arrays are uploaded)
-    if ((rc = trw_verdict_error(v, t->n_pool, msg, sizeof msg))) { g_err = msg; goto fail; }
-    if (!check_only) {
-#define TRW_OUT_BUF(member, type, bytes)                                                    \
-    if (out_dev && out_dev->member) a.member = out_dev->member;                             \
-    else { if ((rc = dev_alloc(s, &d, (size_t)(bytes)))) goto fail; a.member = (type*)d; }
-        TRW_OUT_BUF(rw, u64, n * TRW_RW_NCELLS * 32)
-        TRW_OUT_BUF(rw_flags, u32, n * 4)
-        TRW_OUT_BUF(steps, u64, ns * TRW_STEP_NCELLS * 32)
-#undef TRW_OUT_BUF
-        if ((rc = session_common_init(s))) goto fail;
-    }
-    *out = s;
+    DEV_TRY(hipGetLastError() == hipSuccess, "zk_evm_witness_from_trace: the open's check launch failed");
+    u64 v[TRW_V_WORDS];
+    RC_TRY(d2h_now(s->stream, v, a.verdict, sizeof v));  // (also: the staged host arrays are uploaded)
+    if (int rc = trw_verdict_error(v, t->n_pool, msg, sizeof msg)) { g_err = msg; return rc; }
+    if (check_only) return 0;
+    const zk_trace_witness o = wire_or_nulls(out_dev);
+    RC_TRY(out_buf(s, a.rw, o.rw, n * TRW_RW_NCELLS * 32));
+    RC_TRY(out_buf(s, a.rw_flags, o.rw_flags, n * 4));
+    RC_TRY(out_buf(s, a.steps, o.steps, ns * TRW_STEP_NCELLS * 32));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_evm_witness_from_trace_sizes(const zk_trace* t, uint32_t opts, uint64_t* n_rw_rows, uint64_t* n_step_rows) {
     ARG_TRY(t_device >= 0, "zk_evm_witness_from_trace_sizes: call zk_init first");
     HIP_TRY(hipSetDevice(t_device));
     ARG_TRY(TRW_ARGS_OK(t), "zk_evm_witness_from_trace_sizes: bad arguments");
     if (opts & ZK_OPT_DEVICE_PTRS) {
-        zk_session* s = nullptr;
-        const int rc = trw_open(t, nullptr, opts, true, &s);
-        if (rc) return rc;
-        zk_close(s);
+        RC_TRY(trw_open(t, nullptr, opts, true, nullptr));
     } else {  // host arrays: the same checks in a host loop
         char msg[256];
         int rc = trw_plan_counts(t->n_rw, t->n_steps, t->rw_base, t->rw_counter != nullptr, msg, sizeof msg);
@@ -5012,9 +4555,9 @@ extern "C" int zk_evm_witness_from_trace_read(zk_session* s, const zk_trace_witn
     HIP_TRY(hipSetDevice(s->device));
     const TrwArgs& a = s->trw;
     if (host) {
-        if (host->rw && a.n_rw) HIP_TRY(hipMemcpyAsync(host->rw, a.rw, (size_t)a.n_rw * TRW_RW_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
-        if (host->rw_flags && a.n_rw) HIP_TRY(hipMemcpyAsync(host->rw_flags, a.rw_flags, (size_t)a.n_rw * 4, hipMemcpyDeviceToHost, s->stream));
-        if (host->steps && a.n_steps) HIP_TRY(hipMemcpyAsync(host->steps, a.steps, (size_t)a.n_steps * TRW_STEP_NCELLS * 32, hipMemcpyDeviceToHost, s->stream));
+        RC_TRY(d2h_out(s, host->rw, a.rw, (size_t)a.n_rw * TRW_RW_NCELLS * 32));
+        RC_TRY(d2h_out(s, host->rw_flags, a.rw_flags, (size_t)a.n_rw * 4));
+        RC_TRY(d2h_out(s, host->steps, a.steps, (size_t)a.n_steps * TRW_STEP_NCELLS * 32));
     }
     HIP_TRY(hipStreamSynchronize(s->stream));
     return 0;
@@ -5023,13 +4566,10 @@ extern "C" int zk_evm_witness_from_trace(const zk_trace* t, const zk_trace_witne
     ARG_TRY(result && out_wire && t, "zk_evm_witness_from_trace: null argument");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_evm_witness_from_trace_open(t, dev ? out_wire : nullptr, opts, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc) rc = zk_evm_witness_from_trace_read(s, dev ? nullptr : out_wire);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_evm_witness_from_trace_open(t, dev ? out_wire : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, nullptr, result));
+    return zk_evm_witness_from_trace_read(s, dev ? nullptr : out_wire);
 }
 
 // ---- State circuit from compact trace records (state_trace.hpp, k_state_trace.hip): the records of zk_evm_witness_from_trace without the
@@ -5053,46 +4593,30 @@ static int strc_setup(zk_session* s, const zk_trace* t, bool dev, bool want_ops,
     memset(&c, 0, sizeof(c));
     s->from_trace = true;
     const u64 n = t->n_rw;
-    const void* p = nullptr;
-    void* d = nullptr;
-    u64 v[TRW_V_WORDS];
-    int rc = 0;
-    std::vector<u32> h_masks(2 * RWK_MASK_WORDS_H + RWK_NCLASSES);
-    const size_t mask_bytes = h_masks.size() * 4;
-    if ((rc = stage(s, t->head, (size_t)n * 4, dev, &p))) return rc;
-    w.head_in = (const u32*)p;
-    if (t->rw_counter) {
-        if ((rc = stage(s, t->rw_counter, (size_t)n * 8, dev, &p))) return rc;
-        w.ctr_in = (const u64*)p;
-    }
-    if ((rc = stage(s, t->id, (size_t)n * 8, dev, &p))) return rc;
-    w.id = (const u64*)p;
-    if ((rc = stage(s, t->addr, (size_t)n * 8, dev, &p))) return rc;
-    w.addr = (const u64*)p;
-    if ((rc = stage(s, t->val, (size_t)n * 8, dev, &p))) return rc;
-    w.val = (const u64*)p;
-    if ((rc = stage(s, t->pool, (size_t)t->n_pool * 32, dev, &p))) return rc;
-    w.pool = (const u64*)p;
+    RC_TRY(stage_in(s, w.head_in, t->head, (size_t)n * 4, dev));
+    if (t->rw_counter) RC_TRY(stage_in(s, w.ctr_in, t->rw_counter, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, w.id, t->id, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, w.addr, t->addr, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, w.val, t->val, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, w.pool, t->pool, (size_t)t->n_pool * 32, dev));
     w.n_rw = n; w.n_pool = t->n_pool; w.n_steps = 0; w.rw_base = t->rw_base;  // (prev and the steps are not read)
-    if ((rc = dev_alloc(s, &d, (size_t)n * 4 + 4))) return rc;
-    w.head = (u32*)d;
-    if (w.ctr_in) {
-        if ((rc = dev_alloc(s, &d, (size_t)n * 8))) return rc;
-        w.ctr = (u64*)d;
-    }
-    if ((rc = dev_alloc(s, &d, (size_t)n * 8 + 8))) return rc;
-    w.off = (u64*)d;
-    if ((rc = dev_alloc(s, &d, TRW_V_WORDS * 8))) return rc;
-    w.verdict = (u64*)d;
-    if ((rc = dev_alloc(s, &d, (size_t)((n + 1023) / 1024) * 8))) return rc;  // the offset scan's chunk sums
-    zk_launch_state_trace_check(s->stream, w, (u64*)d);
-    if (hipGetLastError() != hipSuccess) { g_err = std::string(name) + ": the open's check launch failed"; return -2; }
-    if ((rc = d2h_now(s->stream, v, w.verdict, sizeof v))) return rc;
-    if ((rc = trw_verdict_error(v, t->n_pool, msg, sizeof msg))) { g_err = msg; strc_retitle(name); return rc; }
+    RC_TRY(dev_buf(s, w.head, (size_t)n * 4 + 4));
+    if (w.ctr_in) RC_TRY(dev_buf(s, w.ctr, (size_t)n * 8));
+    RC_TRY(dev_buf(s, w.off, (size_t)n * 8 + 8));
+    RC_TRY(dev_buf(s, w.verdict, TRW_V_WORDS * 8));
+    u64* d_sums = nullptr;  // the offset scan's chunk sums
+    RC_TRY(dev_buf(s, d_sums, (size_t)((n + 1023) / 1024) * 8));
+    zk_launch_state_trace_check(s->stream, w, d_sums);
+    DEV_TRY(hipGetLastError() == hipSuccess, std::string(name) + ": the open's check launch failed");
+    u64 v[TRW_V_WORDS];
+    RC_TRY(d2h_now(s->stream, v, w.verdict, sizeof v));
+    if (int rc = trw_verdict_error(v, t->n_pool, msg, sizeof msg)) { g_err = msg; strc_retitle(name); return rc; }
     c.head = w.head; c.ctr = w.ctr; c.id = w.id; c.addr = w.addr; c.val = w.val; c.off = w.off; c.pool = w.pool;
     c.n = n; c.rw_base = t->rw_base;
     a.n = n;
-    if ((rc = dev_alloc(s, (void**)&a.masks, mask_bytes))) return rc;
+    std::vector<u32> h_masks(2 * RWK_MASK_WORDS_H + RWK_NCLASSES);
+    const size_t mask_bytes = h_masks.size() * 4;
+    RC_TRY(dev_buf(s, a.masks, mask_bytes));
     HIP_TRY(hipMemsetAsync(a.masks, 0, mask_bytes, s->stream));
     zk_launch_state_trace_scan(s->stream, a, c);
     HIP_TRY(hipMemcpyAsync(h_masks.data(), a.masks, mask_bytes, hipMemcpyDeviceToHost, s->stream));
@@ -5111,15 +4635,15 @@ extern "C" int zk_state_ops_from_trace_open(const zk_trace* t, uint64_t* ops_dev
     ARG_TRY(out && STRC_ARGS_OK(t), "zk_state_ops_from_trace_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     ARG_TRY(dev || (!ops_dev && !op_flags_dev), "zk_state_ops_from_trace_open: output buffers need ZK_OPT_DEVICE_PTRS");
-    if (int rc = strc_counts(t, "zk_state_ops_from_trace")) return rc;
-    zk_session* s = new zk_session();
+    RC_TRY(strc_counts(t, "zk_state_ops_from_trace"));
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_REKEY;
     s->n = t->n_rw;
-    int rc = strc_setup(s, t, dev, true, ops_dev, op_flags_dev, "zk_state_ops_from_trace");
-    if (!rc) rc = session_common_init(s);
-    if (rc) { zk_close(s); return rc; }
+    RC_TRY(strc_setup(s, t, dev, true, ops_dev, op_flags_dev, "zk_state_ops_from_trace"));
+    RC_TRY(session_common_init(s));
     if (n_ops_out) *n_ops_out = s->rekey.n_ops;
-    *out = s;
+    *out = guard.release();
     return 0;
 }
 extern "C" int zk_state_ops_from_trace_read(zk_session* s, uint64_t* ops_host, uint32_t* op_flags_host, uint64_t* n_ops_out) {
@@ -5131,14 +4655,10 @@ extern "C" int zk_state_ops_from_trace(const zk_trace* t, uint64_t* ops_out, uin
     ARG_TRY(result && n_ops_out, "zk_state_ops_from_trace: null output");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_state_ops_from_trace_open(t, dev ? ops_out : nullptr, dev ? op_flags_out : nullptr, opts, n_ops_out, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && !dev) rc = zk_state_ops_from_trace_read(s, ops_out, op_flags_out, n_ops_out);
-    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_state_ops_from_trace_open(t, dev ? ops_out : nullptr, dev ? op_flags_out : nullptr, opts, n_ops_out, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, status_out, result));
+    return dev ? 0 : zk_state_ops_from_trace_read(s, ops_out, op_flags_out, n_ops_out);
 }
 // Records -> State circuit verdict: the first pass re-keys and sorts the records, writes the sorted packed op stream (48 bytes per op),
 // runs the MPT passes over it and evaluates; once a collect has seen a pass with a witness, later passes stream the ops and evaluate.
@@ -5147,35 +4667,35 @@ extern "C" int zk_state_verify_from_trace_open(const zk_trace* t, uint32_t opts,
     HIP_TRY(hipSetDevice(t_device));
     ARG_TRY(out && STRC_ARGS_OK(t), "zk_state_verify_from_trace_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
-    if (int rc = strc_counts(t, "zk_state_verify_from_trace")) return rc;
+    RC_TRY(strc_counts(t, "zk_state_verify_from_trace"));
     ARG_TRY(t->n_rw < (1ull << 31) - 1, "zk_state_verify_from_trace_open: bad arguments");
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_ASSIGN;
-    int rc = strc_setup(s, t, dev, false, nullptr, nullptr, "zk_state_verify_from_trace");
-    if (rc) { zk_close(s); return rc; }
+    RC_TRY(strc_setup(s, t, dev, false, nullptr, nullptr, "zk_state_verify_from_trace"));
     const u64 n = s->rekey.n_ops, n_rw = t->n_rw;
     s->n = n;
     s->assign_from_rw = true;
     s->fused_verify = true;
     AssignArgs& a = s->assign;
     StateArgs& v = s->state;
-    u32 cap = 16, mcap = 16;
     a.n = n;
     a.nb = (u32)((n + ASG_BLOCK - 1) / ASG_BLOCK);
-    if ((rc = dev_alloc(s, (void**)&s->strc.stream, (size_t)n * STRC_STREAM_WORDS * 8))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.mpt, (size_t)n * ASG_MPT_NCELLS * 32))) goto fail;
+    RC_TRY(dev_buf(s, s->strc.stream, (size_t)n * STRC_STREAM_WORDS * 8));
+    RC_TRY(dev_buf(s, a.mpt, (size_t)n * ASG_MPT_NCELLS * 32));
+    u32 cap = 16;
     while (cap < 2 * n + 2) cap <<= 1;
-    mcap = cap;  // (as many MPT rows as ops at most)
+    const u32 mcap = cap;  // (as many MPT rows as ops at most)
     a.mask = cap - 1;
     a.mpt_mask = mcap - 1;
-    if ((rc = dev_alloc(s, (void**)&a.slots, ((size_t)cap + mcap) * 4))) goto fail;  // key slots, then the MPT index: one fill
+    RC_TRY(dev_buf(s, a.slots, ((size_t)cap + mcap) * 4));  // key slots, then the MPT index: one fill
     a.mpt_slots = a.slots + cap;
-    if ((rc = dev_alloc(s, (void**)&a.first, (size_t)n * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.rank, (size_t)n * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.root_rank, (size_t)n * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.blk_cnt, (size_t)(a.nb + 1) * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.blk_next, (size_t)(a.nb + 1) * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&s->rekey_status, (size_t)n_rw * 4))) goto fail;
+    RC_TRY(dev_buf(s, a.first, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.rank, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.root_rank, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.blk_cnt, (size_t)(a.nb + 1) * 4));
+    RC_TRY(dev_buf(s, a.blk_next, (size_t)(a.nb + 1) * 4));
+    RC_TRY(dev_buf(s, s->rekey_status, (size_t)n_rw * 4));
     v.rows.cells = nullptr;
     v.rows.flags = nullptr;
     v.rows.n = n;
@@ -5187,25 +4707,17 @@ extern "C" int zk_state_verify_from_trace_open(const zk_trace* t, uint32_t opts,
     v.mpt.ncells = MPT_NCELLS;
     v.mpt.slots = a.mpt_slots;
     v.mpt.mask = a.mpt_mask;
-    if ((rc = session_common_init(s))) goto fail;
+    RC_TRY(session_common_init(s));
     if (n_ops_out) *n_ops_out = n;
-    *out = s;
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_state_verify_from_trace(const zk_trace* t, uint32_t opts, uint32_t* status_out, uint64_t* n_ops_out, zk_result* result) {
     ARG_TRY(result, "zk_state_verify_from_trace: result is null");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_state_verify_from_trace_open(t, opts, n_ops_out, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_state_verify_from_trace_open(t, opts, n_ops_out, &s));
+    return one_shot(s, dev, status_out, result);
 }
 // Records -> State witness: every pass re-keys and sorts the records, writes the sorted packed op stream, runs the MPT passes over it and
 // writes the rows from it (assign_rows_trace_kernel); nothing is kept between passes, as in the from-RW
@@ -5217,59 +4729,49 @@ extern "C" int zk_state_assign_from_trace_open(const zk_trace* t, uint64_t* rows
     ARG_TRY(out && STRC_ARGS_OK(t), "zk_state_assign_from_trace_open: bad arguments");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     ARG_TRY(dev || (!rows_dev && !row_flags_dev && !mpt_dev), "zk_state_assign_from_trace_open: output buffers need ZK_OPT_DEVICE_PTRS");
-    if (int rc = strc_counts(t, "zk_state_assign_from_trace")) return rc;
+    RC_TRY(strc_counts(t, "zk_state_assign_from_trace"));
     ARG_TRY(t->n_rw < (1ull << 31) - 1, "zk_state_assign_from_trace_open: bad arguments");
-    zk_session* s = new zk_session();
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
     s->kind = SESSION_ASSIGN;
-    int rc = strc_setup(s, t, dev, false, nullptr, nullptr, "zk_state_assign_from_trace");
-    if (rc) { zk_close(s); return rc; }
+    RC_TRY(strc_setup(s, t, dev, false, nullptr, nullptr, "zk_state_assign_from_trace"));
     const u64 n = s->rekey.n_ops, n_rw = t->n_rw;
     s->n = n;
     s->assign_from_rw = true;
     AssignArgs& a = s->assign;
-    u32 cap = 16, mcap = 16;
     a.n = n;
     a.nb = (u32)((n + ASG_BLOCK - 1) / ASG_BLOCK);
-    a.rows = rows_dev;
-    a.row_flags = row_flags_dev;
-    a.mpt = mpt_dev;
     a.compact = (opts & ZK_OPT_STATE_COMPACT) ? 1u : 0u;
-    if ((rc = dev_alloc(s, (void**)&s->strc.stream, (size_t)n * STRC_STREAM_WORDS * 8))) goto fail;
-    if (!a.rows && (rc = dev_alloc(s, (void**)&a.rows, (size_t)n * (a.compact ? 15 : ASG_ROW_NCELLS) * 32))) goto fail;
-    if (!a.row_flags && (rc = dev_alloc(s, (void**)&a.row_flags, (size_t)n * 4))) goto fail;
-    if (!a.mpt && (rc = dev_alloc(s, (void**)&a.mpt, (size_t)n * ASG_MPT_NCELLS * 32))) goto fail;
+    RC_TRY(dev_buf(s, s->strc.stream, (size_t)n * STRC_STREAM_WORDS * 8));
+    RC_TRY(out_buf(s, a.rows, rows_dev, (size_t)n * (a.compact ? 15 : ASG_ROW_NCELLS) * 32));
+    RC_TRY(out_buf(s, a.row_flags, row_flags_dev, (size_t)n * 4));
+    RC_TRY(out_buf(s, a.mpt, mpt_dev, (size_t)n * ASG_MPT_NCELLS * 32));
+    u32 cap = 16;
     while (cap < 2 * n + 2) cap <<= 1;
-    mcap = cap;  // (the rank pass over the stream enters every MPT row into the State circuit's MPT index: as many rows as ops at most)
+    const u32 mcap = cap;  // (the rank pass over the stream enters every MPT row into the State circuit's MPT index: as many rows as ops at most)
     a.mask = cap - 1;
     a.mpt_mask = mcap - 1;
-    if ((rc = dev_alloc(s, (void**)&a.slots, ((size_t)cap + mcap) * 4))) goto fail;
+    RC_TRY(dev_buf(s, a.slots, ((size_t)cap + mcap) * 4));
     a.mpt_slots = a.slots + cap;
-    if ((rc = dev_alloc(s, (void**)&a.first, (size_t)n * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.rank, (size_t)n * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.blk_cnt, (size_t)(a.nb + 1) * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&a.blk_next, (size_t)(a.nb + 1) * 4))) goto fail;
-    if ((rc = dev_alloc(s, (void**)&s->rekey_status, (size_t)n_rw * 4))) goto fail;
-    if ((rc = session_common_init(s))) goto fail;
+    RC_TRY(dev_buf(s, a.first, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.rank, (size_t)n * 4));
+    RC_TRY(dev_buf(s, a.blk_cnt, (size_t)(a.nb + 1) * 4));
+    RC_TRY(dev_buf(s, a.blk_next, (size_t)(a.nb + 1) * 4));
+    RC_TRY(dev_buf(s, s->rekey_status, (size_t)n_rw * 4));
+    RC_TRY(session_common_init(s));
     if (n_ops_out) *n_ops_out = n;
-    *out = s;
+    *out = guard.release();
     return 0;
-fail:
-    zk_close(s);
-    return rc;
 }
 extern "C" int zk_state_assign_from_trace(const zk_trace* t, uint64_t* rows_out, uint32_t* row_flags_out, uint64_t* mpt_out,
                                           uint64_t* n_mpt_out, uint64_t* n_ops_out, uint32_t opts, uint32_t* status_out, zk_result* result) {
     ARG_TRY(result && n_mpt_out && n_ops_out, "zk_state_assign_from_trace: null output");
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     zk_session* s = nullptr;
-    int rc = zk_state_assign_from_trace_open(t, dev ? rows_out : nullptr, dev ? row_flags_out : nullptr, dev ? mpt_out : nullptr, opts,
-                                             n_ops_out, &s);
-    if (rc) return rc;
-    rc = zk_launch(s, (dev && status_out) ? status_out : nullptr);
-    if (!rc) rc = zk_collect(s, result);
-    if (!rc) rc = dev ? zk_state_assign_read(s, nullptr, nullptr, nullptr, 0, n_mpt_out)
-                      : zk_state_assign_read(s, rows_out, row_flags_out, mpt_out, *n_ops_out, n_mpt_out);
-    if (!rc && status_out && !dev) rc = zk_read_status(s, status_out);
-    zk_close(s);
-    return rc;
+    RC_TRY(zk_state_assign_from_trace_open(t, dev ? rows_out : nullptr, dev ? row_flags_out : nullptr, dev ? mpt_out : nullptr, opts,
+                                           n_ops_out, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, status_out, result));
+    return dev ? zk_state_assign_read(s, nullptr, nullptr, nullptr, 0, n_mpt_out)
+               : zk_state_assign_read(s, rows_out, row_flags_out, mpt_out, *n_ops_out, n_mpt_out);
 }
