@@ -90,6 +90,7 @@ static Fr cell_of(const u64* p) { return fr_load(p); }
 struct zk_session {
     u64 n = 0, lo = 0, hi = 0;            // rows; evaluated range
     std::function<u32(u64)> row;          // status code of row i
+    std::function<void(u64, u64)> before_rows;  // work of a pass over [lo, hi) that its rows share (ECC: stage 1 over the range's pairs)
     std::vector<u32> status;
     u32 launches = 0;
     double ms = 0;
@@ -158,6 +159,8 @@ struct zk_session {
     std::vector<u64> ecl64[10];     // [3..8]: points, pair_out, rows, table candidates, table, aux
     std::vector<u32> ecl32[4];      // pair_off, aux_kind, tdup, pair_flags
     std::vector<bn::Fq12> ecl_f;    // the pairs' Miller values
+    std::vector<u32> ecc_pair_flags;     // ECC verification session: stage 1's per-pair records
+    std::vector<bn::Fq12> ecc_pair_f;
     u64 n_ecl_table = 0;
     std::vector<u64> pia64[20];     // PI assignment: inputs, work buffers and outputs of 64-bit words
     std::vector<u32> pia32[6];
@@ -179,6 +182,7 @@ static void run_pass(zk_session* s, u32* status_out) {
         s->pass(s);
         if (status_out) memcpy(status_out, s->status.data(), s->n * sizeof(u32));
     } else {
+        if (s->before_rows) s->before_rows(s->lo, s->hi);
 #pragma omp parallel for schedule(dynamic, 256)
         for (long long i = lo; i < hi; i++) st[i] = s->row((u64)i);
     }
@@ -1983,7 +1987,9 @@ extern "C" int zk_ecc_verify(const zk_ecc_ops* ops, const uint64_t* rows, uint32
     return one_shot(s, status_out, result);
 }
 
-// ECC sessions: a private copy of the ops (and rows); per-row evaluation by ecc_verify_row / ecc_assign_*_row over the range
+// ECC sessions: a private copy of the ops (and rows).  A verification pass over [lo, hi) takes the HIP session's form: the point rows
+// by ecc_verify_point_row, ecc_pair_stage1 once per pair of the pairing ops in range (pairs pair_off[k_lo] .. pair_off[k_hi]), then
+// ecc_pair_stage2 per pairing row over the records; the one-shot zk_ecc_verify keeps the one-call form ecc_verify_row
 static int ecc_session_ops(zk_session* s, const zk_ecc_ops* ops, EccArgs& a, const char* name) {
     const char* err = ecc_args_from_ops(ops, a);
     if (err) { g_err = std::string(name) + ": " + err; return -1; }
@@ -2009,7 +2015,18 @@ extern "C" int zk_ecc_open(const zk_ecc_ops* ops, const uint64_t* rows, uint32_t
     s->range_ok = s->range_may_be_empty = true;
     s->a64[3].assign(rows, rows + n * ECC_NCELLS * 4);
     a.rows = s->a64[3].data();
-    s->row = [a](u64 i) { return ecc_verify_row(a, i); };
+    const u64 np = a.n_add + a.n_mul;
+    s->ecc_pair_flags.assign(a.n_pairing ? a.pair_off[a.n_pairing] : 0, 0u);
+    s->ecc_pair_f.resize(s->ecc_pair_flags.size());
+    const EccPairArgs pr = {a, s->ecc_pair_flags.data(), s->ecc_pair_f.data()};
+    s->before_rows = [pr, np](u64 lo, u64 hi) {
+        const u64 k_lo = (lo > np ? lo : np) - np, k_hi = (hi > np ? hi : np) - np;
+        if (k_hi <= k_lo) return;
+        const long long t_lo = pr.a.pair_off[k_lo], t_hi = pr.a.pair_off[k_hi];
+#pragma omp parallel for schedule(dynamic, 1)
+        for (long long t = t_lo; t < t_hi; t++) ecc_pair_stage1(pr, (u32)t);
+    };
+    s->row = [pr, np](u64 i) { return i < np ? ecc_verify_point_row(pr.a, i) : ecc_pair_stage2(pr, i); };
     *out = s;
     return 0;
 }
