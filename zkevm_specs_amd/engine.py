@@ -1,5 +1,6 @@
 """Session objects over the C ABI: upload once, launch many passes, collect the tally."""
 import ctypes
+from collections import namedtuple
 
 import numpy as np
 
@@ -476,7 +477,7 @@ class AssignSession(Session):
         flags = np.empty(self.n, dtype=np.uint32)
         mpt = np.empty((m, 12, 4), dtype=np.uint64)
         got = ctypes.c_uint64()
-        check(self._lib.zk_state_assign_read(self._h, ptr(rows), ptr(flags), ptr(mpt, m), m, ctypes.byref(got)), "zk_state_assign_read")
+        check(self._lib.zk_state_assign_read(self._h, ptr(rows), ptr(flags), ptr(mpt, m), m, ctypes.byref(got)), "zk_state_assign_read", self._lib)
         return rows, flags, mpt
 
 
@@ -508,16 +509,35 @@ def open_state_assign(ops, op_flags, rows_dev=None, row_flags_dev=None, mpt_dev=
     return s
 
 
+def _check_flat_outs(outs, n):
+    """flat output buffers of a from-RW / from-trace State session, as (buffer or None, name, itemsize, entries per RW row): each holds
+    room for the n RW rows + StartOp"""
+    for buf, name, size, per_row in outs:
+        _expect(buf, name, size, (None,))
+        if buf is not None and int(buf.shape[0]) < per_row * (n + 1):
+            raise ValueError(f"{name} holds fewer than {per_row * (n + 1)} entries")
+
+
+def _open_n_ops(lib, fn, keep, *args, cls=Session, n=None, compact=None):
+    """one `fn(*args, &n_ops, &handle)` call of a from-RW / from-trace State entry -> a `cls` session over the n_ops = 1 + kept rows State
+    rows; with `n` (the op-list sessions, whose status is per RW row) over n rows, n_ops set on it; `compact`: set on an AssignSession"""
+    h, n_ops = ctypes.c_void_p(), ctypes.c_uint64()
+    check(fn(*args, ctypes.byref(n_ops), ctypes.byref(h)), fn.__name__, lib)
+    s = cls(h, int(n_ops.value) if n is None else n, keep, lib=lib)
+    if n is not None:
+        s.n_ops = int(n_ops.value)
+    if compact is not None:
+        s.compact = bool(compact)
+    return s
+
+
 def _rw_args(rw, rw_flags, outs=()):
     """zk_state_ops_from_rw* / zk_state_assign_from_rw_open / zk_state_verify_from_rw* -> ((rw, rw_flags, n), opts, kept arrays);
     outs: a session's flat output buffers as (buffer, name, itemsize, entries per RW row + 1), prepared with the inputs"""
     _expect(rw, "rw table", 8, (None, 14, 4))
     n = int(rw.shape[0])
     _expect(rw_flags, "rw_flags", 4, (n,))
-    for buf, name, size, per_row in outs:
-        _expect(buf, name, size, (None,))
-        if buf is not None and int(buf.shape[0]) < per_row * (n + 1):
-            raise ValueError(f"{name} holds fewer than {per_row * (n + 1)} entries")
+    _check_flat_outs(outs, n)
     keep, opts = _prep([rw, rw_flags] + [o[0] for o in outs], outputs=range(2, 2 + len(outs)))
     return (ptr(keep[0]), ptr(keep[1]), n), opts, keep
 
@@ -533,12 +553,8 @@ def open_state_assign_from_rw(rw, rw_flags, rows_dev=None, row_flags_dev=None, m
     args, opts, keep = _rw_args(rw, rw_flags, outs)
     if compact:
         opts |= _lib.OPT_STATE_COMPACT
-    h, n_ops = ctypes.c_void_p(), ctypes.c_uint64()
-    check(lib.zk_state_assign_from_rw_open(*args, ptr(keep[2]), ptr(keep[3]), ptr(keep[4]), opts, ctypes.byref(n_ops), ctypes.byref(h)),
-          "zk_state_assign_from_rw_open")
-    s = AssignSession(h, int(n_ops.value), keep, lib=lib)
-    s.compact = bool(compact)
-    return s
+    return _open_n_ops(lib, lib.zk_state_assign_from_rw_open, keep, *args, ptr(keep[2]), ptr(keep[3]), ptr(keep[4]), opts, cls=AssignSession,
+                       compact=compact)
 
 
 def open_state_verify_from_rw(rw, rw_flags, device=None):
@@ -547,9 +563,7 @@ def open_state_verify_from_rw(rw, rw_flags, device=None):
     circuit's Result; an RW row the re-keying rejects or an op the assignment raises on makes collect() raise EngineError."""
     lib = _lib.init(device)
     args, opts, keep = _rw_args(rw, rw_flags)
-    h, n_ops = ctypes.c_void_p(), ctypes.c_uint64()
-    check(lib.zk_state_verify_from_rw_open(*args, opts, ctypes.byref(n_ops), ctypes.byref(h)), "zk_state_verify_from_rw_open", lib)
-    return Session(h, int(n_ops.value), keep, lib=lib)
+    return _open_n_ops(lib, lib.zk_state_verify_from_rw_open, keep, *args, opts)
 
 
 class RekeySession(Session):
@@ -572,11 +586,7 @@ def open_state_ops_from_rw(rw, rw_flags, ops_dev=None, op_flags_dev=None, device
     open_state_assign takes."""
     lib = _lib.init(device)
     args, opts, keep = _rw_args(rw, rw_flags, ((ops_dev, "ops_dev", 8, 48), (op_flags_dev, "op_flags_dev", 4, 1)))
-    h, n_ops = ctypes.c_void_p(), ctypes.c_uint64()
-    check(lib.zk_state_ops_from_rw_open(*args, ptr(keep[2]), ptr(keep[3]), opts, ctypes.byref(n_ops), ctypes.byref(h)), "zk_state_ops_from_rw_open")
-    s = RekeySession(h, args[2], keep, lib=lib)
-    s.n_ops = int(n_ops.value)
-    return s
+    return _open_n_ops(lib, lib.zk_state_ops_from_rw_open, keep, *args, ptr(keep[2]), ptr(keep[3]), opts, cls=RekeySession, n=args[2])
 
 
 class BytecodeAssignSession(Session):
@@ -652,7 +662,7 @@ def copy_assign_sizes(events, flags, data, offsets, device=None):
     (events, flags, data, offsets), opts = _prep([events, flags, data, offsets])
     t = _copy_events_struct(events, flags, data, offsets, None)
     a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-    check(lib.zk_copy_assign_sizes(ctypes.byref(t), opts, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "zk_copy_assign_sizes")
+    check(lib.zk_copy_assign_sizes(ctypes.byref(t), opts, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "zk_copy_assign_sizes", lib)
     return int(a.value), int(b.value), int(c.value)
 
 
@@ -684,7 +694,7 @@ class CopyAssignSession(Session):
         table = np.empty((self.n_table, 14, 4), dtype=np.uint64)
         rw, rwf = np.empty((self.n_rw, 14, 4), dtype=np.uint64), np.empty(self.n_rw, dtype=np.uint32)
         check(self._lib.zk_copy_assign_read(self._h, ptr(rows), ptr(rf), ptr(table, self.n_table), ptr(rw, self.n_rw), ptr(rwf, self.n_rw)),
-              "zk_copy_assign_read")
+              "zk_copy_assign_read", self._lib)
         return rows, rf, table, rw, rwf
 
 
@@ -849,7 +859,7 @@ def fr_op(op, a, b):
     a = np.ascontiguousarray(a, dtype=np.uint64)
     b = np.ascontiguousarray(b, dtype=np.uint64)
     out = np.empty_like(a)
-    check(lib.zk_fr_op(int(op), ptr(a), ptr(b), ptr(out), a.shape[0], 0), "zk_fr_op")
+    check(lib.zk_fr_op(int(op), ptr(a), ptr(b), ptr(out), a.shape[0], 0), "zk_fr_op", lib)
     return out
 
 
@@ -956,6 +966,95 @@ def open_withdrawal(w, randomness, device=None):
     return _open(lib, lib.zk_withdrawal_open, _withdrawal_eval_rows(w), (keep, ww), ctypes.byref(ww), opts)
 
 
+# ---- The wire-struct assignment families ----------------------------------------------------------------------------------------------
+# Seven entry families share one ABI shape (include/zkevm_hip.h): `<stem>_open(&inputs, &wire or NULL, opts, &handle)`,
+# `<stem>_read(handle, &wire or NULL, &count...)`, the one-shot `<stem>(&inputs, &wire, opts, [status,] &count..., &result)` and, for
+# some, `<stem>_sizes(&inputs, opts, &size...)`.  A family is one record, an input check and a struct filler; the rest is written once,
+# here.  The record's fields (an eighth family writes those three things; oneshot._wire_oneshot is the one-shot's body):
+#   stem, inputs, outputs: the entry stem and the ordered array members of the input struct's dict and of the wire struct
+#   wire: the wire struct's ctypes class
+#   check(x, **kw) -> (rows of a session, output name -> (shape or None, dtype)): the wire-format check of the inputs
+#   fill(x, a, cells) -> the input struct over the prepared input arrays `a` and the randomness cells
+#   cut: the outputs that the trailing count out-parameters cut, in ABI order
+#   status: the one-shot returns a status per item
+#   null_empty: an EMPTY output travels as a null pointer, else as the pointer to its empty array (seen with host arrays: read() and
+#     the one-shot; an empty device tensor's own pointer is null already)
+#   n_sizes: the out-parameters of `<stem>_sizes` (0: the family has no such entry)
+WireFamily = namedtuple("WireFamily", "stem inputs outputs wire check fill cut status null_empty n_sizes", defaults=((), False, False, 0))
+Prepared = namedtuple("Prepared", "t w opts keep shapes n")  # one marshalled call: structs, options, kept arrays, output shapes, session rows
+
+
+def _wire_struct(fam, arrs):
+    """the family's wire struct over output arrays in ABI order (None: a null pointer)"""
+    return fam.wire(*[ptr(x, int(np.prod(x.shape)) if fam.null_empty and x is not None else 1) for x in arrs])
+
+
+def _wire_args(fam, x, randomness=(), outs=None, **kw):
+    """`<stem>_open` / `<stem>` over the input dict `x` -> Prepared.  `outs` (device tensors only, each optional): buffers of fam.outputs
+    the session writes in place; w is None for host inputs (the library then keeps the outputs in its own buffers)."""
+    n, shapes = fam.check(x, **kw)
+    outs = dict(outs or {})
+    for k, v in outs.items():
+        if v is not None:
+            _expect(v, k, np.dtype(shapes[k][1]).itemsize, shapes[k][0])
+    out_list, n_in = [outs.get(k) for k in fam.outputs], len(fam.inputs)
+    a, opts = _prep([x.get(k) for k in fam.inputs] + out_list, outputs=range(n_in, n_in + len(out_list)))
+    if any(v is not None for v in out_list) and not opts:
+        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
+    cells = [_randomness_cells(r, a[0]) for r in randomness]
+    return Prepared(fam.fill(x, a, cells), _wire_struct(fam, a[n_in:]) if opts else None, opts, a + cells, shapes, n)
+
+
+def _wire_host_outputs(fam, shapes, names=None):
+    """zeroed host arrays for the outputs in `names` (None: all; an output without a shape stays None) -> (dict, wire struct over them)"""
+    out = {k: None if shp is None else np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items() if names is None or k in names}
+    return out, _wire_struct(fam, [out.get(k) for k in fam.outputs])
+
+
+def _wire_sizes(fam, lib, p):
+    """`<stem>_sizes` over a Prepared call -> the library's own counts"""
+    c = [ctypes.c_uint64() for _ in range(fam.n_sizes)]
+    check(getattr(lib, fam.stem + "_sizes")(ctypes.byref(p.t), p.opts, *(ctypes.byref(x) for x in c)), fam.stem + "_sizes", lib)
+    return tuple(int(x.value) for x in c)
+
+
+class WireSession(Session):
+    """A session of one wire-struct family: launch() / collect() / read_status() like the circuits; read(names=None) -> dict of the
+    last pass's outputs as host arrays (all, or those named), the family's `cut` outputs cut to the library's counts."""
+
+    family = shapes = None  # the WireFamily and output name -> (shape, dtype): set by _wire_open
+
+    def _read(self, w=None):
+        """one `<stem>_read` call (w None: the counts alone) -> the counts, in the order of family.cut"""
+        c = [ctypes.c_uint64() for _ in self.family.cut]
+        check(getattr(self._lib, self.family.stem + "_read")(self._h, ctypes.byref(w) if w is not None else None, *(ctypes.byref(x) for x in c)),
+              self.family.stem + "_read", self._lib)
+        return [int(x.value) for x in c]
+
+    def _count(self, name):
+        return self._read()[self.family.cut.index(name)]
+
+    def read(self, names=None):
+        out, w = _wire_host_outputs(self.family, self.shapes, names)
+        for k, c in zip(self.family.cut, self._read(w)):
+            if k in out:
+                out[k] = out[k][:c]
+        return out
+
+
+def _wire_open(fam, device, x, randomness=(), outs=None, cls=WireSession, agree=None):
+    """`<stem>_open` over the input dict `x` -> a `cls` session that keeps its arrays and structs alive and knows its family and output
+    shapes.  agree(sizes, shapes): raises where the library's own `<stem>_sizes` counts are not what the buffers are shaped for."""
+    lib = _lib.init(device)
+    p = _wire_args(fam, x, randomness, outs)
+    if agree is not None:
+        agree(_wire_sizes(fam, lib, p), p.shapes)
+    s = _open(lib, getattr(lib, fam.stem + "_open"), p.n, (p.keep, p.t, p.w), ctypes.byref(p.t), ctypes.byref(p.w) if p.w is not None else None,
+              p.opts, cls=cls)
+    s.family, s.shapes = fam, p.shapes
+    return s
+
+
 # ---- Tx circuit witness assignment (zk_tx_assign*) --------------------------------------------------------------------------------
 TX_ASSIGN_INPUTS = ("fields", "to_is_none", "calldata", "offsets")
 TX_ASSIGN_OUTPUTS = ("tx_rows", "tx_flags", "bytes", "cells", "meta", "keccak")
@@ -968,59 +1067,216 @@ def tx_assign_shapes(n, max_txs, max_calldata_bytes):
             "cells": ((8, max_txs, 4), np.uint64), "meta": ((max_txs, 4), np.uint32), "keccak": ((n + 1, 5, 4), np.uint64)}
 
 
-def _tx_assign_args(tx, randomness, outs=None):
-    """zk_tx_assign_open / zk_tx_assign over `tx` = dict(fields uint64[n, 8, 4], to_is_none uint32[n], calldata uint8[b], offsets
-    uint64[n + 1], chain_id, max_txs, max_calldata_bytes) -> (ZkTxInputs, ZkTxWire of the device outputs or None, opts, kept arrays).
-    `outs` (device tensors only, each optional): buffers of TX_ASSIGN_OUTPUTS the session writes in place."""
+def _tx_check(tx):
     n = int(tx["fields"].shape[0])
     _expect(tx["fields"], "fields", 8, (None, 8, 4))
     _expect(tx["to_is_none"], "to_is_none", 4, (n,))
     _expect(tx["offsets"], "offsets", 8, (n + 1,))
     _expect(tx["calldata"], "calldata", 1, (None,))
-    mt, mc = int(tx["max_txs"]), int(tx["max_calldata_bytes"])
-    shapes = tx_assign_shapes(n, mt, mc)
-    outs = dict(outs or {})
-    for k, v in outs.items():
-        if v is not None:
-            _expect(v, k, np.dtype(shapes[k][1]).itemsize, shapes[k][0])
-    out_list = [outs.get(k) for k in TX_ASSIGN_OUTPUTS]
-    a, opts = _prep([tx[k] for k in TX_ASSIGN_INPUTS] + out_list, outputs=range(4, 4 + len(out_list)))
-    if any(v is not None for v in out_list) and not opts:
-        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
-    rc = _randomness_cells(randomness, a[0])
-    keep = a + [rc]
-    t = _lib.ZkTxInputs(ptr(a[0], n), ptr(a[1], n), n, ptr(a[2], int(a[2].shape[0])), ptr(a[3]), int(tx["chain_id"]), mt, mc, ptr(rc))
-    w = _lib.ZkTxWire(*[ptr(x) for x in a[4:]]) if opts else None
-    return t, w, opts, keep
+    return n, tx_assign_shapes(n, int(tx["max_txs"]), int(tx["max_calldata_bytes"]))
 
 
-class TxAssignSession(Session):
+def _tx_fill(tx, a, cells):
+    n = _rows(a[0])
+    return _lib.ZkTxInputs(ptr(a[0], n), ptr(a[1], n), n, ptr(a[2], int(a[2].shape[0])), ptr(a[3]), int(tx["chain_id"]), int(tx["max_txs"]),
+                           int(tx["max_calldata_bytes"]), ptr(cells[0]))
+
+
+TX_ASSIGN = WireFamily("zk_tx_assign", TX_ASSIGN_INPUTS, TX_ASSIGN_OUTPUTS, _lib.ZkTxWire, _tx_check, _tx_fill, cut=("keccak",), status=True)
+
+
+def _tx_assign_args(tx, randomness, outs=None):
+    """zk_tx_assign_open / zk_tx_assign over `tx` = dict(fields uint64[n, 8, 4], to_is_none uint32[n], calldata uint8[b], offsets
+    uint64[n + 1], chain_id, max_txs, max_calldata_bytes) -> (ZkTxInputs, ZkTxWire of the device outputs or None, opts, kept arrays).
+    `outs` (device tensors only, each optional): buffers of TX_ASSIGN_OUTPUTS the session writes in place."""
+    return _wire_args(TX_ASSIGN, tx, (randomness,), outs)[:4]
+
+
+class TxAssignSession(WireSession):
     """zk_tx_assign_open: status per tx; read() -> the wire dict of the last pass (host arrays)"""
 
-    def read(self):
-        t = self._keep[-1]
-        shapes = tx_assign_shapes(self.n, t["max_txs"], t["max_calldata_bytes"])
-        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items()}
-        nk = ctypes.c_uint64()
-        w = _lib.ZkTxWire(*[ptr(out[k]) for k in TX_ASSIGN_OUTPUTS])
-        check(self._lib.zk_tx_assign_read(self._h, ctypes.byref(w), ctypes.byref(nk)), "zk_tx_assign_read", self._lib)
-        out["keccak"] = out["keccak"][: nk.value]
-        return out
-
     def n_keccak(self):
-        nk = ctypes.c_uint64()
-        check(self._lib.zk_tx_assign_read(self._h, None, ctypes.byref(nk)), "zk_tx_assign_read", self._lib)
-        return int(nk.value)
+        return self._count("keccak")
 
 
 def open_tx_assign(tx, randomness, outs=None, device=None):
     """Tx circuit witness assignment session over the raw txs of `tx` (see _tx_assign_args).  With device tensors the outputs stay
     in HBM: in `outs`' buffers where given (e.g. for zk_ecdsa_open / zk_sign_open on them), else in the session's own."""
+    return _wire_open(TX_ASSIGN, device, tx, (randomness,), outs, cls=TxAssignSession)
+
+
+# ---- Sig circuit witness assignment (zk_sig_assign*) ------------------------------------------------------------------------------
+SIG_ASSIGN_INPUTS = ("fields", "addr", "expect_valid")
+SIG_ASSIGN_OUTPUTS = ("bytes", "cells", "meta", "keccak", "sig_table", "aux")
+
+
+def sig_assign_shapes(n):
+    """name -> (shape, dtype) of the outputs of zk_sig_assign* (keccak, sig_table: their capacities, n + 1 and n rows)"""
+    return {"bytes": ((n, 9, 32), np.uint8), "cells": ((8, n, 4), np.uint64), "meta": ((n, 4), np.uint32),
+            "keccak": ((n + 1, 5, 4), np.uint64), "sig_table": ((n, 9, 4), np.uint64), "aux": ((n, 12, 4), np.uint64)}
+
+
+def _sig_check(sig):
+    n = int(sig["fields"].shape[0])
+    _expect(sig["fields"], "fields", 8, (None, 4, 4))
+    _expect(sig.get("addr"), "addr", 8, (n, 4))
+    _expect(sig.get("expect_valid"), "expect_valid", 4, (n,))
+    return n, sig_assign_shapes(n)
+
+
+def _sig_fill(sig, a, cells):
+    n = _rows(a[0])
+    return _lib.ZkSigInputs(ptr(a[0], n), ptr(a[1], n), ptr(a[2], n), n, int(sig.get("v_offset", 0)), 0, ptr(cells[0]))
+
+
+SIG_ASSIGN = WireFamily("zk_sig_assign", SIG_ASSIGN_INPUTS, SIG_ASSIGN_OUTPUTS, _lib.ZkSigWire, _sig_check, _sig_fill, cut=("keccak", "sig_table"),
+                        status=True)
+
+
+def _sig_assign_args(sig, randomness, outs=None):
+    """zk_sig_assign_open / zk_sig_assign over `sig` = dict(fields uint64[n, 4, 4]: msg_hash, sig_v, sig_r, sig_s; addr uint64[n, 4] or
+    None: the claimed addresses; expect_valid uint32[n] or None; v_offset: 0 (v is the parity) or 27 (the precompile's input word))
+    -> (ZkSigInputs, ZkSigWire of the device outputs or None, opts, kept arrays).
+    `outs` (device tensors only, each optional): buffers of SIG_ASSIGN_OUTPUTS the session writes in place."""
+    return _wire_args(SIG_ASSIGN, sig, (randomness,), outs)[:4]
+
+
+class SigAssignSession(WireSession):
+    """zk_sig_assign_open: status per signature; read() -> the wire dict of the last pass (host arrays)"""
+
+    def n_keccak(self):
+        return self._count("keccak")
+
+    def n_sig_rows(self):
+        return self._count("sig_table")
+
+
+def open_sig_assign(sig, randomness, outs=None, device=None):
+    """Sig circuit witness assignment session over the signed data of `sig` (see _sig_assign_args).  With device tensors the outputs
+    stay in HBM: in `outs`' buffers where given (e.g. for zk_ecdsa_open / zk_sign_open on them), else in the session's own."""
+    return _wire_open(SIG_ASSIGN, device, sig, (randomness,), outs, cls=SigAssignSession)
+
+
+# ---- ECC precompile calls (zk_ecc_from_calls*) -------------------------------------------------------------------------------------
+ECC_CALLS_INPUTS = ("add_in", "mul_in", "pair_pts", "pair_off")
+ECC_CALLS_OUTPUTS = ("points", "pair_out", "rows", "ecc_table", "aux", "aux_kind")
+
+
+def ecc_calls_shapes(n_add, n_mul, n_pairing):
+    """name -> (shape, dtype) of the outputs of zk_ecc_from_calls* (ecc_table: its capacity, one row per call)"""
+    n = n_add + n_mul + n_pairing
+    return {"points": ((n_add + n_mul, 6, 4), np.uint64), "pair_out": ((n_pairing, 4), np.uint64), "rows": ((n, 13, 4), np.uint64),
+            "ecc_table": ((n, 13, 4), np.uint64), "aux": ((n, 12, 4), np.uint64), "aux_kind": ((n,), np.uint32)}
+
+
+def _ecc_calls_check(calls):
+    add_in, mul_in, pair_pts, pair_off = (calls[k] for k in ECC_CALLS_INPUTS)
+    n_add, n_mul, n_pairing = int(add_in.shape[0]), int(mul_in.shape[0]), int(pair_off.shape[0]) - 1
+    _expect(add_in, "add_in", 8, (None, 4, 4))
+    _expect(mul_in, "mul_in", 8, (None, 3, 4))
+    _expect(pair_pts, "pair_pts", 8, (None, 6, 4))
+    _expect(pair_off, "pair_off", 4, (n_pairing + 1,))
+    return n_add + n_mul + n_pairing, ecc_calls_shapes(n_add, n_mul, n_pairing)
+
+
+def _ecc_calls_fill(calls, a, cells):
+    n_add, n_mul, n_pairing = _rows(a[0]), _rows(a[1]), _rows(a[3]) - 1
+    return _lib.ZkEccCalls(ptr(a[0], n_add), n_add, ptr(a[1], n_mul), n_mul, ptr(a[2], _rows(a[2])), ptr(a[3], n_pairing), n_pairing, ptr(cells[0]))
+
+
+ECC_CALLS = WireFamily("zk_ecc_from_calls", ECC_CALLS_INPUTS, ECC_CALLS_OUTPUTS, _lib.ZkEccCallWire, _ecc_calls_check, _ecc_calls_fill,
+                       cut=("ecc_table",), status=True)
+
+
+def _ecc_calls_args(calls, randomness, outs=None):
+    """zk_ecc_from_calls_open / zk_ecc_from_calls over `calls` = dict(add_in uint64[n_add, 4, 4]: p.x, p.y, q.x, q.y; mul_in
+    uint64[n_mul, 3, 4]: p.x, p.y, s; pair_pts uint64[m, 6, 4] in EIP-197 order + pair_off uint32[n_pairing + 1]) — the arrays of
+    ecc_circuit.ecc_calls_wire — -> (ZkEccCalls, ZkEccCallWire of the device outputs or None, opts, kept arrays, output shapes).
+    `outs` (device tensors only, each optional): buffers of ECC_CALLS_OUTPUTS the session writes in place."""
+    return _wire_args(ECC_CALLS, calls, (randomness,), outs)[:5]
+
+
+class EccCallsSession(WireSession):
+    """zk_ecc_from_calls_open: launch() / collect() like the circuits (every status 0); read() -> the wire dict of the last pass
+    (host arrays, ecc_table cut to its rows); n_table_rows() the table's row count alone"""
+
+    def n_table_rows(self):
+        return self._count("ecc_table")
+
+
+def open_ecc_from_calls(calls, randomness, outs=None, device=None):
+    """ECC precompile calls session (see _ecc_calls_args): from the calls' input words to the ECC circuit's ops and rows and the EVM
+    circuit's ecc table and aux rows.  With device tensors the outputs stay in HBM: in `outs`' buffers where given (ready for
+    open_ecc / open_evm), else in the session's own."""
+    return _wire_open(ECC_CALLS, device, calls, (randomness,), outs, cls=EccCallsSession)
+
+
+# ---- PI circuit witness assignment (zk_pi_assign*) ----------------------------------------------------------------------------------
+PI_ASSIGN_INPUTS = ("block", "state_root_prev", "block_hashes", "tx_fields", "to_is_none", "calldata", "offsets", "withdrawals")
+PI_ASSIGN_OUTPUTS = ("rows", "gas", "keccak", "cc_cells", "cc_bytes", "cc_lens", "block_table", "block_flags", "tx_table", "tx_flags",
+                     "wd_table", "public_inputs", "raw_bytes", "raw_lens")
+
+
+def pi_assign_shapes(max_txs, max_calldata_bytes, max_withdrawals, calldata_bytes):
+    """name -> (shape, dtype) of the outputs of zk_pi_assign* (include/zkevm_hip.h)"""
+    mt, mc, mw = int(max_txs), int(max_calldata_bytes), int(max_withdrawals)
+    n = 8454 + 336 * mt + mc + 56 * mw
+    n_cc = 538 + 4 * (10 * mt + 1) + 2 * mc + 5 * mw
+    t = 10 * mt + 1 + mc
+    return {"rows": ((24, n, 4), np.uint64), "gas": ((1 + int(calldata_bytes), 3, 4), np.uint64), "keccak": ((2, 5, 4), np.uint64),
+            "cc_cells": ((n_cc, 4), np.uint64), "cc_bytes": ((n_cc, 32), np.uint8), "cc_lens": ((n_cc,), np.uint32),
+            "block_table": ((268, 2, 4), np.uint64), "block_flags": ((268,), np.uint32), "tx_table": ((t, 5, 4), np.uint64),
+            "tx_flags": ((t,), np.uint32), "wd_table": ((mw, 5, 4), np.uint64), "public_inputs": ((4, 2, 4), np.uint64),
+            "raw_bytes": ((n,), np.uint8), "raw_lens": ((533 + 33 * mt + mc + 5 * mw,), np.uint32)}
+
+
+def _pi_check(pd):
+    n = _rows(pd["tx_fields"])
+    _expect(pd["block"], "block", 8, (9, 4))
+    _expect(pd["state_root_prev"], "state_root_prev", 8, (4,))
+    _expect(pd["block_hashes"], "block_hashes", 8, (256, 4))
+    _expect(pd["tx_fields"], "tx_fields", 8, (None, 7, 4))
+    _expect(pd["to_is_none"], "to_is_none", 4, (n,))
+    _expect(pd["offsets"], "offsets", 8, (n + 1,))
+    _expect(pd["calldata"], "calldata", 1, (None,))
+    _expect(pd["withdrawals"], "withdrawals", 8, (None, 4, 4))
+    shapes = pi_assign_shapes(pd["max_txs"], pd["max_calldata_bytes"], pd["max_withdrawals"], pd["calldata"].shape[0])
+    return shapes["rows"][0][1], shapes
+
+
+def _pi_fill(pd, a, cells):
+    n, m = _rows(a[3]), _rows(a[7])
+    return _lib.ZkPiInputs(int(pd["chain_id"]), ptr(a[0]), ptr(a[1]), ptr(a[2]), ptr(a[3], n), ptr(a[4], n), n, ptr(a[5], int(a[5].shape[0])),
+                           ptr(a[6]), ptr(a[7], m), m, int(pd["max_txs"]), int(pd["max_calldata_bytes"]), int(pd["max_withdrawals"]),
+                           ptr(cells[0]), ptr(cells[1]))
+
+
+PI_ASSIGN = WireFamily("zk_pi_assign", PI_ASSIGN_INPUTS, PI_ASSIGN_OUTPUTS, _lib.ZkPiWire, _pi_check, _pi_fill, n_sizes=3)
+
+
+def _pi_assign_args(pd, keccak_rand=255, byte_pow_base=255, outs=None):
+    """zk_pi_assign_open / zk_pi_assign over `pd` = dict(chain_id, block uint64[9, 4], state_root_prev uint64[4], block_hashes
+    uint64[256, 4], tx_fields uint64[n, 7, 4], to_is_none uint32[n], calldata uint8[b], offsets uint64[n + 1], withdrawals
+    uint64[m, 4, 4], max_txs, max_calldata_bytes, max_withdrawals) -> (ZkPiInputs, ZkPiWire of the device outputs or None, opts, kept
+    arrays, output shapes).  `outs` (device tensors only, each optional): buffers of PI_ASSIGN_OUTPUTS the session writes in place; they
+    are sized from pd["calldata"], so its extent must be the offsets' last entry."""
+    return _wire_args(PI_ASSIGN, pd, (int(keccak_rand), int(byte_pow_base)), outs)[:5]
+
+
+def pi_assign_sizes(pd, device=None):
+    """(circuit_len, gas-table rows, copy constraints) of the public data `pd`; raises EngineError (rc = _lib.ERR_PI_*) for inputs
+    outside the circuit's domain"""
     lib = _lib.init(device)
-    t, w, opts, keep = _tx_assign_args(tx, randomness, outs)
-    sizes = {"max_txs": int(tx["max_txs"]), "max_calldata_bytes": int(tx["max_calldata_bytes"])}
-    return _open(lib, lib.zk_tx_assign_open, t.n_txs, (keep, t, w, sizes), ctypes.byref(t), ctypes.byref(w) if w is not None else None,
-                 opts, cls=TxAssignSession)
+    return _wire_sizes(PI_ASSIGN, lib, _wire_args(PI_ASSIGN, pd, (255, 255)))
+
+
+PiAssignSession = WireSession  # zk_pi_assign_open: one status per row
+
+def open_pi_assign(pd, keccak_rand=255, byte_pow_base=255, outs=None, device=None):
+    """PI circuit witness assignment session over the public data `pd` (see _pi_assign_args).  With device tensors the outputs stay in
+    HBM: in `outs`' buffers where given (rows / keccak / gas for open_pi, cc_cells / cc_bytes / cc_lens for zk_pi_copy_open), else in
+    the session's own."""
+    return _wire_open(PI_ASSIGN, device, pd, (int(keccak_rand), int(byte_pow_base)), outs)
 
 
 # ---- Bytecode table + circuit rows + keccak rows from raw contract code (zk_bytecode_from_code*) ----------------------------------
@@ -1032,46 +1288,42 @@ def bytecode_from_code_shapes(n_bytes, n_codes, k):
     return {"table": (n_bytes + n_codes, 6, 4), "rows": (12, 1 << int(k), 4) if int(k) else None, "keccak": (n_codes, 5, 4)}
 
 
+def _code_check(x):
+    _expect(x["code"], "code", 1, (None,))
+    _expect(x["offsets"], "offsets", 8, (None,))
+    n_bytes, n_codes = int(x["code"].shape[0]), int(x["offsets"].shape[0]) - 1
+    if n_codes < 0:
+        raise ValueError("offsets: expected n_codes + 1 entries")
+    if not int(x["k"]) and x.get("rows_dev") is not None:
+        raise ValueError("rows_dev needs k > 0")
+    return n_bytes + n_codes, {k: (shp, np.uint64) for k, shp in bytecode_from_code_shapes(n_bytes, n_codes, x["k"]).items()}
+
+
+def _code_fill(x, a, cells):
+    if _is_device(a[0]) and not _is_device(cells[0]):  # (this family alone refuses host randomness beside device inputs)
+        raise ValueError("mix of host and device buffers")
+    n_bytes, n_codes = _rows(a[0]), _rows(a[1]) - 1
+    return _lib.ZkCodeSet(ptr(a[0], n_bytes), n_bytes, ptr(a[1]), n_codes, int(x["k"]), 0, ptr(cells[0]))
+
+
+CODE = WireFamily("zk_bytecode_from_code", ("code", "offsets"), CODE_OUTPUTS, _lib.ZkCodeWire, _code_check, _code_fill, null_empty=True)
+
+
 def _bytecode_from_code_args(code, offsets, k, randomness, outs=None):
     """zk_bytecode_from_code_open / zk_bytecode_from_code over code uint8[n_bytes] (the contracts back to back) and offsets
     uint64[n_codes + 1] -> (ZkCodeSet, ZkCodeWire of the device outputs or None, opts, kept arrays).  `outs` (device tensors only,
     each optional): table / rows / keccak buffers the session writes in place."""
-    _expect(code, "code", 1, (None,))
-    _expect(offsets, "offsets", 8, (None,))
-    n_bytes, n_codes = int(code.shape[0]), int(offsets.shape[0]) - 1
-    if n_codes < 0:
-        raise ValueError("offsets: expected n_codes + 1 entries")
-    shapes = bytecode_from_code_shapes(n_bytes, n_codes, k)
-    outs = dict(outs or {})
-    for name, v in outs.items():
-        if v is not None:
-            if shapes[name] is None:
-                raise ValueError("rows_dev needs k > 0")
-            _expect(v, name, 8, shapes[name])
-    out_list = [outs.get(name) for name in CODE_OUTPUTS]
-    a, opts = _prep([code, offsets] + out_list, outputs=range(2, 5))
-    if any(v is not None for v in out_list) and not opts:
-        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
-    rc = _randomness_cells(randomness, a[0])
-    if opts and not _is_device(rc):
-        raise ValueError("mix of host and device buffers")
-    keep = a + [rc]
-    t = _lib.ZkCodeSet(ptr(a[0], n_bytes), n_bytes, ptr(a[1]), n_codes, int(k), 0, ptr(rc))
-    w = _lib.ZkCodeWire(*[ptr(x) for x in a[2:]]) if opts else None
-    return t, w, opts, keep
+    return _wire_args(CODE, {"code": code, "offsets": offsets, "k": k, "rows_dev": (outs or {}).get("rows")}, (randomness,), outs)[:4]
 
 
-class BytecodeFromCodeSession(Session):
+class BytecodeFromCodeSession(WireSession):
     """zk_bytecode_from_code_open: launch() / collect() like the other assignments (status per table row, always 0);
     read() -> (table uint64[n_bytes + n_codes, 6, 4], rows uint64[12, 2^k, 4] or None when k == 0, keccak uint64[n_codes, 5, 4])
     of the last pass, as host arrays"""
 
-    def read(self):
-        shapes = bytecode_from_code_shapes(*self._keep[-1])
-        out = [None if shapes[name] is None else np.zeros(shapes[name], dtype=np.uint64) for name in CODE_OUTPUTS]
-        w = _lib.ZkCodeWire(*[ptr(x, x.size if x is not None else 0) for x in out])
-        check(self._lib.zk_bytecode_from_code_read(self._h, ctypes.byref(w)), "zk_bytecode_from_code_read", self._lib)
-        return tuple(out)
+    def read(self, names=None):
+        out = super().read(names)
+        return tuple(out.get(name) for name in CODE_OUTPUTS)
 
 
 def open_bytecode_from_code(code, offsets, k, randomness, table_dev=None, rows_dev=None, keccak_dev=None, device=None):
@@ -1079,11 +1331,8 @@ def open_bytecode_from_code(code, offsets, k, randomness, table_dev=None, rows_d
     -> BytecodeFromCodeSession.  numpy inputs are staged to HBM; torch CUDA tensors are used in place, and table_dev / rows_dev /
     keccak_dev (CUDA tensors of the shapes read() returns) then receive the outputs in place: rows_dev and keccak_dev are what
     open_bytecode takes, table_dev is zk_evm_tables.bytecode."""
-    lib = _lib.init(device)
-    t, w, opts, keep = _bytecode_from_code_args(code, offsets, k, randomness, {"table": table_dev, "rows": rows_dev, "keccak": keccak_dev})
-    sizes = (int(t.n_bytes), int(t.n_codes), int(k))
-    return _open(lib, lib.zk_bytecode_from_code_open, sizes[0] + sizes[1], (keep, t, w, sizes), ctypes.byref(t),
-                 ctypes.byref(w) if w is not None else None, opts, cls=BytecodeFromCodeSession)
+    return _wire_open(CODE, device, {"code": code, "offsets": offsets, "k": k, "rows_dev": rows_dev}, (randomness,),
+                      {"table": table_dev, "rows": rows_dev, "keccak": keccak_dev}, cls=BytecodeFromCodeSession)
 
 
 # ---- EVM circuit tx / block / withdrawal tables from raw block data (zk_evm_tables_from_block*) -------------------------------------
@@ -1099,12 +1348,7 @@ def evm_tables_from_block_shapes(n_txs, calldata_bytes, n_history, n_withdrawals
             "withdrawals": ((m, 4, 4), np.uint64)}
 
 
-def _evm_tables_from_block_args(raw, outs=None):
-    """zk_evm_tables_from_block* over `raw` = dict(tx_fields uint64[n, 9, 4], to_is_none uint32[n], access_list uint32[n, 2], calldata
-    uint8[b], offsets uint64[n + 1], block uint64[8, 4] or None, history_hashes uint64[h, 4], withdrawals uint64[m, 4, 4]) -> (ZkBlockData,
-    ZkBlockTables of the device outputs or None, opts, kept arrays, shapes).  `outs` (device tensors only, each optional): buffers of
-    BLOCK_TABLES_OUTPUTS the session writes in place; they are sized from raw["calldata"], whose extent must be the offsets' last entry
-    (the opening functions check that against the library's own count)."""
+def _block_tables_check(raw):
     n, h, m = _rows(raw["tx_fields"]), _rows(raw.get("history_hashes")), _rows(raw.get("withdrawals"))
     _expect(raw["tx_fields"], "tx_fields", 8, (None, 9, 4))
     _expect(raw["to_is_none"], "to_is_none", 4, (n,))
@@ -1115,29 +1359,33 @@ def _evm_tables_from_block_args(raw, outs=None):
     _expect(raw.get("history_hashes"), "history_hashes", 8, (None, 4))
     _expect(raw.get("withdrawals"), "withdrawals", 8, (None, 4, 4))
     shapes = evm_tables_from_block_shapes(n, raw["calldata"].shape[0], h, m, raw.get("block") is not None)
-    outs = dict(outs or {})
-    for k, v in outs.items():
-        if v is not None:
-            _expect(v, k, np.dtype(shapes[k][1]).itemsize, shapes[k][0])
-    out_list = [outs.get(k) for k in BLOCK_TABLES_OUTPUTS]
-    a, opts = _prep([raw.get(k) for k in BLOCK_TABLES_INPUTS] + out_list, outputs=range(8, 8 + len(out_list)))
-    if any(v is not None for v in out_list) and not opts:
-        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
-    t = _lib.ZkBlockData(ptr(a[0], n), ptr(a[1], n), ptr(a[2], n), n, ptr(a[3], int(a[3].shape[0])), ptr(a[4]), ptr(a[5]), ptr(a[6], h), h,
-                         ptr(a[7], m), m)
-    w = _lib.ZkBlockTables(*[ptr(x, int(x.shape[0]) if x is not None else 0) for x in a[8:]]) if opts else None
-    return t, w, opts, a, shapes
+    return shapes["tx"][0][0], shapes
+
+
+def _block_tables_fill(raw, a, cells):
+    n, h, m = _rows(a[0]), _rows(a[6]), _rows(a[7])
+    return _lib.ZkBlockData(ptr(a[0], n), ptr(a[1], n), ptr(a[2], n), n, ptr(a[3], int(a[3].shape[0])), ptr(a[4]), ptr(a[5]), ptr(a[6], h), h,
+                            ptr(a[7], m), m)
+
+
+BLOCK_TABLES = WireFamily("zk_evm_tables_from_block", BLOCK_TABLES_INPUTS, BLOCK_TABLES_OUTPUTS, _lib.ZkBlockTables, _block_tables_check,
+                          _block_tables_fill, null_empty=True, n_sizes=3)
+
+
+def _evm_tables_from_block_args(raw, outs=None):
+    """zk_evm_tables_from_block* over `raw` = dict(tx_fields uint64[n, 9, 4], to_is_none uint32[n], access_list uint32[n, 2], calldata
+    uint8[b], offsets uint64[n + 1], block uint64[8, 4] or None, history_hashes uint64[h, 4], withdrawals uint64[m, 4, 4]) -> (ZkBlockData,
+    ZkBlockTables of the device outputs or None, opts, kept arrays, shapes).  `outs` (device tensors only, each optional): buffers of
+    BLOCK_TABLES_OUTPUTS the session writes in place; they are sized from raw["calldata"], whose extent must be the offsets' last entry
+    (the opening functions check that against the library's own count)."""
+    return _wire_args(BLOCK_TABLES, raw, (), outs)[:5]
 
 
 def evm_tables_from_block_sizes(raw, device=None, _prepared=None):
     """(tx-table rows, block-table rows, withdrawal rows) of the raw block data `raw`; raises EngineError (rc = _lib.ERR_BTB_*) for inputs
-    outside the domain"""
+    outside the domain.  _prepared: the Prepared call of _wire_args, where the caller has made it"""
     lib = _lib.init(device)
-    t, _, opts, keep, _ = _prepared or _evm_tables_from_block_args(raw)
-    a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-    check(lib.zk_evm_tables_from_block_sizes(ctypes.byref(t), opts, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
-          "zk_evm_tables_from_block_sizes", lib)
-    return int(a.value), int(b.value), int(c.value)
+    return _wire_sizes(BLOCK_TABLES, lib, _prepared or _wire_args(BLOCK_TABLES, raw))
 
 
 def _check_block_table_sizes(sizes, shapes):
@@ -1146,30 +1394,14 @@ def _check_block_table_sizes(sizes, shapes):
                          f"are sized for {shapes['tx'][0][0]})")
 
 
-class TablesFromBlockSession(Session):
-    """zk_evm_tables_from_block_open: launch() / collect() like the other assignments (status per tx-table row, always 0);
-    read() -> dict of the last pass's tx / tx_flags / block / block_flags / withdrawals as host arrays"""
-
-    def read(self, names=BLOCK_TABLES_OUTPUTS):
-        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in self.shapes.items() if k in names}
-        w = _lib.ZkBlockTables(*[ptr(out[k], out[k].shape[0]) if k in out else None for k in BLOCK_TABLES_OUTPUTS])
-        check(self._lib.zk_evm_tables_from_block_read(self._h, ctypes.byref(w)), "zk_evm_tables_from_block_read", self._lib)
-        return out
-
+TablesFromBlockSession = WireSession  # zk_evm_tables_from_block_open: status per tx-table row, always 0
 
 def open_evm_tables_from_block(raw, outs=None, device=None):
     """The EVM circuit's tx, block and withdrawal tables from raw block data `raw` (see _evm_tables_from_block_args) ->
     TablesFromBlockSession.  numpy inputs are staged to HBM; torch CUDA tensors are used in place, and the CUDA tensors of `outs` (tx /
     tx_flags / block / block_flags / withdrawals, shapes of evm_tables_from_block_shapes) then receive the tables in place: what
     open_evm's wire and open_copy's tx / tx_flags take."""
-    lib = _lib.init(device)
-    prepared = _evm_tables_from_block_args(raw, outs)
-    t, w, opts, keep, shapes = prepared
-    _check_block_table_sizes(evm_tables_from_block_sizes(raw, device, prepared), shapes)
-    s = _open(lib, lib.zk_evm_tables_from_block_open, shapes["tx"][0][0], (keep, t, w), ctypes.byref(t),
-              ctypes.byref(w) if w is not None else None, opts, cls=TablesFromBlockSession)
-    s.shapes = shapes
-    return s
+    return _wire_open(BLOCK_TABLES, device, raw, (), outs, agree=_check_block_table_sizes)
 
 
 # ---- EVM circuit witness from compact trace records (zk_evm_witness_from_trace*) ---------------------------------------------------
@@ -1182,12 +1414,8 @@ def evm_witness_from_trace_shapes(n_rw, n_steps):
     return {"rw": ((int(n_rw), 14, 4), np.uint64), "rw_flags": ((int(n_rw),), np.uint32), "steps": ((int(n_steps), 13, 4), np.uint64)}
 
 
-def _evm_witness_from_trace_args(trace, outs=None, optional=()):
-    """zk_evm_witness_from_trace* over `trace` = dict(head uint32[n], id / addr / val / prev uint64[n], rw_counter uint64[n] or None (then
-    rw_base, default 1: the counter of op i is rw_base + i), pool uint64[m, 4], steps uint64[k, 13]) -> (ZkTrace, ZkTraceWitness of the
-    device outputs or None, opts, kept arrays, shapes).  trace.py makes such records.  `outs` (device tensors only, each optional):
-    buffers of TRACE_OUTPUTS the session writes in place.  `optional`: per-op arrays the entry does not read and that may be missing."""
-    n, m, k = _rows(trace.get("head")), _rows(trace.get("pool")), _rows(trace.get("steps"))
+def _trace_check(trace, optional=()):
+    n = _rows(trace.get("head"))
     _expect(trace.get("head"), "head", 4, (None,))
     for name in ("id", "addr", "val", "prev", "rw_counter"):
         _expect(trace.get(name), name, 8, (n,))
@@ -1195,52 +1423,41 @@ def _evm_witness_from_trace_args(trace, outs=None, optional=()):
             raise ValueError(f"{name}: missing")
     _expect(trace.get("pool"), "pool", 8, (None, 4))
     _expect(trace.get("steps"), "steps", 8, (None, 13))
-    shapes = evm_witness_from_trace_shapes(n, k)
-    outs = dict(outs or {})
-    for key, v in outs.items():
-        if v is not None:
-            _expect(v, key, np.dtype(shapes[key][1]).itemsize, shapes[key][0])
-    out_list = [outs.get(key) for key in TRACE_OUTPUTS]
-    a, opts = _prep([trace.get(key) for key in TRACE_INPUTS] + out_list, outputs=range(8, 8 + len(out_list)))
-    if any(v is not None for v in out_list) and not opts:
-        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
-    t = _lib.ZkTrace(ptr(a[0], n), ptr(a[1], n), ptr(a[2], n), ptr(a[3], n), ptr(a[4], n), ptr(a[5], n), int(trace.get("rw_base", 1)), n,
-                     ptr(a[6], m), m, ptr(a[7], k), k)
-    w = _lib.ZkTraceWitness(*[ptr(x, int(x.shape[0]) if x is not None else 0) for x in a[8:]]) if opts else None
-    return t, w, opts, a, shapes
+    return n, evm_witness_from_trace_shapes(n, _rows(trace.get("steps")))
+
+
+def _trace_fill(trace, a, cells):
+    n, m, k = _rows(a[0]), _rows(a[6]), _rows(a[7])
+    return _lib.ZkTrace(ptr(a[0], n), ptr(a[1], n), ptr(a[2], n), ptr(a[3], n), ptr(a[4], n), ptr(a[5], n), int(trace.get("rw_base", 1)), n,
+                        ptr(a[6], m), m, ptr(a[7], k), k)
+
+
+TRACE = WireFamily("zk_evm_witness_from_trace", TRACE_INPUTS, TRACE_OUTPUTS, _lib.ZkTraceWitness, _trace_check, _trace_fill,
+                   null_empty=True, n_sizes=2)
+
+
+def _evm_witness_from_trace_args(trace, outs=None, optional=()):
+    """zk_evm_witness_from_trace* over `trace` = dict(head uint32[n], id / addr / val / prev uint64[n], rw_counter uint64[n] or None (then
+    rw_base, default 1: the counter of op i is rw_base + i), pool uint64[m, 4], steps uint64[k, 13]) -> (ZkTrace, ZkTraceWitness of the
+    device outputs or None, opts, kept arrays, shapes).  trace.py makes such records.  `outs` (device tensors only, each optional):
+    buffers of TRACE_OUTPUTS the session writes in place.  `optional`: per-op arrays the entry does not read and that may be missing."""
+    return _wire_args(TRACE, trace, (), outs, optional=optional)[:5]
 
 
 def evm_witness_from_trace_sizes(trace, device=None, _prepared=None):
     """(RW rows, step rows) of the trace records `trace`; raises EngineError (rc = _lib.ERR_TRC_*) for records outside the domain"""
     lib = _lib.init(device)
-    t, _, opts, keep, _ = _prepared or _evm_witness_from_trace_args(trace)
-    a, b = ctypes.c_uint64(), ctypes.c_uint64()
-    check(lib.zk_evm_witness_from_trace_sizes(ctypes.byref(t), opts, ctypes.byref(a), ctypes.byref(b)), "zk_evm_witness_from_trace_sizes", lib)
-    return int(a.value), int(b.value)
+    return _wire_sizes(TRACE, lib, _prepared or _wire_args(TRACE, trace))
 
 
-class WitnessFromTraceSession(Session):
-    """zk_evm_witness_from_trace_open: launch() / collect() like the other assignments (status per RW row, always 0); read() -> dict of
-    the last pass's rw / rw_flags / steps as host arrays"""
-
-    def read(self, names=TRACE_OUTPUTS):
-        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in self.shapes.items() if k in names}
-        w = _lib.ZkTraceWitness(*[ptr(out[k], out[k].shape[0]) if k in out else None for k in TRACE_OUTPUTS])
-        check(self._lib.zk_evm_witness_from_trace_read(self._h, ctypes.byref(w)), "zk_evm_witness_from_trace_read", self._lib)
-        return out
-
+WitnessFromTraceSession = WireSession  # zk_evm_witness_from_trace_open: status per RW row, always 0
 
 def open_evm_witness_from_trace(trace, outs=None, device=None):
     """The EVM circuit's RW table, its flags and its step table from compact trace records `trace` (see _evm_witness_from_trace_args) ->
     WitnessFromTraceSession.  numpy inputs are staged to HBM (the CPU backend reads id / addr / val / prev / pool / steps in place, every
     pass); torch CUDA tensors are used in place, and the CUDA tensors of `outs` (rw / rw_flags / steps, shapes of
     evm_witness_from_trace_shapes) then receive the rows in place: what open_evm's wire and the from-RW State sessions take."""
-    lib = _lib.init(device)
-    t, w, opts, keep, shapes = _evm_witness_from_trace_args(trace, outs)
-    s = _open(lib, lib.zk_evm_witness_from_trace_open, shapes["rw"][0][0], (keep, t, w), ctypes.byref(t),
-              ctypes.byref(w) if w is not None else None, opts, cls=WitnessFromTraceSession)
-    s.shapes = shapes
-    return s
+    return _wire_open(TRACE, device, trace, (), outs)
 
 
 # ---- State circuit from compact trace records (zk_state_verify_from_trace* / zk_state_ops_from_trace* / zk_state_assign_from_trace*) ---------------------------------
@@ -1250,10 +1467,7 @@ def _state_from_trace_args(trace, outs=()):
     rec = {k: trace.get(k) for k in TRACE_INPUTS if k != "steps"}
     rec["rw_base"] = trace.get("rw_base", 1)
     n = _rows(rec.get("head"))
-    for buf, name, size, per_row in outs:
-        _expect(buf, name, size, (None,))
-        if buf is not None and int(buf.shape[0]) < per_row * (n + 1):
-            raise ValueError(f"{name} holds fewer than {per_row * (n + 1)} entries")
+    _check_flat_outs(outs, n)
     t, _, opts, keep, _ = _evm_witness_from_trace_args(rec, optional=("prev",))
     bufs = [o[0] for o in outs]
     if any(b is not None for b in bufs):
@@ -1270,9 +1484,7 @@ def open_state_verify_from_trace(trace, device=None):
     records, without those rows.  CUDA tensors are used in place: id / addr / val / pool must stay unchanged while the session lives."""
     lib = _lib.init(device)
     t, opts, keep, _ = _state_from_trace_args(trace)
-    h, n_ops = ctypes.c_void_p(), ctypes.c_uint64()
-    check(lib.zk_state_verify_from_trace_open(ctypes.byref(t), opts, ctypes.byref(n_ops), ctypes.byref(h)), "zk_state_verify_from_trace_open", lib)
-    return Session(h, int(n_ops.value), keep, lib=lib)
+    return _open_n_ops(lib, lib.zk_state_verify_from_trace_open, keep, ctypes.byref(t), opts)
 
 
 def open_state_ops_from_trace(trace, ops_dev=None, op_flags_dev=None, device=None):
@@ -1280,12 +1492,7 @@ def open_state_ops_from_trace(trace, ops_dev=None, op_flags_dev=None, device=Non
     open_state_ops_from_rw over the expanded rows; ops_dev / op_flags_dev as there (capacity n_rw + 1 ops)."""
     lib = _lib.init(device)
     t, opts, keep, n = _state_from_trace_args(trace, ((ops_dev, "ops_dev", 8, 48), (op_flags_dev, "op_flags_dev", 4, 1)))
-    h, n_ops = ctypes.c_void_p(), ctypes.c_uint64()
-    check(lib.zk_state_ops_from_trace_open(ctypes.byref(t), ptr(ops_dev), ptr(op_flags_dev), opts, ctypes.byref(n_ops), ctypes.byref(h)),
-          "zk_state_ops_from_trace_open", lib)
-    s = RekeySession(h, n, keep, lib=lib)
-    s.n_ops = int(n_ops.value)
-    return s
+    return _open_n_ops(lib, lib.zk_state_ops_from_trace_open, keep, ctypes.byref(t), ptr(ops_dev), ptr(op_flags_dev), opts, cls=RekeySession, n=n)
 
 
 def open_state_assign_from_trace(trace, rows_dev=None, row_flags_dev=None, mpt_dev=None, device=None, compact=False):
@@ -1298,150 +1505,8 @@ def open_state_assign_from_trace(trace, rows_dev=None, row_flags_dev=None, mpt_d
     t, opts, keep, _ = _state_from_trace_args(trace, outs)
     if compact:
         opts |= _lib.OPT_STATE_COMPACT
-    h, n_ops = ctypes.c_void_p(), ctypes.c_uint64()
-    check(lib.zk_state_assign_from_trace_open(ctypes.byref(t), ptr(rows_dev), ptr(row_flags_dev), ptr(mpt_dev), opts, ctypes.byref(n_ops),
-                                              ctypes.byref(h)), "zk_state_assign_from_trace_open", lib)
-    s = AssignSession(h, int(n_ops.value), keep, lib=lib)
-    s.compact = bool(compact)
-    return s
-
-
-# ---- Sig circuit witness assignment (zk_sig_assign*) ------------------------------------------------------------------------------
-SIG_ASSIGN_INPUTS = ("fields", "addr", "expect_valid")
-SIG_ASSIGN_OUTPUTS = ("bytes", "cells", "meta", "keccak", "sig_table", "aux")
-
-
-def sig_assign_shapes(n):
-    """name -> (shape, dtype) of the outputs of zk_sig_assign* (keccak, sig_table: their capacities, n + 1 and n rows)"""
-    return {"bytes": ((n, 9, 32), np.uint8), "cells": ((8, n, 4), np.uint64), "meta": ((n, 4), np.uint32),
-            "keccak": ((n + 1, 5, 4), np.uint64), "sig_table": ((n, 9, 4), np.uint64), "aux": ((n, 12, 4), np.uint64)}
-
-
-def _sig_assign_args(sig, randomness, outs=None):
-    """zk_sig_assign_open / zk_sig_assign over `sig` = dict(fields uint64[n, 4, 4]: msg_hash, sig_v, sig_r, sig_s; addr uint64[n, 4] or
-    None: the claimed addresses; expect_valid uint32[n] or None; v_offset: 0 (v is the parity) or 27 (the precompile's input word))
-    -> (ZkSigInputs, ZkSigWire of the device outputs or None, opts, kept arrays).
-    `outs` (device tensors only, each optional): buffers of SIG_ASSIGN_OUTPUTS the session writes in place."""
-    n = int(sig["fields"].shape[0])
-    _expect(sig["fields"], "fields", 8, (None, 4, 4))
-    _expect(sig.get("addr"), "addr", 8, (n, 4))
-    _expect(sig.get("expect_valid"), "expect_valid", 4, (n,))
-    shapes = sig_assign_shapes(n)
-    outs = dict(outs or {})
-    for k, v in outs.items():
-        if v is not None:
-            _expect(v, k, np.dtype(shapes[k][1]).itemsize, shapes[k][0])
-    out_list = [outs.get(k) for k in SIG_ASSIGN_OUTPUTS]
-    a, opts = _prep([sig.get(k) for k in SIG_ASSIGN_INPUTS] + out_list, outputs=range(3, 3 + len(out_list)))
-    if any(v is not None for v in out_list) and not opts:
-        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
-    rc = _randomness_cells(randomness, a[0])
-    keep = a + [rc]
-    t = _lib.ZkSigInputs(ptr(a[0], n), ptr(a[1], n), ptr(a[2], n), n, int(sig.get("v_offset", 0)), 0, ptr(rc))
-    w = _lib.ZkSigWire(*[ptr(x) for x in a[3:]]) if opts else None
-    return t, w, opts, keep
-
-
-class SigAssignSession(Session):
-    """zk_sig_assign_open: status per signature; read() -> the wire dict of the last pass (host arrays)"""
-
-    def _counts(self, w=None):
-        nk, ns = ctypes.c_uint64(), ctypes.c_uint64()
-        check(self._lib.zk_sig_assign_read(self._h, ctypes.byref(w) if w is not None else None, ctypes.byref(nk), ctypes.byref(ns)),
-              "zk_sig_assign_read", self._lib)
-        return int(nk.value), int(ns.value)
-
-    def read(self):
-        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in sig_assign_shapes(self.n).items()}
-        nk, ns = self._counts(_lib.ZkSigWire(*[ptr(out[k]) for k in SIG_ASSIGN_OUTPUTS]))
-        out["keccak"], out["sig_table"] = out["keccak"][:nk], out["sig_table"][:ns]
-        return out
-
-    def n_keccak(self):
-        return self._counts()[0]
-
-    def n_sig_rows(self):
-        return self._counts()[1]
-
-
-def open_sig_assign(sig, randomness, outs=None, device=None):
-    """Sig circuit witness assignment session over the signed data of `sig` (see _sig_assign_args).  With device tensors the outputs
-    stay in HBM: in `outs`' buffers where given (e.g. for zk_ecdsa_open / zk_sign_open on them), else in the session's own."""
-    lib = _lib.init(device)
-    t, w, opts, keep = _sig_assign_args(sig, randomness, outs)
-    return _open(lib, lib.zk_sig_assign_open, t.n, (keep, t, w), ctypes.byref(t), ctypes.byref(w) if w is not None else None, opts,
-                 cls=SigAssignSession)
-
-
-# ---- ECC precompile calls (zk_ecc_from_calls*) -------------------------------------------------------------------------------------
-ECC_CALLS_INPUTS = ("add_in", "mul_in", "pair_pts", "pair_off")
-ECC_CALLS_OUTPUTS = ("points", "pair_out", "rows", "ecc_table", "aux", "aux_kind")
-
-
-def ecc_calls_shapes(n_add, n_mul, n_pairing):
-    """name -> (shape, dtype) of the outputs of zk_ecc_from_calls* (ecc_table: its capacity, one row per call)"""
-    n = n_add + n_mul + n_pairing
-    return {"points": ((n_add + n_mul, 6, 4), np.uint64), "pair_out": ((n_pairing, 4), np.uint64), "rows": ((n, 13, 4), np.uint64),
-            "ecc_table": ((n, 13, 4), np.uint64), "aux": ((n, 12, 4), np.uint64), "aux_kind": ((n,), np.uint32)}
-
-
-def _ecc_calls_args(calls, randomness, outs=None):
-    """zk_ecc_from_calls_open / zk_ecc_from_calls over `calls` = dict(add_in uint64[n_add, 4, 4]: p.x, p.y, q.x, q.y; mul_in
-    uint64[n_mul, 3, 4]: p.x, p.y, s; pair_pts uint64[m, 6, 4] in EIP-197 order + pair_off uint32[n_pairing + 1]) — the arrays of
-    ecc_circuit.ecc_calls_wire — -> (ZkEccCalls, ZkEccCallWire of the device outputs or None, opts, kept arrays, output shapes).
-    `outs` (device tensors only, each optional): buffers of ECC_CALLS_OUTPUTS the session writes in place."""
-    add_in, mul_in, pair_pts, pair_off = (calls[k] for k in ECC_CALLS_INPUTS)
-    n_add, n_mul, n_pairing = int(add_in.shape[0]), int(mul_in.shape[0]), int(pair_off.shape[0]) - 1
-    _expect(add_in, "add_in", 8, (None, 4, 4))
-    _expect(mul_in, "mul_in", 8, (None, 3, 4))
-    _expect(pair_pts, "pair_pts", 8, (None, 6, 4))
-    _expect(pair_off, "pair_off", 4, (n_pairing + 1,))
-    shapes = ecc_calls_shapes(n_add, n_mul, n_pairing)
-    outs = dict(outs or {})
-    for k, v in outs.items():
-        if v is not None:
-            _expect(v, k, np.dtype(shapes[k][1]).itemsize, shapes[k][0])
-    out_list = [outs.get(k) for k in ECC_CALLS_OUTPUTS]
-    a, opts = _prep([add_in, mul_in, pair_pts, pair_off] + out_list, outputs=range(4, 4 + len(out_list)))
-    if any(v is not None for v in out_list) and not opts:
-        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
-    rc = _randomness_cells(randomness, a[0])
-    keep = a + [rc]
-    t = _lib.ZkEccCalls(ptr(a[0], n_add), n_add, ptr(a[1], n_mul), n_mul, ptr(a[2], _rows(a[2])), ptr(a[3], n_pairing), n_pairing, ptr(rc))
-    w = _lib.ZkEccCallWire(*[ptr(x) for x in a[4:]]) if opts else None
-    return t, w, opts, keep, shapes
-
-
-class EccCallsSession(Session):
-    """zk_ecc_from_calls_open: launch() / collect() like the circuits (every status 0); read() -> the wire dict of the last pass
-    (host arrays, ecc_table cut to its rows); n_table_rows() the table's row count alone"""
-
-    def _count(self, w=None):
-        nt = ctypes.c_uint64()
-        check(self._lib.zk_ecc_from_calls_read(self._h, ctypes.byref(w) if w is not None else None, ctypes.byref(nt)),
-              "zk_ecc_from_calls_read", self._lib)
-        return int(nt.value)
-
-    def read(self):
-        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in self.shapes.items()}
-        nt = self._count(_lib.ZkEccCallWire(*[ptr(out[k]) for k in ECC_CALLS_OUTPUTS]))
-        out["ecc_table"] = out["ecc_table"][:nt]
-        return out
-
-    def n_table_rows(self):
-        return self._count()
-
-
-def open_ecc_from_calls(calls, randomness, outs=None, device=None):
-    """ECC precompile calls session (see _ecc_calls_args): from the calls' input words to the ECC circuit's ops and rows and the EVM
-    circuit's ecc table and aux rows.  With device tensors the outputs stay in HBM: in `outs`' buffers where given (ready for
-    open_ecc / open_evm), else in the session's own."""
-    lib = _lib.init(device)
-    t, w, opts, keep, shapes = _ecc_calls_args(calls, randomness, outs)
-    s = _open(lib, lib.zk_ecc_from_calls_open, int(t.n_add + t.n_mul + t.n_pairing), (keep, t, w), ctypes.byref(t),
-              ctypes.byref(w) if w is not None else None, opts, cls=EccCallsSession)
-    s.shapes = shapes
-    return s
+    return _open_n_ops(lib, lib.zk_state_assign_from_trace_open, keep, ctypes.byref(t), ptr(rows_dev), ptr(row_flags_dev), ptr(mpt_dev), opts,
+                       cls=AssignSession, compact=compact)
 
 
 # ---- Exp circuit witness assignment (zk_exp_assign*) ------------------------------------------------------------------------------
@@ -1500,87 +1565,4 @@ def open_exp_assign(events, max_exp_steps=0, rows_dev=None, table_dev=None, devi
     a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
     check(lib.zk_exp_assign_counts(s._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "zk_exp_assign_counts", lib)
     s.n, s.n_step, s.n_table = int(a.value), int(b.value), int(c.value)
-    return s
-
-
-# ---- PI circuit witness assignment (zk_pi_assign*) ----------------------------------------------------------------------------------
-PI_ASSIGN_INPUTS = ("block", "state_root_prev", "block_hashes", "tx_fields", "to_is_none", "calldata", "offsets", "withdrawals")
-PI_ASSIGN_OUTPUTS = ("rows", "gas", "keccak", "cc_cells", "cc_bytes", "cc_lens", "block_table", "block_flags", "tx_table", "tx_flags",
-                     "wd_table", "public_inputs", "raw_bytes", "raw_lens")
-
-
-def pi_assign_shapes(max_txs, max_calldata_bytes, max_withdrawals, calldata_bytes):
-    """name -> (shape, dtype) of the outputs of zk_pi_assign* (include/zkevm_hip.h)"""
-    mt, mc, mw = int(max_txs), int(max_calldata_bytes), int(max_withdrawals)
-    n = 8454 + 336 * mt + mc + 56 * mw
-    n_cc = 538 + 4 * (10 * mt + 1) + 2 * mc + 5 * mw
-    t = 10 * mt + 1 + mc
-    return {"rows": ((24, n, 4), np.uint64), "gas": ((1 + int(calldata_bytes), 3, 4), np.uint64), "keccak": ((2, 5, 4), np.uint64),
-            "cc_cells": ((n_cc, 4), np.uint64), "cc_bytes": ((n_cc, 32), np.uint8), "cc_lens": ((n_cc,), np.uint32),
-            "block_table": ((268, 2, 4), np.uint64), "block_flags": ((268,), np.uint32), "tx_table": ((t, 5, 4), np.uint64),
-            "tx_flags": ((t,), np.uint32), "wd_table": ((mw, 5, 4), np.uint64), "public_inputs": ((4, 2, 4), np.uint64),
-            "raw_bytes": ((n,), np.uint8), "raw_lens": ((533 + 33 * mt + mc + 5 * mw,), np.uint32)}
-
-
-def _pi_assign_args(pd, keccak_rand=255, byte_pow_base=255, outs=None):
-    """zk_pi_assign_open / zk_pi_assign over `pd` = dict(chain_id, block uint64[9, 4], state_root_prev uint64[4], block_hashes
-    uint64[256, 4], tx_fields uint64[n, 7, 4], to_is_none uint32[n], calldata uint8[b], offsets uint64[n + 1], withdrawals
-    uint64[m, 4, 4], max_txs, max_calldata_bytes, max_withdrawals) -> (ZkPiInputs, ZkPiWire of the device outputs or None, opts, kept
-    arrays).  `outs` (device tensors only, each optional): buffers of PI_ASSIGN_OUTPUTS the session writes in place; they are sized
-    from pd["calldata"], so its extent must be the offsets' last entry."""
-    n, m = _rows(pd["tx_fields"]), _rows(pd["withdrawals"])
-    _expect(pd["block"], "block", 8, (9, 4))
-    _expect(pd["state_root_prev"], "state_root_prev", 8, (4,))
-    _expect(pd["block_hashes"], "block_hashes", 8, (256, 4))
-    _expect(pd["tx_fields"], "tx_fields", 8, (None, 7, 4))
-    _expect(pd["to_is_none"], "to_is_none", 4, (n,))
-    _expect(pd["offsets"], "offsets", 8, (n + 1,))
-    _expect(pd["calldata"], "calldata", 1, (None,))
-    _expect(pd["withdrawals"], "withdrawals", 8, (None, 4, 4))
-    shapes = pi_assign_shapes(pd["max_txs"], pd["max_calldata_bytes"], pd["max_withdrawals"], pd["calldata"].shape[0])
-    outs = dict(outs or {})
-    for k, v in outs.items():
-        if v is not None:
-            _expect(v, k, np.dtype(shapes[k][1]).itemsize, shapes[k][0])
-    out_list = [outs.get(k) for k in PI_ASSIGN_OUTPUTS]
-    a, opts = _prep([pd[k] for k in PI_ASSIGN_INPUTS] + out_list, outputs=range(8, 8 + len(out_list)))
-    if any(v is not None for v in out_list) and not opts:
-        raise ValueError("output buffers need device inputs (ZK_OPT_DEVICE_PTRS)")
-    kr, bp = _randomness_cells(int(keccak_rand), a[0]), _randomness_cells(int(byte_pow_base), a[0])
-    keep = a + [kr, bp]
-    t = _lib.ZkPiInputs(int(pd["chain_id"]), ptr(a[0]), ptr(a[1]), ptr(a[2]), ptr(a[3], n), ptr(a[4], n), n, ptr(a[5], int(a[5].shape[0])),
-                        ptr(a[6]), ptr(a[7], m), m, int(pd["max_txs"]), int(pd["max_calldata_bytes"]), int(pd["max_withdrawals"]), ptr(kr), ptr(bp))
-    w = _lib.ZkPiWire(*[ptr(x) for x in a[8:]]) if opts else None
-    return t, w, opts, keep, shapes
-
-
-def pi_assign_sizes(pd, device=None):
-    """(circuit_len, gas-table rows, copy constraints) of the public data `pd`; raises EngineError (rc = _lib.ERR_PI_*) for inputs
-    outside the circuit's domain"""
-    lib = _lib.init(device)
-    t, _, opts, keep, _ = _pi_assign_args(pd)
-    a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
-    check(lib.zk_pi_assign_sizes(ctypes.byref(t), opts, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "zk_pi_assign_sizes", lib)
-    return int(a.value), int(b.value), int(c.value)
-
-
-class PiAssignSession(Session):
-    """zk_pi_assign_open: one status per row; read() -> the wire dict of the last pass (host arrays)"""
-
-    def read(self, names=PI_ASSIGN_OUTPUTS):
-        out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in self.shapes.items() if k in names}
-        w = _lib.ZkPiWire(*[ptr(out[k]) if k in out else None for k in PI_ASSIGN_OUTPUTS])
-        check(self._lib.zk_pi_assign_read(self._h, ctypes.byref(w)), "zk_pi_assign_read", self._lib)
-        return out
-
-
-def open_pi_assign(pd, keccak_rand=255, byte_pow_base=255, outs=None, device=None):
-    """PI circuit witness assignment session over the public data `pd` (see _pi_assign_args).  With device tensors the outputs stay in
-    HBM: in `outs`' buffers where given (rows / keccak / gas for open_pi, cc_cells / cc_bytes / cc_lens for zk_pi_copy_open), else in
-    the session's own."""
-    lib = _lib.init(device)
-    t, w, opts, keep, shapes = _pi_assign_args(pd, keccak_rand, byte_pow_base, outs)
-    s = _open(lib, lib.zk_pi_assign_open, shapes["rows"][0][1], (keep, t, w), ctypes.byref(t), ctypes.byref(w) if w is not None else None,
-              opts, cls=PiAssignSession)
-    s.shapes = shapes
     return s

@@ -2,7 +2,9 @@
 host buffers in, tally + per-row status out — exactly the calls INTEGRATION.md's reference-side stub makes.  The host
 mirrors (`evm_circuit.verify_steps`, `state_circuit.verify_state_rows`, ...) go through these; `engine.py` is the session
 form (upload once, many passes) for benchmarks and device-resident pipelines.  Both forms check and marshal their arguments
-with the same builders (engine._*_args and kin); a one-shot first makes its inputs host arrays of the wire dtype.
+with the same builders (engine._*_args and kin); a one-shot first makes its inputs host arrays of the wire dtype.  The seven
+"input struct + wire struct of outputs" families (tx, sig, ecc calls, pi, code, block tables, trace: engine.WireFamily) share one
+body here, _wire_oneshot; the from-RW and from-trace State one-shots share _state_verify_from and _state_ops_from.
 """
 import ctypes
 
@@ -13,18 +15,37 @@ from ._lib import ZkResult, check, ptr
 from .engine import Result, _expect, _host, _randomness_cells, withdrawal_arrays  # noqa: F401 (withdrawal_arrays: kept importable here)
 
 
-def _verify(fn, n, *args):
-    """one `fn(*args, status, &result)` call of a zk_*_verify entry -> (Result, status uint32[n])"""
+def _verify(lib, fn, n, *args):
+    """one `fn(*args, status, &result)` call of a zk_*_verify entry of `lib` -> (Result, status uint32[n])"""
     status, r = np.zeros(n, dtype=np.uint32), ZkResult()
-    check(fn(*args, ptr(status), ctypes.byref(r)), fn.__name__)
+    check(fn(*args, ptr(status), ctypes.byref(r)), fn.__name__, lib)
     return Result(r), status
+
+
+def _host_inputs(fam, x):
+    """the input dict `x` of a wire-struct family (engine.WireFamily) with its arrays made C-contiguous host arrays"""
+    return {k: (_host(v) if k in fam.inputs else v) for k, v in x.items()}
+
+
+def _wire_oneshot(fam, lib, p):
+    """The one-shot entry of a wire-struct family over a prepared call `p` (engine._wire_args): allocate the host outputs, one
+    `<stem>(&inputs, &wire, opts, [status,] &count..., &result)` call, cut the family's `cut` outputs to the counts -> (Result,
+    [status uint32[n],] dict of the outputs)"""
+    out, w = engine._wire_host_outputs(fam, p.shapes)
+    status = np.zeros(max(p.n, 1), dtype=np.uint32) if fam.status else None
+    counts, r = [ctypes.c_uint64() for _ in fam.cut], ZkResult()
+    check(getattr(lib, fam.stem)(ctypes.byref(p.t), ctypes.byref(w), p.opts, *([ptr(status)] if fam.status else []),
+                                 *(ctypes.byref(c) for c in counts), ctypes.byref(r)), fam.stem, lib)
+    for k, c in zip(fam.cut, counts):
+        out[k] = out[k][: c.value]
+    return (Result(r), status[: p.n], out) if fam.status else (Result(r), out)
 
 
 def state_verify(rows, flags, mpt, device=None):
     """zk_state_verify -> (Result, status uint32[n])"""
     lib = _lib.init(device)
     args, opts, keep = engine._state_args(_host(rows), _host(flags), _host(mpt))
-    return _verify(lib.zk_state_verify, args[2], *args, opts)
+    return _verify(lib, lib.zk_state_verify, args[2], *args, opts)
 
 
 def evm_verify(wire, begin_with_first_step=False, end_with_last_step=False, opts=0, device=None):
@@ -32,33 +53,33 @@ def evm_verify(wire, begin_with_first_step=False, end_with_last_step=False, opts
     lib = _lib.init(device)
     t, o, keep, n_pairs = engine._evm_tables({k: _host(wire.get(k)) for k in engine._EVM_WIRE}, begin_with_first_step, end_with_last_step)
     status, r = np.zeros(max(n_pairs, 1), dtype=np.uint32), ZkResult()
-    check(lib.zk_evm_verify(ctypes.byref(t), o | int(opts), ptr(status), ctypes.byref(r)), "zk_evm_verify")
+    check(lib.zk_evm_verify(ctypes.byref(t), o | int(opts), ptr(status), ctypes.byref(r)), "zk_evm_verify", lib)
     return Result(r), status[:n_pairs]
 
 
 def bytecode_verify(rows, keccak, randomness, device=None):
     lib = _lib.init(device)
     args, opts, keep = engine._bytecode_args(_host(rows), _host(keccak), randomness)
-    return _verify(lib.zk_bytecode_verify, args[1], *args, opts)
+    return _verify(lib, lib.zk_bytecode_verify, args[1], *args, opts)
 
 
 def exp_verify(rows, device=None):
     lib = _lib.init(device)
     args, opts, keep = engine._exp_args(_host(rows))
-    return _verify(lib.zk_exp_verify, args[1], *args, opts)
+    return _verify(lib, lib.zk_exp_verify, args[1], *args, opts)
 
 
 def copy_verify(rows, row_flags, randomness, rw, rw_flags, bytecode, tx, tx_flags, opts=0, device=None):
     lib = _lib.init(device)
     rows, row_flags, rw, rw_flags, bytecode, tx, tx_flags = (_host(x) for x in (rows, row_flags, rw, rw_flags, bytecode, tx, tx_flags))
     t, o, keep = engine._copy_tables(rows, row_flags, randomness, rw, rw_flags, bytecode, tx, tx_flags)
-    return _verify(lib.zk_copy_verify, t.n_rows, ctypes.byref(t), o | int(opts))
+    return _verify(lib, lib.zk_copy_verify, t.n_rows, ctypes.byref(t), o | int(opts))
 
 
 def sign_verify(wire, randomness, is_sig, device=None):
     lib = _lib.init(device)
     t, opts, keep = engine._sign_units({k: _host(wire.get(k)) for k in engine._SIGN_WIRE}, randomness, is_sig)
-    return _verify(lib.zk_sign_verify, t.n_units, ctypes.byref(t), opts)
+    return _verify(lib, lib.zk_sign_verify, t.n_units, ctypes.byref(t), opts)
 
 
 def keccak_table(data, offsets, randomness, mode=0, device=None):
@@ -67,7 +88,7 @@ def keccak_table(data, offsets, randomness, mode=0, device=None):
     data, offsets = _host(data, np.uint8), _host(offsets, np.uint64)
     rows = np.zeros((int(offsets.shape[0]) - 1, 5, 4), dtype=np.uint64)
     args, opts, keep = engine._keccak_args(data, offsets, randomness, mode, rows)
-    return (*_verify(lib.zk_keccak_table, args[3], *args, opts), rows)
+    return (*_verify(lib, lib.zk_keccak_table, args[3], *args, opts), rows)
 
 
 def state_assign(ops, op_flags, device=None):
@@ -78,29 +99,39 @@ def state_assign(ops, op_flags, device=None):
     rows, rflags = np.zeros((57, n, 4), dtype=np.uint64), np.zeros(n, dtype=np.uint32)
     mpt, n_mpt = np.zeros((n, 12, 4), dtype=np.uint64), ctypes.c_uint64()
     status, r = np.zeros(n, dtype=np.uint32), ZkResult()
-    check(lib.zk_state_assign(*args, ptr(rows), ptr(rflags), ptr(mpt), ctypes.byref(n_mpt), opts, ptr(status), ctypes.byref(r)), "zk_state_assign")
+    check(lib.zk_state_assign(*args, ptr(rows), ptr(rflags), ptr(mpt), ctypes.byref(n_mpt), opts, ptr(status), ctypes.byref(r)), "zk_state_assign", lib)
     return Result(r), status, rows, rflags, mpt[: int(n_mpt.value)]
+
+
+def _state_ops_from(lib, fn, n, opts, *source):
+    """one `fn(*source, ops, op_flags, &n_ops, opts, status, &result)` call over n RW rows or ops (the from-RW and the from-trace form)
+    -> (Result, status uint32[n], ops uint64[12, n_ops, 4], op_flags uint32[n_ops])"""
+    ops, flags = np.zeros(12 * (n + 1) * 4, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint32)
+    status, r, n_ops = np.zeros(n, dtype=np.uint32), ZkResult(), ctypes.c_uint64()
+    check(fn(*source, ptr(ops), ptr(flags), ctypes.byref(n_ops), opts, ptr(status), ctypes.byref(r)), fn.__name__, lib)
+    m = int(n_ops.value)
+    return Result(r), status, ops[: 48 * m].reshape(12, m, 4), flags[:m]
+
+
+def _state_verify_from(lib, fn, n, opts, *source):
+    """one `fn(*source, opts, status, &n_ops, &result)` call over n RW rows or ops -> (Result of the State circuit, status uint32[n_ops])"""
+    status, r, n_ops = np.zeros(n + 1, dtype=np.uint32), ZkResult(), ctypes.c_uint64()
+    check(fn(*source, opts, ptr(status), ctypes.byref(n_ops), ctypes.byref(r)), fn.__name__, lib)
+    return Result(r), status[: int(n_ops.value)]
 
 
 def state_ops_from_rw(rw, rw_flags, device=None):
     """zk_state_ops_from_rw -> (Result, status uint32[n] per RW row, ops uint64[12, n_ops, 4], op_flags uint32[n_ops])"""
     lib = _lib.init(device)
     args, opts, keep = engine._rw_args(_host(rw), _host(rw_flags, np.uint32))
-    n = args[2]
-    ops, flags = np.zeros(12 * (n + 1) * 4, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint32)
-    status, r, n_ops = np.zeros(n, dtype=np.uint32), ZkResult(), ctypes.c_uint64()
-    check(lib.zk_state_ops_from_rw(*args, ptr(ops), ptr(flags), ctypes.byref(n_ops), opts, ptr(status), ctypes.byref(r)), "zk_state_ops_from_rw")
-    m = int(n_ops.value)
-    return Result(r), status, ops[: 48 * m].reshape(12, m, 4), flags[:m]
+    return _state_ops_from(lib, lib.zk_state_ops_from_rw, args[2], opts, *args)
 
 
 def state_verify_from_rw(rw, rw_flags, device=None):
     """zk_state_verify_from_rw -> (Result of the State circuit, status uint32[n_ops] per State row)"""
     lib = _lib.init(device)
     args, opts, keep = engine._rw_args(_host(rw), _host(rw_flags, np.uint32))
-    status, r, n_ops = np.zeros(args[2] + 1, dtype=np.uint32), ZkResult(), ctypes.c_uint64()
-    check(lib.zk_state_verify_from_rw(*args, opts, ptr(status), ctypes.byref(n_ops), ctypes.byref(r)), "zk_state_verify_from_rw", lib)
-    return Result(r), status[: int(n_ops.value)]
+    return _state_verify_from(lib, lib.zk_state_verify_from_rw, args[2], opts, *args)
 
 
 def bytecode_assign(in_rows, offsets, lengths, k, randomness, device=None):
@@ -108,7 +139,7 @@ def bytecode_assign(in_rows, offsets, lengths, k, randomness, device=None):
     lib = _lib.init(device)
     rows, r = np.zeros((12, 1 << int(k), 4), dtype=np.uint64), ZkResult()
     args, opts, keep = engine._bytecode_assign_args(_host(in_rows), _host(offsets, np.uint64), _host(lengths, np.uint64), k, randomness, rows)
-    check(lib.zk_bytecode_assign(*args, opts, ctypes.byref(r)), "zk_bytecode_assign")
+    check(lib.zk_bytecode_assign(*args, opts, ctypes.byref(r)), "zk_bytecode_assign", lib)
     return Result(r), rows
 
 
@@ -116,12 +147,9 @@ def bytecode_from_code(code, offsets, k, randomness, device=None):
     """zk_bytecode_from_code over raw contract code (engine._bytecode_from_code_args) -> (Result, table uint64[n_bytes + n_codes, 6, 4],
     rows uint64[12, 2^k, 4] (None when k == 0), keccak uint64[n_codes, 5, 4])"""
     lib = _lib.init(device)
-    t, _, opts, keep = engine._bytecode_from_code_args(_host(code, np.uint8), _host(offsets, np.uint64), k, randomness)
-    shapes = engine.bytecode_from_code_shapes(int(t.n_bytes), int(t.n_codes), k)
-    out = [None if shapes[name] is None else np.zeros(shapes[name], dtype=np.uint64) for name in engine.CODE_OUTPUTS]
-    w, r = _lib.ZkCodeWire(*[ptr(x, x.size if x is not None else 0) for x in out]), ZkResult()
-    check(lib.zk_bytecode_from_code(ctypes.byref(t), ctypes.byref(w), opts, ctypes.byref(r)), "zk_bytecode_from_code", lib)
-    return (Result(r), *out)
+    x = {"code": _host(code, np.uint8), "offsets": _host(offsets, np.uint64), "k": k}
+    res, out = _wire_oneshot(engine.CODE, lib, engine._wire_args(engine.CODE, x, (randomness,)))
+    return (res, *(out[name] for name in engine.CODE_OUTPUTS))
 
 
 def evm_tables_from_block(raw, device=None):
@@ -130,13 +158,9 @@ def evm_tables_from_block(raw, device=None):
     lib = _lib.init(device)
     dtypes = {"calldata": np.uint8, "to_is_none": np.uint32, "access_list": np.uint32}
     raw = {k: _host(raw.get(k), dtypes.get(k, np.uint64)) for k in engine.BLOCK_TABLES_INPUTS}
-    prepared = engine._evm_tables_from_block_args(raw)
-    t, _, opts, keep, shapes = prepared
-    engine._check_block_table_sizes(engine.evm_tables_from_block_sizes(raw, device, prepared), shapes)
-    out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items()}
-    w, r = _lib.ZkBlockTables(*[ptr(out[k], out[k].shape[0]) for k in engine.BLOCK_TABLES_OUTPUTS]), ZkResult()
-    check(lib.zk_evm_tables_from_block(ctypes.byref(t), ctypes.byref(w), opts, ctypes.byref(r)), "zk_evm_tables_from_block", lib)
-    return Result(r), out
+    p = engine._wire_args(engine.BLOCK_TABLES, raw)
+    engine._check_block_table_sizes(engine._wire_sizes(engine.BLOCK_TABLES, lib, p), p.shapes)
+    return _wire_oneshot(engine.BLOCK_TABLES, lib, p)
 
 
 def evm_witness_from_trace(trace, device=None):
@@ -145,11 +169,7 @@ def evm_witness_from_trace(trace, device=None):
     lib = _lib.init(device)
     rec = {k: _host(trace.get(k), np.uint32 if k == "head" else np.uint64) for k in engine.TRACE_INPUTS}
     rec["rw_base"] = trace.get("rw_base", 1)
-    t, _, opts, keep, shapes = engine._evm_witness_from_trace_args(rec)
-    out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items()}
-    w, r = _lib.ZkTraceWitness(*[ptr(out[k], out[k].shape[0]) for k in engine.TRACE_OUTPUTS]), ZkResult()
-    check(lib.zk_evm_witness_from_trace(ctypes.byref(t), ctypes.byref(w), opts, ctypes.byref(r)), "zk_evm_witness_from_trace", lib)
-    return Result(r), out
+    return _wire_oneshot(engine.TRACE, lib, engine._wire_args(engine.TRACE, rec))
 
 
 def _state_trace_records(trace):
@@ -163,9 +183,7 @@ def state_verify_from_trace(trace, device=None):
     what state_verify_from_rw returns over evm_witness_from_trace's rw / rw_flags"""
     lib = _lib.init(device)
     t, opts, keep, n = engine._state_from_trace_args(_state_trace_records(trace))
-    status, r, n_ops = np.zeros(n + 1, dtype=np.uint32), ZkResult(), ctypes.c_uint64()
-    check(lib.zk_state_verify_from_trace(ctypes.byref(t), opts, ptr(status), ctypes.byref(n_ops), ctypes.byref(r)), "zk_state_verify_from_trace", lib)
-    return Result(r), status[: int(n_ops.value)]
+    return _state_verify_from(lib, lib.zk_state_verify_from_trace, n, opts, ctypes.byref(t))
 
 
 def state_ops_from_trace(trace, device=None):
@@ -173,12 +191,7 @@ def state_ops_from_trace(trace, device=None):
     state_ops_from_rw returns over evm_witness_from_trace's rw / rw_flags"""
     lib = _lib.init(device)
     t, opts, keep, n = engine._state_from_trace_args(_state_trace_records(trace))
-    ops, flags = np.zeros(12 * (n + 1) * 4, dtype=np.uint64), np.zeros(n + 1, dtype=np.uint32)
-    status, r, n_ops = np.zeros(n, dtype=np.uint32), ZkResult(), ctypes.c_uint64()
-    check(lib.zk_state_ops_from_trace(ctypes.byref(t), ptr(ops), ptr(flags), ctypes.byref(n_ops), opts, ptr(status), ctypes.byref(r)),
-          "zk_state_ops_from_trace", lib)
-    m = int(n_ops.value)
-    return Result(r), status, ops[: 48 * m].reshape(12, m, 4), flags[:m]
+    return _state_ops_from(lib, lib.zk_state_ops_from_trace, n, opts, ctypes.byref(t))
 
 
 def state_assign_from_trace(trace, device=None, compact=False):
@@ -203,7 +216,7 @@ def ecdsa_verify(sig_bytes, v=None, layout=0, v_stride=1, device=None):
     """zk_ecdsa_verify -> (Result, status uint32[n])"""
     lib = _lib.init(device)
     args, opts, keep = engine._ecdsa_args(_host(sig_bytes, np.uint8), _host(v, np.uint32), layout, v_stride)
-    return _verify(lib.zk_ecdsa_verify, args[4], *args, opts)
+    return _verify(lib, lib.zk_ecdsa_verify, args[4], *args, opts)
 
 
 def copy_assign(events, flags, data, offsets, randomness, device=None):
@@ -215,7 +228,7 @@ def copy_assign(events, flags, data, offsets, randomness, device=None):
     table = np.zeros((n_table, 14, 4), dtype=np.uint64)
     rw, rwf = np.zeros((n_rw, 14, 4), dtype=np.uint64), np.zeros(n_rw, dtype=np.uint32)
     r = ZkResult()
-    check(lib.zk_copy_assign(ctypes.byref(t), ptr(rows), ptr(rf), ptr(table, n_table), ptr(rw, n_rw), ptr(rwf, n_rw), opts, ctypes.byref(r)), "zk_copy_assign")
+    check(lib.zk_copy_assign(ctypes.byref(t), ptr(rows), ptr(rf), ptr(table, n_table), ptr(rw, n_rw), ptr(rwf, n_rw), opts, ctypes.byref(r)), "zk_copy_assign", lib)
     return Result(r), rows, rf, table, rw, rwf
 
 
@@ -260,14 +273,14 @@ def pi_verify(rows, keccak, gas, circuit_len, keccak_rand=255, byte_pow_base=255
     """zk_pi_verify -> (Result, status uint32[n])"""
     lib = _lib.init(device)
     args, opts, keep = engine._pi_args(_host(rows), _host(keccak), _host(gas), circuit_len, keccak_rand, byte_pow_base)
-    return _verify(lib.zk_pi_verify, args[1], *args, opts)
+    return _verify(lib, lib.zk_pi_verify, args[1], *args, opts)
 
 
 def pi_copy_verify(cells, data, lens, device=None):
     """zk_pi_copy_verify over cells uint64[n, 4], data uint8[n, 32], lens uint32[n] -> (Result, status uint32[n])"""
     lib = _lib.init(device)
     args, opts, keep = engine._pi_copy_args(_host(cells), _host(data), _host(lens))
-    return _verify(lib.zk_pi_copy_verify, args[3], *args, opts)
+    return _verify(lib, lib.zk_pi_copy_verify, args[3], *args, opts)
 
 
 def ecc_assign(w, randomness, device=None):
@@ -286,14 +299,14 @@ def ecc_verify(w, rows, randomness, device=None):
     ops, opts, keep = engine._ecc_ops(w, randomness)
     rows = _host(rows)
     _expect(rows, "ecc rows", 8, (ops.n_add + ops.n_mul + ops.n_pairing, 13, 4))
-    return _verify(lib.zk_ecc_verify, rows.shape[0], ctypes.byref(ops), ptr(rows), opts)
+    return _verify(lib, lib.zk_ecc_verify, rows.shape[0], ctypes.byref(ops), ptr(rows), opts)
 
 
 def withdrawal_verify(w, randomness, device=None):
     """zk_withdrawal_verify over flatten_withdrawal_witness output -> (Result, status uint32[n]); status[j] is global row row_base + j"""
     lib = _lib.init(device)
     ww, opts, keep = engine._withdrawal_witness(w, randomness)
-    return _verify(lib.zk_withdrawal_verify, engine._withdrawal_eval_rows(w), ctypes.byref(ww), opts)
+    return _verify(lib, lib.zk_withdrawal_verify, engine._withdrawal_eval_rows(w), ctypes.byref(ww), opts)
 
 
 def withdrawal_assign(withdrawals, max_withdrawals, randomness, keccak_rows=True, device=None):
@@ -314,53 +327,24 @@ def tx_assign(tx, randomness, device=None):
     """zk_tx_assign over raw txs (engine._tx_assign_args) -> (Result, status uint32[n], wire dict: tx_rows, tx_flags, bytes, cells,
     meta, keccak — the arrays flatten_tx_witness makes)"""
     lib = _lib.init(device)
-    t, _, opts, keep = engine._tx_assign_args({k: (_host(v) if k in engine.TX_ASSIGN_INPUTS else v) for k, v in tx.items()}, randomness)
-    n = int(t.n_txs)
-    shapes = engine.tx_assign_shapes(n, int(t.max_txs), int(t.max_calldata_bytes))
-    out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items()}
-    w = _lib.ZkTxWire(*[ptr(out[k]) for k in engine.TX_ASSIGN_OUTPUTS])
-    status, r, nk = np.zeros(max(n, 1), dtype=np.uint32), ZkResult(), ctypes.c_uint64()
-    check(lib.zk_tx_assign(ctypes.byref(t), ctypes.byref(w), opts, ptr(status), ctypes.byref(nk), ctypes.byref(r)), "zk_tx_assign")
-    out["keccak"] = out["keccak"][: nk.value]
-    return Result(r), status[:n], out
+    return _wire_oneshot(engine.TX_ASSIGN, lib, engine._wire_args(engine.TX_ASSIGN, _host_inputs(engine.TX_ASSIGN, tx), (randomness,)))
 
 
 def sig_assign(sig, randomness, device=None):
     """zk_sig_assign over signed data (engine._sig_assign_args) -> (Result, status uint32[n], wire dict: bytes, cells, meta, keccak,
     sig_table, aux — the units as flatten_sig_witness makes them, the EVM circuit's sig table and its aux rows of kind 5)"""
     lib = _lib.init(device)
-    t, _, opts, keep = engine._sig_assign_args({k: (_host(v) if k in engine.SIG_ASSIGN_INPUTS else v) for k, v in sig.items()}, randomness)
-    n = int(t.n)
-    out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in engine.sig_assign_shapes(n).items()}
-    w = _lib.ZkSigWire(*[ptr(out[k]) for k in engine.SIG_ASSIGN_OUTPUTS])
-    status, r, nk, ns = np.zeros(max(n, 1), dtype=np.uint32), ZkResult(), ctypes.c_uint64(), ctypes.c_uint64()
-    check(lib.zk_sig_assign(ctypes.byref(t), ctypes.byref(w), opts, ptr(status), ctypes.byref(nk), ctypes.byref(ns), ctypes.byref(r)),
-          "zk_sig_assign", lib)
-    out["keccak"], out["sig_table"] = out["keccak"][: nk.value], out["sig_table"][: ns.value]
-    return Result(r), status[:n], out
+    return _wire_oneshot(engine.SIG_ASSIGN, lib, engine._wire_args(engine.SIG_ASSIGN, _host_inputs(engine.SIG_ASSIGN, sig), (randomness,)))
 
 
 def ecc_from_calls(calls, randomness, device=None):
     """zk_ecc_from_calls over the input words of ecAdd / ecMul / ecPairing calls (engine._ecc_calls_args) -> (Result, status uint32[n],
     wire dict: points, pair_out, rows, ecc_table (cut to its rows), aux, aux_kind)"""
     lib = _lib.init(device)
-    t, _, opts, keep, shapes = engine._ecc_calls_args({k: _host(calls[k]) for k in engine.ECC_CALLS_INPUTS}, randomness)
-    n = int(t.n_add + t.n_mul + t.n_pairing)
-    out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items()}
-    w = _lib.ZkEccCallWire(*[ptr(out[k]) for k in engine.ECC_CALLS_OUTPUTS])
-    status, r, nt = np.zeros(max(n, 1), dtype=np.uint32), ZkResult(), ctypes.c_uint64()
-    check(lib.zk_ecc_from_calls(ctypes.byref(t), ctypes.byref(w), opts, ptr(status), ctypes.byref(nt), ctypes.byref(r)), "zk_ecc_from_calls", lib)
-    out["ecc_table"] = out["ecc_table"][: nt.value]
-    return Result(r), status[:n], out
+    return _wire_oneshot(engine.ECC_CALLS, lib, engine._wire_args(engine.ECC_CALLS, _host_inputs(engine.ECC_CALLS, calls), (randomness,)))
 
 
 def pi_assign(pd, keccak_rand=255, byte_pow_base=255, device=None):
     """zk_pi_assign over raw public data (engine._pi_assign_args) -> (Result, wire dict of engine.PI_ASSIGN_OUTPUTS)"""
     lib = _lib.init(device)
-    t, _, opts, keep, shapes = engine._pi_assign_args({k: (_host(v) if k in engine.PI_ASSIGN_INPUTS else v) for k, v in pd.items()},
-                                                      keccak_rand, byte_pow_base)
-    out = {k: np.zeros(shp, dtype=dt) for k, (shp, dt) in shapes.items()}
-    w = _lib.ZkPiWire(*[ptr(out[k]) for k in engine.PI_ASSIGN_OUTPUTS])
-    r = ZkResult()
-    check(lib.zk_pi_assign(ctypes.byref(t), ctypes.byref(w), opts, ctypes.byref(r)), "zk_pi_assign", lib)
-    return Result(r), out
+    return _wire_oneshot(engine.PI_ASSIGN, lib, engine._wire_args(engine.PI_ASSIGN, _host_inputs(engine.PI_ASSIGN, pd), (int(keccak_rand), int(byte_pow_base))))
