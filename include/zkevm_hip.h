@@ -1151,6 +1151,86 @@ int zk_copy_assign_from_sources(const zk_copy_sources* in, uint64_t* rows_out, u
                                 uint64_t* rw_out, uint32_t* rw_flags_out, uint16_t* data_out, uint64_t* data_offsets_out,
                                 uint32_t opts, uint32_t* status_out, zk_result* result);
 
+/* ---- Copy and EXP events from compact trace records: the event lists zk_copy_assign_from_sources / zk_copy_assign / zk_exp_assign take,
+ *      which a producer of traces so far built in a host loop beside its trace.  Every field of those events is in the trace: they are the
+ *      arguments of the copy_lookup / exp_lookup calls of the reference's gadgets (execution/sha3.py:20, calldatacopy.py:41, codecopy.py:
+ *      26, extcodecopy.py:39, returndatacopy.py:36, log.py:65, exp.py:31), computed from the step and from the RW ops at fixed offsets
+ *      behind step.rw_counter.  With this entry a caller uploads trace records, code and block data, and every table and witness of the
+ *      block follows on the device.
+ *      Inputs (zk_trace_sources): trace - a zk_trace of which head, id, addr, val, rw_counter / rw_base, n_rw, pool, n_pool, steps and
+ *      n_steps are read (prev never is and may be NULL); the code set code, n_code_bytes, code_offsets, n_codes as in zk_copy_sources;
+ *      code_hashes uint64[n_codes][4], the 256-bit hash of each code.  The hashes and the offsets are read at open and kept by the
+ *      session (a sorted directory); of duplicate hashes the lowest index wins.
+ *      Outputs (zk_trace_events), each pointer nullable, each with capacity n_steps: copy_events uint64[n_copy][12][4], copy_flags
+ *      uint32[n_copy], copy_src_ref uint32[n_copy] - exactly the events / flags / src_ref zk_copy_sources takes (no derived event
+ *      writes a code: dst_ref is never needed); copy_step uint32[n_copy], the step that produced each copy event; exp_events
+ *      uint64[n_exp][5][4], zk_exp_events' rows; exp_step uint32[n_exp].  Both lists are packed, in step order.
+ *      Derivation.  "Op k" is the op whose counter is step.rw_counter + k (rw_counter NULL: its index is counter - rw_base; else it is
+ *      found by binary search).  A stack read j is a read with tag Stack, id == call_id and addr == stack_pointer + j; a CallContext
+ *      read is a read with tag CallContext, id == call_id and addr == the field tag (neither address a pool word).  Values are taken as
+ *      integers: val, or the pool word when the head says so.  rwc = step.rw_counter; event = (src id, tag -> dst id, tag; src_addr,
+ *      src_addr_end, dst_addr, length; log_id; rw_counter):
+ *        SHA3            ops 0 offset, 1 size: (call_id Memory -> call_id RlcAcc; offset, offset + size, 0, size; 0; rwc + 3) when size != 0;
+ *        CALLDATACOPY    ops 0 mem, 1 data, 2 len, 3 TxId (root) / CallerId, 4 CallDataLength, 5 CallDataOffset (cdo; not read and 0 in a
+ *                        root call): (v3 TxCalldata (root) / Memory -> call_id Memory; cdo + data, cdo + CallDataLength, mem, len; 0;
+ *                        rwc + 5 (root) / rwc + 6) when len != 0;
+ *        CODECOPY        ops 0 mem, 1 code offset, 2 size: (the step's code hash (a Word: flag bit 0) Bytecode -> call_id Memory; code
+ *                        offset, the length of that code, mem, size; 0; rwc + 3) when size != 0;
+ *        EXTCODECOPY     ops 1 mem, 2 code offset, 3 size, 8 the Account read of CodeHash (a read, tag Account, field_tag CodeHash): (that
+ *                        hash (a Word) Bytecode -> call_id Memory; code offset, the code's length (0 for a zero hash), mem, size; 0;
+ *                        rwc + 9) when size != 0;
+ *        RETURNDATACOPY  ops 0 mem, 2 size, 3 LastCalleeId, 5 LastCalleeReturnDataOffset (rdo): (v3 Memory -> call_id Memory; rdo, rdo +
+ *                        size, mem, size; 0; rwc + 6) always, also with size 0 (the reference looks it up unconditionally, and ignores
+ *                        the popped data offset);
+ *        LOG             ops 0 mstart, 1 msize, 2 TxId, 5 IsPersistent: (call_id Memory -> tx_id TxLog; mstart, mstart + msize, 0, msize;
+ *                        step.log_id + 1; rwc + 7 + 2 t, t = code[pc] - 0xA0 in the step's code) when msize != 0 and IsPersistent == 1;
+ *        EXP             ops 0 base, 1 exponent: (rwc + 3, base lo, hi, exponent lo, hi) when exponent > 1.
+ *      src_ref: a Bytecode source's index in the code set (0 for the zero hash, whose event reads no byte); tx_id - 1 for a TxCalldata
+ *      source; else 0.  The code set is consulted only for an event that is emitted.
+ *      Status per step (zk_launch: status_dev uint32[n_steps]; the zk_result's tally runs over the steps, rows_evaluated = n_steps): 0,
+ *      or (ZK_KIND_VALUE_ERROR << 24) | site, never a guess; a failing step emits nothing:
+ *        1  no op has a counter the step reads;     2  the op there is not the one described above (1 and 2 are checked in ascending k,
+ *           the first failure wins);
+ *        3  an integer of an emitted event is 2^62 or more (the domain of zk_copy_assign): step.rw_counter, the event's rw_counter, a
+ *           value that enters an address, a length, a log id or an integer id, or one of the sums; or the tx_id of a TxCalldata
+ *           source is 0 or above 2^32 (src_ref could not hold tx_id - 1);
+ *        4  the code hash is not in the set, pc lies outside the code, or the byte at pc is not 0xA0..0xA4 (with site 3 and site 4
+ *           both, 3 is reported; the LOG event's counter is then tested without its topics).
+ *      The states whose gadgets call copy_lookup with arguments this entry does not derive - BeginTx, RETURN, CREATE, CREATE2, CALL_OP and
+ *      DATACOPY (begin_tx.py, return_revert.py, create.py, callop.py, dataCopy.py) - get (ZK_KIND_UNSUPPORTED << 24) | 1 and emit
+ *      nothing: a caller then knows to supply those events itself.  They count in fail_count.  Every other state has status 0.
+ *      zk_events_from_trace_sizes: the checks below, and the capacity every output needs (n_steps).  _open: with ZK_OPT_DEVICE_PTRS
+ *      every input is a device pointer and the non-null pointers of `out_dev` receive the outputs in place (null: the session owns that
+ *      buffer); without the flag out_dev must be NULL.  The session keeps its own copy of the heads, the counters, the pool offsets,
+ *      the code offsets and the hash directory; id, addr, val, the pool, the steps and the code bytes stay the caller's and are read
+ *      by every pass.  zk_launch (with status_dev) / zk_collect / zk_read_status / zk_session_set_stream / zk_close as on the other
+ *      assignment sessions; every launch runs the whole chain (the steps, a scan of the per-block counts, the packed stores): nothing
+ *      is carried from one pass to the next.  _counts returns n_copy and n_exp of the last pass; _read copies the outputs to the
+ *      non-null HOST pointers of `host` and returns the counts.  The one-shot's status_out is a device pointer with
+ *      ZK_OPT_DEVICE_PTRS, like its other outputs.
+ *      Domain, rejected at sizes / open with an error code and its text in zk_last_error:
+ *        ZK_ERR_TRC_HEAD / _ORDER / _POOL / _ROWS exactly as zk_evm_witness_from_trace_open reports them (on the device, with one
+ *        verdict block read back), under this entry's name;
+ *        ZK_ERR_TEV_OFFSETS  code offsets that do not start at 0, that decrease, or whose last value differs from n_code_bytes;
+ *        ZK_ERR_TEV_ROWS     2^31 or more steps, code bytes or codes. */
+#define ZK_ERR_TEV_OFFSETS (-100)
+#define ZK_ERR_TEV_ROWS (-101)
+typedef struct zk_trace_sources {
+    zk_trace trace;
+    const uint8_t* code;        uint64_t n_code_bytes;       const uint64_t* code_offsets;  uint64_t n_codes;
+    const uint64_t* code_hashes;                             /* uint64[n_codes][4] */
+} zk_trace_sources;
+typedef struct zk_trace_events {                             /* each pointer nullable; capacity n_steps each */
+    uint64_t* copy_events;      uint32_t* copy_flags;        uint32_t* copy_src_ref;        uint32_t* copy_step;
+    uint64_t* exp_events;       uint32_t* exp_step;
+} zk_trace_events;
+int zk_events_from_trace_sizes(const zk_trace_sources* in, uint32_t opts, uint64_t* capacity);
+int zk_events_from_trace_open(const zk_trace_sources* in, const zk_trace_events* out_dev, uint32_t opts, zk_session** out);
+int zk_events_from_trace_read(zk_session* s, const zk_trace_events* host, uint64_t* n_copy, uint64_t* n_exp);
+int zk_events_from_trace_counts(zk_session* s, uint64_t* n_copy, uint64_t* n_exp);
+int zk_events_from_trace(const zk_trace_sources* in, const zk_trace_events* out, uint32_t opts, uint32_t* status_out, uint64_t* n_copy,
+                         uint64_t* n_exp, zk_result* result);
+
 #ifdef __cplusplus
 }
 #endif

@@ -35,6 +35,7 @@ EXPORTED_SYMBOLS = [
     "zk_state_verify_from_trace_open", "zk_state_verify_from_trace", "zk_state_ops_from_trace_open", "zk_state_ops_from_trace_read", "zk_state_ops_from_trace",
     "zk_state_assign_from_trace_open", "zk_state_assign_from_trace",
     "zk_copy_assign_from_sources_sizes", "zk_copy_assign_from_sources_open", "zk_copy_assign_from_sources_read", "zk_copy_assign_from_sources",
+    "zk_events_from_trace_sizes", "zk_events_from_trace_open", "zk_events_from_trace_read", "zk_events_from_trace_counts", "zk_events_from_trace",
 ]
 
 OPT_DEVICE_PTRS = 1
@@ -157,6 +158,16 @@ class ZkCopySources(ctypes.Structure):
                 ("trace", ZkTrace)]
 
 
+class ZkTraceSources(ctypes.Structure):
+    """zk_trace_sources (include/zkevm_hip.h): trace records, a code set and the codes' hashes"""
+    _fields_ = [("trace", ZkTrace), ("code", ctypes.c_void_p), ("n_code_bytes", ctypes.c_uint64), ("code_offsets", ctypes.c_void_p),
+                ("n_codes", ctypes.c_uint64), ("code_hashes", ctypes.c_void_p)]
+
+
+class ZkTraceEvents(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("copy_events", "copy_flags", "copy_src_ref", "copy_step", "exp_events", "exp_step")]
+
+
 class ZkTraceWitness(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("rw", "rw_flags", "steps")]
 
@@ -207,6 +218,7 @@ ERR_BTB_ID, ERR_BTB_OFFSETS, ERR_BTB_HISTORY, ERR_BTB_ROWS = -60, -61, -62, -63 
 ERR_TRC_HEAD, ERR_TRC_ORDER, ERR_TRC_POOL, ERR_TRC_ROWS = -70, -71, -72, -73  # ZK_ERR_TRC_*: why zk_evm_witness_from_trace* rejected its records
 ERR_ECL_OFFSETS, ERR_ECL_ROWS, ERR_ECL_RANDOMNESS = -80, -81, -82  # ZK_ERR_ECL_*: why zk_ecc_from_calls* rejected its calls
 ERR_CPS_OFFSETS, ERR_CPS_ROWS = -90, -91  # ZK_ERR_CPS_*: why zk_copy_assign_from_sources* rejected its sources
+ERR_TEV_OFFSETS, ERR_TEV_ROWS = -100, -101  # ZK_ERR_TEV_*: why zk_events_from_trace* rejected its code set or its counts
 
 
 class ZkBlock(ctypes.Structure):
@@ -384,6 +396,12 @@ def _bind(lib):
     lib.zk_copy_assign_from_sources_open.argtypes = [ctypes.POINTER(ZkCopySources), vp, vp, vp, vp, vp, vp, u32, ctypes.POINTER(vp)]
     lib.zk_copy_assign_from_sources_read.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     lib.zk_copy_assign_from_sources.argtypes = [ctypes.POINTER(ZkCopySources), vp, vp, vp, vp, vp, vp, vp, u32, vp, ctypes.POINTER(ZkResult)]
+    lib.zk_events_from_trace_sizes.argtypes = [ctypes.POINTER(ZkTraceSources), u32, ctypes.POINTER(u64)]
+    lib.zk_events_from_trace_open.argtypes = [ctypes.POINTER(ZkTraceSources), ctypes.POINTER(ZkTraceEvents), u32, ctypes.POINTER(vp)]
+    lib.zk_events_from_trace_read.argtypes = [vp, ctypes.POINTER(ZkTraceEvents), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_events_from_trace_counts.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_events_from_trace.argtypes = [ctypes.POINTER(ZkTraceSources), ctypes.POINTER(ZkTraceEvents), u32, vp, ctypes.POINTER(u64),
+                                         ctypes.POINTER(u64), ctypes.POINTER(ZkResult)]
     lib.zk_launch.argtypes = [vp, vp]
     lib.zk_collect.argtypes = [vp, ctypes.POINTER(ZkResult)]
     lib.zk_read_status.argtypes = [vp, vp]

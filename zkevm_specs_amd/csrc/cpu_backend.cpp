@@ -47,6 +47,7 @@ static thread_local std::string g_err;
 #define ARG_TRY(cond, msg) do { if (!(cond)) { g_err = msg; return -1; } } while (0)
 #include "copy_assign_plan.hpp"  // (uses ARG_TRY)
 #include "copy_sources_plan.hpp"
+#include "trace_events_plan.hpp"
 
 extern "C" const char* zk_last_error(void) { return g_err.c_str(); }
 extern "C" int zk_init(int) { return 0; }
@@ -106,7 +107,7 @@ struct zk_session {
     std::vector<u64> w64[4];              // assignment sessions: work / output buffers
     std::vector<u32> out32;
     void (*pass)(zk_session*) = nullptr;  // assignment sessions: one pass computes the outputs and fills `status`
-    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code, 11 tables from block, 12 witness from trace, 13 ECC precompile calls, 14 copy from sources
+    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code, 11 tables from block, 12 witness from trace, 13 ECC precompile calls, 14 copy from sources, 15 events from trace
     u64 n_ops = 0;                        // RW -> State ops: 1 + kept rows
     std::vector<u32> rekey_plan;          // RW -> State ops: the RwkHostPlan's plan (as words) ...
     std::vector<u32> rekey_jobs;          // ... and its rank jobs (cls, field, base, count)
@@ -142,6 +143,10 @@ struct zk_session {
     CpsPlan cps_plan;
     std::vector<u64> cps64[4];      // is_code mask, counters, code offsets, per-event failing byte
     std::vector<u32> cps32[1];      // heads
+    TevArgs tev;                    // Copy and EXP events from compact trace records
+    TevPlan tev_plan;               // ... the sorted hash directory
+    std::vector<u64> tev64[6];      // counters, pool offsets, code offsets, copy events, EXP events, counts
+    std::vector<u32> tev32[5];      // heads, copy flags, copy refs, copy steps, EXP steps
     EcdsaArgs ecdsa;
     KeccakGenArgs kgen;
     TxAssignArgs txa;
@@ -1696,6 +1701,105 @@ extern "C" int zk_copy_assign_from_sources(const zk_copy_sources* t, uint64_t* r
     if (!rc) rc = zk_collect(s, result);
     if (!rc && status_out) rc = zk_read_status(s, status_out);
     if (!rc) rc = zk_copy_assign_from_sources_read(s, rows_out, row_flags_out, table_out, rw_out, rw_flags_out, data_out, data_offsets_out);
+    zk_close(s);
+    return rc;
+}
+
+// ---- Copy and EXP events from compact trace records (trace_events.hpp): the per-step function in a host loop.  The session keeps its own
+//      heads, counters, pool offsets, code offsets and hash directory; id / addr / val / pool / steps / code stay the caller's arrays and
+//      every pass reads them.
+static void events_from_trace_pass(zk_session* s) { tev_pass_host(s->tev, s->status.data()); }
+#define TEV_ARGS_OK(t) ((t) && ((t)->trace.n_rw == 0 || ((t)->trace.head && (t)->trace.id && (t)->trace.addr && (t)->trace.val)) &&                        \
+                        ((t)->trace.n_pool == 0 || (t)->trace.pool) && ((t)->trace.n_steps == 0 || (t)->trace.steps) &&                                      \
+                        ((t)->n_codes == 0 || ((t)->code_offsets && (t)->code_hashes)) && ((t)->n_code_bytes == 0 || (t)->code))
+// the domain checks; head / ctr / off (nullable) receive the session's copies
+static int tev_prepare(const zk_trace_sources* t, u32* head, u64* ctr, u64* off) {
+    const char* const name = "zk_events_from_trace";
+    const zk_trace& tr = t->trace;
+    char msg[256];
+    int rc = tev_counts_check(tr.n_steps, t->n_code_bytes, t->n_codes);  // (before any array is read)
+    if (rc) return rc;
+    if ((rc = trw_plan_counts(tr.n_rw, tr.n_steps, tr.rw_base, tr.rw_counter != nullptr, msg, sizeof msg))) { g_err = msg; cps_retitle(name); return rc; }
+    if ((rc = tev_offsets_check(t->code_offsets, t->n_codes, t->n_code_bytes))) return rc;
+    u64 v[TRW_V_WORDS];
+    trw_check_host(tr.head, tr.rw_counter, tr.n_rw, tr.steps, tr.n_steps, head, ctr, off, v);
+    if ((rc = trw_verdict_error(v, tr.n_pool, msg, sizeof msg))) { g_err = msg; cps_retitle(name); }
+    return rc;
+}
+extern "C" int zk_events_from_trace_sizes(const zk_trace_sources* t, uint32_t opts, uint64_t* capacity) {
+    NO_DEVICE_PTRS(opts, "zk_events_from_trace_sizes");
+    ARG_TRY(TEV_ARGS_OK(t), "zk_events_from_trace_sizes: bad arguments");
+    const int rc = tev_prepare(t, nullptr, nullptr, nullptr);
+    if (rc) return rc;
+    if (capacity) *capacity = t->trace.n_steps;
+    return 0;
+}
+extern "C" int zk_events_from_trace_open(const zk_trace_sources* t, const zk_trace_events* out_dev, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_events_from_trace_open");
+    ARG_TRY(TEV_ARGS_OK(t) && out, "zk_events_from_trace_open: bad arguments");
+    ARG_TRY(!out_dev, "zk_events_from_trace_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    const zk_trace& tr = t->trace;
+    int rc = tev_counts_check(tr.n_steps, t->n_code_bytes, t->n_codes);  // (before anything is allocated)
+    if (rc) return rc;
+    char msg[256];
+    if ((rc = trw_plan_counts(tr.n_rw, tr.n_steps, tr.rw_base, tr.rw_counter != nullptr, msg, sizeof msg))) { g_err = msg; cps_retitle("zk_events_from_trace"); return rc; }
+    const u64 n = tr.n_rw, ns = tr.n_steps, nc = t->n_codes;
+    zk_session* s = new_session(ns, false);
+    s->tev32[0].assign(n + 1, 0);                        // heads
+    s->tev64[0].assign(tr.rw_counter ? n + 1 : 0, 0);    // counters
+    s->tev64[1].assign(n + 1, 0);                        // pool offsets
+    if ((rc = tev_prepare(t, s->tev32[0].data(), tr.rw_counter ? s->tev64[0].data() : nullptr, s->tev64[1].data()))) { delete s; return rc; }
+    s->tev64[2].assign(t->code_offsets, t->code_offsets + (nc ? nc + 1 : 0));  // the session's copy of the code offsets
+    s->tev64[2].push_back(0);
+    tev_dir_build(t->code_hashes, nc, s->tev_plan);
+    s->tev64[3].assign(ns * TEV_COPY_NCELLS * 4 + 4, 0);  // copy events
+    s->tev64[4].assign(ns * TEV_EXP_NCELLS * 4 + 4, 0);   // EXP events
+    s->tev64[5].assign(2, 0);                             // counts
+    for (int k = 1; k < 5; k++) s->tev32[k].assign(ns + 1, 0);  // copy flags, refs, steps; EXP steps
+    TevArgs& a = s->tev;
+    memset(&a, 0, sizeof(a));
+    a.head = s->tev32[0].data(); a.ctr = tr.rw_counter ? s->tev64[0].data() : nullptr; a.off = s->tev64[1].data();
+    a.id = tr.id; a.addr = tr.addr; a.val = tr.val; a.pool = tr.pool; a.steps = tr.steps;
+    a.n_rw = n; a.n_pool = tr.n_pool; a.n_steps = ns; a.rw_base = tr.rw_base;
+    a.code = t->code; a.code_off = s->tev64[2].data(); a.dir_hash = s->tev_plan.dir_hash.data(); a.dir_idx = s->tev_plan.dir_idx.data(); a.n_codes = (u32)nc;
+    a.counts = s->tev64[5].data();
+    a.copy_events = s->tev64[3].data(); a.copy_flags = s->tev32[1].data(); a.copy_src_ref = s->tev32[2].data(); a.copy_step = s->tev32[3].data();
+    a.exp_events = s->tev64[4].data(); a.exp_step = s->tev32[4].data();
+    s->pass = events_from_trace_pass;
+    s->assign_kind = 15;
+    *out = s;
+    return 0;
+}
+extern "C" int zk_events_from_trace_read(zk_session* s, const zk_trace_events* host, uint64_t* n_copy, uint64_t* n_exp) {
+    ARG_TRY(s && s->assign_kind == 15, "zk_events_from_trace_read: bad arguments");
+    const TevArgs& a = s->tev;
+    const u64 nc = a.counts[0], ne = a.counts[1];
+    if (host) {
+        if (host->copy_events && nc) memcpy(host->copy_events, a.copy_events, nc * TEV_COPY_NCELLS * 32);
+        if (host->copy_flags && nc) memcpy(host->copy_flags, a.copy_flags, nc * 4);
+        if (host->copy_src_ref && nc) memcpy(host->copy_src_ref, a.copy_src_ref, nc * 4);
+        if (host->copy_step && nc) memcpy(host->copy_step, a.copy_step, nc * 4);
+        if (host->exp_events && ne) memcpy(host->exp_events, a.exp_events, ne * TEV_EXP_NCELLS * 32);
+        if (host->exp_step && ne) memcpy(host->exp_step, a.exp_step, ne * 4);
+    }
+    if (n_copy) *n_copy = nc;
+    if (n_exp) *n_exp = ne;
+    return 0;
+}
+extern "C" int zk_events_from_trace_counts(zk_session* s, uint64_t* n_copy, uint64_t* n_exp) {
+    ARG_TRY(s && s->assign_kind == 15, "zk_events_from_trace_counts: bad arguments");
+    return zk_events_from_trace_read(s, nullptr, n_copy, n_exp);
+}
+extern "C" int zk_events_from_trace(const zk_trace_sources* t, const zk_trace_events* out_wire, uint32_t opts, uint32_t* status_out,
+                                    uint64_t* n_copy, uint64_t* n_exp, zk_result* result) {
+    ARG_TRY(result && out_wire && t, "zk_events_from_trace: null argument");
+    zk_session* s = nullptr;
+    int rc = zk_events_from_trace_open(t, nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && status_out) rc = zk_read_status(s, status_out);
+    if (!rc) rc = zk_events_from_trace_read(s, out_wire, n_copy, n_exp);
     zk_close(s);
     return rc;
 }

@@ -19,6 +19,7 @@
 #include "state_trace.hpp"
 #include "copy_assign.hpp"
 #include "copy_sources.hpp"
+#include "trace_events.hpp"
 #include "pi_circuit.hpp"
 #include "state_rekey.hpp"
 #include "ecc_circuit.hpp"
@@ -113,6 +114,9 @@ void zk_launch_copy_assign(hipStream_t st, const CpaArgs& a, u32* status, ZkTall
 // The Copy assignment's source data from code, calldata and trace records (k_copy_sources.hip): the is_code scan of the code set (c.n_segs
 // > 0), the gather into a.data, the status per event and its tally; zk_launch_copy_assign over a.data follows in stream order
 void zk_launch_copy_sources(hipStream_t st, const CpsArgs& a, const CpsCodeArgs& c, u32* status, ZkTally* tally);
+// Copy and EXP events from compact trace records (k_trace_events.hip): a status per step and its tally, what each step emits, a scan of the
+// per-block counts into a.blk / a.counts, the packed ordered stores
+void zk_launch_trace_events(hipStream_t st, const TevArgs& a, u32* status, ZkTally* tally);
 void zk_launch_ecdsa(hipStream_t st, const EcdsaArgs& a, u32* status, ZkTally* tally);
 void zk_launch_ecdsa_comb_build(hipStream_t st, u32* table);  // the device's 8-bit fixed-base table of G (522 KB), built once
 // ECC circuit (k_ecc.hip): assign = circuit2rows into a.rows_out, else verify a.rows (status / tally)

@@ -606,7 +606,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_CPS = 26, SESSION_ECL = 25, SESSION_TRW = 24, SESSION_BTB = 23, SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_TEV = 27, SESSION_CPS = 26, SESSION_ECL = 25, SESSION_TRW = 24, SESSION_BTB = 23, SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -671,6 +671,7 @@ struct zk_session {
     CpsArgs cps;                    // SESSION_CPS (zk_copy_assign_from_sources*): the gather in front of the Copy assignment in `cpa`
     CpsCodeArgs cps_code;           // ... its is_code scan (n_segs = 0: no event has a Bytecode side)
     std::vector<u64> cps_data0;     // ... the gathered array's offsets (host copy: zk_copy_assign_from_sources_read hands them out)
+    TevArgs tev;                    // SESSION_TEV (zk_events_from_trace*): the open's checks and the session's heads / counters / pool offsets sit in `trw`
     u32* d_hist = nullptr;   // EVM: (group, state) bins (histogram -> cursors)
     u32* d_cursor = nullptr; // EVM: per-bin scatter cursors (cleared by every histogram pass)
     u32* d_hist2 = nullptr;  // EVM: the other histogram buffer (the two alternate between passes)
@@ -2342,6 +2343,130 @@ extern "C" int zk_copy_assign_from_sources(const zk_copy_sources* t, uint64_t* r
                : zk_copy_assign_from_sources_read(s, rows_out, row_flags_out, table_out, rw_out, rw_flags_out, data_out, data_offsets_out);
 }
 
+// ---- Copy and EXP events from compact trace records (trace_events.hpp, k_trace_events.hip)
+#include "trace_events_plan.hpp"
+#define TEV_ARGS_OK(t) ((t) && ((t)->trace.n_rw == 0 || ((t)->trace.head && (t)->trace.id && (t)->trace.addr && (t)->trace.val)) &&                        \
+                        ((t)->trace.n_pool == 0 || (t)->trace.pool) && ((t)->trace.n_steps == 0 || (t)->trace.steps) &&                                      \
+                        ((t)->n_codes == 0 || ((t)->code_offsets && (t)->code_hashes)) && ((t)->n_code_bytes == 0 || (t)->code))
+// Open a session over the records and the code set: the counts and the code offsets checked on the host, the trace's heads, counters and
+// step words on the device (one verdict block read back, as zk_evm_witness_from_trace_open), the hash directory sorted on the host.
+// check_only: the checks alone (the _sizes entry: the session is closed again).
+static int tev_open(const zk_trace_sources* t, const zk_trace_events* out_dev, uint32_t opts, bool check_only, zk_session** out) {
+    const char* const name = "zk_events_from_trace";
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    const zk_trace& tr = t->trace;
+    char msg[256];
+    RC_TRY(tev_counts_check(tr.n_steps, t->n_code_bytes, t->n_codes));  // (before anything is read)
+    if (int rc = trw_plan_counts(tr.n_rw, tr.n_steps, tr.rw_base, tr.rw_counter != nullptr, msg, sizeof msg)) { g_err = msg; cps_retitle(name); return rc; }
+    std::vector<u64> k_off, k_hash;
+    TevPlan pl;
+    const u64 *code_off, *hashes;
+    RC_TRY(cps_host_view(t->code_offsets, t->n_codes ? (size_t)t->n_codes + 1 : 0, dev, k_off, &code_off));
+    RC_TRY(tev_offsets_check(code_off, t->n_codes, t->n_code_bytes));
+    const u64 n = tr.n_rw, ns = tr.n_steps, nc = t->n_codes;
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
+    s->kind = SESSION_TEV;
+    s->n = ns;
+    TrwArgs& w = s->trw;
+    TevArgs& a = s->tev;
+    memset(&w, 0, sizeof(w));
+    memset(&a, 0, sizeof(a));
+    // the trace's heads, counters and step words: checked as zk_evm_witness_from_trace_open checks them; the session keeps its own heads,
+    // counters and pool offsets (a caller that rewrites a head cannot move a load)
+    RC_TRY(stage_in(s, w.head_in, tr.head, (size_t)n * 4, dev));
+    if (tr.rw_counter && n) RC_TRY(stage_in(s, w.ctr_in, tr.rw_counter, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, w.steps_in, tr.steps, (size_t)ns * TRW_STEP_WORDS * 8, dev));
+    w.n_rw = n; w.n_pool = tr.n_pool; w.n_steps = ns; w.rw_base = tr.rw_base;
+    RC_TRY(dev_buf(s, w.head, (size_t)n * 4 + 4));
+    if (w.ctr_in) RC_TRY(dev_buf(s, w.ctr, (size_t)n * 8));
+    RC_TRY(dev_buf(s, w.off, (size_t)n * 8 + 8));
+    RC_TRY(dev_buf(s, w.verdict, TRW_V_WORDS * 8));
+    zk_launch_trace_witness_check(s->stream, w);
+    DEV_TRY(hipGetLastError() == hipSuccess, "zk_events_from_trace: the open's check launch failed");
+    u64 v[TRW_V_WORDS];
+    RC_TRY(d2h_now(s->stream, v, w.verdict, sizeof v));
+    if (int rc = trw_verdict_error(v, tr.n_pool, msg, sizeof msg)) { g_err = msg; cps_retitle(name); return rc; }
+    if (check_only) return 0;
+    RC_TRY(cps_host_view(t->code_hashes, (size_t)nc * 4, dev, k_hash, &hashes));
+    tev_dir_build(hashes, nc, pl);
+    a.head = w.head; a.ctr = w.ctr; a.off = w.off; a.steps = w.steps_in;
+    a.n_rw = n; a.n_pool = tr.n_pool; a.n_steps = ns; a.rw_base = tr.rw_base; a.n_codes = (u32)nc;
+    RC_TRY(stage_in(s, a.id, tr.id, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, a.addr, tr.addr, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, a.val, tr.val, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, a.pool, tr.pool, (size_t)tr.n_pool * 32, dev));
+    RC_TRY(stage_in(s, a.code, t->code, (size_t)t->n_code_bytes, dev));
+    RC_TRY(stage_in(s, a.code_off, nc ? code_off : nullptr, nc ? ((size_t)nc + 1) * 8 : 0, false));
+    RC_TRY(stage_in(s, a.dir_hash, pl.dir_hash.data(), pl.dir_hash.size() * 8, false));
+    RC_TRY(stage_in(s, a.dir_idx, pl.dir_idx.data(), pl.dir_idx.size() * 4, false));
+    // the plan vectors and the host views go out of scope with this call
+    DEV_TRY(hipStreamSynchronize(s->stream) == hipSuccess, "zk_events_from_trace_open: upload failed");
+    const size_t n_blocks = (size_t)((ns + 255) / 256);
+    RC_TRY(dev_buf(s, a.kind, (size_t)ns));
+    RC_TRY(dev_buf(s, a.blk, n_blocks * 8));
+    RC_TRY(dev_buf(s, a.counts, 16));
+    HIP_TRY(hipMemsetAsync(a.counts, 0, 16, s->stream));  // (no pass yet: no event)
+    const zk_trace_events o = wire_or_nulls(out_dev);
+    RC_TRY(out_buf(s, a.copy_events, o.copy_events, (size_t)ns * TEV_COPY_NCELLS * 32));
+    RC_TRY(out_buf(s, a.copy_flags, o.copy_flags, (size_t)ns * 4));
+    RC_TRY(out_buf(s, a.copy_src_ref, o.copy_src_ref, (size_t)ns * 4));
+    RC_TRY(out_buf(s, a.copy_step, o.copy_step, (size_t)ns * 4));
+    RC_TRY(out_buf(s, a.exp_events, o.exp_events, (size_t)ns * TEV_EXP_NCELLS * 32));
+    RC_TRY(out_buf(s, a.exp_step, o.exp_step, (size_t)ns * 4));
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
+    return 0;
+}
+extern "C" int zk_events_from_trace_sizes(const zk_trace_sources* t, uint32_t opts, uint64_t* capacity) {
+    ARG_TRY(t_device >= 0, "zk_events_from_trace_sizes: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(TEV_ARGS_OK(t), "zk_events_from_trace_sizes: bad arguments");
+    RC_TRY(tev_open(t, nullptr, opts, true, nullptr));
+    if (capacity) *capacity = t->trace.n_steps;
+    return 0;
+}
+extern "C" int zk_events_from_trace_open(const zk_trace_sources* t, const zk_trace_events* out_dev, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_events_from_trace_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(TEV_ARGS_OK(t) && out, "zk_events_from_trace_open: bad arguments");
+    ARG_TRY((opts & ZK_OPT_DEVICE_PTRS) || !out_dev, "zk_events_from_trace_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    return tev_open(t, out_dev, opts, false, out);
+}
+extern "C" int zk_events_from_trace_read(zk_session* s, const zk_trace_events* host, uint64_t* n_copy, uint64_t* n_exp) {
+    ARG_TRY(s && s->kind == SESSION_TEV, "zk_events_from_trace_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    const TevArgs& a = s->tev;
+    u64 c[2];
+    RC_TRY(d2h_now(s->stream, c, a.counts, sizeof c));  // (the counts of the last pass size the copies)
+    if (host) {
+        RC_TRY(d2h_out(s, host->copy_events, a.copy_events, (size_t)c[0] * TEV_COPY_NCELLS * 32));
+        RC_TRY(d2h_out(s, host->copy_flags, a.copy_flags, (size_t)c[0] * 4));
+        RC_TRY(d2h_out(s, host->copy_src_ref, a.copy_src_ref, (size_t)c[0] * 4));
+        RC_TRY(d2h_out(s, host->copy_step, a.copy_step, (size_t)c[0] * 4));
+        RC_TRY(d2h_out(s, host->exp_events, a.exp_events, (size_t)c[1] * TEV_EXP_NCELLS * 32));
+        RC_TRY(d2h_out(s, host->exp_step, a.exp_step, (size_t)c[1] * 4));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    if (n_copy) *n_copy = c[0];
+    if (n_exp) *n_exp = c[1];
+    return 0;
+}
+extern "C" int zk_events_from_trace_counts(zk_session* s, uint64_t* n_copy, uint64_t* n_exp) {
+    ARG_TRY(s && s->kind == SESSION_TEV, "zk_events_from_trace_counts: bad arguments");
+    return zk_events_from_trace_read(s, nullptr, n_copy, n_exp);
+}
+extern "C" int zk_events_from_trace(const zk_trace_sources* t, const zk_trace_events* out_wire, uint32_t opts, uint32_t* status_out,
+                                    uint64_t* n_copy, uint64_t* n_exp, zk_result* result) {
+    ARG_TRY(result && out_wire && t, "zk_events_from_trace: null argument");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    RC_TRY(zk_events_from_trace_open(t, dev ? out_wire : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, status_out, result));
+    return zk_events_from_trace_read(s, dev ? nullptr : out_wire, n_copy, n_exp);
+}
+
 // ---- Exp-circuit witness assignment
 // The size pass of an open: events staged, counts / first rows / reject word computed on the session's stream and the two words
 // read back (the one wait of the open).  `s` owns the buffers; on a rejected event the error code is returned with its text.
@@ -2935,6 +3060,7 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     }
     case SESSION_BTB: zk_launch_block_tables(s->stream, s->btb, status); break;
     case SESSION_TRW: zk_launch_trace_witness(s->stream, s->trw, status); break;
+    case SESSION_TEV: zk_launch_trace_events(s->stream, s->tev, status, s->d_tally); break;
     case SESSION_ECL: zk_launch_ecc_calls(s->stream, s->ecl, s->ecl_n_pairs, status); break;
     case SESSION_REKEY:
         if (s->from_trace) zk_launch_state_trace_rekey(s->stream, s->rekey, s->strc, status, s->d_tally);

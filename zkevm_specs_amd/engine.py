@@ -1460,6 +1460,100 @@ def open_evm_witness_from_trace(trace, outs=None, device=None):
     return _wire_open(TRACE, device, trace, (), outs)
 
 
+# ---- Copy and EXP events from compact trace records (zk_events_from_trace*) ---------------------------------------------------------
+TRACE_EVENTS_INPUTS = ("head", "id", "addr", "val", "rw_counter", "pool", "steps", "code", "code_offsets", "code_hashes")
+TRACE_EVENTS_OUTPUTS = ("copy_events", "copy_flags", "copy_src_ref", "copy_step", "exp_events", "exp_step")
+
+
+def events_from_trace_shapes(n_steps):
+    """name -> (shape, dtype) of the outputs of zk_events_from_trace*: each has the capacity n_steps (include/zkevm_hip.h)"""
+    n = int(n_steps)
+    return {"copy_events": ((n, 12, 4), np.uint64), "copy_flags": ((n,), np.uint32), "copy_src_ref": ((n,), np.uint32),
+            "copy_step": ((n,), np.uint32), "exp_events": ((n, 5, 4), np.uint64), "exp_step": ((n,), np.uint32)}
+
+
+def trace_event_sources(trace, codes, code_hashes):
+    """The input dict of the family: the records of `trace` (trace.py; prev is not read) with the code set.  codes: a list of byte
+    strings, or dict(code uint8[b], code_offsets uint64[n + 1]) of arrays or CUDA tensors; code_hashes: a list of ints, or uint64[n, 4]."""
+    x = {k: trace.get(k) for k in TRACE_EVENTS_INPUTS[:7]}
+    x["rw_base"] = trace.get("rw_base", 1)
+    if isinstance(codes, dict):
+        x["code"], x["code_offsets"] = codes.get("code"), codes.get("code_offsets")
+    else:
+        codes = [bytes(c) for c in codes]
+        x["code"] = np.frombuffer(b"".join(codes), dtype=np.uint8).copy()
+        x["code_offsets"] = np.cumsum([0] + [len(c) for c in codes]).astype(np.uint64)
+    if isinstance(code_hashes, (list, tuple)):
+        code_hashes = np.frombuffer(b"".join(int(h).to_bytes(32, "little") for h in code_hashes), dtype="<u8").astype(np.uint64).reshape(-1, 4)
+    x["code_hashes"] = code_hashes
+    return x
+
+
+def _trace_events_check(x):
+    n = _rows(x.get("head"))
+    _expect(x.get("head"), "head", 4, (None,))
+    for name in ("id", "addr", "val", "rw_counter"):
+        _expect(x.get(name), name, 8, (n,))
+        if n and name != "rw_counter" and x.get(name) is None:
+            raise ValueError(f"{name}: missing")
+    _expect(x.get("pool"), "pool", 8, (None, 4))
+    _expect(x.get("steps"), "steps", 8, (None, 13))
+    nc = _rows(x.get("code_hashes"))
+    _expect(x.get("code"), "code", 1, (None,))
+    _expect(x.get("code_hashes"), "code_hashes", 8, (None, 4))
+    _expect(x.get("code_offsets"), "code_offsets", 8, (None,))
+    if nc and _rows(x.get("code_offsets")) != nc + 1:
+        raise ValueError(f"code_offsets: expected {nc + 1} entries for {nc} code hashes, got {_rows(x.get('code_offsets'))}")
+    ns = _rows(x.get("steps"))
+    return ns, events_from_trace_shapes(ns)
+
+
+def _trace_events_fill(x, a, cells):
+    n, m, k, nb, nc = _rows(a[0]), _rows(a[5]), _rows(a[6]), _rows(a[7]), _rows(a[9])
+    t = _lib.ZkTrace(ptr(a[0], n), ptr(a[1], n), ptr(a[2], n), ptr(a[3], n), None, ptr(a[4], n), int(x.get("rw_base", 1)), n, ptr(a[5], m), m,
+                     ptr(a[6], k), k)
+    return _lib.ZkTraceSources(t, ptr(a[7], nb), nb, ptr(a[8], nc), nc, ptr(a[9], nc))
+
+
+TRACE_EVENTS = WireFamily("zk_events_from_trace", TRACE_EVENTS_INPUTS, TRACE_EVENTS_OUTPUTS, _lib.ZkTraceEvents, _trace_events_check,
+                          _trace_events_fill, cut=("copy_events", "exp_events"), status=True, null_empty=True, n_sizes=1)
+
+
+def cut_trace_events(out, n_copy, n_exp):
+    """the outputs of the family cut to the pass's counts: the copy_* arrays to n_copy, the exp_* arrays to n_exp"""
+    return {k: (v if v is None else v[: n_copy if k.startswith("copy") else n_exp]) for k, v in out.items()}
+
+
+def events_from_trace_sizes(trace, codes, code_hashes, device=None, _prepared=None):
+    """the capacity every output of zk_events_from_trace* needs (n_steps); raises EngineError (rc = _lib.ERR_TRC_* / ERR_TEV_*) for
+    inputs outside the domain"""
+    lib = _lib.init(device)
+    return _wire_sizes(TRACE_EVENTS, lib, _prepared or _wire_args(TRACE_EVENTS, trace_event_sources(trace, codes, code_hashes)))[0]
+
+
+class EventsFromTraceSession(WireSession):
+    """zk_events_from_trace_open: a status per step; counts() -> (n_copy, n_exp) of the last pass; read(names=None) -> dict of the
+    outputs cut to those counts (copy_events / copy_flags / copy_src_ref: what open_copy_assign_from_sources takes; exp_events: what
+    open_exp_assign takes; copy_step / exp_step: the step of each event)"""
+
+    def counts(self):
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._lib.zk_events_from_trace_counts(self._h, ctypes.byref(a), ctypes.byref(b)), "zk_events_from_trace_counts", self._lib)
+        return int(a.value), int(b.value)
+
+    def read(self, names=None):
+        out, w = _wire_host_outputs(self.family, self.shapes, names)
+        return cut_trace_events(out, *self._read(w))
+
+
+def open_events_from_trace(trace, codes, code_hashes, outs=None, device=None):
+    """The copy and EXP events of the steps of compact trace records `trace` (see trace_event_sources) -> EventsFromTraceSession over the
+    steps.  numpy inputs are staged to HBM (the CPU backend reads id / addr / val / pool / steps / code in place, every pass); torch CUDA
+    tensors are used in place, and the CUDA tensors of `outs` (TRACE_EVENTS_OUTPUTS, shapes of events_from_trace_shapes: capacity
+    n_steps each) then receive the packed lists in place."""
+    return _wire_open(TRACE_EVENTS, device, trace_event_sources(trace, codes, code_hashes), (), outs, cls=EventsFromTraceSession)
+
+
 # ---- State circuit from compact trace records (zk_state_verify_from_trace* / zk_state_ops_from_trace* / zk_state_assign_from_trace*) ---------------------------------
 def _state_from_trace_args(trace, outs=()):
     """The RW half of `trace` (see _evm_witness_from_trace_args; prev and steps are not read and may be missing) -> (ZkTrace, opts, kept

@@ -172,6 +172,18 @@ def evm_witness_from_trace(trace, device=None):
     return _wire_oneshot(engine.TRACE, lib, engine._wire_args(engine.TRACE, rec))
 
 
+def events_from_trace(trace, codes, code_hashes, device=None):
+    """zk_events_from_trace over trace records of host arrays, the code set `codes` and its hashes (engine.trace_event_sources) ->
+    (Result over the STEPS, status uint32[n_steps], dict of copy_events uint64[n_copy, 12, 4], copy_flags, copy_src_ref, copy_step
+    uint32[n_copy], exp_events uint64[n_exp, 5, 4], exp_step uint32[n_exp])"""
+    lib = _lib.init(device)
+    x = engine.trace_event_sources(trace, codes, code_hashes)
+    dtypes = {"head": np.uint32, "code": np.uint8}
+    x = {k: (_host(v, dtypes.get(k, np.uint64)) if k in engine.TRACE_EVENTS_INPUTS else v) for k, v in x.items()}
+    res, status, out = _wire_oneshot(engine.TRACE_EVENTS, lib, engine._wire_args(engine.TRACE_EVENTS, x))
+    return res, status, engine.cut_trace_events(out, len(out["copy_events"]), len(out["exp_events"]))
+
+
 def _state_trace_records(trace):
     rec = {k: _host(trace.get(k), np.uint32 if k == "head" else np.uint64) for k in engine.TRACE_INPUTS if k != "steps"}
     rec["rw_base"] = trace.get("rw_base", 1)
