@@ -2204,7 +2204,7 @@ extern "C" int zk_withdrawal_verify(const zk_withdrawal_witness* w, uint32_t opt
 extern "C" int zk_withdrawal_assign(const uint64_t* withdrawals, uint64_t n, uint64_t max_withdrawals, const uint64_t* randomness,
                                     uint32_t opts, uint64_t* rows_out, uint64_t* keccak_out) {
     NO_DEVICE_PTRS(opts, "zk_withdrawal_assign");
-    ARG_TRY(randomness && rows_out && (withdrawals || n == 0), "zk_withdrawal_assign: bad arguments");
+    ARG_TRY(randomness && (rows_out || (n == 0 && max_withdrawals == 0)) && (withdrawals || n == 0), "zk_withdrawal_assign: bad arguments");
     ARG_TRY(n < (1ull << 32) && max_withdrawals < (1ull << 32), "zk_withdrawal_assign: too many rows");
     WithdrawalArgs a = {};
     a.in = withdrawals;

@@ -4082,7 +4082,7 @@ extern "C" int zk_withdrawal_assign(const uint64_t* withdrawals, uint64_t n, uin
                                     uint32_t opts, uint64_t* rows_out, uint64_t* keccak_out) {
     ARG_TRY(t_device >= 0, "zk_withdrawal_assign: call zk_init first");
     ARG_TRY(!(opts & ZK_OPT_DEVICE_PTRS), "zk_withdrawal_assign: ZK_OPT_DEVICE_PTRS is not supported");
-    ARG_TRY(randomness && rows_out && (withdrawals || n == 0), "zk_withdrawal_assign: bad arguments");
+    ARG_TRY(randomness && (rows_out || (n == 0 && max_withdrawals == 0)) && (withdrawals || n == 0), "zk_withdrawal_assign: bad arguments");
     ARG_TRY(n < (1ull << 32) && max_withdrawals < (1ull << 32), "zk_withdrawal_assign: too many rows");
     HIP_TRY(hipSetDevice(t_device));
     WithdrawalArgs a = {};
