@@ -1199,6 +1199,8 @@ int zk_copy_assign_from_sources(const zk_copy_sources* in, uint64_t* rows_out, u
  *      The states whose gadgets call copy_lookup with arguments this entry does not derive - BeginTx, RETURN, CREATE, CREATE2, CALL_OP and
  *      DATACOPY (begin_tx.py, return_revert.py, create.py, callop.py, dataCopy.py) - get (ZK_KIND_UNSUPPORTED << 24) | 1 and emit
  *      nothing: a caller then knows to supply those events itself.  They count in fail_count.  Every other state has status 0.
+ *      (The keccak lookups are not this entry's: zk_sha3_from_trace below derives the SHA3 steps' keccak rows; CREATE2's keccak lookup
+ *      of its init code is derived by neither.)
  *      zk_events_from_trace_sizes: the checks below, and the capacity every output needs (n_steps).  _open: with ZK_OPT_DEVICE_PTRS
  *      every input is a device pointer and the non-null pointers of `out_dev` receive the outputs in place (null: the session owns that
  *      buffer); without the flag out_dev must be NULL.  The session keeps its own copy of the heads, the counters, the pool offsets,
@@ -1230,6 +1232,70 @@ int zk_events_from_trace_read(zk_session* s, const zk_trace_events* host, uint64
 int zk_events_from_trace_counts(zk_session* s, uint64_t* n_copy, uint64_t* n_exp);
 int zk_events_from_trace(const zk_trace_sources* in, const zk_trace_events* out, uint32_t opts, uint32_t* status_out, uint64_t* n_copy,
                          uint64_t* n_exp, zk_result* result);
+
+/* ---- SHA3 inputs and keccak rows from compact trace records: the keccak rows the SHA3 steps look up (zk_evm_tables' keccak table), which a
+ *      producer of traces so far got by walking its memory image per SHA3 step, concatenating the bytes, uploading them and calling
+ *      zk_keccak_table.  The bytes are in the trace already: execution/sha3.py pops offset and size and pushes the digest; its copy
+ *      lookup reads `size` Memory bytes at the counters rw_counter + 3 + i; its keccak lookup is (size, RLC of those bytes) -> the
+ *      pushed word.  This entry gathers the messages where the records are, runs the keccak table's own code over them and checks what
+ *      no other entry does: that the word the trace pushed is the digest of the bytes the trace read.
+ *      Of zk_trace, head, id, addr, val, rw_counter / rw_base, n_rw, pool, n_pool, steps and n_steps are read; prev never is and may be
+ *      NULL.  randomness: uint64[4], the keccak randomness (as zk_keccak_table's).
+ *      Outputs (zk_trace_sha3), each pointer nullable: rows uint64[n_msgs][5][4], zk_keccak_table's mode-0 rows (KeccakCircuit.add), one
+ *      per message in step order, duplicates kept; step uint32[n_msgs], the step that produced each row; data uint8[n_bytes], the hashed
+ *      bytes back to back; data_offsets uint64[n_msgs + 1].  Each row is bit for bit what zk_keccak_table(data, data_offsets, mode 0)
+ *      returns over the gathered data / data_offsets.
+ *      Derivation.  "Op k" of a step is the op whose counter is step.rw_counter + k (rw_counter NULL: its index is counter - rw_base;
+ *      else it is found by binary search).  Values are taken as integers: val, or the pool word when the head says so.  For a step
+ *      whose execution state is SHA3: op 0 is a Stack read of call_id at stack_pointer (the offset), op 1 a Stack read at stack_pointer
+ *      + 1 (the size), op 2 a Stack WRITE at stack_pointer + 1 (the pushed word); none of the three addresses is a pool word.  Byte i
+ *      of the message is the val of op 3 + i, which must be a Memory read (not a write) of id == call_id at addr == offset + i (not a
+ *      pool word) with a value below 256 (not a pool word).  A step with size 0 is a message too, the empty string: row (2, 0, 0,
+ *      keccak256("")), which is what sha3.py looks up; its offset is not read for anything (it may be a pool word), as
+ *      memory_offset_and_length ignores it.  Steps of any other state have status 0 and produce nothing; CREATE2's keccak lookup of
+ *      its init code is not derived.
+ *      Status per step (zk_launch: status_dev uint32[n_steps]; the zk_result's tally runs over the steps, rows_evaluated = n_steps): 0,
+ *      or (ZK_KIND_VALUE_ERROR << 24) | site, never a guess.  Sites 1 and 2 are checked in ascending k and the first failure wins, then
+ *      site 3, then the lowest failing byte index, then site 7:
+ *        1  no op has the counter of op 0, 1 or 2;     2  the op there is not the one described;
+ *        3  the size taken as an integer is 2^62 or more; or, with size != 0, the offset is, or offset + size is, or step.rw_counter + 3
+ *           is (the domain of zk_copy_assign and zk_events_from_trace's site 3: the two entries accept the same SHA3 steps);
+ *        4  no op has the counter of byte i;     5  the op there is not a Memory read of call_id at offset + i;
+ *        6  its value is 256 or more;
+ *        7  every byte was read, but the 256-bit word pushed by op 2 differs from the digest.
+ *      A step failing 1-3 is no message: it gets no row and no bytes.  A step failing 4-6 keeps its place: the failing byte is gathered
+ *      as 0 (as zk_copy_assign_from_sources gathers it) and the row is the one over the data as gathered.  A step failing 7 has a
+ *      correct row; the status is the finding.
+ *      Sessions.  What indexes a load or a store is derived on the device at _sizes / _open and kept by the session: which steps are
+ *      messages, their call_id, offset, size and first counter, the data offsets, the heads, the counters and the pool offsets.  Sites
+ *      1-3 are decided at open; sites 4-7 by every pass.  The randomness is read at open, as zk_keccak_open reads it (its powers are
+ *      the session's); id / addr / val and the pool are re-read by every pass (a caller that rewrites val between passes changes
+ *      bytes, rows and site 7, and cannot move a store).  zk_sha3_from_trace_sizes: the checks below and n_msgs / n_bytes; rows, step and
+ *      data_offsets are sized by n_msgs (+ 1), data by n_bytes.  _open: with ZK_OPT_DEVICE_PTRS every input is a device pointer and the
+ *      non-null pointers of `out_dev` receive the outputs in place, every pass (null: the session owns that buffer; a caller's data
+ *      buffer is read in whole aligned 64-bit words, as zk_keccak_open reads its data); without the flag out_dev must be NULL.
+ *      zk_launch (with status_dev) / zk_collect / zk_read_status / zk_session_set_stream / zk_close as on the other assignment
+ *      sessions; every launch runs the whole pass (the gather, the keccak table, the comparison) and carries nothing over.  _read copies
+ *      the outputs to the non-null HOST pointers of `host` and returns the counts.  The one-shot's status_out is a device pointer with
+ *      ZK_OPT_DEVICE_PTRS, like its other outputs.
+ *      Domain, rejected at sizes / open with an error code and its text in zk_last_error:
+ *        ZK_ERR_TRC_HEAD / _ORDER / _POOL exactly as zk_evm_witness_from_trace_open reports them (on the device, one verdict block read
+ *        back, which also holds n_msgs and n_bytes), under this entry's name;
+ *        ZK_ERR_TS3_ROWS   2^31 or more steps or RW ops;
+ *        ZK_ERR_TS3_BYTES  the messages hold 2^31 bytes or more; the text names the step that takes the total there. */
+#define ZK_ERR_TS3_ROWS (-110)
+#define ZK_ERR_TS3_BYTES (-111)
+typedef struct zk_trace_sha3 {                               /* each pointer nullable */
+    uint64_t* rows;             /* uint64[n_msgs][5][4] */
+    uint32_t* step;             /* uint32[n_msgs] */
+    uint8_t* data;              /* uint8[n_bytes] */
+    uint64_t* data_offsets;     /* uint64[n_msgs + 1] */
+} zk_trace_sha3;
+int zk_sha3_from_trace_sizes(const zk_trace* in, uint32_t opts, uint64_t* n_msgs, uint64_t* n_bytes);
+int zk_sha3_from_trace_open(const zk_trace* in, const uint64_t* randomness, const zk_trace_sha3* out_dev, uint32_t opts, zk_session** out);
+int zk_sha3_from_trace_read(zk_session* s, const zk_trace_sha3* host, uint64_t* n_msgs, uint64_t* n_bytes);
+int zk_sha3_from_trace(const zk_trace* in, const uint64_t* randomness, const zk_trace_sha3* out, uint32_t opts, uint32_t* status_out,
+                       uint64_t* n_msgs, uint64_t* n_bytes, zk_result* result);
 
 #ifdef __cplusplus
 }

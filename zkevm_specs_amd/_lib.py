@@ -36,6 +36,7 @@ EXPORTED_SYMBOLS = [
     "zk_state_assign_from_trace_open", "zk_state_assign_from_trace",
     "zk_copy_assign_from_sources_sizes", "zk_copy_assign_from_sources_open", "zk_copy_assign_from_sources_read", "zk_copy_assign_from_sources",
     "zk_events_from_trace_sizes", "zk_events_from_trace_open", "zk_events_from_trace_read", "zk_events_from_trace_counts", "zk_events_from_trace",
+    "zk_sha3_from_trace_sizes", "zk_sha3_from_trace_open", "zk_sha3_from_trace_read", "zk_sha3_from_trace",
 ]
 
 OPT_DEVICE_PTRS = 1
@@ -168,6 +169,11 @@ class ZkTraceEvents(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("copy_events", "copy_flags", "copy_src_ref", "copy_step", "exp_events", "exp_step")]
 
 
+class ZkTraceSha3(ctypes.Structure):
+    """zk_trace_sha3 (include/zkevm_hip.h): the keccak rows of the SHA3 steps, their steps, the hashed bytes and their offsets"""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("rows", "step", "data", "data_offsets")]
+
+
 class ZkTraceWitness(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("rw", "rw_flags", "steps")]
 
@@ -219,6 +225,7 @@ ERR_TRC_HEAD, ERR_TRC_ORDER, ERR_TRC_POOL, ERR_TRC_ROWS = -70, -71, -72, -73  # 
 ERR_ECL_OFFSETS, ERR_ECL_ROWS, ERR_ECL_RANDOMNESS = -80, -81, -82  # ZK_ERR_ECL_*: why zk_ecc_from_calls* rejected its calls
 ERR_CPS_OFFSETS, ERR_CPS_ROWS = -90, -91  # ZK_ERR_CPS_*: why zk_copy_assign_from_sources* rejected its sources
 ERR_TEV_OFFSETS, ERR_TEV_ROWS = -100, -101  # ZK_ERR_TEV_*: why zk_events_from_trace* rejected its code set or its counts
+ERR_TS3_ROWS, ERR_TS3_BYTES = -110, -111  # ZK_ERR_TS3_*: why zk_sha3_from_trace* rejected its counts
 
 
 class ZkBlock(ctypes.Structure):
@@ -402,6 +409,11 @@ def _bind(lib):
     lib.zk_events_from_trace_counts.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.zk_events_from_trace.argtypes = [ctypes.POINTER(ZkTraceSources), ctypes.POINTER(ZkTraceEvents), u32, vp, ctypes.POINTER(u64),
                                          ctypes.POINTER(u64), ctypes.POINTER(ZkResult)]
+    lib.zk_sha3_from_trace_sizes.argtypes = [ctypes.POINTER(ZkTrace), u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_sha3_from_trace_open.argtypes = [ctypes.POINTER(ZkTrace), vp, ctypes.POINTER(ZkTraceSha3), u32, ctypes.POINTER(vp)]
+    lib.zk_sha3_from_trace_read.argtypes = [vp, ctypes.POINTER(ZkTraceSha3), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_sha3_from_trace.argtypes = [ctypes.POINTER(ZkTrace), vp, ctypes.POINTER(ZkTraceSha3), u32, vp, ctypes.POINTER(u64), ctypes.POINTER(u64),
+                                       ctypes.POINTER(ZkResult)]
     lib.zk_launch.argtypes = [vp, vp]
     lib.zk_collect.argtypes = [vp, ctypes.POINTER(ZkResult)]
     lib.zk_read_status.argtypes = [vp, vp]

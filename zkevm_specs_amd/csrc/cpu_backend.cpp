@@ -48,6 +48,7 @@ static thread_local std::string g_err;
 #include "copy_assign_plan.hpp"  // (uses ARG_TRY)
 #include "copy_sources_plan.hpp"
 #include "trace_events_plan.hpp"
+#include "trace_sha3.hpp"
 
 extern "C" const char* zk_last_error(void) { return g_err.c_str(); }
 extern "C" int zk_init(int) { return 0; }
@@ -107,7 +108,7 @@ struct zk_session {
     std::vector<u64> w64[4];              // assignment sessions: work / output buffers
     std::vector<u32> out32;
     void (*pass)(zk_session*) = nullptr;  // assignment sessions: one pass computes the outputs and fills `status`
-    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code, 11 tables from block, 12 witness from trace, 13 ECC precompile calls, 14 copy from sources, 15 events from trace
+    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code, 11 tables from block, 12 witness from trace, 13 ECC precompile calls, 14 copy from sources, 15 events from trace, 16 SHA3 from trace
     u64 n_ops = 0;                        // RW -> State ops: 1 + kept rows
     std::vector<u32> rekey_plan;          // RW -> State ops: the RwkHostPlan's plan (as words) ...
     std::vector<u32> rekey_jobs;          // ... and its rank jobs (cls, field, base, count)
@@ -147,6 +148,12 @@ struct zk_session {
     TevPlan tev_plan;               // ... the sorted hash directory
     std::vector<u64> tev64[6];      // counters, pool offsets, code offsets, copy events, EXP events, counts
     std::vector<u32> tev32[5];      // heads, copy flags, copy refs, copy steps, EXP steps
+    Ts3Args ts3;                    // SHA3 inputs and keccak rows from compact trace records
+    KeccakGenArgs ts3_kgen;         // ... the keccak table over the gathered bytes
+    std::vector<u64> ts364[8];      // counters, pool offsets, sizes, session offsets, fail words, rows, out offsets, powers of the randomness
+    std::vector<u32> ts332[3];      // heads, open-time statuses, steps
+    std::vector<Ts3Msg> ts3_msg;
+    std::vector<uint8_t> ts3_data;
     EcdsaArgs ecdsa;
     KeccakGenArgs kgen;
     TxAssignArgs txa;
@@ -1800,6 +1807,102 @@ extern "C" int zk_events_from_trace(const zk_trace_sources* t, const zk_trace_ev
     if (!rc) rc = zk_collect(s, result);
     if (!rc && status_out) rc = zk_read_status(s, status_out);
     if (!rc) rc = zk_events_from_trace_read(s, out_wire, n_copy, n_exp);
+    zk_close(s);
+    return rc;
+}
+
+// ---- SHA3 inputs and keccak rows from compact trace records (trace_sha3.hpp): the per-step and per-byte functions in host loops.  The
+//      session keeps its own heads, counters, pool offsets, sizes, records and data offsets; id / addr / val / pool stay the caller's
+//      arrays and every pass reads them.
+static void sha3_from_trace_pass(zk_session* s) { ts3_pass_host(s->ts3, s->ts3_kgen, s->status.data()); }
+#define TS3_ARGS_OK(t) ((t) && ((t)->n_rw == 0 || ((t)->head && (t)->id && (t)->addr && (t)->val)) && ((t)->n_pool == 0 || (t)->pool) &&                  \
+                        ((t)->n_steps == 0 || (t)->steps))
+// The open: the counts, the trace checks, every step's open-time status and size, the verdict.  check_only: no session is left.
+static int ts3_open_host(const zk_trace* tr, const uint64_t* randomness, bool check_only, uint64_t* n_msgs, uint64_t* n_bytes, zk_session** out) {
+    const char* const name = "zk_sha3_from_trace";
+    char msg[256];
+    int rc = ts3_counts_check(tr->n_rw, tr->n_steps, msg, sizeof msg);  // (before any array is read or anything allocated)
+    if (rc) { g_err = msg; return rc; }
+    if ((rc = trw_plan_counts(tr->n_rw, tr->n_steps, tr->rw_base, tr->rw_counter != nullptr, msg, sizeof msg))) { g_err = msg; cps_retitle(name); return rc; }
+    const u64 n = tr->n_rw, ns = tr->n_steps;
+    zk_session* s = new_session(ns, false);
+    s->ts332[0].assign(n + 1, 0);                         // heads
+    s->ts364[0].assign(tr->rw_counter ? n + 1 : 0, 0);    // counters
+    s->ts364[1].assign(n + 1, 0);                         // pool offsets
+    u64 v[TRW_V_WORDS];
+    trw_check_host(tr->head, tr->rw_counter, n, tr->steps, ns, s->ts332[0].data(), tr->rw_counter ? s->ts364[0].data() : nullptr, s->ts364[1].data(), v);
+    if ((rc = trw_verdict_error(v, tr->n_pool, msg, sizeof msg))) { g_err = msg; cps_retitle(name); delete s; return rc; }
+    Ts3Args& a = s->ts3;
+    memset(&a, 0, sizeof(a));
+    TevArgs& t = a.t;
+    t.head = s->ts332[0].data(); t.ctr = tr->rw_counter ? s->ts364[0].data() : nullptr; t.off = s->ts364[1].data();
+    t.id = tr->id; t.addr = tr->addr; t.val = tr->val; t.pool = tr->pool; t.steps = tr->steps;
+    t.n_rw = n; t.n_pool = tr->n_pool; t.n_steps = ns; t.rw_base = tr->rw_base;
+    s->ts332[1].assign(ns + 1, 0);                        // open-time statuses
+    s->ts364[2].assign(ns + 1, 0);                        // sizes
+    u64 c[TS3_V_WORDS];
+    a.st_open = s->ts332[1].data(); a.sz = s->ts364[2].data(); a.verdict = c;
+    ts3_count_host(a);
+    a.verdict = nullptr;
+    if (c[TS3_V_BYTES] >= TS3_BYTES_LIMIT) { rc = ts3_bytes_error(c[TS3_V_CROSS], msg, sizeof msg); g_err = msg; delete s; return rc; }
+    if (n_msgs) *n_msgs = c[TS3_V_MSGS];
+    if (n_bytes) *n_bytes = c[TS3_V_BYTES];
+    if (check_only) { delete s; return 0; }
+    const u64 nm = a.n_msgs = c[TS3_V_MSGS], nby = a.n_bytes = c[TS3_V_BYTES];
+    s->ts3_msg.assign(nm + 1, Ts3Msg{0, 0, 0, 0, 0, 0});
+    s->ts364[3].assign(nm + 1, 0);                        // the session's offsets
+    s->ts364[4].assign(nm + 1, 0);                        // fail words
+    s->ts364[5].assign(nm * KT_NCELLS * 4 + 4, 0);        // rows
+    s->ts364[6].assign(nm + 1, 0);                        // out offsets
+    s->ts364[7].assign(KT_RPOW_ROWS * 4, 0);
+    s->ts332[2].assign(nm + 1, 0);                        // steps
+    s->ts3_data.assign((size_t)((nby + 15) & ~7ull), 0);  // (the sponge reads whole aligned words)
+    a.msg = s->ts3_msg.data(); a.data_off = s->ts364[3].data(); a.fail = (unsigned long long*)s->ts364[4].data();
+    a.rows = s->ts364[5].data(); a.data_offsets = s->ts364[6].data(); a.step = s->ts332[2].data(); a.data = s->ts3_data.data();
+    ts3_write_host(a);
+    kt_fill_rpow(cell_of(randomness), s->ts364[7].data());
+    KeccakGenArgs& g = s->ts3_kgen;
+    g.data = a.data; g.offsets = a.data_off; g.n = nm; g.rpow = s->ts364[7].data(); g.rows = a.rows; g.mode = KT_MODE_CIRCUIT;
+    g.long_list = nullptr; g.long_count = nullptr;
+    s->pass = sha3_from_trace_pass;
+    s->assign_kind = 16;
+    *out = s;
+    return 0;
+}
+extern "C" int zk_sha3_from_trace_sizes(const zk_trace* t, uint32_t opts, uint64_t* n_msgs, uint64_t* n_bytes) {
+    NO_DEVICE_PTRS(opts, "zk_sha3_from_trace_sizes");
+    ARG_TRY(TS3_ARGS_OK(t), "zk_sha3_from_trace_sizes: bad arguments");
+    return ts3_open_host(t, nullptr, true, n_msgs, n_bytes, nullptr);
+}
+extern "C" int zk_sha3_from_trace_open(const zk_trace* t, const uint64_t* randomness, const zk_trace_sha3* out_dev, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_sha3_from_trace_open");
+    ARG_TRY(TS3_ARGS_OK(t) && randomness && out, "zk_sha3_from_trace_open: bad arguments");
+    ARG_TRY(!out_dev, "zk_sha3_from_trace_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    return ts3_open_host(t, randomness, false, nullptr, nullptr, out);
+}
+extern "C" int zk_sha3_from_trace_read(zk_session* s, const zk_trace_sha3* host, uint64_t* n_msgs, uint64_t* n_bytes) {
+    ARG_TRY(s && s->assign_kind == 16, "zk_sha3_from_trace_read: bad arguments");
+    const Ts3Args& a = s->ts3;
+    if (host) {
+        if (host->rows && a.n_msgs) memcpy(host->rows, a.rows, a.n_msgs * KT_NCELLS * 32);
+        if (host->step && a.n_msgs) memcpy(host->step, a.step, a.n_msgs * 4);
+        if (host->data && a.n_bytes) memcpy(host->data, a.data, a.n_bytes);
+        if (host->data_offsets) memcpy(host->data_offsets, a.data_offsets, (a.n_msgs + 1) * 8);
+    }
+    if (n_msgs) *n_msgs = a.n_msgs;
+    if (n_bytes) *n_bytes = a.n_bytes;
+    return 0;
+}
+extern "C" int zk_sha3_from_trace(const zk_trace* t, const uint64_t* randomness, const zk_trace_sha3* out_wire, uint32_t opts, uint32_t* status_out,
+                                  uint64_t* n_msgs, uint64_t* n_bytes, zk_result* result) {
+    ARG_TRY(result && out_wire && t, "zk_sha3_from_trace: null argument");
+    zk_session* s = nullptr;
+    int rc = zk_sha3_from_trace_open(t, randomness, nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && status_out) rc = zk_read_status(s, status_out);
+    if (!rc) rc = zk_sha3_from_trace_read(s, out_wire, n_msgs, n_bytes);
     zk_close(s);
     return rc;
 }

@@ -20,6 +20,7 @@
 #include "copy_assign.hpp"
 #include "copy_sources.hpp"
 #include "trace_events.hpp"
+#include "trace_sha3.hpp"
 #include "pi_circuit.hpp"
 #include "state_rekey.hpp"
 #include "ecc_circuit.hpp"
@@ -117,6 +118,13 @@ void zk_launch_copy_sources(hipStream_t st, const CpsArgs& a, const CpsCodeArgs&
 // Copy and EXP events from compact trace records (k_trace_events.hip): a status per step and its tally, what each step emits, a scan of the
 // per-block counts into a.blk / a.counts, the packed ordered stores
 void zk_launch_trace_events(hipStream_t st, const TevArgs& a, u32* status, ZkTally* tally);
+// SHA3 inputs and keccak rows from compact trace records (k_trace_sha3.hip).  _count: every step's open-time status and size, the scan of
+// the per-block counts, the totals in a.verdict;  _write: the message records and the session's data offsets (cross_only: nothing but
+// the step that takes the byte total to 2^31);  the pass: the gather into a.data, zk_launch_keccak_table over it (g), the digest
+// comparison, a status per step and its tally
+void zk_launch_trace_sha3_count(hipStream_t st, const Ts3Args& a);
+void zk_launch_trace_sha3_write(hipStream_t st, const Ts3Args& a, bool cross_only);
+void zk_launch_trace_sha3(hipStream_t st, const Ts3Args& a, const KeccakGenArgs& g, u32* status, ZkTally* tally);
 void zk_launch_ecdsa(hipStream_t st, const EcdsaArgs& a, u32* status, ZkTally* tally);
 void zk_launch_ecdsa_comb_build(hipStream_t st, u32* table);  // the device's 8-bit fixed-base table of G (522 KB), built once
 // ECC circuit (k_ecc.hip): assign = circuit2rows into a.rows_out, else verify a.rows (status / tally)

@@ -606,7 +606,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_TEV = 27, SESSION_CPS = 26, SESSION_ECL = 25, SESSION_TRW = 24, SESSION_BTB = 23, SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_TS3 = 28, SESSION_TEV = 27, SESSION_CPS = 26, SESSION_ECL = 25, SESSION_TRW = 24, SESSION_BTB = 23, SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -672,6 +672,8 @@ struct zk_session {
     CpsCodeArgs cps_code;           // ... its is_code scan (n_segs = 0: no event has a Bytecode side)
     std::vector<u64> cps_data0;     // ... the gathered array's offsets (host copy: zk_copy_assign_from_sources_read hands them out)
     TevArgs tev;                    // SESSION_TEV (zk_events_from_trace*): the open's checks and the session's heads / counters / pool offsets sit in `trw`
+    Ts3Args ts3;                    // SESSION_TS3 (zk_sha3_from_trace*): likewise; the keccak pass over the gathered bytes in ts3_kgen
+    KeccakGenArgs ts3_kgen;
     u32* d_hist = nullptr;   // EVM: (group, state) bins (histogram -> cursors)
     u32* d_cursor = nullptr; // EVM: per-bin scatter cursors (cleared by every histogram pass)
     u32* d_hist2 = nullptr;  // EVM: the other histogram buffer (the two alternate between passes)
@@ -2467,6 +2469,137 @@ extern "C" int zk_events_from_trace(const zk_trace_sources* t, const zk_trace_ev
     return zk_events_from_trace_read(s, dev ? nullptr : out_wire, n_copy, n_exp);
 }
 
+// ---- SHA3 inputs and keccak rows from compact trace records (trace_sha3.hpp, k_trace_sha3.hip)
+#define TS3_ARGS_OK(t) ((t) && ((t)->n_rw == 0 || ((t)->head && (t)->id && (t)->addr && (t)->val)) && ((t)->n_pool == 0 || (t)->pool) &&                  \
+                        ((t)->n_steps == 0 || (t)->steps))
+// Open a session over the records: the trace's heads, counters and step words checked on the device as zk_evm_witness_from_trace_open
+// checks them, the steps' open-time statuses and sizes and their scan behind that on the same stream, ONE verdict block read back (the
+// trace checks' words, then the messages and the bytes); then the buffers the counts size, the records and the data offsets.
+// check_only: the checks and the counts alone (the _sizes entry: the session is closed again).
+static int ts3_open(const zk_trace* tr, const uint64_t* randomness, const zk_trace_sha3* out_dev, uint32_t opts, bool check_only, uint64_t* n_msgs,
+                    uint64_t* n_bytes, zk_session** out) {
+    const char* const name = "zk_sha3_from_trace";
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    char msg[256];
+    if (int rc = ts3_counts_check(tr->n_rw, tr->n_steps, msg, sizeof msg)) { g_err = msg; return rc; }  // (before anything is read)
+    if (int rc = trw_plan_counts(tr->n_rw, tr->n_steps, tr->rw_base, tr->rw_counter != nullptr, msg, sizeof msg)) { g_err = msg; cps_retitle(name); return rc; }
+    const u64 n = tr->n_rw, ns = tr->n_steps;
+    SessionGuard guard(new zk_session());
+    zk_session* const s = guard.get();
+    s->kind = SESSION_TS3;
+    s->n = ns;
+    TrwArgs& w = s->trw;
+    Ts3Args& a = s->ts3;
+    KeccakGenArgs& g = s->ts3_kgen;
+    memset(&w, 0, sizeof(w));
+    memset(&a, 0, sizeof(a));
+    memset(&g, 0, sizeof(g));
+    // the session keeps its own heads, counters and pool offsets (a caller that rewrites a head cannot move a load)
+    RC_TRY(stage_in(s, w.head_in, tr->head, (size_t)n * 4, dev));
+    if (tr->rw_counter && n) RC_TRY(stage_in(s, w.ctr_in, tr->rw_counter, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, w.steps_in, tr->steps, (size_t)ns * TRW_STEP_WORDS * 8, dev));
+    w.n_rw = n; w.n_pool = tr->n_pool; w.n_steps = ns; w.rw_base = tr->rw_base;
+    RC_TRY(dev_buf(s, w.head, (size_t)n * 4 + 4));
+    if (w.ctr_in) RC_TRY(dev_buf(s, w.ctr, (size_t)n * 8));
+    RC_TRY(dev_buf(s, w.off, (size_t)n * 8 + 8));
+    RC_TRY(dev_buf(s, w.verdict, (size_t)(TRW_V_WORDS + TS3_V_WORDS) * 8));
+    zk_launch_trace_witness_check(s->stream, w);
+    TevArgs& t = a.t;
+    t.head = w.head; t.ctr = w.ctr; t.off = w.off; t.steps = w.steps_in;
+    t.n_rw = n; t.n_pool = tr->n_pool; t.n_steps = ns; t.rw_base = tr->rw_base;
+    RC_TRY(stage_in(s, t.id, tr->id, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, t.addr, tr->addr, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, t.val, tr->val, (size_t)n * 8, dev));
+    RC_TRY(stage_in(s, t.pool, tr->pool, (size_t)tr->n_pool * 32, dev));
+    const size_t n_blocks = (size_t)((ns + 255) / 256);
+    RC_TRY(dev_buf(s, a.st_open, (size_t)ns * 4));
+    RC_TRY(dev_buf(s, a.sz, (size_t)ns * 8));
+    RC_TRY(dev_buf(s, a.blk, n_blocks * 16));
+    a.verdict = w.verdict + TRW_V_WORDS;
+    zk_launch_trace_sha3_count(s->stream, a);
+    DEV_TRY(hipGetLastError() == hipSuccess, "zk_sha3_from_trace: the open's check launch failed");
+    u64 v[TRW_V_WORDS + TS3_V_WORDS];
+    RC_TRY(d2h_now(s->stream, v, w.verdict, sizeof v));
+    if (int rc = trw_verdict_error(v, tr->n_pool, msg, sizeof msg)) { g_err = msg; cps_retitle(name); return rc; }
+    const u64* const c = v + TRW_V_WORDS;
+    if (c[TS3_V_BYTES] >= TS3_BYTES_LIMIT) {  // the rejected open names the step: one more walk over the sizes, nothing stored
+        zk_launch_trace_sha3_write(s->stream, a, true);
+        u64 cross = 0;
+        RC_TRY(d2h_now(s->stream, &cross, a.verdict + TS3_V_CROSS, sizeof cross));
+        const int rc = ts3_bytes_error(cross, msg, sizeof msg);
+        g_err = msg;
+        return rc;
+    }
+    if (n_msgs) *n_msgs = c[TS3_V_MSGS];
+    if (n_bytes) *n_bytes = c[TS3_V_BYTES];
+    if (check_only) return 0;
+    const u64 nm = a.n_msgs = c[TS3_V_MSGS], nby = a.n_bytes = c[TS3_V_BYTES];
+    RC_TRY(dev_buf(s, a.msg, (size_t)nm * sizeof(Ts3Msg)));
+    RC_TRY(dev_buf(s, a.data_off, ((size_t)nm + 1) * 8));
+    RC_TRY(dev_buf(s, a.fail, (size_t)nm * 8));
+    HIP_TRY(hipMemsetAsync(a.data_off, 0, 8, s->stream));  // (no message: the one offset)
+    zk_launch_trace_sha3_write(s->stream, a, false);
+    const zk_trace_sha3 o = wire_or_nulls(out_dev);
+    RC_TRY(out_buf(s, a.rows, o.rows, (size_t)nm * KT_NCELLS * 32));
+    RC_TRY(out_buf(s, a.step, o.step, (size_t)nm * 4));
+    // (a buffer of the session's own holds its last aligned word whole: the sponge reads whole aligned words, as over zk_keccak_open's data)
+    RC_TRY(out_buf(s, a.data, o.data, (size_t)((nby + 15) & ~7ull)));
+    RC_TRY(out_buf(s, a.data_offsets, o.data_offsets, ((size_t)nm + 1) * 8));
+    // the keccak pass over the gathered bytes (KeccakCircuit.add mode), as zk_keccak_open sets it up
+    g.data = a.data; g.offsets = a.data_off; g.n = nm; g.rows = a.rows; g.mode = KT_MODE_CIRCUIT;
+    if (nm && !getenv("ZK_KECCAK_NO_GROUPS")) {
+        u32* d_list = nullptr;
+        RC_TRY(dev_buf(s, d_list, ((size_t)nm + 1) * sizeof(u32)));
+        g.long_list = d_list + 1;
+        g.long_count = d_list;
+    }
+    u64 rh[4];
+    RC_TRY(host_words(s, rh, randomness, 32, dev, "randomness"));
+    RC_TRY(keccak_rpow_open(s, rh, &g.rpow));
+    DEV_TRY(hipGetLastError() == hipSuccess, "zk_sha3_from_trace_open: the open's launches failed");
+    RC_TRY(session_common_init(s));
+    *out = guard.release();
+    return 0;
+}
+extern "C" int zk_sha3_from_trace_sizes(const zk_trace* t, uint32_t opts, uint64_t* n_msgs, uint64_t* n_bytes) {
+    ARG_TRY(t_device >= 0, "zk_sha3_from_trace_sizes: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(TS3_ARGS_OK(t), "zk_sha3_from_trace_sizes: bad arguments");
+    return ts3_open(t, nullptr, nullptr, opts, true, n_msgs, n_bytes, nullptr);
+}
+extern "C" int zk_sha3_from_trace_open(const zk_trace* t, const uint64_t* randomness, const zk_trace_sha3* out_dev, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_sha3_from_trace_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(TS3_ARGS_OK(t) && randomness && out, "zk_sha3_from_trace_open: bad arguments");
+    ARG_TRY((opts & ZK_OPT_DEVICE_PTRS) || !out_dev, "zk_sha3_from_trace_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    return ts3_open(t, randomness, out_dev, opts, false, nullptr, nullptr, out);
+}
+extern "C" int zk_sha3_from_trace_read(zk_session* s, const zk_trace_sha3* host, uint64_t* n_msgs, uint64_t* n_bytes) {
+    ARG_TRY(s && s->kind == SESSION_TS3, "zk_sha3_from_trace_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    const Ts3Args& a = s->ts3;
+    if (host) {
+        RC_TRY(d2h_out(s, host->rows, a.rows, (size_t)a.n_msgs * KT_NCELLS * 32));
+        RC_TRY(d2h_out(s, host->step, a.step, (size_t)a.n_msgs * 4));
+        RC_TRY(d2h_out(s, host->data, a.data, (size_t)a.n_bytes));
+        RC_TRY(d2h_out(s, host->data_offsets, a.data_offsets, ((size_t)a.n_msgs + 1) * 8));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    if (n_msgs) *n_msgs = a.n_msgs;
+    if (n_bytes) *n_bytes = a.n_bytes;
+    return 0;
+}
+extern "C" int zk_sha3_from_trace(const zk_trace* t, const uint64_t* randomness, const zk_trace_sha3* out_wire, uint32_t opts, uint32_t* status_out,
+                                  uint64_t* n_msgs, uint64_t* n_bytes, zk_result* result) {
+    ARG_TRY(result && out_wire && t, "zk_sha3_from_trace: null argument");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    RC_TRY(zk_sha3_from_trace_open(t, randomness, dev ? out_wire : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, status_out, result));
+    return zk_sha3_from_trace_read(s, dev ? nullptr : out_wire, n_msgs, n_bytes);
+}
+
 // ---- Exp-circuit witness assignment
 // The size pass of an open: events staged, counts / first rows / reject word computed on the session's stream and the two words
 // read back (the one wait of the open).  `s` owns the buffers; on a rejected event the error code is returned with its text.
@@ -3061,6 +3194,7 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     case SESSION_BTB: zk_launch_block_tables(s->stream, s->btb, status); break;
     case SESSION_TRW: zk_launch_trace_witness(s->stream, s->trw, status); break;
     case SESSION_TEV: zk_launch_trace_events(s->stream, s->tev, status, s->d_tally); break;
+    case SESSION_TS3: zk_launch_trace_sha3(s->stream, s->ts3, s->ts3_kgen, status, s->d_tally); break;
     case SESSION_ECL: zk_launch_ecc_calls(s->stream, s->ecl, s->ecl_n_pairs, status); break;
     case SESSION_REKEY:
         if (s->from_trace) zk_launch_state_trace_rekey(s->stream, s->rekey, s->strc, status, s->d_tally);

@@ -1554,6 +1554,78 @@ def open_events_from_trace(trace, codes, code_hashes, outs=None, device=None):
     return _wire_open(TRACE_EVENTS, device, trace_event_sources(trace, codes, code_hashes), (), outs, cls=EventsFromTraceSession)
 
 
+# ---- SHA3 inputs and keccak rows from compact trace records (zk_sha3_from_trace*) ----------------------------------------------------
+TRACE_SHA3_INPUTS = ("head", "id", "addr", "val", "rw_counter", "pool", "steps")
+TRACE_SHA3_OUTPUTS = ("rows", "step", "data", "data_offsets")
+
+
+def sha3_from_trace_shapes(n_msgs, n_bytes):
+    """name -> (shape, dtype) of the outputs of zk_sha3_from_trace* for the counts of sha3_from_trace_sizes (include/zkevm_hip.h)"""
+    m, b = int(n_msgs), int(n_bytes)
+    return {"rows": ((m, 5, 4), np.uint64), "step": ((m,), np.uint32), "data": ((b,), np.uint8), "data_offsets": ((m + 1,), np.uint64)}
+
+
+def _trace_sha3_check(x):
+    n = _rows(x.get("head"))
+    _expect(x.get("head"), "head", 4, (None,))
+    for name in ("id", "addr", "val", "rw_counter"):
+        _expect(x.get(name), name, 8, (n,))
+        if n and name != "rw_counter" and x.get(name) is None:
+            raise ValueError(f"{name}: missing")
+    _expect(x.get("pool"), "pool", 8, (None, 4))
+    _expect(x.get("steps"), "steps", 8, (None, 13))
+    return _rows(x.get("steps")), sha3_from_trace_shapes(*x.get("counts", (0, 0)))
+
+
+def _trace_sha3_fill(x, a, cells):
+    n, m, k = _rows(a[0]), _rows(a[5]), _rows(a[6])
+    return _lib.ZkTrace(ptr(a[0], n), ptr(a[1], n), ptr(a[2], n), ptr(a[3], n), None, ptr(a[4], n), int(x.get("rw_base", 1)), n, ptr(a[5], m), m,
+                        ptr(a[6], k), k)
+
+
+# (the randomness travels as an argument of its own behind the inputs: the open and the one-shot below make the call themselves)
+TRACE_SHA3 = WireFamily("zk_sha3_from_trace", TRACE_SHA3_INPUTS, TRACE_SHA3_OUTPUTS, _lib.ZkTraceSha3, _trace_sha3_check, _trace_sha3_fill,
+                        cut=("rows", "data"), status=True, null_empty=True, n_sizes=2)
+
+
+def _trace_sha3_records(trace, counts=None):
+    x = {k: trace.get(k) for k in TRACE_SHA3_INPUTS}
+    x["rw_base"] = trace.get("rw_base", 1)
+    if counts is not None:
+        x["counts"] = counts
+    return x
+
+
+def sha3_from_trace_sizes(trace, device=None):
+    """(n_msgs, n_bytes) of the SHA3 steps of the trace records `trace`: what sizes the outputs of zk_sha3_from_trace*; raises
+    EngineError (rc = _lib.ERR_TRC_* / ERR_TS3_*) for records outside the domain"""
+    lib = _lib.init(device)
+    return _wire_sizes(TRACE_SHA3, lib, _wire_args(TRACE_SHA3, _trace_sha3_records(trace)))
+
+
+class Sha3FromTraceSession(WireSession):
+    """zk_sha3_from_trace_open: a status per step; counts() -> (n_msgs, n_bytes); read(names=None) -> dict of rows uint64[n_msgs, 5, 4]
+    (what zk_evm_tables' keccak table takes), step uint32[n_msgs], data uint8[n_bytes], data_offsets uint64[n_msgs + 1] of the last pass"""
+
+    def counts(self):
+        return tuple(self._read())
+
+
+def open_sha3_from_trace(trace, randomness, outs=None, device=None):
+    """The SHA3 steps' messages and keccak rows of compact trace records `trace` (trace.py; prev is not read) -> Sha3FromTraceSession
+    over the steps.  numpy inputs are staged to HBM (the CPU backend reads id / addr / val / pool in place, every pass); torch CUDA
+    tensors are used in place, and the CUDA tensors of `outs` (TRACE_SHA3_OUTPUTS, shapes of sha3_from_trace_shapes over
+    sha3_from_trace_sizes) then receive the outputs in place, every pass."""
+    lib = _lib.init(device)
+    fam = TRACE_SHA3
+    counts = _wire_sizes(fam, lib, _wire_args(fam, _trace_sha3_records(trace)))
+    p = _wire_args(fam, _trace_sha3_records(trace, counts), (int(randomness),), outs)
+    s = _open(lib, lib.zk_sha3_from_trace_open, p.n, (p.keep, p.t, p.w), ctypes.byref(p.t), ptr(p.keep[-1]),
+              ctypes.byref(p.w) if p.w is not None else None, p.opts, cls=Sha3FromTraceSession)
+    s.family, s.shapes = fam, p.shapes
+    return s
+
+
 # ---- State circuit from compact trace records (zk_state_verify_from_trace* / zk_state_ops_from_trace* / zk_state_assign_from_trace*) ---------------------------------
 def _state_from_trace_args(trace, outs=()):
     """The RW half of `trace` (see _evm_witness_from_trace_args; prev and steps are not read and may be missing) -> (ZkTrace, opts, kept

@@ -184,6 +184,24 @@ def events_from_trace(trace, codes, code_hashes, device=None):
     return res, status, engine.cut_trace_events(out, len(out["copy_events"]), len(out["exp_events"]))
 
 
+def sha3_from_trace(trace, randomness, device=None):
+    """zk_sha3_from_trace over trace records of host arrays -> (Result over the STEPS, status uint32[n_steps], dict of rows
+    uint64[n_msgs, 5, 4], step uint32[n_msgs], data uint8[n_bytes], data_offsets uint64[n_msgs + 1]); the outputs are sized by one
+    zk_sha3_from_trace_sizes call in front"""
+    lib = _lib.init(device)
+    fam = engine.TRACE_SHA3
+    x = engine._trace_sha3_records(trace)
+    x = {k: (_host(v, np.uint32 if k == "head" else np.uint64) if k in engine.TRACE_SHA3_INPUTS else v) for k, v in x.items()}
+    x["counts"] = engine._wire_sizes(fam, lib, engine._wire_args(fam, x))
+    p = engine._wire_args(fam, x, (int(randomness),))
+    out, w = engine._wire_host_outputs(fam, p.shapes)
+    status, r = np.zeros(max(p.n, 1), dtype=np.uint32), ZkResult()
+    counts = [ctypes.c_uint64(), ctypes.c_uint64()]
+    check(lib.zk_sha3_from_trace(ctypes.byref(p.t), ptr(p.keep[-1]), ctypes.byref(w), p.opts, ptr(status), ctypes.byref(counts[0]),
+                                 ctypes.byref(counts[1]), ctypes.byref(r)), "zk_sha3_from_trace", lib)
+    return Result(r), status[: p.n], out
+
+
 def _state_trace_records(trace):
     rec = {k: _host(trace.get(k), np.uint32 if k == "head" else np.uint64) for k in engine.TRACE_INPUTS if k != "steps"}
     rec["rw_base"] = trace.get("rw_base", 1)
