@@ -1198,7 +1198,8 @@ int zk_copy_assign_from_sources(const zk_copy_sources* in, uint64_t* rows_out, u
  *           both, 3 is reported; the LOG event's counter is then tested without its topics).
  *      The states whose gadgets call copy_lookup with arguments this entry does not derive - BeginTx, RETURN, CREATE, CREATE2, CALL_OP and
  *      DATACOPY (begin_tx.py, return_revert.py, create.py, callop.py, dataCopy.py) - get (ZK_KIND_UNSUPPORTED << 24) | 1 and emit
- *      nothing: a caller then knows to supply those events itself.  They count in fail_count.  Every other state has status 0.
+ *      nothing: a caller then knows to supply those events itself (or calls zk_events_from_trace_ext below, which derives BeginTx,
+ *      RETURN and DATACOPY too).  They count in fail_count.  Every other state has status 0.
  *      (The keccak lookups are not this entry's: zk_sha3_from_trace below derives the SHA3 steps' keccak rows; CREATE2's keccak lookup
  *      of its init code is derived by neither.)
  *      zk_events_from_trace_sizes: the checks below, and the capacity every output needs (n_steps).  _open: with ZK_OPT_DEVICE_PTRS
@@ -1232,6 +1233,67 @@ int zk_events_from_trace_read(zk_session* s, const zk_trace_events* host, uint64
 int zk_events_from_trace_counts(zk_session* s, uint64_t* n_copy, uint64_t* n_exp);
 int zk_events_from_trace(const zk_trace_sources* in, const zk_trace_events* out, uint32_t opts, uint32_t* status_out, uint64_t* n_copy,
                          uint64_t* n_exp, zk_result* result);
+
+/* ---- The same, with the copy events of BeginTx, RETURN / REVERT and DATACOPY (begin_tx.py:147-177, return_revert.py:54-93, dataCopy.py:
+ *      38-61): the states of which every block has one per tx and one per call, and whose events may WRITE a code (a deployment, a create
+ *      tx's init code), which zk_trace_events cannot say.  zk_events_from_trace* above is unchanged; this family stands beside it.
+ *      Inputs: zk_trace_sources, exactly as above.
+ *      Outputs (zk_trace_events_ext), each pointer nullable: copy_events, copy_flags, copy_src_ref, copy_step, exp_events, exp_step as
+ *      above, and copy_dst_ref uint32[n_copy]: for an event with a Bytecode destination the index in the code set of the code it writes
+ *      (the dst_ref zk_copy_sources takes), else 0.  Both lists are packed, in step order; the events of one step are in the order its
+ *      gadget calls copy_lookup.  Capacities (zk_events_from_trace_ext_sizes returns both): the exp_* outputs n_steps; the copy_* outputs
+ *      n_steps + the number of steps whose state is BeginTx or DATACOPY (the two states that may emit two events), counted at sizes /
+ *      open where the steps' word 0 is read anyway.
+ *      Derivation.  Every state zk_events_from_trace derives has the same event, status and refs here (one per-step function serves
+ *      both), with copy_dst_ref 0.  CREATE, CREATE2 and CALL_OP keep (ZK_KIND_UNSUPPORTED << 24) | 1: no reference-recorded case reaches
+ *      their copy_lookup (CALL_OP's lengths are aux_data, which a step record does not carry).  Terms as above: rwc, "op k", values
+ *      taken as integers; a stack read at position j is a read with tag Stack, id == call_id, addr == stack_pointer + j (here j is not
+ *      k); `next` is step record i + 1; is_create is bit 9 and is_root bit 8 of a record's word 0.
+ *        RETURN (RETURN and REVERT)  op 1 off (stack position 0), op 2 len (position 1); op 0 (IsSuccess) is not read: the reference's
+ *                        `if curr.is_create and is_success` tests an FQ object, so the branch is is_create alone.
+ *                        is_create:  op 4 the Account WRITE of CodeHash (a write, tag Account, field_tag CodeHash), value the word h:
+ *                          (call_id Memory -> h (a Word: flag bit 1) Bytecode; off, off + len, 0, len; 0; rwc + 5) when len != 0,
+ *                          dst_ref the index of h;
+ *                        neither is_root nor is_create:  ops 3 ReturnDataOffset (ro), 4 ReturnDataLength (rl), CallContext reads:
+ *                          (call_id Memory -> next.call_id Memory; off, off + len, ro, min(len, rl); 0; rwc + 5) always, also with
+ *                          length 0 (the reference looks it up unconditionally);
+ *                        is_root and not is_create:  nothing, status 0, no op is read.
+ *        DATACOPY        ops 1 CallerId (c), 2 CallDataOffset (cdo), 3 CallDataLength (cdl), 4 ReturnDataOffset (rdo), 5 ReturnDataLength
+ *                        (rdl), CallContext reads with id == call_id.  Two events, always:
+ *                          (c Memory -> c Memory; cdo, cdo + cdl, rdo, rdo + rdl; 0; rwc + 6) - the reference passes rdo + rdl as the
+ *                          length, and so does this entry;
+ *                          (c Memory -> call_id Memory; cdo, cdo + cdl, 0, rdl; 0; rwc + 6 + inc), inc = the counters the first event
+ *                          consumes: with L = rdo + rdl its L writes plus its reads below src_addr_end, inc = L + min(L, cdl)
+ *                          (CopyCircuit.copy appends a Memory write per byte and a Memory read per byte with src_addr + i <
+ *                          src_addr_end; copy_lookup returns that row's rwc_inc).
+ *        BeginTx         the gadget's branch is in the tx table; here it is told from the successor: the create path with init code is
+ *                        taken iff next.is_create and next.rw_counter == rwc + 23 (ten ops up to the transfer, thirteen CallContext
+ *                        lookups; the other paths end at rwc + 10 or have is_create clear).  On that path the call id is rwc itself:
+ *                        ops 0 TxId (tx), 14 CallDataLength (n), 22 CodeHash (the word h), CallContext reads with id == rwc:
+ *                          (tx TxCalldata -> rwc RlcAcc; 0, n, 0, n; 0; rwc + 10), then
+ *                          (tx TxCalldata -> h (a Word: flag bit 1) Bytecode; 0, n, 0, n; 0; rwc + 10);
+ *                        both with src_ref tx - 1, the second with dst_ref the index of h.  Every other BeginTx: nothing, status 0.
+ *      Status per step: as above (sites 1 and 2 in ascending k, then 3, then 4; site 4 also when h is not in the code set; site 3's tx
+ *      check is CALLDATACOPY's; the values c, cdo, cdl, rdo, rdl, ro, rl, off, len, tx, n and the sums off + len, cdo + cdl, rdo + rdl
+ *      and every event counter are in site 3's domain), and a step emits all of its events or none.  One more site:
+ *        5  the step needs a successor and is the last step (a RETURN that is neither root nor create, every BeginTx; checked before
+ *           any op is read); or BeginTx's create path has n == 0 (checked after sites 1 and 2); or the step's events would lie past the
+ *           copy capacity the session computed.  The last cannot happen while the steps are as the open saw them and is checked anyway:
+ *           no store passes a capacity, the counts read back never exceed it; on the device the write pass sets that status behind
+ *           the tally.
+ *      Sessions, ZK_OPT_DEVICE_PTRS, zk_launch / zk_collect / zk_read_status / zk_session_set_stream / zk_close, what the session keeps
+ *      a copy of, _read and _counts: all as zk_events_from_trace_open.  Domain errors: ZK_ERR_TRC_* and ZK_ERR_TEV_* exactly as above,
+ *      under this entry's name. */
+typedef struct zk_trace_events_ext {                         /* each pointer nullable; copy_*: the copy capacity, exp_*: n_steps */
+    uint64_t* copy_events;      uint32_t* copy_flags;        uint32_t* copy_src_ref;        uint32_t* copy_dst_ref;
+    uint32_t* copy_step;        uint64_t* exp_events;        uint32_t* exp_step;
+} zk_trace_events_ext;
+int zk_events_from_trace_ext_sizes(const zk_trace_sources* in, uint32_t opts, uint64_t* copy_capacity, uint64_t* exp_capacity);
+int zk_events_from_trace_ext_open(const zk_trace_sources* in, const zk_trace_events_ext* out_dev, uint32_t opts, zk_session** out);
+int zk_events_from_trace_ext_read(zk_session* s, const zk_trace_events_ext* host, uint64_t* n_copy, uint64_t* n_exp);
+int zk_events_from_trace_ext_counts(zk_session* s, uint64_t* n_copy, uint64_t* n_exp);
+int zk_events_from_trace_ext(const zk_trace_sources* in, const zk_trace_events_ext* out, uint32_t opts, uint32_t* status_out, uint64_t* n_copy,
+                             uint64_t* n_exp, zk_result* result);
 
 /* ---- SHA3 inputs and keccak rows from compact trace records: the keccak rows the SHA3 steps look up (zk_evm_tables' keccak table), which a
  *      producer of traces so far got by walking its memory image per SHA3 step, concatenating the bytes, uploading them and calling

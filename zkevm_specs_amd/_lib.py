@@ -37,6 +37,8 @@ EXPORTED_SYMBOLS = [
     "zk_copy_assign_from_sources_sizes", "zk_copy_assign_from_sources_open", "zk_copy_assign_from_sources_read", "zk_copy_assign_from_sources",
     "zk_events_from_trace_sizes", "zk_events_from_trace_open", "zk_events_from_trace_read", "zk_events_from_trace_counts", "zk_events_from_trace",
     "zk_sha3_from_trace_sizes", "zk_sha3_from_trace_open", "zk_sha3_from_trace_read", "zk_sha3_from_trace",
+    "zk_events_from_trace_ext_sizes", "zk_events_from_trace_ext_open", "zk_events_from_trace_ext_read", "zk_events_from_trace_ext_counts",
+    "zk_events_from_trace_ext",
 ]
 
 OPT_DEVICE_PTRS = 1
@@ -167,6 +169,11 @@ class ZkTraceSources(ctypes.Structure):
 
 class ZkTraceEvents(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("copy_events", "copy_flags", "copy_src_ref", "copy_step", "exp_events", "exp_step")]
+
+
+class ZkTraceEventsExt(ctypes.Structure):
+    """zk_trace_events_ext (include/zkevm_hip.h): zk_trace_events with the dst_ref of the events that write a code"""
+    _fields_ = [(k, ctypes.c_void_p) for k in ("copy_events", "copy_flags", "copy_src_ref", "copy_dst_ref", "copy_step", "exp_events", "exp_step")]
 
 
 class ZkTraceSha3(ctypes.Structure):
@@ -409,6 +416,12 @@ def _bind(lib):
     lib.zk_events_from_trace_counts.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.zk_events_from_trace.argtypes = [ctypes.POINTER(ZkTraceSources), ctypes.POINTER(ZkTraceEvents), u32, vp, ctypes.POINTER(u64),
                                          ctypes.POINTER(u64), ctypes.POINTER(ZkResult)]
+    lib.zk_events_from_trace_ext_sizes.argtypes = [ctypes.POINTER(ZkTraceSources), u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_events_from_trace_ext_open.argtypes = [ctypes.POINTER(ZkTraceSources), ctypes.POINTER(ZkTraceEventsExt), u32, ctypes.POINTER(vp)]
+    lib.zk_events_from_trace_ext_read.argtypes = [vp, ctypes.POINTER(ZkTraceEventsExt), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_events_from_trace_ext_counts.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64)]
+    lib.zk_events_from_trace_ext.argtypes = [ctypes.POINTER(ZkTraceSources), ctypes.POINTER(ZkTraceEventsExt), u32, vp, ctypes.POINTER(u64),
+                                             ctypes.POINTER(u64), ctypes.POINTER(ZkResult)]
     lib.zk_sha3_from_trace_sizes.argtypes = [ctypes.POINTER(ZkTrace), u32, ctypes.POINTER(u64), ctypes.POINTER(u64)]
     lib.zk_sha3_from_trace_open.argtypes = [ctypes.POINTER(ZkTrace), vp, ctypes.POINTER(ZkTraceSha3), u32, ctypes.POINTER(vp)]
     lib.zk_sha3_from_trace_read.argtypes = [vp, ctypes.POINTER(ZkTraceSha3), ctypes.POINTER(u64), ctypes.POINTER(u64)]

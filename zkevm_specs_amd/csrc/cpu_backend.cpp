@@ -108,7 +108,7 @@ struct zk_session {
     std::vector<u64> w64[4];              // assignment sessions: work / output buffers
     std::vector<u32> out32;
     void (*pass)(zk_session*) = nullptr;  // assignment sessions: one pass computes the outputs and fills `status`
-    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code, 11 tables from block, 12 witness from trace, 13 ECC precompile calls, 14 copy from sources, 15 events from trace, 16 SHA3 from trace
+    int assign_kind = 0;                  // 1 state, 2 bytecode, 3 copy, 4 RW -> State ops, 5 tx, 6 exp, 7 PI, 8 ECC, 9 sig, 10 bytecode from code, 11 tables from block, 12 witness from trace, 13 ECC precompile calls, 14 copy from sources, 15 events from trace, 16 SHA3 from trace, 17 events from trace (ext)
     u64 n_ops = 0;                        // RW -> State ops: 1 + kept rows
     std::vector<u32> rekey_plan;          // RW -> State ops: the RwkHostPlan's plan (as words) ...
     std::vector<u32> rekey_jobs;          // ... and its rank jobs (cls, field, base, count)
@@ -148,6 +148,8 @@ struct zk_session {
     TevPlan tev_plan;               // ... the sorted hash directory
     std::vector<u64> tev64[6];      // counters, pool offsets, code offsets, copy events, EXP events, counts
     std::vector<u32> tev32[5];      // heads, copy flags, copy refs, copy steps, EXP steps
+    TevxArgs tevx;                  // ... the wider entry (zk_events_from_trace_ext*): its TevArgs in tevx.t, the buffers above
+    std::vector<u32> tevx_dst;      // ... its copy dst refs
     Ts3Args ts3;                    // SHA3 inputs and keccak rows from compact trace records
     KeccakGenArgs ts3_kgen;         // ... the keccak table over the gathered bytes
     std::vector<u64> ts364[8];      // counters, pool offsets, sizes, session offsets, fail words, rows, out offsets, powers of the randomness
@@ -1807,6 +1809,103 @@ extern "C" int zk_events_from_trace(const zk_trace_sources* t, const zk_trace_ev
     if (!rc) rc = zk_collect(s, result);
     if (!rc && status_out) rc = zk_read_status(s, status_out);
     if (!rc) rc = zk_events_from_trace_read(s, out_wire, n_copy, n_exp);
+    zk_close(s);
+    return rc;
+}
+// zk_events_from_trace_ext*: the same checks under that entry's name, the wider per-step function, the copy capacity of the two-event
+// states (counted over the steps' word 0) and the dst refs
+static void events_from_trace_ext_pass(zk_session* s) { tevx_pass_host(s->tevx, s->status.data()); }
+static int tevx_prepare(const zk_trace_sources* t, u32* head, u64* ctr, u64* off, u64* cap_copy) {
+    const int rc = tev_prepare(t, head, ctr, off);
+    if (rc) { cps_retitle("zk_events_from_trace_ext"); return rc; }
+    u64 pairs = 0;
+    for (u64 s = 0; s < t->trace.n_steps; s++) pairs += tevx_is_pair_state(t->trace.steps[s * TRW_STEP_WORDS]);
+    *cap_copy = t->trace.n_steps + pairs;
+    return 0;
+}
+extern "C" int zk_events_from_trace_ext_sizes(const zk_trace_sources* t, uint32_t opts, uint64_t* copy_capacity, uint64_t* exp_capacity) {
+    NO_DEVICE_PTRS(opts, "zk_events_from_trace_ext_sizes");
+    ARG_TRY(TEV_ARGS_OK(t), "zk_events_from_trace_ext_sizes: bad arguments");
+    u64 cap = 0;
+    const int rc = tevx_prepare(t, nullptr, nullptr, nullptr, &cap);
+    if (rc) return rc;
+    if (copy_capacity) *copy_capacity = cap;
+    if (exp_capacity) *exp_capacity = t->trace.n_steps;
+    return 0;
+}
+extern "C" int zk_events_from_trace_ext_open(const zk_trace_sources* t, const zk_trace_events_ext* out_dev, uint32_t opts, zk_session** out) {
+    NO_DEVICE_PTRS(opts, "zk_events_from_trace_ext_open");
+    ARG_TRY(TEV_ARGS_OK(t) && out, "zk_events_from_trace_ext_open: bad arguments");
+    ARG_TRY(!out_dev, "zk_events_from_trace_ext_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    const zk_trace& tr = t->trace;
+    int rc = tev_counts_check(tr.n_steps, t->n_code_bytes, t->n_codes);  // (before anything is allocated)
+    char msg[256];
+    if (!rc && (rc = trw_plan_counts(tr.n_rw, tr.n_steps, tr.rw_base, tr.rw_counter != nullptr, msg, sizeof msg))) g_err = msg;
+    if (rc) { cps_retitle("zk_events_from_trace_ext"); return rc; }
+    const u64 n = tr.n_rw, ns = tr.n_steps, nc = t->n_codes;
+    zk_session* s = new_session(ns, false);
+    s->tev32[0].assign(n + 1, 0);                        // heads
+    s->tev64[0].assign(tr.rw_counter ? n + 1 : 0, 0);    // counters
+    s->tev64[1].assign(n + 1, 0);                        // pool offsets
+    u64 cap = 0;
+    if ((rc = tevx_prepare(t, s->tev32[0].data(), tr.rw_counter ? s->tev64[0].data() : nullptr, s->tev64[1].data(), &cap))) { delete s; return rc; }
+    s->tev64[2].assign(t->code_offsets, t->code_offsets + (nc ? nc + 1 : 0));  // the session's copy of the code offsets
+    s->tev64[2].push_back(0);
+    tev_dir_build(t->code_hashes, nc, s->tev_plan);
+    s->tev64[3].assign(cap * TEV_COPY_NCELLS * 4 + 4, 0);  // copy events
+    s->tev64[4].assign(ns * TEV_EXP_NCELLS * 4 + 4, 0);    // EXP events
+    s->tev64[5].assign(2, 0);                              // counts
+    for (int k = 1; k < 4; k++) s->tev32[k].assign(cap + 1, 0);  // copy flags, refs, steps
+    s->tev32[4].assign(ns + 1, 0);                               // EXP steps
+    s->tevx_dst.assign(cap + 1, 0);
+    TevxArgs& ax = s->tevx;
+    memset(&ax, 0, sizeof(ax));
+    TevArgs& a = ax.t;
+    a.head = s->tev32[0].data(); a.ctr = tr.rw_counter ? s->tev64[0].data() : nullptr; a.off = s->tev64[1].data();
+    a.id = tr.id; a.addr = tr.addr; a.val = tr.val; a.pool = tr.pool; a.steps = tr.steps;
+    a.n_rw = n; a.n_pool = tr.n_pool; a.n_steps = ns; a.rw_base = tr.rw_base;
+    a.code = t->code; a.code_off = s->tev64[2].data(); a.dir_hash = s->tev_plan.dir_hash.data(); a.dir_idx = s->tev_plan.dir_idx.data(); a.n_codes = (u32)nc;
+    a.counts = s->tev64[5].data();
+    a.copy_events = s->tev64[3].data(); a.copy_flags = s->tev32[1].data(); a.copy_src_ref = s->tev32[2].data(); a.copy_step = s->tev32[3].data();
+    a.exp_events = s->tev64[4].data(); a.exp_step = s->tev32[4].data();
+    ax.copy_dst_ref = s->tevx_dst.data();
+    ax.cap_copy = cap;
+    s->pass = events_from_trace_ext_pass;
+    s->assign_kind = 17;
+    *out = s;
+    return 0;
+}
+extern "C" int zk_events_from_trace_ext_read(zk_session* s, const zk_trace_events_ext* host, uint64_t* n_copy, uint64_t* n_exp) {
+    ARG_TRY(s && s->assign_kind == 17, "zk_events_from_trace_ext_read: bad arguments");
+    const TevArgs& a = s->tevx.t;
+    const u64 nc = a.counts[0], ne = a.counts[1];
+    if (host) {
+        if (host->copy_events && nc) memcpy(host->copy_events, a.copy_events, nc * TEV_COPY_NCELLS * 32);
+        if (host->copy_flags && nc) memcpy(host->copy_flags, a.copy_flags, nc * 4);
+        if (host->copy_src_ref && nc) memcpy(host->copy_src_ref, a.copy_src_ref, nc * 4);
+        if (host->copy_dst_ref && nc) memcpy(host->copy_dst_ref, s->tevx.copy_dst_ref, nc * 4);
+        if (host->copy_step && nc) memcpy(host->copy_step, a.copy_step, nc * 4);
+        if (host->exp_events && ne) memcpy(host->exp_events, a.exp_events, ne * TEV_EXP_NCELLS * 32);
+        if (host->exp_step && ne) memcpy(host->exp_step, a.exp_step, ne * 4);
+    }
+    if (n_copy) *n_copy = nc;
+    if (n_exp) *n_exp = ne;
+    return 0;
+}
+extern "C" int zk_events_from_trace_ext_counts(zk_session* s, uint64_t* n_copy, uint64_t* n_exp) {
+    ARG_TRY(s && s->assign_kind == 17, "zk_events_from_trace_ext_counts: bad arguments");
+    return zk_events_from_trace_ext_read(s, nullptr, n_copy, n_exp);
+}
+extern "C" int zk_events_from_trace_ext(const zk_trace_sources* t, const zk_trace_events_ext* out_wire, uint32_t opts, uint32_t* status_out,
+                                        uint64_t* n_copy, uint64_t* n_exp, zk_result* result) {
+    ARG_TRY(result && out_wire && t, "zk_events_from_trace_ext: null argument");
+    zk_session* s = nullptr;
+    int rc = zk_events_from_trace_ext_open(t, nullptr, opts, &s);
+    if (rc) return rc;
+    rc = zk_launch(s, nullptr);
+    if (!rc) rc = zk_collect(s, result);
+    if (!rc && status_out) rc = zk_read_status(s, status_out);
+    if (!rc) rc = zk_events_from_trace_ext_read(s, out_wire, n_copy, n_exp);
     zk_close(s);
     return rc;
 }

@@ -90,6 +90,93 @@ __global__ __launch_bounds__(TEV_BLOCK) void tev_write_kernel(TevArgs a) {
     else tev_store_exp(a, pos, s, e);
 }
 
+// ---- the wider entry (zk_events_from_trace_ext*): a lane emits 0, 1 or 2 copy events, or an EXP event --------------------------------
+enum { TEVX_NONE = 0, TEVX_COPY1 = 1, TEVX_EXP = 2, TEVX_COPY2 = 3 };  // what a step emits, as a.kind keeps it between the passes
+
+// As tev_block_rank with lanes of 0..2 copy events: the ballots "emits at least one" and "emits two" give a wave's events (their two
+// popcounts) and a lane's rank (the popcounts below the lane); total[0] counts EVENTS.  rank[0]: the lane's first copy event among the
+// block's, rank[1]: its EXP event.
+__device__ __forceinline__ void tevx_block_rank(u32 kind, u32 (&wc)[TEV_WAVES][2], u32 (&total)[2], u32 (&rank)[2]) {
+    const u32 lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    const unsigned long long m_one = __ballot(kind == (u32)TEVX_COPY1 || kind == (u32)TEVX_COPY2), m_two = __ballot(kind == (u32)TEVX_COPY2),
+                             m_exp = __ballot(kind == (u32)TEVX_EXP);
+    if (lane == 0u) { wc[w][0] = (u32)(__popcll(m_one) + __popcll(m_two)); wc[w][1] = (u32)__popcll(m_exp); }
+    __syncthreads();
+    rank[0] = rank[1] = 0;
+    total[0] = total[1] = 0;
+#pragma unroll
+    for (u32 k = 0; k < (u32)TEV_WAVES; k++) {
+        if (k < w) { rank[0] += wc[k][0]; rank[1] += wc[k][1]; }
+        total[0] += wc[k][0];
+        total[1] += wc[k][1];
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    rank[0] += (u32)(__popcll(m_one & below) + __popcll(m_two & below));
+    rank[1] += (u32)__popcll(m_exp & below);
+}
+__device__ __forceinline__ u32 tevx_kind_of(const TevxEvent (&x)[2]) {
+    return x[0].e.kind == (u32)TEV_EXP ? (u32)TEVX_EXP : x[0].e.kind != (u32)TEV_COPY ? (u32)TEVX_NONE : x[1].e.kind == (u32)TEV_COPY ? (u32)TEVX_COPY2 : (u32)TEVX_COPY1;
+}
+// The open's count: the BeginTx and DATACOPY steps (the copy capacity is n_steps + that), a ballot per wave and one add per wave
+__global__ __launch_bounds__(TEV_BLOCK) void tevx_count_kernel(const u64* steps, u64 n_steps, unsigned long long* n_pair) {
+    const u64 s = (u64)blockIdx.x * TEV_BLOCK + threadIdx.x;
+    const bool pair = s < n_steps && tevx_is_pair_state(steps[s * TRW_STEP_WORDS]);
+    const unsigned long long m = __ballot(pair);
+    if ((threadIdx.x & 63u) == 0u && m) atomicAdd(n_pair, (unsigned long long)__popcll(m));
+}
+// Pass 1: as tev_step_kernel over tevx_step
+__global__ __launch_bounds__(TEV_BLOCK) void tevx_step_kernel(TevxArgs ax, u32* status, ZkTally* tally) {
+    __shared__ u32 wc[TEV_WAVES][2];
+    const TevArgs& a = ax.t;
+    const u64 s = (u64)blockIdx.x * TEV_BLOCK + threadIdx.x;
+    u32 st = 0, kind = TEVX_NONE;
+    if (s < a.n_steps) {
+        TevxEvent x[2];
+        st = tevx_step(a, s, x);
+        kind = tevx_kind_of(x);
+        status[s] = st;
+        a.kind[s] = (uint8_t)kind;
+    }
+    tally_commit(tally, s, st);
+    u32 total[2], rank[2];
+    tevx_block_rank(kind, wc, total, rank);
+    if (threadIdx.x == 0u) { a.blk[2 * (u64)blockIdx.x] = total[0]; a.blk[2 * (u64)blockIdx.x + 1] = total[1]; }
+}
+// Pass 3: as tev_write_kernel; a lane's events stand together.  With the records as the open saw them every position is below the
+// capacity; a lane whose events would pass it (records rewritten under the session) stores nothing and its status becomes site 5.
+__global__ __launch_bounds__(TEV_BLOCK) void tevx_write_kernel(TevxArgs ax, u32* status) {
+    __shared__ u32 wc[TEV_WAVES][2];
+    const TevArgs& a = ax.t;
+    const u64 s = (u64)blockIdx.x * TEV_BLOCK + threadIdx.x;
+    const u32 kind = s < a.n_steps ? a.kind[s] : (u32)TEVX_NONE;
+    u32 total[2], rank[2];
+    tevx_block_rank(kind, wc, total, rank);
+    if (kind == (u32)TEVX_NONE) return;
+    TevxEvent x[2];
+    (void)tevx_step(a, s, x);
+    if (tevx_kind_of(x) != kind) return;  // (a caller rewrote its records under the pass)
+    if (kind == (u32)TEVX_EXP) {
+        const u64 pos = (u64)a.blk[2 * (u64)blockIdx.x + 1] + rank[1];
+        if (pos < a.n_steps) tev_store_exp(a, pos, s, x[0].e);
+        return;
+    }
+    const u64 pos = (u64)a.blk[2 * (u64)blockIdx.x] + rank[0];
+    const u32 n = kind == (u32)TEVX_COPY2 ? 2u : 1u;
+    if (pos + n > ax.cap_copy) { status[s] = tev_status(TEV_SITE_EXT); return; }
+    tevx_store_copy(ax, pos, s, x[0]);
+    if (n == 2u) tevx_store_copy(ax, pos + 1, s, x[1]);
+}
+
+void zk_launch_trace_events_count(hipStream_t st, const u64* steps, u64 n_steps, u64* n_pair) {
+    const u32 nb = (u32)((n_steps + TEV_BLOCK - 1) / TEV_BLOCK);
+    if (nb) hipLaunchKernelGGL(tevx_count_kernel, dim3(nb), dim3(TEV_BLOCK), 0, st, steps, n_steps, (unsigned long long*)n_pair);
+}
+void zk_launch_trace_events_ext(hipStream_t st, const TevxArgs& ax, u32* status, ZkTally* tally) {
+    const u32 nb = (u32)((ax.t.n_steps + TEV_BLOCK - 1) / TEV_BLOCK);
+    if (nb) hipLaunchKernelGGL(tevx_step_kernel, dim3(nb), dim3(TEV_BLOCK), 0, st, ax, status, tally);
+    hipLaunchKernelGGL(tev_scan_kernel, dim3(1), dim3(1024), 0, st, ax.t, nb);  // (the same scan: the block counts are events of either entry)
+    if (nb) hipLaunchKernelGGL(tevx_write_kernel, dim3(nb), dim3(TEV_BLOCK), 0, st, ax, status);
+}
 void zk_launch_trace_events(hipStream_t st, const TevArgs& a, u32* status, ZkTally* tally) {
     const u32 nb = (u32)((a.n_steps + TEV_BLOCK - 1) / TEV_BLOCK);
     if (nb) hipLaunchKernelGGL(tev_step_kernel, dim3(nb), dim3(TEV_BLOCK), 0, st, a, status, tally);

@@ -118,6 +118,8 @@ void zk_launch_copy_sources(hipStream_t st, const CpsArgs& a, const CpsCodeArgs&
 // Copy and EXP events from compact trace records (k_trace_events.hip): a status per step and its tally, what each step emits, a scan of the
 // per-block counts into a.blk / a.counts, the packed ordered stores
 void zk_launch_trace_events(hipStream_t st, const TevArgs& a, u32* status, ZkTally* tally);
+void zk_launch_trace_events_count(hipStream_t st, const u64* steps, u64 n_steps, u64* n_pair);
+void zk_launch_trace_events_ext(hipStream_t st, const TevxArgs& ax, u32* status, ZkTally* tally);
 // SHA3 inputs and keccak rows from compact trace records (k_trace_sha3.hip).  _count: every step's open-time status and size, the scan of
 // the per-block counts, the totals in a.verdict;  _write: the message records and the session's data offsets (cross_only: nothing but
 // the step that takes the byte total to 2^31);  the pass: the gather into a.data, zk_launch_keccak_table over it (g), the digest

@@ -269,8 +269,190 @@ ZK_HD void tev_store_exp(const TevArgs& a, u64 pos, u64 s, const TevEvent& e) {
     a.exp_step[pos] = (u32)s;
 }
 
+// ---- the wider entry (zk_events_from_trace_ext*): BeginTx, RETURN / REVERT and DATACOPY derived too -----------------------------------
+// Their gadgets (begin_tx.py:147-177, return_revert.py:54-93, dataCopy.py:38-61) look up 0, 1 or 2 events per step, read ops up to
+// k = 22 under a call id that is not always the step's, read an Account WRITE, and write a code (a Word destination with a dst_ref).
+//   tevx_read      one op of such a step: the counter offset, the stack position and the call id are arguments of their own
+//   tevx_step      a step's status and its 0, 1 or 2 copy events (or its EXP event); every state tev_step derives goes through tev_step
+//   tevx_store_copy  tev_store_copy with a 256-bit destination id and the dst_ref
+enum { TEV_SITE_EXT = 5, TEV_FLAG_SRC_WORD = 1, TEV_FLAG_DST_WORD = 2, TEV_STEP_CREATE_BIT = 9, TEVX_BEGIN_TX_OPS = 23, TEVX_BEGIN_TX_COPY = 10 };
+struct TevxArgs {
+    TevArgs t;              // (t.blk: [2 * blocks of 256 steps] copy EVENTS / EXP events per block, then the events in front of the block)
+    u32* copy_dst_ref;      // out [n_copy]
+    u64 cap_copy;           // the capacity of the copy outputs: n_steps + the BeginTx and DATACOPY steps counted at open (EXP: n_steps)
+};
+struct TevxEvent {
+    TevEvent e;
+    TevWord dst;            // the destination id (e.dst_id is not read)
+    u32 dst_ref;
+};
+
+// Op k of a step with counter rwc: a read (or, with `write`, a write) of `want`; a Stack / CallContext op has id == id, a Stack op the
+// address sp + pos, a CallContext / Account op the field `pos`.  0 and the value, or site 1 / 2.
+ZK_HD u32 tevx_read(const TevArgs& a, u64 rwc, u32 k, u32 want, bool write, u64 id, u64 sp, u32 pos, TevWord& v) {
+    v.w[0] = v.w[1] = v.w[2] = v.w[3] = 0;
+    const u64 c = rwc + k;
+    const u64 i = c < rwc ? a.n_rw : tev_find_op(a, c);
+    if (i >= a.n_rw) return TEV_SITE_NO_OP;
+    const u32 h = a.head[i];
+    const u64 oid = a.id[i], addr = a.addr[i], val = a.val[i], off = a.off[i];
+    const u32 tag = (h >> TRW_H_TAG_SHIFT) & 0xfu;
+    bool ok = ((h & TRW_H_WRITE) != 0) == write;
+    if (want == TEV_WANT_STACK) ok = ok && tag == TG_Stack && oid == id && !(h & TRW_H_ADDR_POOL) && addr >= sp && addr - sp == pos;
+    else if (want == TEV_WANT_CONTEXT) ok = ok && tag == TG_CallContext && oid == id && !(h & TRW_H_ADDR_POOL) && addr == pos;
+    else ok = ok && tag == TG_Account && ((h >> TRW_H_FIELD_SHIFT) & 0xffu) == pos;
+    if (!ok) return TEV_SITE_NOT_THE_OP;
+    if (h & TRW_H_VALUE_POOL) {
+        const u64* p = a.pool + 4 * (off + ((h >> 20) & 1u) + ((h >> 21) & 1u));
+        v.w[0] = p[0]; v.w[1] = p[1]; v.w[2] = p[2]; v.w[3] = p[3];
+    } else {
+        v.w[0] = val;
+    }
+    return 0;
+}
+ZK_HD void tevx_clear(TevxEvent& x, u64 call_id) {
+    TevEvent& e = x.e;
+    e.kind = TEV_NONE; e.flag = 0; e.src_ref = 0; e.src_tag = TEV_TAG_MEMORY; e.dst_tag = TEV_TAG_MEMORY; e.log_id = 0; e.dst_id = 0;
+    e.src_addr = 0; e.src_end = 0; e.dst_addr = 0; e.length = 0; e.rwc = 0;
+    e.src_id.w[0] = call_id; e.src_id.w[1] = e.src_id.w[2] = e.src_id.w[3] = 0;
+    e.exponent.w[0] = e.exponent.w[1] = e.exponent.w[2] = e.exponent.w[3] = 0;
+    x.dst.w[0] = x.dst.w[1] = x.dst.w[2] = x.dst.w[3] = 0;
+    x.dst_ref = 0;
+}
+// Step s: its status; x[0], x[1]: its events in the gadget's lookup order (x[1].e.kind != TEV_NONE only behind a copy event in x[0]).
+// A failing step emits nothing.
+ZK_HD u32 tevx_step(const TevArgs& a, u64 s, TevxEvent (&x)[2]) {
+    const u64* r = a.steps + s * TRW_STEP_WORDS;
+    const u64 w0 = r[0];
+    const u32 state = (u32)(w0 & 0xffu);
+    const u64 rwc = r[1], call_id = r[2], sp = r[4];
+    tevx_clear(x[0], call_id);
+    tevx_clear(x[1], call_id);
+    if (state != ES_BeginTx && state != ES_RETURN && state != ES_DATACOPY) {  // (CREATE, CREATE2 and CALL_OP stay unsupported there)
+        const u32 st = tev_step(a, s, x[0].e);
+        x[0].dst.w[0] = x[0].e.dst_id;
+        return st;
+    }
+    const bool root = (w0 >> 8) & 1u, create = (w0 >> TEV_STEP_CREATE_BIT) & 1u;
+    const bool last = s + 1 >= a.n_steps;
+    const u64* nx = a.steps + (last ? s : s + 1) * TRW_STEP_WORDS;  // (the last step: never used)
+    TevWord v[TEV_READS];
+#pragma unroll
+    for (int q = 0; q < TEV_READS; q++) v[q].w[0] = v[q].w[1] = v[q].w[2] = v[q].w[3] = 0;
+    u32 site = 0, sq;
+    bool bad = rwc >= TEV_LIMIT;
+    if (state == ES_RETURN) {
+        if (root && !create) return 0;
+        if (!create && last) return tev_status(TEV_SITE_EXT);
+        sq = tevx_read(a, rwc, 1, TEV_WANT_STACK, false, call_id, sp, 0, v[0]); if (!site) site = sq;
+        sq = tevx_read(a, rwc, 2, TEV_WANT_STACK, false, call_id, sp, 1, v[1]); if (!site) site = sq;
+        if (create) {
+            sq = tevx_read(a, rwc, 4, TEV_WANT_ACCOUNT, true, 0, 0, ACC_CodeHash, v[2]); if (!site) site = sq;
+        } else {
+            sq = tevx_read(a, rwc, 3, TEV_WANT_CONTEXT, false, call_id, 0, CC_ReturnDataOffset, v[2]); if (!site) site = sq;
+            sq = tevx_read(a, rwc, 4, TEV_WANT_CONTEXT, false, call_id, 0, CC_ReturnDataLength, v[3]); if (!site) site = sq;
+        }
+        if (site) return tev_status(site);
+        if (create && tev_is_zero(v[1])) return 0;
+        bad = bad || !tev_fits(v[0]) || !tev_fits(v[1]) || (!create && (!tev_fits(v[2]) || !tev_fits(v[3])));
+        TevEvent& e = x[0].e;
+        e.src_addr = v[0].w[0]; e.src_end = v[0].w[0] + v[1].w[0];
+        bad = bad || e.src_end >= TEV_LIMIT || rwc + 5 >= TEV_LIMIT;
+        if (bad) return tev_status(TEV_SITE_DOMAIN);
+        e.rwc = rwc + 5;
+        if (create) {  // the deployed code: Memory -> the written code hash
+            const u32 j = tev_code_of(a, v[2]);
+            if (j == TEV_NO_CODE) return tev_status(TEV_SITE_CODE);
+            e.flag = TEV_FLAG_DST_WORD; e.dst_tag = TEV_TAG_BYTECODE; e.length = v[1].w[0];
+            x[0].dst = v[2]; x[0].dst_ref = j;
+        } else {       // the return data: Memory -> the caller's Memory
+            e.dst_addr = v[2].w[0]; e.length = v[1].w[0] < v[3].w[0] ? v[1].w[0] : v[3].w[0];
+            x[0].dst.w[0] = nx[2];
+        }
+        e.kind = TEV_COPY;
+        return 0;
+    }
+    if (state == ES_DATACOPY) {
+        const u32 field[5] = {CC_CallerId, CC_CallDataOffset, CC_CallDataLength, CC_ReturnDataOffset, CC_ReturnDataLength};
+#pragma unroll
+        for (int q = 0; q < 5; q++) {
+            sq = tevx_read(a, rwc, (u32)q + 1, TEV_WANT_CONTEXT, false, call_id, 0, field[q], v[q]); if (!site) site = sq;
+        }
+        if (site) return tev_status(site);
+#pragma unroll
+        for (int q = 0; q < 5; q++) bad = bad || !tev_fits(v[q]);
+        const u64 c = v[0].w[0], cdo = v[1].w[0], cdl = v[2].w[0], rdo = v[3].w[0], rdl = v[4].w[0];
+        const u64 len0 = rdo + rdl;                          // (the reference passes rdo + rdl as the first event's length)
+        const u64 inc = len0 + (len0 < cdl ? len0 : cdl);    // its writes, and its reads below src_addr_end
+        bad = bad || cdo + cdl >= TEV_LIMIT || len0 >= TEV_LIMIT || rwc + 6 + inc >= TEV_LIMIT;
+        if (bad) return tev_status(TEV_SITE_DOMAIN);
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            TevEvent& e = x[q].e;
+            e.src_id.w[0] = c; e.src_addr = cdo; e.src_end = cdo + cdl;
+            e.kind = TEV_COPY;
+        }
+        x[0].dst.w[0] = c; x[0].e.dst_addr = rdo; x[0].e.length = len0; x[0].e.rwc = rwc + 6;
+        x[1].dst.w[0] = call_id; x[1].e.length = rdl; x[1].e.rwc = rwc + 6 + inc;
+        return 0;
+    }
+    // BeginTx: the create path with init code, told from the successor
+    if (last) return tev_status(TEV_SITE_EXT);
+    if (!((nx[0] >> TEV_STEP_CREATE_BIT) & 1u) || nx[1] < rwc || nx[1] - rwc != TEVX_BEGIN_TX_OPS) return 0;
+    sq = tevx_read(a, rwc, 0, TEV_WANT_CONTEXT, false, rwc, 0, CC_TxId, v[0]); if (!site) site = sq;
+    sq = tevx_read(a, rwc, 14, TEV_WANT_CONTEXT, false, rwc, 0, CC_CallDataLength, v[1]); if (!site) site = sq;
+    sq = tevx_read(a, rwc, 22, TEV_WANT_CONTEXT, false, rwc, 0, CC_CodeHash, v[2]); if (!site) site = sq;
+    if (site) return tev_status(site);
+    if (tev_is_zero(v[1])) return tev_status(TEV_SITE_EXT);  // (that path needs calldata: begin_tx.py:130)
+    bad = bad || !tev_fits(v[0]) || !tev_fits(v[1]) || v[0].w[0] == 0 || v[0].w[0] - 1 > 0xffffffffull || rwc + TEVX_BEGIN_TX_COPY >= TEV_LIMIT;
+    if (bad) return tev_status(TEV_SITE_DOMAIN);
+    const u32 j = tev_code_of(a, v[2]);
+    if (j == TEV_NO_CODE) return tev_status(TEV_SITE_CODE);
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+        TevEvent& e = x[q].e;
+        e.src_id = v[0]; e.src_tag = TEV_TAG_TX_CALLDATA; e.src_ref = (u32)(v[0].w[0] - 1);
+        e.src_end = v[1].w[0]; e.length = v[1].w[0]; e.rwc = rwc + TEVX_BEGIN_TX_COPY;
+        e.kind = TEV_COPY;
+    }
+    x[0].e.dst_tag = TEV_TAG_RLC_ACC; x[0].dst.w[0] = rwc;
+    x[1].e.dst_tag = TEV_TAG_BYTECODE; x[1].e.flag = TEV_FLAG_DST_WORD; x[1].dst = v[2]; x[1].dst_ref = j;
+    return 0;
+}
+ZK_HD void tevx_store_copy(const TevxArgs& ax, u64 pos, u64 s, const TevxEvent& x) {
+    const TevArgs& a = ax.t;
+    const TevEvent& e = x.e;
+    u64* c = a.copy_events + pos * TEV_COPY_NCELLS * 4;
+    const u64 cell[TEV_COPY_NCELLS][2] = {{e.src_id.w[0], e.src_id.w[1]}, {e.src_id.w[2], e.src_id.w[3]}, {e.src_tag, 0}, {x.dst.w[0], x.dst.w[1]},
+                                          {x.dst.w[2], x.dst.w[3]}, {e.dst_tag, 0}, {e.src_addr, 0}, {e.src_end, 0}, {e.dst_addr, 0}, {e.length, 0},
+                                          {e.log_id, 0}, {e.rwc, 0}};
+#pragma unroll
+    for (int q = 0; q < TEV_COPY_NCELLS; q++) { c[4 * q] = cell[q][0]; c[4 * q + 1] = cell[q][1]; c[4 * q + 2] = 0; c[4 * q + 3] = 0; }
+    a.copy_flags[pos] = e.flag;
+    a.copy_src_ref[pos] = e.src_ref;
+    ax.copy_dst_ref[pos] = x.dst_ref;
+    a.copy_step[pos] = (u32)s;
+}
+// a step of one of the two states that may emit two events: what the copy capacity counts
+ZK_HD u32 tevx_is_pair_state(u64 w0) { return (u32)(w0 & 0xffu) == ES_BeginTx || (u32)(w0 & 0xffu) == ES_DATACOPY; }
+
 // ---- host form (CPU backend, hostsim): the steps in order, the events packed as they come -------------------------------------------
 #if defined(ZK_HOSTSIM)
+static inline void tevx_pass_host(const TevxArgs& ax, u32* status) {
+    const TevArgs& a = ax.t;
+    u64 n_copy = 0, n_exp = 0;
+    for (u64 s = 0; s < a.n_steps; s++) {
+        TevxEvent x[2];
+        u32 st = tevx_step(a, s, x);
+        const u32 k0 = x[0].e.kind, n = k0 == TEV_COPY ? (x[1].e.kind == TEV_COPY ? 2u : 1u) : 0u;
+        if (n_copy + n > ax.cap_copy) st = tev_status(TEV_SITE_EXT);  // (records rewritten under the session; nothing is emitted)
+        else if (k0 == TEV_EXP) tev_store_exp(a, n_exp++, s, x[0].e);
+        else for (u32 q = 0; q < n; q++) tevx_store_copy(ax, n_copy++, s, x[q]);
+        status[s] = st;
+    }
+    a.counts[0] = n_copy;
+    a.counts[1] = n_exp;
+}
 static inline void tev_pass_host(const TevArgs& a, u32* status) {
     u64 n_copy = 0, n_exp = 0;
     for (u64 s = 0; s < a.n_steps; s++) {

@@ -606,7 +606,7 @@ struct EvmResultBlock {
     u32 pad1[8 - (EVM_N_GROUPS + 1)];
 };
 static_assert(sizeof(EvmDyn) <= 64 && sizeof(EvmResultBlock) == 128, "EvmResultBlock layout");
-enum SessionKind { SESSION_TS3 = 28, SESSION_TEV = 27, SESSION_CPS = 26, SESSION_ECL = 25, SESSION_TRW = 24, SESSION_BTB = 23, SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
+enum SessionKind { SESSION_TEVX = 29, SESSION_TS3 = 28, SESSION_TEV = 27, SESSION_CPS = 26, SESSION_ECL = 25, SESSION_TRW = 24, SESSION_BTB = 23, SESSION_BCC = 22, SESSION_SGA = 21, SESSION_ECC_ASSIGN = 20, SESSION_ECC = 19, SESSION_PIA = 18, SESSION_EXA = 17, SESSION_TXA = 16, SESSION_WITHDRAWAL = 15, SESSION_REKEY = 14, SESSION_PICOPY = 13, SESSION_PI = 12, SESSION_CPA = 11, SESSION_STATE = 1, SESSION_EVM = 2, SESSION_BYTECODE = 3, SESSION_EXP = 4, SESSION_COPY = 5, SESSION_SIGN = 6, SESSION_KECCAK = 7, SESSION_ASSIGN = 8, SESSION_ECDSA = 9, SESSION_BCA = 10 };
 
 struct zk_session {
     SessionKind kind;
@@ -672,6 +672,7 @@ struct zk_session {
     CpsCodeArgs cps_code;           // ... its is_code scan (n_segs = 0: no event has a Bytecode side)
     std::vector<u64> cps_data0;     // ... the gathered array's offsets (host copy: zk_copy_assign_from_sources_read hands them out)
     TevArgs tev;                    // SESSION_TEV (zk_events_from_trace*): the open's checks and the session's heads / counters / pool offsets sit in `trw`
+    TevxArgs tevx;                  // SESSION_TEVX (zk_events_from_trace_ext*): likewise, its TevArgs in tevx.t
     Ts3Args ts3;                    // SESSION_TS3 (zk_sha3_from_trace*): likewise; the keccak pass over the gathered bytes in ts3_kgen
     KeccakGenArgs ts3_kgen;
     u32* d_hist = nullptr;   // EVM: (group, state) bins (histogram -> cursors)
@@ -2352,28 +2353,32 @@ extern "C" int zk_copy_assign_from_sources(const zk_copy_sources* t, uint64_t* r
                         ((t)->n_codes == 0 || ((t)->code_offsets && (t)->code_hashes)) && ((t)->n_code_bytes == 0 || (t)->code))
 // Open a session over the records and the code set: the counts and the code offsets checked on the host, the trace's heads, counters and
 // step words on the device (one verdict block read back, as zk_evm_witness_from_trace_open), the hash directory sorted on the host.
-// check_only: the checks alone (the _sizes entry: the session is closed again).
-static int tev_open(const zk_trace_sources* t, const zk_trace_events* out_dev, uint32_t opts, bool check_only, zk_session** out) {
-    const char* const name = "zk_events_from_trace";
+// check_only: the checks alone (the _sizes entry: the session is closed again).  ext (zk_events_from_trace_ext*): out_dev's lists and
+// the dst_ref in out_ext, the copy capacity n_steps + the BeginTx and DATACOPY steps (counted behind the check launch) in *cap_copy,
+// every error under that entry's name.
+static int tev_open(const zk_trace_sources* t, const zk_trace_events* out_dev, uint32_t opts, bool check_only, zk_session** out, bool ext = false,
+                    uint32_t* dst_ref_dev = nullptr, uint64_t* cap_copy = nullptr) {
+    const char* const name = ext ? "zk_events_from_trace_ext" : "zk_events_from_trace";
     const bool dev = opts & ZK_OPT_DEVICE_PTRS;
     const zk_trace& tr = t->trace;
     char msg[256];
-    RC_TRY(tev_counts_check(tr.n_steps, t->n_code_bytes, t->n_codes));  // (before anything is read)
+    if (int rc = tev_counts_check(tr.n_steps, t->n_code_bytes, t->n_codes)) { if (ext) cps_retitle(name); return rc; }  // (before anything is read)
     if (int rc = trw_plan_counts(tr.n_rw, tr.n_steps, tr.rw_base, tr.rw_counter != nullptr, msg, sizeof msg)) { g_err = msg; cps_retitle(name); return rc; }
     std::vector<u64> k_off, k_hash;
     TevPlan pl;
     const u64 *code_off, *hashes;
     RC_TRY(cps_host_view(t->code_offsets, t->n_codes ? (size_t)t->n_codes + 1 : 0, dev, k_off, &code_off));
-    RC_TRY(tev_offsets_check(code_off, t->n_codes, t->n_code_bytes));
+    if (int rc = tev_offsets_check(code_off, t->n_codes, t->n_code_bytes)) { if (ext) cps_retitle(name); return rc; }
     const u64 n = tr.n_rw, ns = tr.n_steps, nc = t->n_codes;
     SessionGuard guard(new zk_session());
     zk_session* const s = guard.get();
-    s->kind = SESSION_TEV;
+    s->kind = ext ? SESSION_TEVX : SESSION_TEV;
     s->n = ns;
     TrwArgs& w = s->trw;
-    TevArgs& a = s->tev;
+    TevArgs& a = ext ? s->tevx.t : s->tev;
     memset(&w, 0, sizeof(w));
-    memset(&a, 0, sizeof(a));
+    memset(&s->tev, 0, sizeof(s->tev));
+    memset(&s->tevx, 0, sizeof(s->tevx));
     // the trace's heads, counters and step words: checked as zk_evm_witness_from_trace_open checks them; the session keeps its own heads,
     // counters and pool offsets (a caller that rewrites a head cannot move a load)
     RC_TRY(stage_in(s, w.head_in, tr.head, (size_t)n * 4, dev));
@@ -2385,10 +2390,24 @@ static int tev_open(const zk_trace_sources* t, const zk_trace_events* out_dev, u
     RC_TRY(dev_buf(s, w.off, (size_t)n * 8 + 8));
     RC_TRY(dev_buf(s, w.verdict, TRW_V_WORDS * 8));
     zk_launch_trace_witness_check(s->stream, w);
+    u64* d_pairs = nullptr;
+    if (ext) {  // the steps' word 0 once more, behind the check on the same stream: the steps that may emit two events
+        RC_TRY(dev_buf(s, d_pairs, 8));
+        HIP_TRY(hipMemsetAsync(d_pairs, 0, 8, s->stream));
+        zk_launch_trace_events_count(s->stream, w.steps_in, ns, d_pairs);
+    }
     DEV_TRY(hipGetLastError() == hipSuccess, "zk_events_from_trace: the open's check launch failed");
     u64 v[TRW_V_WORDS];
     RC_TRY(d2h_now(s->stream, v, w.verdict, sizeof v));
     if (int rc = trw_verdict_error(v, tr.n_pool, msg, sizeof msg)) { g_err = msg; cps_retitle(name); return rc; }
+    u64 cap = ns;
+    if (ext) {
+        u64 pairs = 0;
+        RC_TRY(d2h_now(s->stream, &pairs, d_pairs, sizeof pairs));
+        cap = ns + (pairs < ns ? pairs : ns);
+        if (cap_copy) *cap_copy = cap;
+        s->tevx.cap_copy = cap;
+    }
     if (check_only) return 0;
     RC_TRY(cps_host_view(t->code_hashes, (size_t)nc * 4, dev, k_hash, &hashes));
     tev_dir_build(hashes, nc, pl);
@@ -2410,10 +2429,11 @@ static int tev_open(const zk_trace_sources* t, const zk_trace_events* out_dev, u
     RC_TRY(dev_buf(s, a.counts, 16));
     HIP_TRY(hipMemsetAsync(a.counts, 0, 16, s->stream));  // (no pass yet: no event)
     const zk_trace_events o = wire_or_nulls(out_dev);
-    RC_TRY(out_buf(s, a.copy_events, o.copy_events, (size_t)ns * TEV_COPY_NCELLS * 32));
-    RC_TRY(out_buf(s, a.copy_flags, o.copy_flags, (size_t)ns * 4));
-    RC_TRY(out_buf(s, a.copy_src_ref, o.copy_src_ref, (size_t)ns * 4));
-    RC_TRY(out_buf(s, a.copy_step, o.copy_step, (size_t)ns * 4));
+    RC_TRY(out_buf(s, a.copy_events, o.copy_events, (size_t)cap * TEV_COPY_NCELLS * 32));
+    RC_TRY(out_buf(s, a.copy_flags, o.copy_flags, (size_t)cap * 4));
+    RC_TRY(out_buf(s, a.copy_src_ref, o.copy_src_ref, (size_t)cap * 4));
+    RC_TRY(out_buf(s, a.copy_step, o.copy_step, (size_t)cap * 4));
+    if (ext) RC_TRY(out_buf(s, s->tevx.copy_dst_ref, dst_ref_dev, (size_t)cap * 4));
     RC_TRY(out_buf(s, a.exp_events, o.exp_events, (size_t)ns * TEV_EXP_NCELLS * 32));
     RC_TRY(out_buf(s, a.exp_step, o.exp_step, (size_t)ns * 4));
     RC_TRY(session_common_init(s));
@@ -2467,6 +2487,67 @@ extern "C" int zk_events_from_trace(const zk_trace_sources* t, const zk_trace_ev
     SessionGuard guard(s);
     RC_TRY(one_shot_pass(s, dev, status_out, result));
     return zk_events_from_trace_read(s, dev ? nullptr : out_wire, n_copy, n_exp);
+}
+// zk_events_from_trace_ext*: the same open with the wider per-step function, the copy capacity of its two-event states and the dst_ref
+static zk_trace_events tevx_lists(const zk_trace_events_ext* o) {
+    zk_trace_events l;
+    memset(&l, 0, sizeof l);
+    if (o) { l.copy_events = o->copy_events; l.copy_flags = o->copy_flags; l.copy_src_ref = o->copy_src_ref; l.copy_step = o->copy_step;
+             l.exp_events = o->exp_events; l.exp_step = o->exp_step; }
+    return l;
+}
+extern "C" int zk_events_from_trace_ext_sizes(const zk_trace_sources* t, uint32_t opts, uint64_t* copy_capacity, uint64_t* exp_capacity) {
+    ARG_TRY(t_device >= 0, "zk_events_from_trace_ext_sizes: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(TEV_ARGS_OK(t), "zk_events_from_trace_ext_sizes: bad arguments");
+    u64 cap = 0;
+    RC_TRY(tev_open(t, nullptr, opts, true, nullptr, true, nullptr, &cap));
+    if (copy_capacity) *copy_capacity = cap;
+    if (exp_capacity) *exp_capacity = t->trace.n_steps;
+    return 0;
+}
+extern "C" int zk_events_from_trace_ext_open(const zk_trace_sources* t, const zk_trace_events_ext* out_dev, uint32_t opts, zk_session** out) {
+    ARG_TRY(t_device >= 0, "zk_events_from_trace_ext_open: call zk_init first");
+    HIP_TRY(hipSetDevice(t_device));
+    ARG_TRY(TEV_ARGS_OK(t) && out, "zk_events_from_trace_ext_open: bad arguments");
+    ARG_TRY((opts & ZK_OPT_DEVICE_PTRS) || !out_dev, "zk_events_from_trace_ext_open: out_dev needs ZK_OPT_DEVICE_PTRS");
+    const zk_trace_events lists = tevx_lists(out_dev);
+    return tev_open(t, out_dev ? &lists : nullptr, opts, false, out, true, out_dev ? out_dev->copy_dst_ref : nullptr, nullptr);
+}
+extern "C" int zk_events_from_trace_ext_read(zk_session* s, const zk_trace_events_ext* host, uint64_t* n_copy, uint64_t* n_exp) {
+    ARG_TRY(s && s->kind == SESSION_TEVX, "zk_events_from_trace_ext_read: bad arguments");
+    HIP_TRY(hipSetDevice(s->device));
+    const TevArgs& a = s->tevx.t;
+    u64 c[2];
+    RC_TRY(d2h_now(s->stream, c, a.counts, sizeof c));  // (the counts of the last pass size the copies)
+    if (c[0] > s->tevx.cap_copy) c[0] = s->tevx.cap_copy;  // (records rewritten under the session: no store passed the capacity)
+    if (host) {
+        RC_TRY(d2h_out(s, host->copy_events, a.copy_events, (size_t)c[0] * TEV_COPY_NCELLS * 32));
+        RC_TRY(d2h_out(s, host->copy_flags, a.copy_flags, (size_t)c[0] * 4));
+        RC_TRY(d2h_out(s, host->copy_src_ref, a.copy_src_ref, (size_t)c[0] * 4));
+        RC_TRY(d2h_out(s, host->copy_dst_ref, s->tevx.copy_dst_ref, (size_t)c[0] * 4));
+        RC_TRY(d2h_out(s, host->copy_step, a.copy_step, (size_t)c[0] * 4));
+        RC_TRY(d2h_out(s, host->exp_events, a.exp_events, (size_t)c[1] * TEV_EXP_NCELLS * 32));
+        RC_TRY(d2h_out(s, host->exp_step, a.exp_step, (size_t)c[1] * 4));
+        HIP_TRY(hipStreamSynchronize(s->stream));
+    }
+    if (n_copy) *n_copy = c[0];
+    if (n_exp) *n_exp = c[1];
+    return 0;
+}
+extern "C" int zk_events_from_trace_ext_counts(zk_session* s, uint64_t* n_copy, uint64_t* n_exp) {
+    ARG_TRY(s && s->kind == SESSION_TEVX, "zk_events_from_trace_ext_counts: bad arguments");
+    return zk_events_from_trace_ext_read(s, nullptr, n_copy, n_exp);
+}
+extern "C" int zk_events_from_trace_ext(const zk_trace_sources* t, const zk_trace_events_ext* out_wire, uint32_t opts, uint32_t* status_out,
+                                        uint64_t* n_copy, uint64_t* n_exp, zk_result* result) {
+    ARG_TRY(result && out_wire && t, "zk_events_from_trace_ext: null argument");
+    const bool dev = opts & ZK_OPT_DEVICE_PTRS;
+    zk_session* s = nullptr;
+    RC_TRY(zk_events_from_trace_ext_open(t, dev ? out_wire : nullptr, opts, &s));
+    SessionGuard guard(s);
+    RC_TRY(one_shot_pass(s, dev, status_out, result));
+    return zk_events_from_trace_ext_read(s, dev ? nullptr : out_wire, n_copy, n_exp);
 }
 
 // ---- SHA3 inputs and keccak rows from compact trace records (trace_sha3.hpp, k_trace_sha3.hip)
@@ -3194,6 +3275,7 @@ extern "C" int zk_launch(zk_session* s, uint32_t* status_dev) {
     case SESSION_BTB: zk_launch_block_tables(s->stream, s->btb, status); break;
     case SESSION_TRW: zk_launch_trace_witness(s->stream, s->trw, status); break;
     case SESSION_TEV: zk_launch_trace_events(s->stream, s->tev, status, s->d_tally); break;
+    case SESSION_TEVX: zk_launch_trace_events_ext(s->stream, s->tevx, status, s->d_tally); break;
     case SESSION_TS3: zk_launch_trace_sha3(s->stream, s->ts3, s->ts3_kgen, status, s->d_tally); break;
     case SESSION_ECL: zk_launch_ecc_calls(s->stream, s->ecl, s->ecl_n_pairs, status); break;
     case SESSION_REKEY:

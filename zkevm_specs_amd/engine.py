@@ -1554,6 +1554,63 @@ def open_events_from_trace(trace, codes, code_hashes, outs=None, device=None):
     return _wire_open(TRACE_EVENTS, device, trace_event_sources(trace, codes, code_hashes), (), outs, cls=EventsFromTraceSession)
 
 
+# ---- The same with the events of BeginTx, RETURN / REVERT and DATACOPY (zk_events_from_trace_ext*) ----------------------------------
+TRACE_EVENTS_EXT_OUTPUTS = ("copy_events", "copy_flags", "copy_src_ref", "copy_dst_ref", "copy_step", "exp_events", "exp_step")
+
+
+def events_from_trace_ext_shapes(copy_capacity, n_steps):
+    """name -> (shape, dtype) of the outputs of zk_events_from_trace_ext* for the capacities of events_from_trace_ext_sizes"""
+    c, n = int(copy_capacity), int(n_steps)
+    return {"copy_events": ((c, 12, 4), np.uint64), "copy_flags": ((c,), np.uint32), "copy_src_ref": ((c,), np.uint32),
+            "copy_dst_ref": ((c,), np.uint32), "copy_step": ((c,), np.uint32), "exp_events": ((n, 5, 4), np.uint64), "exp_step": ((n,), np.uint32)}
+
+
+def _trace_events_ext_check(x):
+    ns, _ = _trace_events_check(x)
+    return ns, events_from_trace_ext_shapes(x.get("copy_capacity", ns), ns)  # (no capacity yet: the `_sizes` call, which shapes nothing)
+
+
+TRACE_EVENTS_EXT = WireFamily("zk_events_from_trace_ext", TRACE_EVENTS_INPUTS, TRACE_EVENTS_EXT_OUTPUTS, _lib.ZkTraceEventsExt,
+                              _trace_events_ext_check, _trace_events_fill, cut=("copy_events", "exp_events"), status=True, null_empty=True, n_sizes=2)
+
+
+def _trace_events_ext_sized(lib, x):
+    """the input dict `x` with the library's own copy capacity (one `_sizes` call)"""
+    x = dict(x)
+    x["copy_capacity"] = _wire_sizes(TRACE_EVENTS_EXT, lib, _wire_args(TRACE_EVENTS_EXT, x))[0]
+    return x
+
+
+def events_from_trace_ext_sizes(trace, codes, code_hashes, device=None):
+    """(copy capacity, EXP capacity) of zk_events_from_trace_ext*: n_steps + the BeginTx and DATACOPY steps, and n_steps; raises
+    EngineError (rc = _lib.ERR_TRC_* / ERR_TEV_*) for inputs outside the domain"""
+    lib = _lib.init(device)
+    return _wire_sizes(TRACE_EVENTS_EXT, lib, _wire_args(TRACE_EVENTS_EXT, trace_event_sources(trace, codes, code_hashes)))
+
+
+class EventsFromTraceExtSession(WireSession):
+    """zk_events_from_trace_ext_open: a status per step; counts() -> (n_copy, n_exp) of the last pass; read(names=None) -> dict of the
+    outputs cut to those counts (copy_events / copy_flags / copy_src_ref / copy_dst_ref: what open_copy_assign_from_sources takes)"""
+
+    def counts(self):
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        check(self._lib.zk_events_from_trace_ext_counts(self._h, ctypes.byref(a), ctypes.byref(b)), "zk_events_from_trace_ext_counts", self._lib)
+        return int(a.value), int(b.value)
+
+    def read(self, names=None):
+        out, w = _wire_host_outputs(self.family, self.shapes, names)
+        return cut_trace_events(out, *self._read(w))
+
+
+def open_events_from_trace_ext(trace, codes, code_hashes, outs=None, device=None):
+    """open_events_from_trace with the copy events of BeginTx, RETURN / REVERT and DATACOPY steps -> EventsFromTraceExtSession.  The CUDA
+    tensors of `outs` (TRACE_EVENTS_EXT_OUTPUTS, shapes of events_from_trace_ext_shapes over events_from_trace_ext_sizes) receive the
+    packed lists in place."""
+    lib = _lib.init(device)
+    x = _trace_events_ext_sized(lib, trace_event_sources(trace, codes, code_hashes))
+    return _wire_open(TRACE_EVENTS_EXT, device, x, (), outs, cls=EventsFromTraceExtSession)
+
+
 # ---- SHA3 inputs and keccak rows from compact trace records (zk_sha3_from_trace*) ----------------------------------------------------
 TRACE_SHA3_INPUTS = ("head", "id", "addr", "val", "rw_counter", "pool", "steps")
 TRACE_SHA3_OUTPUTS = ("rows", "step", "data", "data_offsets")

@@ -184,6 +184,18 @@ def events_from_trace(trace, codes, code_hashes, device=None):
     return res, status, engine.cut_trace_events(out, len(out["copy_events"]), len(out["exp_events"]))
 
 
+def events_from_trace_ext(trace, codes, code_hashes, device=None):
+    """zk_events_from_trace_ext: events_from_trace with the copy events of BeginTx, RETURN / REVERT and DATACOPY steps and the extra
+    output copy_dst_ref uint32[n_copy]; the copy outputs are sized by one zk_events_from_trace_ext_sizes call in front"""
+    lib = _lib.init(device)
+    x = engine.trace_event_sources(trace, codes, code_hashes)
+    dtypes = {"head": np.uint32, "code": np.uint8}
+    x = {k: (_host(v, dtypes.get(k, np.uint64)) if k in engine.TRACE_EVENTS_INPUTS else v) for k, v in x.items()}
+    fam = engine.TRACE_EVENTS_EXT
+    res, status, out = _wire_oneshot(fam, lib, engine._wire_args(fam, engine._trace_events_ext_sized(lib, x)))
+    return res, status, engine.cut_trace_events(out, len(out["copy_events"]), len(out["exp_events"]))
+
+
 def sha3_from_trace(trace, randomness, device=None):
     """zk_sha3_from_trace over trace records of host arrays -> (Result over the STEPS, status uint32[n_steps], dict of rows
     uint64[n_msgs, 5, 4], step uint32[n_msgs], data uint8[n_bytes], data_offsets uint64[n_msgs + 1]); the outputs are sized by one
